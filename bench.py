@@ -7,15 +7,24 @@ driver's 20 steps time a third of a second — one 64-frame batch (0.7 ms) is to
 the host.  `value` = frames / total time of the K steps; `value_p50` = the same
 from the median step.  Inputs (uint16 depth frames + poses) are resident in
 HBM before the timed region starts.  Workload at N=1 = BASELINE config 2 (640x480 stream, 0.1 m local map,
-S1 parameters); `--workload cfg3` selects config 3 (1280x720, 0.05 m).  At N=1 the same run also times a short
-config-3 stream (`extra.cfg3`, with its own `roofline` and one-core `cpu_baseline`), the per-call latency of single frames
+S1 parameters); `--workload cfg3` selects config 3 (1280x720, 0.05 m).
+
+A plain run sets up, warms up, times the K steps and prints the headline line, nothing else.  `--dump-outputs DIR` then writes
+the map the timed path has built after its last step (what mlm_export_blocks hands a caller; float32 / float64 .npy files, a
+seeded sample of the blocks when the map is larger than 64 MB) so that two builds can be compared output for output: the inputs
+depend on the arguments only.  (`--full` integrates a few instrumented batches before its timed region, so its map differs from
+a plain run's: compare like with like.)  Everything below is measured with `--full` only.
+
+With `--full` the dominant kernel's launches are bracketed with events in the timed region (`roofline`), the same batches are
+timed from host buffers (`pcie_inclusive_frames_per_s`), and at N=1 the same run also times a short config-3 stream
+(`extra.cfg3`, with its own `roofline` and one-core `cpu_baseline`), the per-call latency of single frames
 (`extra.single_frame_us`, the reference's own call pattern, with the CPU oracle's rate beside it) and compares the map of
 the first >= 128 frames of the stream — submitted exactly like the timed loop: asynchronous 64-frame device batches on a
 handle with three slot sets — with the CPU oracle's (`parity_check`).
 
 Multi-GPU = BASELINE config 4: N independent config-2 streams, pose seeds 42 + rank, one rank per GPU, no data-path
 collective (the path shards by stream: SURVEY.md §8e); the barrier and the max-over-ranks reduction of the elapsed time go
-through torch.distributed (RCCL), and after the stream ONE global-map merge over RCCL is timed (`merge`).
+through torch.distributed (RCCL), and with `--full`, after the stream, ONE global-map merge over RCCL is timed (`merge`).
 `python bench.py --gpus N` with no rank environment starts the N ranks itself (a child `python -m torch.distributed.run
 --nproc-per-node N bench.py --gpus N ...`, started before this process touches the GPU); under the driver's own
 `torch.distributed.run` it is simply rank RANK of WORLD_SIZE.  "scaling": "weak".
@@ -146,11 +155,12 @@ def cpu_baseline(cfg, workload, frames, q, t, budget_s: float, gpu_check=None, m
 
 
 # ---- helpers of the GPU legs --------------------------------------------------------------------------------------
-def measure_stream(m, cfg, d_frames, q, t, B, BPS, K, W, distinct, barrier, kernel_timing=True, n_settle=24, n_instr=6):
+def measure_stream(m, cfg, d_frames, q, t, B, BPS, K, W, distinct, barrier, kernel_timing=True, n_settle=24, n_instr=6, after_timed=None):
     """The measurement protocol of one stream on handle `m` (asynchronous mode): W untimed steps, a few fully instrumented
     batches to find the kernel with the largest summed device time, `n_settle` untimed batches back in the pipelined regime,
     then K timed steps of BPS batches of B frames between barriers (only the dominant kernel's launches are bracketed there),
-    then two synchronous batches with every launch bracketed (each kernel alone on the GPU).  Returns a dict."""
+    `after_timed()` (the map as the timed steps left it), then two synchronous batches with every launch bracketed (each
+    kernel alone on the GPU).  Returns a dict."""
     fsz = cfg.width * cfg.height
 
     def run_batch(j):
@@ -207,6 +217,8 @@ def measure_stream(m, cfg, d_frames, q, t, B, BPS, K, W, distinct, barrier, kern
     barrier()
     dt = time.perf_counter() - t0
     gc.enable()
+    if after_timed is not None:
+        after_timed()
     # per-step durations: a step's submissions return once the batch three sets back is confirmed, so in steady state the host
     # clock after a step trails the GPU by a constant two batches; the last step also takes the final drain
     step_dt = np.diff(np.array([t0] + step_end[:-1] + [t0 + dt]))
@@ -387,6 +399,28 @@ def newest_profile(pattern: str):
     return files[-1] if files else None
 
 
+DUMP_BYTES = 64 * 1000 * 1000  # --dump-outputs: at most this much in all (the files of every rank together)
+
+
+def dump_outputs(m, out_dir, rank=0, world=1):
+    """`--dump-outputs DIR`: the map as the timed steps left it, as a caller receives it from mlm_export_blocks (blocks sorted by
+    key).  block_keys [n, 3] and block_collapsed [n] of every block; log_odds / occ / infl [k, cells] of the blocks whose rows in
+    block_keys sample_rows [k] names: all n, or k drawn with a fixed seed when all n do not fit.  Keys and rows are float64
+    (exact), the rest float32.  With several ranks each writes its own files (suffix _rank<r>) within its share of the bytes."""
+    os.makedirs(out_dir, exist_ok=True)
+    b = m.export_blocks()
+    n, C = b["log_odds"].shape
+    budget = DUMP_BYTES // world - 8192 - n * (3 * 8 + 4)  # (npy headers; keys and flags of every block)
+    k = max(0, min(n, budget // (3 * C * 4 + 8)))
+    rows = np.arange(n) if k == n else np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+    arrays = {"block_keys": b["keys"].astype(np.float64), "block_collapsed": b["collapsed"].astype(np.float32),
+              "sample_rows": rows.astype(np.float64), "log_odds": b["log_odds"][rows].astype(np.float32),
+              "occ": b["occ"][rows].astype(np.float32), "infl": b["infl"][rows].astype(np.float32)}
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), np.ascontiguousarray(a))
+
+
 def launch_ranks(args) -> int:
     """`bench.py --gpus N` without a rank environment: start the N ranks as a child torch.distributed.run — this process
     has not touched the GPU (torch.cuda.device_count() does not initialise it) and only waits for the child."""
@@ -403,6 +437,8 @@ def launch_ranks(args) -> int:
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", args.dump_outputs]
     return subprocess.call(cmd, env=env, cwd=ROOT)
 
 
@@ -577,7 +613,14 @@ def main():
     ap.add_argument("--no-kernel-timing", action="store_true", help="do not record HIP events around the kernels")
     ap.add_argument("--no-extra", action="store_true", help="skip the short config-3 measurement and the latency rows")
     ap.add_argument("--cpu-budget", type=float, default=10.0)
+    ap.add_argument("--full", action="store_true", help="also measure what is not the headline: roofline (kernel events in the timed region), "
+                    "PCIe-inclusive rate, multi-GPU merge, config 3, latency rows, other scenes, CPU baseline and parity check")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the map the timed steps built (DIR/<name>.npy, float32 / float64, <= 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)  # (the ranks of --gpus N run in the repository root)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))  # (nothing above has touched the GPU)
@@ -636,7 +679,12 @@ def main():
         if dist is not None:
             dist.barrier()
 
-    res = measure_stream(m, cfg, d_frames, q, t, B, BPS, K, W, args.distinct, barrier, kernel_timing=not args.no_kernel_timing)
+    def dump():
+        if args.dump_outputs:
+            dump_outputs(m, args.dump_outputs, rank, world)
+
+    res = measure_stream(m, cfg, d_frames, q, t, B, BPS, K, W, args.distinct, barrier, kernel_timing=args.full and not args.no_kernel_timing,
+                         after_timed=dump)
     dt, stats = res["dt"], res["stats"]
     if os.environ.get("MLM_BENCH_STEP_TIMES"):  # diagnostic: host time of every step of the timed region
         print("step ms:", [round(float(x) * 1e3, 2) for x in res["step_dt"]], file=sys.stderr)
@@ -649,7 +697,7 @@ def main():
 
     # ---- config 4's exchange step: ONE global-map merge over the communicator after the streams (no reference counterpart)
     merge = None
-    if dist is not None:
+    if dist is not None and args.full:
         from mlmapping_amd.merge import merge_device_maps
 
         barrier()
@@ -673,22 +721,24 @@ def main():
                  "includes": "key union, mlm_merge_pack, all-to-all reduce-scatter, mlm_merge_finish, all-gather (no load-back)"}
         del merged
 
-    # PCIe-inclusive rate: the same batches handed over as HOST buffers (uploads overlap with compute); reported, never
-    # `value`
-    n_host = 16
-    host_batch = np.ascontiguousarray(frames[[b % args.distinct for b in range(B)]])
-    m.host_register(host_batch)  # (a replay tool pins its frame buffer once: DMA straight from it, mlm_host_register)
-    for s in range(4):  # the first host-buffer submission of every slot set allocates its image buffers
-        m.update_map_batch(host_batch, q[s * B:s * B + B], t[s * B:s * B + B])
-    m.sync()
-    th = time.perf_counter()
-    for s in range(n_host):
-        k0 = (s * B) % (n_total - B + 1)
-        m.update_map_batch(host_batch, q[k0:k0 + B], t[k0:k0 + B])
-    m.sync()
-    pcie_fps = n_host * B / (time.perf_counter() - th)
+    pcie_fps = None
+    if args.full:
+        # PCIe-inclusive rate: the same batches handed over as HOST buffers (uploads overlap with compute); reported, never
+        # `value`
+        n_host = 16
+        host_batch = np.ascontiguousarray(frames[[b % args.distinct for b in range(B)]])
+        m.host_register(host_batch)  # (a replay tool pins its frame buffer once: DMA straight from it, mlm_host_register)
+        for s in range(4):  # the first host-buffer submission of every slot set allocates its image buffers
+            m.update_map_batch(host_batch, q[s * B:s * B + B], t[s * B:s * B + B])
+        m.sync()
+        th = time.perf_counter()
+        for s in range(n_host):
+            k0 = (s * B) % (n_total - B + 1)
+            m.update_map_batch(host_batch, q[k0:k0 + B], t[k0:k0 + B])
+        m.sync()
+        pcie_fps = n_host * B / (time.perf_counter() - th)
+        m.host_unregister(host_batch)
     last_stats = m.frame_stats()
-    m.host_unregister(host_batch)
     m.close()
 
     if rank == 0:
@@ -696,37 +746,40 @@ def main():
         fps = world * K * F_STEP / dt
         step_p50 = float(np.median(res["step_dt"]))
         pmc, pmc_file, pmc_b, pmc_b_file = None, None, None, None
-        try:
-            f = newest_profile("pmc_traffic.json")
-            if f and args.workload == "cfg2":
-                pmc_file, pmc = os.path.basename(f), json.load(open(f))
-            f = newest_profile("pmc_traffic_batch.json" if args.workload == "cfg2" else "pmc_traffic_batch_cfg3.json")
-            if f:
-                pmc_b_file, pmc_b = os.path.basename(f), json.load(open(f))
-        except Exception:
-            pass
+        if args.full:
+            try:
+                f = newest_profile("pmc_traffic.json")
+                if f and args.workload == "cfg2":
+                    pmc_file, pmc = os.path.basename(f), json.load(open(f))
+                f = newest_profile("pmc_traffic_batch.json" if args.workload == "cfg2" else "pmc_traffic_batch_cfg3.json")
+                if f:
+                    pmc_b_file, pmc_b = os.path.basename(f), json.load(open(f))
+            except Exception:
+                pass
+        # (without --full no kernel was timed: roofline_of then only counts the algorithmic bytes of the timed frames)
         roof, mean_bytes = roofline_of(res, cfg, B, BPS, K, fps / world, pmc, pmc_file, pmc_b, pmc_b_file)
         out = {
             "metric": "depth frames/s into local map", "value": fps, "unit": "frames/s", "n_gpus": world,
             "steps": K, "warmup": W, "ms_per_step": dt / K * 1e3, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f64 index / f32 log-odds", "data": "synthetic",
             "config": {"workload": ("BASELINE cfg2: 640x480 room+jitter stream, random SE(3) poses, S1 0.1 m map"
-                                    if world == 1 else f"BASELINE cfg4: {world} independent cfg2 streams (pose seeds 42..{41 + world}), one per GPU, "
-                                                       "then one RCCL global-map merge (timed separately: merge)")
+                                    if world == 1 else f"BASELINE cfg4: {world} independent cfg2 streams (pose seeds 42..{41 + world}), one per GPU"
+                                                       + (", then one RCCL global-map merge (timed separately: merge)" if args.full else ""))
                        if args.workload == "cfg2" else "BASELINE cfg3: 1280x720 room+jitter stream, S3 0.05 m map",
                        "frames_per_step": F_STEP, "batch": B, "batches_per_step": BPS, "streams": world,
                        "parallelism": f"{world} independent streams"},
             "value_p50": world * F_STEP / step_p50, "ms_per_step_p50": step_p50 * 1e3,
             "ms_per_step_min_max": [float(res["step_dt"].min() * 1e3), float(res["step_dt"].max() * 1e3)],
             "achieved_hbm_gbs_whole_path": fps * mean_bytes / 1e9,
-            "pcie_inclusive_frames_per_s": pcie_fps * world,
             "path": {"sector_fallbacks": last_stats["n_sector_fallbacks"], "spec_replays": last_stats["n_spec_replays"],
                      "logit_bit_exact": last_stats["logit_bit_exact"]},
-            "roofline": roof,
         }
+        if args.full:
+            out["pcie_inclusive_frames_per_s"] = pcie_fps * world
+            out["roofline"] = roof
         if merge is not None:
             out["merge"] = merge
-        if world == 1 and args.workload == "cfg2" and not args.no_extra:
+        if args.full and world == 1 and args.workload == "cfg2" and not args.no_extra:
             # config 3 (1280x720, 0.05 m) in the same invocation: a short stream, same protocol (its own roofline; its CPU
             # baseline below)
             # (96 frame slots of 2 GB each: 190 GB of the 288 GB; a step = as many batches as there are slot sets, so that the host
@@ -773,7 +826,7 @@ def main():
             out["extra"]["other_scenes"] = other_scenes(MLMap, cfg, frames, q, t, d_frames, local_rank)
             if not args.no_cpu_baseline:
                 out["extra"]["cfg3"]["cpu_baseline"], _ = cpu_baseline(S3, "cfg3", f3, q3, t3, args.cpu_budget, None, min_frames=3, per_core=False)
-        if not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only
             def gpu_check(oracle_map, n):
                 """A fresh GPU handle fed the frames leg (i) integrated — submitted EXACTLY like the timed loop: asynchronous
                 B-frame contiguous device batches (mlm_integrate_depth_batch_dev) on a handle with max_batch = B and three slot

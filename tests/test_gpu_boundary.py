@@ -491,7 +491,8 @@ def test_bench_launcher_contract_two_ranks():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "8", "--batches-per-step", "2", "--no-cpu-baseline", "--no-extra"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "8", "--batches-per-step", "2", "--no-cpu-baseline", "--no-extra",
+           "--full"]  # (roofline and the merge leg: --full)
     if torch.cuda.device_count() < 2:
         r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode != 0 and "one rank per GPU" in r.stderr, (r.returncode, r.stderr[-500:])

@@ -1,6 +1,6 @@
 """The ROS wire schemas carried under msg/ must stay byte-identical to the reference's (msg/*.msg): a ROS message type
-is identified by the MD5 of its definition text.  The fixture hashes below were taken from /root/reference/msg in the
-authoring container (md5sum); when the reference tree is present the files are also compared byte for byte."""
+is identified by the MD5 of its definition text.  The fixture hashes below are md5sum of the reference's msg/*.msg, so a file
+that matches its hash is the reference's file byte for byte."""
 import hashlib
 import os
 
@@ -18,9 +18,6 @@ def test_msg_files_are_the_reference_schemas():
     for name, want in MD5.items():
         data = open(os.path.join(ROOT, "msg", name), "rb").read()
         assert hashlib.md5(data).hexdigest() == want, name
-        ref = os.path.join("/root/reference/msg", name)
-        if os.path.exists(ref):  # authoring container only; the GPU box has no reference tree
-            assert open(ref, "rb").read() == data, name
     assert sorted(f for f in os.listdir(os.path.join(ROOT, "msg")) if f.endswith(".msg")) == sorted(MD5)
 
 

@@ -1,5 +1,5 @@
 # usage: bash tools/prof_round.sh [tag] [sections]   (everything under gpurun_out/<tag>/; copy the summaries to profiles/<tag>_*)
-# sections (default "test bench times rows kt pmc sq"): test = pytest -m gpu; bench = bench.py; times = isolated kernel times;
+# sections (default "test bench times rows kt pmc sq"): test = pytest -m gpu; bench = bench.py --full; times = isolated kernel times;
 # (kt also traces a config-3 run, sq also runs tools/sq_cfg3.sh)
 # rows = the widened rows; kt = rocprofv3 kernel trace of bench.py; pmc = FETCH/WRITE passes over the batched path (cfg2 from a fresh
 # stream and in the steady state after eight warm-up batches, cfg3) and
@@ -14,7 +14,7 @@ O=$R/gpurun_out/$TAG
 python -c "import bench, json, subprocess; print(json.dumps({'tag': '$TAG', 'csrc_sha16': bench.csrc_sha16()}))" > $O/meta.json
 has() { case " $SEC " in *" $1 "*) return 0;; *) return 1;; esac; }
 if has test; then timeout 2400 python -m pytest tests -m gpu -x -q --durations=8 > $O/pytest.log 2>&1; echo "pytest rc=$?" >> $O/pytest.log; fi
-if has bench; then timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; fi
+if has bench; then timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; fi
 if has times; then
 timeout 300 python tools/kernel_times.py > $O/kernel_times.txt 2>&1
 timeout 300 python tools/kernel_times.py cfg3 4 > $O/kernel_times_cfg3.txt 2>&1
@@ -25,9 +25,9 @@ fi
 if has rows; then timeout 900 python tools/bench_rows.py > $O/rows.json 2> $O/rows.err; fi
 cd /tmp && export TMPDIR=/tmp
 if has kt; then
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 $R/bench.py --no-cpu-baseline --no-extra --steps 12 > $O/kt.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 $R/bench.py --full --no-cpu-baseline --no-extra --steps 12 > $O/kt.log 2>&1
 cp $(find $O/kt -name '*kernel_stats.csv' | head -1) $O/kernel_stats.csv; rm -rf $O/kt
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt3 -- python3 $R/bench.py --workload cfg3 --batch 32 --batches-per-step 3 --distinct 32 --no-cpu-baseline --no-extra --steps 12 > $O/kt3.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt3 -- python3 $R/bench.py --full --workload cfg3 --batch 32 --batches-per-step 3 --distinct 32 --no-cpu-baseline --no-extra --steps 12 > $O/kt3.log 2>&1
 cp $(find $O/kt3 -name '*kernel_stats.csv' | head -1) $O/kernel_stats_cfg3.csv; rm -rf $O/kt3
 fi
 if has pmc; then
