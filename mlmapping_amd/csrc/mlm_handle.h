@@ -27,7 +27,7 @@ struct KernelTime {
 const char *const kKnobNames[] = {"agg_lds", "big_arm", "big_grid", "bin_block", "chain_grid", "collect_grid", "cu_reserve", "cu_split",
                                   "debug_fail_slot", "ex_spec", "expand_block", "graph", "lean_slots", "logit_exact", "mirror", "mirror_max", "mirror_mb", "need_slots", "node_lds", "pool_grow",
                                   "rank_grid", "sc_block", "sc_grid", "sec_backoff", "sec_fail_every", "sec_tab", "sec_tab_big", "sec_threads",
-                                  "sectors", "single_chain_grid", "single_rank_grid", "slot_sets", "sort_block", "sort_grid", "tile_grid", "tile_sh"};
+                                  "sectors", "single_apply_grid", "single_chain_grid", "single_rank_grid", "slot_sets", "sort_block", "sort_grid", "tile_grid", "tile_sh"};
 struct KnobStore {
     std::mutex mu;
     std::unordered_map<std::string, long long> v;
@@ -35,6 +35,20 @@ struct KnobStore {
 KnobStore &knob_store() {
     static KnobStore k;
     return k;
+}
+// Values the kernels cannot run are refused by mlm_debug_set (MLM_ERR_INVALID) instead of being clamped or launched: the block sizes of
+// k_expand_nodes, k_sort_contribs and the per-frame apply kernels are whole waves (their lanes work in groups of 64: lane =
+// threadIdx.x & 63, wave = threadIdx.x >> 6) and at most MLM_BLOCK (__launch_bounds__); k_bin_points has three instantiations of its
+// tile; a grid has one workgroup at least (and at most 2^20: a launch multiplies some of them by up to four).  (cu_split / cu_reserve are checked by mlm_create, which knows the CU count.)
+bool knob_value_ok(const char *name, long long v) {
+    auto is = [&](const char *k) { return strcmp(name, k) == 0; };
+    if (is("expand_block") || is("sort_block") || is("sc_block")) return v >= 64 && v <= 256 && v % 64 == 0;
+    if (is("bin_block")) return v == 256 || v == 512 || v == 1024;
+    if (is("big_grid") || is("chain_grid") || is("collect_grid") || is("rank_grid") || is("sc_grid") || is("single_apply_grid") ||
+        is("single_chain_grid") || is("single_rank_grid") || is("sort_grid") || is("tile_grid"))
+        return v >= 1 && v <= (1ll << 20);
+    if (is("cu_split") || is("cu_reserve")) return v >= 0 && v <= 0x7FFFFFFFll;
+    return true;
 }
 bool knob(const char *name, long long &out) {
     KnobStore &k = knob_store();

@@ -47,6 +47,7 @@ int mlm_debug_set(const char *name, long long value) {
     bool known = false;
     for (const char *k : kKnobNames) known = known || strcmp(k, name) == 0;
     if (!known) return MLM_ERR_INVALID;
+    if (!knob_value_ok(name, value)) return MLM_ERR_INVALID;
     KnobStore &k = knob_store();
     std::lock_guard<std::mutex> lock(k.mu);
     k.v[name] = value;
@@ -143,14 +144,14 @@ int mlm_create(const mlm_config *cfg, const mlm_limits *lim_in, int device, mlm_
         // leaves the rest to Stage A, so that the chain is not stretched by queueing behind Stage A's waves.
         int lo = 0, hi = 0; // numerically lower = higher priority
         HIPCHK(h, hipDeviceGetStreamPriorityRange(&lo, &hi));
-        if (knob("expand_block", kv)) h->expand_block = (unsigned int)std::max(64, (int)kv);
-        if (knob("sort_block", kv)) h->sort_block = (unsigned int)std::min(256, std::max(64, (int)kv));
+        if (knob("expand_block", kv)) h->expand_block = (unsigned int)kv; // (whole waves in [64, 256]: knob_value_ok)
+        if (knob("sort_block", kv)) h->sort_block = (unsigned int)kv;
         if (knob("sort_grid", kv)) h->sort_grid = (unsigned int)std::max(1, (int)kv);
         if (knob("chain_grid", kv)) h->chain_grid = (unsigned int)std::max(1, (int)kv);
         if (knob("rank_grid", kv)) h->rank_grid = (unsigned int)std::max(1, (int)kv);
         else if ((long long)cfg->am_n_rho * cfg->am_n_z_below > 4000) h->rank_grid = 384; // (fine maps order a hundred thousand cells per frame: config 3 128 blocks 33.0 us, 256: 31.0, 512: 29.2)
         if (knob("collect_grid", kv)) h->collect_grid = (unsigned int)std::max(1, (int)kv);
-        if (knob("sc_block", kv)) h->sc_block = (unsigned int)std::min(256, std::max(64, (int)kv));
+        if (knob("sc_block", kv)) h->sc_block = (unsigned int)kv;
         if (knob("sc_grid", kv)) {
             h->sc_grid = (unsigned int)std::max(1, (int)kv);
             h->sc_grid_fixed = true;
@@ -161,7 +162,11 @@ int mlm_create(const mlm_config *cfg, const mlm_limits *lim_in, int device, mlm_
         hipDeviceProp_t prop;
         HIPCHK(h, hipGetDeviceProperties(&prop, device));
         const int ncu = prop.multiProcessorCount;
-        if (h->cu_split > 0 && h->cu_split < ncu) {
+        if (std::max(h->cu_split, h->cu_reserve) >= ncu) { // (Stage A's streams would get an empty CU mask: nothing of theirs could run)
+            h->err = "knobs cu_split / cu_reserve must leave Stage A at least one of the device's " + std::to_string(ncu) + " CUs";
+            return MLM_ERR_INVALID;
+        }
+        if (h->cu_split > 0) {
             std::vector<uint32_t> mask((size_t)(ncu + 31) / 32, 0u);
             for (int c = 0; c < h->cu_split; ++c) mask[(size_t)c / 32] |= 1u << (c % 32);
             HIPCHK(h, hipExtStreamCreateWithCUMask(&h->stream, (uint32_t)mask.size(), mask.data()));
@@ -457,6 +462,7 @@ int mlm_create(const mlm_config *cfg, const mlm_limits *lim_in, int device, mlm_
         if (knob("ex_spec", kv)) h->ex_spec = (int)kv;
         if (knob("single_chain_grid", kv)) h->single_chain_grid = (unsigned int)std::max(1, (int)kv);
         if (knob("single_rank_grid", kv)) h->single_rank_grid = (unsigned int)std::max(1, (int)kv);
+        if (knob("single_apply_grid", kv)) h->single_apply_grid = (unsigned int)std::max(1, (int)kv);
         if (knob("mirror", kv)) h->mir.enabled = (int)kv != 0;
         if (knob("mirror_mb", kv)) h->mir.max_bytes = (size_t)std::max(0, (int)kv) << 20;
         if (knob("mirror_max", kv)) h->mir.max_clean = std::max(0, (int)kv), h->mir.max_dirty = std::min(h->mir.max_dirty, h->mir.max_clean);

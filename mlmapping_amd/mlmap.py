@@ -153,7 +153,7 @@ def load_library(path: Optional[str] = None):
         for kv in os.environ["MLM_KNOBS"].split(","):
             k, _, v = kv.partition("=")
             if k.strip() and L.mlm_debug_set(k.strip().encode(), int(v)) != MLM_OK:
-                raise MlmError(f"MLM_KNOBS: unknown knob {k.strip()!r}")
+                raise MlmError(f"MLM_KNOBS: unknown knob {k.strip()!r} or a value the kernels cannot run: {v}")
     if path is None:
         _lib = L
     return L
@@ -170,7 +170,7 @@ def _f64(a) -> np.ndarray:
 def debug_set(name: str, value: int):
     """Test / experiment knob read by the next mlm_create of this process (mlm_debug_set; not part of the drop-in contract)."""
     if load_library().mlm_debug_set(name.encode(), int(value)) != MLM_OK:
-        raise MlmError(f"mlm_debug_set: unknown knob {name!r}")
+        raise MlmError(f"mlm_debug_set: unknown knob {name!r} or a value the kernels cannot run: {value}")
 
 
 def debug_reset():

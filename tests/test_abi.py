@@ -60,3 +60,37 @@ def test_facade_compiles(tmp_path):
     src = tmp_path / "t.cpp"
     src.write_text('#include "mlmap_facade.hpp"\nint main(){ mlmap_hip::mlmap m; (void)m; return 0; }\n')
     subprocess.check_call(["g++", "-std=c++17", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(src)])
+
+
+def test_knob_values_the_kernels_cannot_run_are_refused():
+    """mlm_debug_set refuses launch geometries no kernel can run (MLM_ERR_INVALID) and accepts the ones they can: block sizes of whole
+    waves up to __launch_bounds__(256) (k_expand_nodes / k_sort_contribs take lane = threadIdx.x & 63, wave = threadIdx.x >> 6),
+    the three tiles of k_bin_points, grids of one workgroup or more.  Host only: nothing here is launched."""
+    from mlmapping_amd.mlmap import MLM_OK, load_library
+    from tests.util import BLOCK_KNOBS, GRID_KNOBS
+
+    L = load_library()
+    ERR_INVALID = -1
+    try:
+        for name in BLOCK_KNOBS:
+            for v in (64, 128, 192, 256):
+                assert L.mlm_debug_set(name.encode(), v) == MLM_OK, (name, v)
+            for v in (-64, 0, 1, 32, 63, 65, 96, 100, 160, 255, 257, 320, 512, 1024, 1 << 40):
+                assert L.mlm_debug_set(name.encode(), v) == ERR_INVALID, (name, v)
+        for v in (256, 512, 1024):
+            assert L.mlm_debug_set(b"bin_block", v) == MLM_OK, v
+        for v in (-256, 0, 1, 64, 128, 255, 257, 384, 511, 768, 1023, 1025, 2048):
+            assert L.mlm_debug_set(b"bin_block", v) == ERR_INVALID, v
+        for name in GRID_KNOBS:
+            for v in (1, 2, 3, 7, 13, 256, 4096, 1 << 20):
+                assert L.mlm_debug_set(name.encode(), v) == MLM_OK, (name, v)
+            for v in (0, -1, -256, (1 << 20) + 1, 1 << 31, 1 << 40):
+                assert L.mlm_debug_set(name.encode(), v) == ERR_INVALID, (name, v)
+        for name in ("cu_split", "cu_reserve"):  # (the upper bound is the CU count: mlm_create checks it, tests/test_gpu_geometry.py)
+            for v in (0, 8, 16, 255):
+                assert L.mlm_debug_set(name.encode(), v) == MLM_OK, (name, v)
+            for v in (-1, -16, 1 << 40):
+                assert L.mlm_debug_set(name.encode(), v) == ERR_INVALID, (name, v)
+        assert L.mlm_debug_set(b"no_such_grid", 1) == ERR_INVALID  # (names outside kKnobNames: refused whatever the value)
+    finally:
+        L.mlm_debug_reset()

@@ -1,7 +1,8 @@
 """Fuzz of the RECOVERY paths: the random map geometries of test_random_configurations (tests/util.py fuzz_trial) on handles whose
 limits and knobs force what a camera stream rarely does — column tables too small for the scene (large-table pass, its arming and
 the redo at drain), forced sector fall-backs every 2nd / 3rd frame, a pool of 16 blocks and lists sized for a quarter of the frame
-(growth of pool and slots while frames are in flight), no graph — fed frame by frame, in batches, synchronously and asynchronously.
+(growth of pool and slots while frames are in flight), no graph, launch geometries far from the defaults (tests/util.py
+draw_geometry: grids of one workgroup, odd block sizes, CU masks) — fed frame by frame, in batches, synchronously and asynchronously.
 Every combination must leave the oracle's map, bit for bit.  (Fuzz seed 4242 found a rerun of Stage A counting a column's points
 twice exactly where two of these paths met: test_gpu_slots.py::test_rerun_with_a_column_waiting_for_the_large_table.)
 MLM_RFUZZ_SEED / MLM_RFUZZ_TRIALS: other or longer runs."""
@@ -11,7 +12,7 @@ import numpy as np
 import pytest
 
 from mlmapping_amd import synthetic as syn
-from tests.util import compare_maps, fuzz_trial
+from tests.util import compare_maps, draw_geometry, fuzz_trial
 
 pytestmark = pytest.mark.gpu
 
@@ -37,6 +38,7 @@ def _recovery_fuzz(knobs, seed, trials, expect_all_paths, only_trial=None):
     rng = np.random.default_rng(seed)
     krng = np.random.default_rng(seed + 1)  # (limits, knobs and call pattern: a stream of its own, so the inputs are fuzz_trial's)
     srng = np.random.default_rng(seed + 2)  # (which frame-by-frame trials integrate pixel lists: small frames start without the prologue kernel)
+    grng = np.random.default_rng(seed + 3)  # (launch geometry: grids, block sizes, CU masks — a stream of its own, so the draws above stay)
     seen = {"n_sector_fallbacks": 0, "n_slot_grows": 0, "n_pool_grows": 0, "n_spec_replays": 0}
     for trial in range(trials):
         cfg, depths, pos = fuzz_trial(rng, trial)
@@ -59,6 +61,7 @@ def _recovery_fuzz(knobs, seed, trials, expect_all_paths, only_trial=None):
         max_points = int(krng.choice([320 * 240, 320 * 240, 4 * 320 * 240]))
         max_batch = int(krng.choice([1, 2, 3, 4]))
         pattern = str(krng.choice(["single", "single_async", "batch", "batch_async", "twice"]))
+        geo = draw_geometry(grng)
         if only_trial is not None and trial != only_trial:  # (a replay of one trial: the others only take their draws)
             if not (pattern.startswith("batch") and max_batch >= 2):
                 small = srng.random() < 0.3
@@ -66,9 +69,9 @@ def _recovery_fuzz(knobs, seed, trials, expect_all_paths, only_trial=None):
                     if small and k != 1:
                         srng.integers(0, depths[0].size, int(srng.choice([300, 1500, 4000])))
             continue
-        for name, v in kn.items():
+        for name, v in {**kn, **geo}.items():
             knobs.set(name, v)
-        what = f"recovery fuzz seed {seed} trial {trial}: knobs {kn} max_blocks {max_blocks} max_points {max_points} max_batch {max_batch} {pattern} cfg {cfg}"
+        what = f"recovery fuzz seed {seed} trial {trial}: knobs {kn} geometry {geo} max_blocks {max_blocks} max_points {max_points} max_batch {max_batch} {pattern} cfg {cfg}"
         gpu, cpu = MLMap(cfg, max_blocks=max_blocks, max_points=max_points, max_batch=max_batch), OracleMap(cfg)
         from mlmapping_amd import mlmap
 

@@ -80,3 +80,28 @@ def fuzz_trial(rng, trial: int):
         depths.append(depth)
     pos = rng.uniform(-8, 8, size=(20000, 3))
     return cfg, depths, pos
+
+
+# launch-geometry knobs of the library (mlm_debug_set; mlmapping_amd/csrc/mlm_handle.h kKnobNames) and their defaults on the maps the
+# tests use — chain_grid 0: adapts to the last frame's cells; tile_grid: the handle's own choice per map
+GRID_KNOBS = {"big_grid": 256, "chain_grid": 0, "collect_grid": 16, "rank_grid": 128, "sc_grid": 80, "single_apply_grid": 256,
+              "single_chain_grid": 64, "single_rank_grid": 256, "sort_grid": 256, "tile_grid": 0}
+BLOCK_KNOBS = ("expand_block", "sort_block", "sc_block")  # whole waves, 64 .. 256
+
+
+def draw_geometry(rng) -> dict:
+    """Launch geometry for a fuzz trial, drawn from `rng` (a fixed number of draws whatever comes out, so a replay of trial k sees
+    the draws of a full run): most trials keep the defaults; the others get some grids of 1 to 13 workgroups or a few times the default,
+    block sizes of whole waves, CU masks."""
+    use = rng.random() < 0.4
+    grids = {k: int(rng.choice([1, 2, 3, 7, 13, 3 * max(d, 64)])) for k, d in GRID_KNOBS.items()}
+    pick_g = rng.random(len(grids)) < 0.4
+    blocks = {k: int(rng.choice([64, 128, 192, 256])) for k in BLOCK_KNOBS}
+    pick_b = rng.random(len(blocks)) < 0.4
+    cu = {"cu_split": int(rng.choice([0, 8])), "cu_reserve": int(rng.choice([0, 16]))}
+    if not use:
+        return {}
+    g = {k: v for (k, v), p in zip(grids.items(), pick_g) if p}
+    g.update({k: v for (k, v), p in zip(blocks.items(), pick_b) if p})
+    g.update({k: v for k, v in cu.items() if v})
+    return g
