@@ -137,6 +137,9 @@ struct mlm_handle {
     double *d_qpos = nullptr; // query positions
     void *d_qout = nullptr;
     size_t q_cap = 0;
+    // mlm_export_window: odds of the haloed tile (gradients) and the staging of host destinations, kept and enlarged by need
+    void *d_win_scratch = nullptr, *d_win_stage = nullptr;
+    size_t win_scratch_bytes = 0, win_stage_bytes = 0;
     // sort buffers (rehash frames only)
     unsigned long long *sk_in = nullptr, *sk_out = nullptr;
     uint32_t *sv_in = nullptr, *sv_out = nullptr;

@@ -1748,6 +1748,51 @@ __device__ __forceinline__ void mlm_neighbor(const MlmDev &P, int dir, int &gx, 
     cid = cz * P.n * P.n + cy * P.n + cx;
 }
 
+// The walk of getOddGrad (mlmap.h:237-295) from voxel (g, cid) whose odds are ori_odd, (x, y, z) the query position.  odd(gx, gy, gz,
+// cid, dir, step) answers the odds of the neighbour `step` voxels away in direction `dir` (order +z,-z,+y,-y,+x,-x), i.e. getOdd of
+// (gx, gy, gz, cid): k_query looks every neighbour up, k_window_grad reads most of them from a dense array.  The first iteration
+// that finds a strictly lower neighbour ends the walk after its six directions; the last lower one of that iteration wins.
+template <class Odd>
+__device__ __forceinline__ void mlm_odd_grad_walk(const MlmDev &P, int gx, int gy, int gz, int cid, double x, double y, double z,
+                                                  int max_iter, float ori_odd, Odd &&odd, double &rx, double &ry, double &rz) {
+    float min_odd = ori_odd;
+    int ngx[6], ngy[6], ngz[6], ncid[6];
+    int mgx = 0, mgy = 0, mgz = 0, mcid = 0;
+    bool flag = false;
+    for (int iter = 0; iter < max_iter && !flag; ++iter) {
+#pragma unroll // (the six neighbours stay in registers)
+        for (int d = 0; d < 6; ++d) {
+            if (iter == 0) {
+                ngx[d] = gx;
+                ngy[d] = gy;
+                ngz[d] = gz;
+                ncid[d] = cid;
+            }
+            mlm_neighbor(P, d, ngx[d], ngy[d], ngz[d], ncid[d]);
+            const float tmp = odd(ngx[d], ngy[d], ngz[d], ncid[d], d, iter + 1);
+            if (tmp < min_odd) {
+                min_odd = tmp;
+                mgx = ngx[d];
+                mgy = ngy[d];
+                mgz = ngz[d];
+                mcid = ncid[d];
+                flag = true;
+            }
+        }
+    }
+    rx = ry = rz = 0.0;
+    if (flag) {
+        // subbox_id2xyz_glb_vec, map_local.h:208-213
+        const int cz = mcid / (P.n * P.n);
+        const int cy = (mcid - cz * P.n * P.n) / P.n;
+        const int cx = mcid - cz * P.n * P.n - cy * P.n;
+        const double s = (double)(ori_odd - min_odd);
+        rx = ((mgx * P.d_glb + cx * P.d_sub + P.d_sub_half) - x) * s;
+        ry = ((mgy * P.d_glb + cy * P.d_sub + P.d_sub_half) - y) * s;
+        rz = ((mgz * P.d_glb + cz * P.d_sub + P.d_sub_half) - z) * s;
+    }
+}
+
 // mode 0: getOccupancy  1: getOccupancy(pos, inflate)  2: getInflateOccupancy  3: getOdd  4: getOddGrad
 __global__ __launch_bounds__(MLM_BLOCK) void k_query(const MlmDev P, int mode, const double *pos, int n, float inflate,
                                                      int max_iter, int8_t *out_i8, float *out_f, double *out_d3) {
@@ -1788,42 +1833,9 @@ __global__ __launch_bounds__(MLM_BLOCK) void k_query(const MlmDev P, int mode, c
         // getOddGrad, mlmap.h:237-295
         int gx, gy, gz, cid;
         mlm_voxel_of(P, x, y, z, gx, gy, gz, cid);
-        float min_odd = mlm_get_odd_at(P, gx, gy, gz, cid);
-        const float ori_odd = min_odd;
-        int ngx[6], ngy[6], ngz[6], ncid[6];
-        int mgx = 0, mgy = 0, mgz = 0, mcid = 0;
-        bool flag = false;
-        for (int iter = 0; iter < max_iter && !flag; ++iter) {
-            for (int d = 0; d < 6; ++d) {
-                if (iter == 0) {
-                    ngx[d] = gx;
-                    ngy[d] = gy;
-                    ngz[d] = gz;
-                    ncid[d] = cid;
-                }
-                mlm_neighbor(P, d, ngx[d], ngy[d], ngz[d], ncid[d]);
-                const float tmp = mlm_get_odd_at(P, ngx[d], ngy[d], ngz[d], ncid[d]);
-                if (tmp < min_odd) {
-                    min_odd = tmp;
-                    mgx = ngx[d];
-                    mgy = ngy[d];
-                    mgz = ngz[d];
-                    mcid = ncid[d];
-                    flag = true;
-                }
-            }
-        }
-        double rx = 0.0, ry = 0.0, rz = 0.0;
-        if (flag) {
-            // subbox_id2xyz_glb_vec, map_local.h:208-213
-            const int cz = mcid / (P.n * P.n);
-            const int cy = (mcid - cz * P.n * P.n) / P.n;
-            const int cx = mcid - cz * P.n * P.n - cy * P.n;
-            const double s = (double)(ori_odd - min_odd);
-            rx = ((mgx * P.d_glb + cx * P.d_sub + P.d_sub_half) - x) * s;
-            ry = ((mgy * P.d_glb + cy * P.d_sub + P.d_sub_half) - y) * s;
-            rz = ((mgz * P.d_glb + cz * P.d_sub + P.d_sub_half) - z) * s;
-        }
+        double rx, ry, rz;
+        mlm_odd_grad_walk(P, gx, gy, gz, cid, x, y, z, max_iter, mlm_get_odd_at(P, gx, gy, gz, cid),
+                          [&](int ngx, int ngy, int ngz, int ncid, int, int) { return mlm_get_odd_at(P, ngx, ngy, ngz, ncid); }, rx, ry, rz);
         out_d3[3 * (size_t)i] = rx;
         out_d3[3 * (size_t)i + 1] = ry;
         out_d3[3 * (size_t)i + 2] = rz;

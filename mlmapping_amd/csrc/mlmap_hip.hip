@@ -28,6 +28,7 @@
 #include "../../include/mlmap_hip.h"
 #include "mlm_kernels_explore.h"
 #include "mlm_kernels_sector.h"
+#include "mlm_kernels_window.h"
 #include "mlm_host.h"
 #include "mlm_mapview.h"
 
@@ -1085,6 +1086,155 @@ int mlm_export_blocks(mlm_handle *h, int cap, int32_t *keys, float *log_odds, ui
     if (log_odds) HIPCHK(h, hipMemcpyAsync(log_odds, h->P.log_odds, m * C * sizeof(float), hipMemcpyDefault, h->stream));
     if (occ) HIPCHK(h, hipMemcpyAsync(occ, h->P.occ, m * C, hipMemcpyDefault, h->stream));
     if (infl) HIPCHK(h, hipMemcpyAsync(infl, h->P.infl, m * C, hipMemcpyDefault, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MLM_OK;
+}
+
+namespace {
+// mlm_export_window's tiles (mlm_kernels_window.h): the haloed tile's odds take at most kWinBoxVoxels floats (128 MB), a tile staged
+// for host destinations at most kWinStageVoxels voxels (<= 30 bytes each)
+constexpr long long kWinBoxVoxels = 1ll << 25;
+constexpr long long kWinStageVoxels = 1ll << 22;
+constexpr unsigned int kWinFillGrid = 2048, kWinGradGrid = 8192;
+
+// device memory this device's kernels write in place; anything else (pageable, pinned or managed host memory) is staged
+bool win_in_place(const void *p) {
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError(); // (pageable host memory is unknown to the runtime)
+        return false;
+    }
+    return a.type == hipMemoryTypeDevice;
+}
+
+// a kept buffer of at least `bytes`; a failed allocation leaves the handle as it was, minus the old buffer
+int win_reserve(mlm_handle *h, void *&p, size_t &cap, size_t bytes) {
+    if (bytes <= cap) return MLM_OK;
+    dev_free(h, p, cap);
+    p = nullptr;
+    cap = 0;
+    void *v = nullptr;
+    if (hipMalloc(&v, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        h->err = "mlm_export_window: no device memory for " + std::to_string(bytes >> 20) + " MB of scratch";
+        return MLM_ERR_CAPACITY;
+    }
+    h->alloc_bytes += bytes;
+    h->allocs.push_back(v);
+    p = v;
+    cap = bytes;
+    return MLM_OK;
+}
+} // namespace
+
+int mlm_export_window(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], int max_iter, float *odds, int8_t *occ, int8_t *infl,
+                      double *grad3) {
+    if (!h) return MLM_ERR_INVALID;
+    MLM_LOCK(h);
+    if (!lo || !dims || max_iter < 0 || (!odds && !occ && !infl && !grad3)) {
+        h->err = "mlm_export_window: null window, negative max_iter or no output";
+        return MLM_ERR_INVALID;
+    }
+    long long D[3], nvox = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (dims[a] < 1 || (long long)lo[a] + dims[a] > 0x7FFFFFFFll) {
+            h->err = "mlm_export_window: dims must be >= 1 and lo + dims must fit an int32";
+            return MLM_ERR_INVALID;
+        }
+        D[a] = dims[a];
+        nvox *= D[a];
+        if (nvox > 0x7FFFFFFFll) {
+            h->err = "mlm_export_window: more than 2^31 - 1 voxels";
+            return MLM_ERR_INVALID;
+        }
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = drain(h);
+    if (rc) return rc;
+
+    // channels: destination, element size, written in place or staged
+    void *dst[4] = {odds, occ, infl, grad3};
+    const size_t elem[4] = {sizeof(float), 1, 1, 3 * sizeof(double)};
+    bool staged[4];
+    bool any_staged = false;
+    for (int c = 0; c < 4; ++c) {
+        staged[c] = dst[c] && !win_in_place(dst[c]);
+        any_staged |= staged[c];
+    }
+    // tile dims: whole planes if one fits, else rows of one plane, else pieces of one row — every tile's output is a contiguous range
+    // of the window's layout
+    const long long H = grad3 ? std::min(max_iter, MLM_WIN_HALO) : 0;
+    const long long box_cap = grad3 ? kWinBoxVoxels : (1ll << 62), out_cap = any_staged ? kWinStageVoxels : (1ll << 62);
+    auto fits = [&](long long tx, long long ty, long long tz) { return (tx + 2 * H) * (ty + 2 * H) * (tz + 2 * H) <= box_cap && tx * ty * tz <= out_cap; };
+    long long T[3];
+    if (fits(D[0], D[1], 1)) {
+        T[0] = D[0];
+        T[1] = D[1];
+        T[2] = std::min({D[2], box_cap / ((D[0] + 2 * H) * (D[1] + 2 * H)) - 2 * H, out_cap / (D[0] * D[1])});
+    } else if (fits(D[0], 1, 1)) {
+        T[0] = D[0];
+        T[1] = std::min({D[1], box_cap / ((D[0] + 2 * H) * (1 + 2 * H)) - 2 * H, out_cap / D[0]});
+        T[2] = 1;
+    } else {
+        T[0] = std::min({D[0], box_cap / ((1 + 2 * H) * (1 + 2 * H)) - 2 * H, out_cap});
+        T[1] = T[2] = 1;
+    }
+    const long long tile_vox = T[0] * T[1] * T[2];
+    size_t stage_off[4] = {0, 0, 0, 0}, stage_bytes = 0;
+    for (int c = 0; c < 4; ++c)
+        if (staged[c]) {
+            stage_off[c] = stage_bytes;
+            stage_bytes += ((size_t)tile_vox * elem[c] + 255) & ~(size_t)255;
+        }
+    if (grad3 && (rc = win_reserve(h, h->d_win_scratch, h->win_scratch_bytes,
+                                   (size_t)((T[0] + 2 * H) * (T[1] + 2 * H) * (T[2] + 2 * H)) * sizeof(float))))
+        return rc;
+    if (stage_bytes && (rc = win_reserve(h, h->d_win_stage, h->win_stage_bytes, stage_bytes))) return rc;
+
+    const int n = h->P.n;
+    auto floor_div = [n](long long v) { return v >= 0 ? v / n : -((-v + n - 1) / n); };
+    for (long long z0 = 0; z0 < D[2]; z0 += T[2])
+        for (long long y0 = 0; y0 < D[1]; y0 += T[1])
+            for (long long x0 = 0; x0 < D[0]; x0 += T[0]) {
+                MlmWin W{};
+                const long long org[3] = {x0, y0, z0};
+                for (int a = 0; a < 3; ++a) {
+                    W.wlo[a] = lo[a];
+                    W.wd[a] = dims[a];
+                    W.tlo[a] = lo[a] + org[a];
+                    W.td[a] = (int)std::min(T[a], D[a] - org[a]);
+                    W.hlo[a] = W.tlo[a] - H;
+                    W.hd[a] = W.td[a] + (int)(2 * H);
+                    W.b0[a] = floor_div(W.hlo[a]);
+                    W.nb[a] = (int)(floor_div(W.hlo[a] + W.hd[a] - 1) - W.b0[a] + 1);
+                }
+                // (every channel pointer is where the tile's first voxel goes: out_base is the tile's index in the window)
+                W.out_base = (z0 * D[1] + y0) * D[0] + x0;
+                void *ch[4];
+                for (int c = 0; c < 4; ++c)
+                    ch[c] = !dst[c] ? nullptr
+                                    : staged[c] ? (void *)((char *)h->d_win_stage + stage_off[c])
+                                                : (void *)((char *)dst[c] + (size_t)W.out_base * elem[c]);
+                W.odds = (float *)ch[0];
+                W.occ = (int8_t *)ch[1];
+                W.infl = (int8_t *)ch[2];
+                W.grad = (double *)ch[3];
+                W.scratch = grad3 ? (float *)h->d_win_scratch : nullptr;
+                W.halo = (int)H;
+                W.max_iter = max_iter;
+                const long long n_bricks = (long long)W.nb[0] * W.nb[1] * W.nb[2];
+                hipLaunchKernelGGL(k_window_fill, dim3((unsigned int)std::min<long long>(n_bricks, kWinFillGrid)), dim3(MLM_BLOCK), 0, h->stream,
+                                   h->P, W);
+                const long long nt = (long long)W.td[0] * W.td[1] * W.td[2];
+                if (grad3)
+                    hipLaunchKernelGGL(k_window_grad, dim3(std::min<unsigned int>(grid_for((size_t)nt), kWinGradGrid)), dim3(MLM_BLOCK), 0,
+                                       h->stream, h->P, W);
+                HIPCHK(h, hipGetLastError());
+                for (int c = 0; c < 4; ++c)
+                    if (staged[c])
+                        HIPCHK(h, hipMemcpyAsync((char *)dst[c] + (size_t)W.out_base * elem[c], ch[c], (size_t)nt * elem[c], hipMemcpyDefault,
+                                                 h->stream));
+            }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MLM_OK;
 }

@@ -35,7 +35,7 @@ ABI_SYMBOLS = [
     "mlm_query_odds", "mlm_query_odd_grad", "mlm_query_odds_at", "mlm_export_frontier_points", "mlm_import_blocks",
     "mlm_merge_pack", "mlm_merge_finish",
     "mlm_set_free_in_bound", "mlm_inflate_map", "mlm_block_count",
-    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
+    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
     "mlm_get_awareness_hits",
     "mlm_get_awareness_misses", "mlm_get_T_ls", "mlm_get_odds_table", "mlm_get_kernel_times",
     "mlm_enable_kernel_timing", "mlm_set_timed_kernel", "mlm_host_register", "mlm_host_unregister", "mlm_debug_set", "mlm_debug_reset",
@@ -128,6 +128,7 @@ def load_library(path: Optional[str] = None):
     L.mlm_inflate_map.argtypes = [vp, vp]
     L.mlm_block_count.argtypes = [vp, vp]
     L.mlm_export_blocks.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    L.mlm_export_window.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
     L.mlm_export_global_map.argtypes = [vp, i32, vp, vp]
     L.mlm_export_block_flags.argtypes = [vp, i32, vp, vp]
     L.mlm_export_frontier.argtypes = [vp, i32, vp, vp]
@@ -414,6 +415,39 @@ class MLMap:
         holds = [ptr(log_odds, np.float32), ptr(occ, np.uint8), ptr(infl, np.uint8), ptr(collapsed, np.uint8)]
         self._chk(self._L.mlm_import_blocks(self._h, n, kp, holds[0][0], holds[1][0], holds[2][0], holds[3][0]),
                   "mlm_import_blocks")
+
+    def export_window(self, lo, dims, odds=True, occ=False, infl=False, grad=False, max_iter: int = 5) -> Dict[str, np.ndarray]:
+        """Dense read-out of the voxel box lo <= v < lo + dims (voxel indices v = block key * subbox_n + cell coordinate, per axis
+        (x, y, z)): {"odds": float32, "occ": int8, "infl": int8 shaped (dz, dy, dx), "grad": float64 (dz, dy, dx, 3)} for the
+        channels asked for — getOdd / getOccupancy / getInflateOccupancy / getOddGrad(max_iter) at every voxel (mlm_export_window)."""
+        lo_a, dims_a = self._window_args(lo, dims)
+        shape = (int(dims_a[2]), int(dims_a[1]), int(dims_a[0]))
+        out = {}
+        if odds:
+            out["odds"] = np.empty(shape, dtype=np.float32)
+        if occ:
+            out["occ"] = np.empty(shape, dtype=np.int8)
+        if infl:
+            out["infl"] = np.empty(shape, dtype=np.int8)
+        if grad:
+            out["grad"] = np.empty(shape + (3,), dtype=np.float64)
+        ptr = [_p(out[k]) if k in out else None for k in ("odds", "occ", "infl", "grad")]
+        self._chk(self._L.mlm_export_window(self._h, _p(lo_a), _p(dims_a), int(max_iter), *ptr), "mlm_export_window")
+        return out
+
+    def export_window_dev(self, lo, dims, max_iter: int = 5, odds: Optional[int] = None, occ: Optional[int] = None,
+                          infl: Optional[int] = None, grad: Optional[int] = None):
+        """Same into device memory: pointers (ints) to dz*dy*dx float32 / int8 / int8 / (x3) float64 elements, None = skipped."""
+        lo_a, dims_a = self._window_args(lo, dims)
+        ptr = [None if v is None else ctypes.c_void_p(v) for v in (odds, occ, infl, grad)]
+        self._chk(self._L.mlm_export_window(self._h, _p(lo_a), _p(dims_a), int(max_iter), *ptr), "mlm_export_window")
+
+    @staticmethod
+    def _window_args(lo, dims):
+        lo_a, dims_a = np.asarray(lo, dtype=np.int64).reshape(3), np.asarray(dims, dtype=np.int64).reshape(3)
+        if ((lo_a < -2 ** 31) | (lo_a >= 2 ** 31) | (dims_a < 1) | (dims_a >= 2 ** 31)).any():
+            raise MlmError("export_window: lo and dims are int32, dims >= 1")
+        return lo_a.astype(np.int32), dims_a.astype(np.int32)
 
     def export_block_keys_dev(self, keys_dev_ptr: int, cap: int) -> int:
         """Block keys straight into device memory ([cap,3] int32); returns the block count."""
