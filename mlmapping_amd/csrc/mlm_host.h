@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
+#include <cstdint>
 #include <unordered_map>
 #include <utility>
 #include <vector>
@@ -90,6 +91,22 @@ MLM_HD inline float mlm_glibc_log10f(float x) {
     const float xm = __builtin_bit_cast(float, hx);
     const float z = y * log10_2lo + ivln10 * mlm_glibc_logf_core(xm);
     return z + y * log10_2hi;
+}
+
+// Dynamic LDS of k_apply_tiles for a tile of edge x edge columns of nz layers, blocks of n^3 voxels (byte offsets):
+// per voxel its log-odds (f32) and class (u8, 0: not fetched yet); per layer the block index and cell coordinate (u32); per
+// block the tile overlaps the pool address of its cell 0 (u32).  mlm_create sizes the kernel for nz = two grid heights.
+struct MlmApplyLds {
+    uint32_t occ, ztab, blk, total;
+};
+MLM_HD inline MlmApplyLds mlm_apply_lds(uint32_t edge, uint32_t nz, uint32_t n) {
+    const uint32_t nv = edge * edge * nz, cx = (edge - 1u) / n + 2u, cz = (nz - 1u) / n + 2u; // (an extent of e touches <= (e - 1) / n + 2 blocks)
+    MlmApplyLds L;
+    L.occ = 4u * nv;
+    L.ztab = (5u * nv + 3u) & ~3u;
+    L.blk = L.ztab + 4u * nz;
+    L.total = (L.blk + 4u * cx * cx * cz + 15u) & ~15u;
+    return L;
 }
 
 namespace mlm_host {

@@ -2258,6 +2258,7 @@ __global__ __launch_bounds__(MLM_TILE_THREADS) void k_tile(MLM_SLOT_ARGS) {
 // One voxel record applied to the voxel's state (L, o): its hits in the reference's iteration order (descending key,
 // map_local.cpp:157-171), then its misses (map_local.cpp:188-203).  hits: the frame's vr_hit; xkeys: exact keys of a replayed
 // frame (by hit-list position), else null.
+template <int REGS = MLM_APPLY_REGS>
 __device__ __forceinline__ void mlm_apply_record(const MlmDev &P0, const mlm_u32x4 &r, const MLM_GLOBAL MlmVoxHit *hits,
                                                  const MLM_GLOBAL unsigned long long *xkeys, float &L, uint8_t &o) {
     const float lo_max = P0.lo_max, lo_sh = P0.lo_sh;
@@ -2278,11 +2279,11 @@ __device__ __forceinline__ void mlm_apply_record(const MlmDev &P0, const mlm_u32
         auto key_of = [&](const mlm_u32x4 &e) -> unsigned long long {
             return xkeys ? xkeys[e.w] : ((unsigned long long)e.x | ((unsigned long long)e.y << 32));
         };
-        if (nh <= MLM_APPLY_REGS) {
-            unsigned long long ks[MLM_APPLY_REGS];
-            float vs[MLM_APPLY_REGS];
+        if (nh <= REGS) {
+            unsigned long long ks[REGS];
+            float vs[REGS];
 #pragma unroll
-            for (int q = 0; q < MLM_APPLY_REGS; ++q) {
+            for (int q = 0; q < REGS; ++q) {
                 ks[q] = 0; // real keys are never 0
                 vs[q] = 0.0f;
             }
@@ -2291,7 +2292,7 @@ __device__ __forceinline__ void mlm_apply_record(const MlmDev &P0, const mlm_u32
                 unsigned long long kk = key_of(e);
                 float inc = __uint_as_float(e.z);
 #pragma unroll
-                for (int q = 0; q < MLM_APPLY_REGS; ++q) {
+                for (int q = 0; q < REGS; ++q) {
                     if (kk > ks[q]) {
                         const unsigned long long tk = ks[q];
                         const float tv = vs[q];
@@ -2303,7 +2304,7 @@ __device__ __forceinline__ void mlm_apply_record(const MlmDev &P0, const mlm_u32
                 }
             }
 #pragma unroll
-            for (int q = 0; q < MLM_APPLY_REGS; ++q)
+            for (int q = 0; q < REGS; ++q)
                 if ((uint32_t)q < nh) hit(vs[q]);
         } else {
             // more hits than registers: repeated selection of the next key straight from memory
@@ -2340,10 +2341,16 @@ __device__ __forceinline__ void mlm_apply_record(const MlmDev &P0, const mlm_u32
 // (redone on the cell-table path by the host), it does not fit the emulated hit container without a rehash (the host computes
 // exact keys: MLM_FRAME_EXACT_KEYS), or k_tile could not create its blocks (the host grows the pool).  g->fail_frame tells the
 // host which (sticky: batches behind it do nothing).  f_begin: first frame of the slot range to apply (replays).
+// Footprint: the kernel runs beside two Stage A batches of the other slot sets and stays resident for its whole walk of the batch:
+// 5 bytes of LDS per voxel and at most 64 VGPRs (8 waves per SIMD, k_sector's granule).  Measured on config 2 against 9 bytes and
+// 99 VGPRs (4 waves per SIMD): 1.8 % more frames/s, the kernel alone 10 % faster — its waves hide each other's trips to memory.
 #ifndef MLM_APPLY_U
-#define MLM_APPLY_U 2 // records of a thread loaded together (4: 170 VGPRs and 1 % fewer frames/s in the pipeline — the kernel is hidden behind Stage A, its footprint is not)
+#define MLM_APPLY_U 1 // records of a thread loaded together (2 with 12 hits in registers: 99 VGPRs; 4: 170 VGPRs and 1 % fewer frames/s)
 #endif
-__global__ __launch_bounds__(MLM_BLOCK) void k_apply_tiles(const MlmDev *__restrict__ slot_tab, const MlmFrame *__restrict__ frame_tab, int slot_base,
+#ifndef MLM_APPLY_TILE_REGS
+#define MLM_APPLY_TILE_REGS 8 // hit contributions of one voxel ordered in registers by k_apply_tiles (more: from memory) — 64 VGPRs, no scratch
+#endif
+__global__ __launch_bounds__(MLM_BLOCK) __attribute__((amdgpu_waves_per_eu(8))) void k_apply_tiles(const MlmDev *__restrict__ slot_tab, const MlmFrame *__restrict__ frame_tab, int slot_base,
                                                            int n_frames, int f_begin, int z_span) {
     __builtin_amdgcn_s_setprio(3); // the serial chain of the pipeline: its few waves issue ahead of Stage A's
     // The tile's voxels stay in LDS for the whole batch: a voxel is fetched from the map when a frame first touches it and
@@ -2360,6 +2367,7 @@ __global__ __launch_bounds__(MLM_BLOCK) void k_apply_tiles(const MlmDev *__restr
     __shared__ uint32_t s_count[64];
     __shared__ int s_dz[64];                         // the frame's z origin above the range's lowest
     __shared__ int s_wx0, s_wy0, s_stop, s_nwx, s_z0;
+    __shared__ uint32_t s_xytab[16]; // per x (first `edge` entries) and per y of the tile: block index relative to the tile's first | cell coordinate << 16
     const int lane = threadIdx.x & 63;
     const MlmDev &P0 = slot_tab[slot_base];
     const int sh = P0.tile_sh, lv_nz = P0.lv_nz;
@@ -2402,12 +2410,36 @@ __global__ __launch_bounds__(MLM_BLOCK) void k_apply_tiles(const MlmDev *__restr
     }
     __syncthreads();
     const int f_stop = s_stop;
-    const uint32_t NZ = (uint32_t)(lv_nz + z_span), NV = NZ << (2 * sh);
-    float *s_L = (float *)s_dyn;                         // [NV] log-odds of the tile's voxels (valid where s_at != NIL)
-    uint32_t *s_at = (uint32_t *)(s_dyn + 4u * NV);      // [NV] the voxel's address in the pool (slot * cells + cell id), MLM_NIL: not fetched
-    uint8_t *s_o = (uint8_t *)(s_dyn + 8u * NV);         // [NV] occupancy class
-    for (uint32_t v = threadIdx.x; v < NV; v += blockDim.x) s_at[v] = MLM_NIL;
+    const uint32_t edge = 1u << sh, NZ = (uint32_t)(lv_nz + z_span), NV = NZ << (2 * sh);
+    const MlmApplyLds AL = mlm_apply_lds(edge, NZ, (uint32_t)P0.n);
+    float *s_L = (float *)s_dyn;                         // [NV] log-odds of the tile's voxels (valid where s_o != 0)
+    uint8_t *s_o = (uint8_t *)(s_dyn + AL.occ);          // [NV] occupancy class ('u', 'f', 'o'; 0: not fetched)
+    uint32_t *s_ztab = (uint32_t *)(s_dyn + AL.ztab);    // [NZ] per layer: block index relative to the tile's first | cell coordinate << 16
+    uint32_t *s_blk = (uint32_t *)(s_dyn + AL.blk);      // per block the tile overlaps: pool address of its cell 0 (written at first touch)
+    for (uint32_t v = threadIdx.x; v < (NV + 3u) / 4u; v += blockDim.x) ((uint32_t *)s_o)[v] = 0u; // (up to ztab: mlm_apply_lds)
     const int WX = s_wx0 + (int)(blockIdx.x % (unsigned int)s_nwx), WY = s_wy0 + (int)(blockIdx.x / (unsigned int)s_nwx);
+    // where a voxel of the tile lies in the map, as k_tile composes it (mlm_tile_one): the blocks the tile's column of NZ layers
+    // from the range's lowest origin overlaps, and per x, y and layer the block index among them and the cell coordinate.  A
+    // voxel's pool address is then its block's base (taken from the record of its first touch) plus its cell id — integer
+    // arithmetic on the same grid coordinates, so the write-back lands where the records pointed.
+    const int X0 = WX << sh, Y0 = WY << sh, n = P0.n;
+    const int gx0 = mlm_floor_div(X0, n), gy0 = mlm_floor_div(Y0, n), gz0 = mlm_floor_div(s_z0, n);
+    const int ngx = mlm_floor_div(X0 + (int)edge - 1, n) - gx0 + 1, ngy = mlm_floor_div(Y0 + (int)edge - 1, n) - gy0 + 1;
+    for (uint32_t z = threadIdx.x; z < NZ; z += blockDim.x) {
+        const int Z = s_z0 + (int)z, gz = mlm_floor_div(Z, n);
+        s_ztab[z] = (uint32_t)(gz - gz0) | ((uint32_t)(Z - gz * n) << 16);
+    }
+    if (threadIdx.x < 2u * edge) {
+        const bool is_y = threadIdx.x >= edge;
+        const int C = (is_y ? Y0 : X0) + (int)(threadIdx.x & (edge - 1u)), g = mlm_floor_div(C, n);
+        s_xytab[threadIdx.x] = (uint32_t)(g - (is_y ? gy0 : gx0)) | ((uint32_t)(C - g * n) << 16);
+    }
+    // (block index among the overlapped ones, cell id) of tile voxel (column, layer)
+    auto place_of = [&](uint32_t col, uint32_t z, uint32_t &cid) {
+        const uint32_t xt = s_xytab[col & (edge - 1u)], yt = s_xytab[edge + (col >> sh)], zt = s_ztab[z];
+        cid = ((zt >> 16) * (uint32_t)n + (yt >> 16)) * (uint32_t)n + (xt >> 16);
+        return ((zt & 0xFFFFu) * (uint32_t)ngy + (yt & 0xFFFFu)) * (uint32_t)ngx + (xt & 0xFFFFu);
+    };
     // this world tile's records in every frame of the range (one lane per frame: the directory entries arrive together)
     if (threadIdx.x < 64) {
         uint32_t count = 0;
@@ -2438,8 +2470,8 @@ __global__ __launch_bounds__(MLM_BLOCK) void k_apply_tiles(const MlmDev *__restr
     }
     __syncthreads();
     // The records of the next frame that has any for this tile are fetched while the current frame is applied (they do not depend
-    // on the map).  Two records per thread are held in registers; a tile with more takes the rest straight from memory.
-    constexpr int PRE = 2;
+    // on the map).  A thread's first chunk of records is held in registers; a tile with more takes the rest straight from memory.
+    constexpr int PRE = MLM_APPLY_U;
     mlm_u32x4 nx[PRE];
     auto next_frame = [&](int f) {
         while (f < f_stop && s_count[f] == 0u) ++f;
@@ -2468,7 +2500,7 @@ __global__ __launch_bounds__(MLM_BLOCK) void k_apply_tiles(const MlmDev *__restr
         for (int k = 0; k < PRE; ++k) cur[k] = nx[k];
         const int f_next = next_frame(f + 1);
         prefetch(f_next);
-        // a thread's records in chunks of U: the records of a chunk are loaded together (the first two came with the previous
+        // a thread's records in chunks of U: the records of a chunk are loaded together (the first chunk came with the previous
         // frame), then the voxels that are not in LDS yet are fetched together, then the chunk is applied — the round trips of
         // a chunk overlap instead of following each other
         constexpr int U = MLM_APPLY_U;
@@ -2490,17 +2522,21 @@ __global__ __launch_bounds__(MLM_BLOCK) void k_apply_tiles(const MlmDev *__restr
                 Lv[u] = 0.0f;
                 ov[u] = 'u';
                 if (i >= count) continue;
-                const uint32_t vt = (r[u].y >> 26) * NZ + ((r[u].y >> 16) & 1023u) + dz; // (tile column, layer above the range's lowest origin)
-                if ((int)r[u].x < 0 || vt >= NV) continue; // (cannot happen: a frame whose blocks could not be created is not applied)
+                const uint32_t col = r[u].y >> 26, z = ((r[u].y >> 16) & 1023u) + dz; // (tile column, layer above the range's lowest origin)
+                const uint32_t vt = col * NZ + z;
+                if ((int)r[u].x < 0 || z >= NZ || vt >= NV) continue; // (cannot happen: a frame whose blocks could not be created is not applied)
                 vts[u] = vt;
-                if (s_at[vt] == MLM_NIL) { // first touch of the voxel in this batch (one record per voxel and frame: no other lane has it now)
+                const uint8_t o = s_o[vt];
+                if (o == 0u) { // first touch of the voxel in this batch (one record per voxel and frame: no other lane has it now)
                     const uint32_t at = r[u].x;
                     Lv[u] = pool_L[at];
-                    ov[u] = pool_o[at];
-                    s_at[vt] = at;
+                    ov[u] = pool_o[at]; // (never 0: blocks are created 'u', and only 'u', 'f', 'o' are stored)
+                    uint32_t cid;
+                    const uint32_t b = place_of(col, z, cid);
+                    s_blk[b] = at - cid; // (every voxel of the block gives the same base)
                 } else {
                     Lv[u] = s_L[vt];
-                    ov[u] = s_o[vt];
+                    ov[u] = o;
                 }
             }
 #pragma unroll
@@ -2509,7 +2545,7 @@ __global__ __launch_bounds__(MLM_BLOCK) void k_apply_tiles(const MlmDev *__restr
                 if (vt == MLM_NIL) continue;
                 float L = Lv[u];
                 uint8_t o = ov[u];
-                mlm_apply_record(P0, r[u], hits, xkeys, L, o);
+                mlm_apply_record<MLM_APPLY_TILE_REGS>(P0, r[u], hits, xkeys, L, o);
                 s_L[vt] = L;
                 s_o[vt] = o;
             }
@@ -2518,11 +2554,17 @@ __global__ __launch_bounds__(MLM_BLOCK) void k_apply_tiles(const MlmDev *__restr
         f = f_next;
     }
     // the voxels the batch touched go back to the map
+    const unsigned long long cap = (unsigned long long)P0.max_blocks * (unsigned long long)P0.cells; // (the addresses came from the records: always below)
     for (uint32_t v = threadIdx.x; v < NV; v += blockDim.x) {
-        const uint32_t at = s_at[v];
-        if (at != MLM_NIL) {
-            pool_L[at] = s_L[v];
-            pool_o[at] = s_o[v];
+        const uint8_t o = s_o[v];
+        if (o) {
+            const uint32_t col = v / NZ;
+            uint32_t cid;
+            const uint32_t at = s_blk[place_of(col, v - col * NZ, cid)] + cid;
+            if (at < cap) {
+                pool_L[at] = s_L[v];
+                pool_o[at] = o;
+            }
         }
     }
 }

@@ -43,7 +43,7 @@ int launch_apply_tiles(mlm_handle *h, int base, int n, int f_begin = 0) {
                     (MlmCounters *)nullptr, (MlmGlobal *)nullptr);
         else
             tlaunch(h, "k_apply_tiles", k_apply_tiles, dim3((unsigned int)grid), dim3(MLM_BLOCK),
-                    (size_t)(P.lv_nz + (z1 - z0)) * 9u * (1u << (2 * sh)) + 16u, h->stream, h->d_slot_tab, h->d_frame_tab, base + j0, j1 - j0, 0, z1 - z0);
+                    (size_t)mlm_apply_lds(1u << sh, (unsigned int)(P.lv_nz + (z1 - z0)), (unsigned int)P.n).total, h->stream, h->d_slot_tab, h->d_frame_tab, base + j0, j1 - j0, 0, z1 - z0);
         j0 = j1;
     }
     return MLM_OK;

@@ -353,7 +353,8 @@ int mlm_create(const mlm_config *cfg, const mlm_limits *lim_in, int device, mlm_
                 P.tile_combos = (unsigned int)std::min<long long>((cx * cx * cz + 3) & ~3ll, 1ll << 20);
             }
             h->tile_lds_bytes = mlm_tile_lds((unsigned int)(edge * edge * P.lv_nz), (unsigned int)P.lv_nz, P.tile_combos).total;
-            h->apply_lds_bytes = (unsigned int)(edge * edge * 2 * P.lv_nz) * 9u + 16u; // (two grid heights of layers: frames of a range differ in z origin)
+            // (two grid heights of layers: frames of a range differ in z origin; launch_apply_tiles keeps a launch's spread within one)
+            h->apply_lds_bytes = mlm_apply_lds((unsigned int)edge, 2u * (unsigned int)P.lv_nz, (unsigned int)P.n).total;
         }
         // (frontier mode: no tiles; its insertion times hold point index * 256 + ray step in 32 bits)
         // (k_sector lists a column's miss cells in its cell table's space; k_tile counts a voxel's misses and hits in 16 bits each:
