@@ -221,6 +221,13 @@ class mlmap {
         return lm;
     }
 
+    // truncated Euclidean distance field of a voxel box (mlm_export_esdf; flags MLM_ESDF_*; outputs host or device memory, NULL =
+    // skipped)
+    void export_esdf(const int32_t lo[3], const int32_t dims[3], int max_dist, int flags, int32_t *sqdist, float *dist = nullptr,
+                     float *grad3 = nullptr) {
+        check(mlm_export_esdf(h_, lo, dims, max_dist, flags, sqdist, dist, grad3), "mlm_export_esdf");
+    }
+
     // planners that query thousands of positions per cycle should use the batched entry points directly
     mlm_handle *handle() { return h_; }
 

@@ -224,6 +224,32 @@ int mlm_export_frontier_points(mlm_handle *h, int cap_points, float *xyz, int *n
  * window is processed in tiles that bound both, kept by the handle and counted in mlm_frame_stats.device_bytes). */
 int mlm_export_window(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], int max_iter,
                       float *odds, int8_t *occ, int8_t *infl, double *grad3);
+/* Truncated Euclidean distance field of a box of voxels (no reference counterpart: the reference's l2esdfs_batch_3d is disabled
+ * upstream and is not a Euclidean transform).  Voxel indices, window, layout and centres are those of mlm_export_window.
+ * C = max_dist (voxels, 1..64), d = (float)subbox_d_xyz.  The obstacle predicate O(v) is the union of what `flags` selects
+ * (at least one of the first three bits):
+ *   MLM_ESDF_OCC      getOccupancy(centre) == OCCUPIED
+ *   MLM_ESDF_INFL     getInflateOccupancy(centre) == OCCUPIED
+ *   MLM_ESDF_UNKNOWN  getOccupancy(centre) == UNKNOWN
+ * i.e. a function of what mlm_export_window's occ / infl channels return at v (released frontier-mode blocks, absent blocks and
+ * voxels beyond the int32 range of block keys included).  D_out(v) = min(C^2, min over all voxels o of the map with O(o) of
+ * |v - o|^2) (integer squared index distance over the whole map, not the window; 0 on obstacles); D_in(v) the same with the
+ * predicate negated (0 off obstacles).  Per voxel, x fastest:
+ *   sqdist int32   D_out off obstacles; on obstacles 0, or -D_in with MLM_ESDF_SIGNED
+ *   dist   float   d * sqrtf((float)D) for the sqdist D >= 0, -(d * sqrtf((float)-D)) for D < 0
+ *   grad3  float   x,y,z: (dist(v + e_a) - dist(v - e_a)) * (float)(0.5 / subbox_d_xyz), neighbours outside the box included
+ * (sqrtf correctly rounded, every other operation IEEE single without contraction).  Any output may be NULL (channel
+ * skipped), at least one must not be; outputs may be host or device memory; returns when they are written; observes the map as
+ * queries do.  MLM_ERR_INVALID: mlm_export_window's window errors, max_dist outside [1, 64], no obstacle bit or an unknown bit
+ * in flags, no output.  MLM_ERR_CAPACITY: no device memory for the scratch (a mask and two u16 (SIGNED: 2 x u16) fields of
+ * the tile grown by max_dist - 1 (+1 with grad3), and a staging copy of host outputs, kept by the handle and counted in
+ * mlm_frame_stats.device_bytes). */
+#define MLM_ESDF_OCC 1
+#define MLM_ESDF_INFL 2
+#define MLM_ESDF_UNKNOWN 4
+#define MLM_ESDF_SIGNED 8
+int mlm_export_esdf(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], int max_dist, int flags,
+                    int32_t *sqdist, float *dist, float *grad3);
 /* Load blocks into the map (no reference counterpart: the reference never persists or merges maps; this is how a
  * merged global map, mlmapping_amd/merge.py, is put back behind the query interface).  keys [n*3]; log_odds / occ /
  * infl [n*cells] and collapsed [n] as mlm_export_blocks / mlm_export_block_flags write them, any of them may be NULL

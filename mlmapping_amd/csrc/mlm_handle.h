@@ -25,7 +25,7 @@ struct KernelTime {
 // simulated allocation failures.  Process-wide, not part of the drop-in contract; the library reads no environment variable
 // for them (only the three diagnostic switches MLM_DEBUG_CREATE / MLM_DEBUG_ALLOC / MLM_DEBUG_DRAIN, which print).
 const char *const kKnobNames[] = {"agg_lds", "big_arm", "big_grid", "bin_block", "chain_grid", "collect_grid", "cu_reserve", "cu_split",
-                                  "debug_fail_slot", "ex_spec", "expand_block", "graph", "lean_slots", "logit_exact", "mirror", "mirror_max", "mirror_mb", "need_slots", "node_lds", "pool_grow",
+                                  "debug_fail_slot", "esdf_tile_vox", "ex_spec", "expand_block", "graph", "lean_slots", "logit_exact", "mirror", "mirror_max", "mirror_mb", "need_slots", "node_lds", "pool_grow",
                                   "rank_grid", "sc_block", "sc_grid", "sec_backoff", "sec_fail_every", "sec_tab", "sec_tab_big", "sec_threads",
                                   "sectors", "single_apply_grid", "single_chain_grid", "single_rank_grid", "slot_sets", "sort_block", "sort_grid", "tile_grid", "tile_sh"};
 struct KnobStore {
@@ -48,6 +48,7 @@ bool knob_value_ok(const char *name, long long v) {
         is("single_chain_grid") || is("single_rank_grid") || is("sort_grid") || is("tile_grid"))
         return v >= 1 && v <= (1ll << 20);
     if (is("cu_split") || is("cu_reserve")) return v >= 0 && v <= 0x7FFFFFFFll;
+    if (is("esdf_tile_vox")) return v >= kEsdfMinBoxVoxels && v <= kEsdfBoxVoxels; // (mlm_esdf_plan fits every call's tile then)
     return true;
 }
 bool knob(const char *name, long long &out) {
@@ -140,6 +141,9 @@ struct mlm_handle {
     // mlm_export_window: odds of the haloed tile (gradients) and the staging of host destinations, kept and enlarged by need
     void *d_win_scratch = nullptr, *d_win_stage = nullptr;
     size_t win_scratch_bytes = 0, win_stage_bytes = 0;
+    // mlm_export_esdf: obstacle mask and the two fields of the grown tile (staging shares d_win_stage), kept and enlarged by need
+    void *d_esdf_scratch = nullptr;
+    size_t esdf_scratch_bytes = 0;
     // sort buffers (rehash frames only)
     unsigned long long *sk_in = nullptr, *sk_out = nullptr;
     uint32_t *sv_in = nullptr, *sv_out = nullptr;

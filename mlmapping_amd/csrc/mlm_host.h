@@ -109,6 +109,43 @@ MLM_HD inline MlmApplyLds mlm_apply_lds(uint32_t edge, uint32_t nz, uint32_t n) 
     return L;
 }
 
+// Tiles of mlm_export_esdf (mlm_kernels_esdf.h) for a window of D[0] x D[1] x D[2] voxels, truncation C (voxels), central
+// gradients or not.  A tile is whole planes, else rows of one plane, else a piece of one row, so that its output is one
+// contiguous range of the window's [D2][D1][D0] layout and a staged tile goes back in one copy.  The grown tile (the tile plus
+// H = C - 1 + grad voxels per side: every obstacle that can lower a clamped value, and the gradient's neighbours) holds at most
+// box_cap voxels, the tile itself at most out_cap (the staging of host destinations).  Tile origins are the multiples of T per
+// axis, n[a] = ceil(D[a] / T[a]) of them, the last one cut to the window.  T[0] == 0: box_cap < (2H + 1)^3, no tile fits.
+constexpr long long kEsdfBoxVoxels = 1ll << 25;           // grown tile: mask (1 B) + two fields (<= 4 B) per voxel, 288 MB
+constexpr long long kEsdfMinBoxVoxels = 129ll * 129 * 129; // the smallest box every call fits: one voxel grown by H = 64
+constexpr long long kEsdfStageVoxels = 1ll << 22;         // staged tile: <= 20 bytes per voxel
+struct MlmEsdfPlan {
+    long long T[3], n[3];
+    long long H, grown; // grown: voxels of a full grown tile (the scratch the fields need)
+};
+inline MlmEsdfPlan mlm_esdf_plan(const long long D[3], int C, bool grad, long long box_cap, long long out_cap) {
+    MlmEsdfPlan p{};
+    const long long H = C - 1 + (grad ? 1 : 0), h2 = 2 * H;
+    p.H = H;
+    auto fits = [&](long long tx, long long ty, long long tz) { return (tx + h2) * (ty + h2) * (tz + h2) <= box_cap && tx * ty * tz <= out_cap; };
+    if (fits(D[0], D[1], 1)) {
+        p.T[0] = D[0];
+        p.T[1] = D[1];
+        p.T[2] = std::min({D[2], box_cap / ((D[0] + h2) * (D[1] + h2)) - h2, out_cap / (D[0] * D[1])});
+    } else if (fits(D[0], 1, 1)) {
+        p.T[0] = D[0];
+        p.T[1] = std::min({D[1], box_cap / ((D[0] + h2) * (1 + h2)) - h2, out_cap / D[0]});
+        p.T[2] = 1;
+    } else if (fits(1, 1, 1)) {
+        p.T[0] = std::min({D[0], box_cap / ((1 + h2) * (1 + h2)) - h2, out_cap});
+        p.T[1] = p.T[2] = 1;
+    } else {
+        return p;
+    }
+    for (int a = 0; a < 3; ++a) p.n[a] = (D[a] + p.T[a] - 1) / p.T[a];
+    p.grown = (p.T[0] + h2) * (p.T[1] + h2) * (p.T[2] + h2);
+    return p;
+}
+
 namespace mlm_host {
 
 // Does this host's libm log10f (what the reference's logit macro calls) agree with mlm_glibc_log10f?  Checked on the values the

@@ -41,6 +41,18 @@ __device__ __forceinline__ void mlm_win_axis(long long v, int n, int &g, int &c)
     g = mlm_win_key(g64);
 }
 
+// what the occ / infl channels say of the voxel at pool index `at` (= slot * cells + cid, cid 0 in a released block) of block `slot`
+// (-1: absent): getOccupancy (mlmap.h:170-193) and getInflateOccupancy (mlmap.h:195-211, UNKNOWN in released blocks).  The one
+// statement of these classes for every dense read-out (k_window_fill, k_esdf_mask).
+__device__ __forceinline__ int mlm_win_occ(const MlmDev &P, int slot, size_t at) {
+    if (slot < 0) return -1;
+    const uint8_t c = P.occ[at];
+    return c == 'o' ? 0 : (c == 'f' ? 1 : -1);
+}
+__device__ __forceinline__ int mlm_win_infl(const MlmDev &P, int slot, bool collapsed, size_t at) {
+    return (slot >= 0 && !collapsed && P.infl[at] == 'o') ? 0 : -1;
+}
+
 __global__ __launch_bounds__(MLM_BLOCK) void k_window_fill(const MlmDev P, const MlmWin W) {
     __shared__ int s_slot;
     const long long n_bricks = (long long)W.nb[0] * W.nb[1] * W.nb[2];
@@ -73,16 +85,8 @@ __global__ __launch_bounds__(MLM_BLOCK) void k_window_fill(const MlmDev P, const
             if (!inside) continue;
             const long long o = ((z - W.wlo[2]) * W.wd[1] + (y - W.wlo[1])) * W.wd[0] + (x - W.wlo[0]) - W.out_base;
             if (W.odds) W.odds[o] = odd;
-            if (W.occ) {
-                int r = -1; // getOccupancy, mlmap.h:170-193
-                if (slot >= 0) {
-                    const uint8_t c = P.occ[base + cid];
-                    r = c == 'o' ? 0 : (c == 'f' ? 1 : -1);
-                }
-                W.occ[o] = (int8_t)r;
-            }
-            if (W.infl) // getInflateOccupancy, mlmap.h:195-211: UNKNOWN in released blocks
-                W.infl[o] = (int8_t)((slot >= 0 && !collapsed && P.infl[base + cid] == 'o') ? 0 : -1);
+            if (W.occ) W.occ[o] = (int8_t)mlm_win_occ(P, slot, base + cid);
+            if (W.infl) W.infl[o] = (int8_t)mlm_win_infl(P, slot, collapsed, base + cid);
         }
     }
 }

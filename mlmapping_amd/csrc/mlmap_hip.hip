@@ -20,6 +20,7 @@
 #include <deque>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 #include <atomic>
@@ -29,6 +30,7 @@
 #include "mlm_kernels_explore.h"
 #include "mlm_kernels_sector.h"
 #include "mlm_kernels_window.h"
+#include "mlm_kernels_esdf.h"
 #include "mlm_host.h"
 #include "mlm_mapview.h"
 
@@ -1109,7 +1111,7 @@ bool win_in_place(const void *p) {
 }
 
 // a kept buffer of at least `bytes`; a failed allocation leaves the handle as it was, minus the old buffer
-int win_reserve(mlm_handle *h, void *&p, size_t &cap, size_t bytes) {
+int win_reserve(mlm_handle *h, void *&p, size_t &cap, size_t bytes, const char *what = "mlm_export_window") {
     if (bytes <= cap) return MLM_OK;
     dev_free(h, p, cap);
     p = nullptr;
@@ -1117,7 +1119,7 @@ int win_reserve(mlm_handle *h, void *&p, size_t &cap, size_t bytes) {
     void *v = nullptr;
     if (hipMalloc(&v, bytes) != hipSuccess) {
         (void)hipGetLastError();
-        h->err = "mlm_export_window: no device memory for " + std::to_string(bytes >> 20) + " MB of scratch";
+        h->err = std::string(what) + ": no device memory for " + std::to_string(bytes >> 20) + " MB of scratch";
         return MLM_ERR_CAPACITY;
     }
     h->alloc_bytes += bytes;
@@ -1234,6 +1236,145 @@ int mlm_export_window(mlm_handle *h, const int32_t lo[3], const int32_t dims[3],
                 for (int c = 0; c < 4; ++c)
                     if (staged[c])
                         HIPCHK(h, hipMemcpyAsync((char *)dst[c] + (size_t)W.out_base * elem[c], ch[c], (size_t)nt * elem[c], hipMemcpyDefault,
+                                                 h->stream));
+            }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MLM_OK;
+}
+
+extern "C++" {
+namespace {
+constexpr unsigned int kEsdfMaskGrid = 2048, kEsdfPassGrid = 4096;
+
+// the four passes and the outputs of one tile of mlm_export_esdf (mlm_kernels_esdf.h); T: u16 (unsigned) or u16x2 (signed)
+template <bool SIGNED>
+void esdf_tile(mlm_handle *h, const MlmEsdf &E, int C, uint8_t *mask, void *fa, void *fb, const MlmEsdfOut &Q) {
+    using T = typename std::conditional<SIGNED, mlm_u16x2, uint16_t>::type;
+    const int ex = Q.fd[0], ey = Q.fd[1], ez = Q.fd[2];
+    const long long n_bricks = (long long)E.nb[0] * E.nb[1] * E.nb[2];
+    hipLaunchKernelGGL(k_esdf_mask, dim3((unsigned int)std::min<long long>(n_bricks, kEsdfMaskGrid)), dim3(MLM_BLOCK), 0, h->stream, h->P, E);
+    // x: mask [gd2 * gd1][gd0] -> fa [gd2 * gd1][ex]
+    const long long rows = (long long)E.gd[2] * E.gd[1], xtasks = rows * ((ex + 63) / 64);
+    hipLaunchKernelGGL(k_esdf_x<SIGNED>, dim3((unsigned int)std::min<long long>((xtasks + 3) / 4, kEsdfPassGrid)), dim3(MLM_BLOCK), 0,
+                       h->stream, mask, fa, rows, E.gd[0], ex, C);
+    // y: fa [gd2][gd1][ex] -> fb [gd2][ey][ex];  z: fb [gd2][ey * ex] -> fa [ez][ey * ex]
+    const int TLmax = SIGNED ? MLM_ESDF_LINE_TL / 2 : MLM_ESDF_LINE_TL;
+    auto line = [&](const void *in, void *out, long long X, int Lout, int outer) {
+        const int lc = (Lout + TLmax - 1) / TLmax, TL = (Lout + lc - 1) / lc; // (rows spread evenly over the line chunks)
+        const long long tiles = (long long)outer * lc * ((X + 63) / 64);
+        const size_t lds = (size_t)(TL + 2 * C - 2) * 64 * sizeof(T);
+        hipLaunchKernelGGL(k_esdf_line<T>, dim3((unsigned int)std::min<long long>(tiles, kEsdfPassGrid)), dim3(MLM_BLOCK), lds, h->stream,
+                           (const T *)in, (T *)out, X, Lout, outer, C, TL);
+    };
+    line(fa, fb, ex, ey, E.gd[2]);
+    line(fb, fa, (long long)ey * ex, ez, 1);
+    const long long nt = (long long)Q.td[0] * Q.td[1] * Q.td[2];
+    hipLaunchKernelGGL(k_esdf_out<SIGNED>, dim3(std::min<unsigned int>(grid_for((size_t)nt), kEsdfPassGrid)), dim3(MLM_BLOCK), 0, h->stream,
+                       (const void *)fa, Q);
+}
+} // namespace
+} // extern "C++"
+
+int mlm_export_esdf(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], int max_dist, int flags, int32_t *sqdist, float *dist,
+                    float *grad3) {
+    if (!h) return MLM_ERR_INVALID;
+    MLM_LOCK(h);
+    if (!lo || !dims || max_dist < 1 || max_dist > 64 || (flags & 7) == 0 || (flags & ~15) || (!sqdist && !dist && !grad3)) {
+        h->err = "mlm_export_esdf: null window, max_dist outside [1, 64], no obstacle bit or an unknown bit in flags, or no output";
+        return MLM_ERR_INVALID;
+    }
+    long long D[3], nvox = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (dims[a] < 1 || (long long)lo[a] + dims[a] > 0x7FFFFFFFll) {
+            h->err = "mlm_export_esdf: dims must be >= 1 and lo + dims must fit an int32";
+            return MLM_ERR_INVALID;
+        }
+        D[a] = dims[a];
+        nvox *= D[a];
+        if (nvox > 0x7FFFFFFFll) {
+            h->err = "mlm_export_esdf: more than 2^31 - 1 voxels";
+            return MLM_ERR_INVALID;
+        }
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = drain(h);
+    if (rc) return rc;
+
+    void *dst[3] = {sqdist, dist, grad3};
+    const size_t elem[3] = {sizeof(int32_t), sizeof(float), 3 * sizeof(float)};
+    bool staged[3];
+    bool any_staged = false;
+    for (int c = 0; c < 3; ++c) {
+        staged[c] = dst[c] && !win_in_place(dst[c]);
+        any_staged |= staged[c];
+    }
+    const bool sgn = (flags & MLM_ESDF_SIGNED) != 0;
+    const int C = max_dist, G = grad3 ? 1 : 0;
+    long long box_cap = kEsdfBoxVoxels, kv;
+    if (knob("esdf_tile_vox", kv)) box_cap = kv;
+    const MlmEsdfPlan plan = mlm_esdf_plan(D, C, G != 0, box_cap, any_staged ? kEsdfStageVoxels : (1ll << 62));
+    if (plan.T[0] < 1) { // (not with the caps mlm_debug_set admits)
+        h->err = "mlm_export_esdf: no tile fits the voxel cap";
+        return MLM_ERR_INVALID;
+    }
+    const long long tile_vox = plan.T[0] * plan.T[1] * plan.T[2];
+    size_t stage_off[3] = {0, 0, 0}, stage_bytes = 0;
+    for (int c = 0; c < 3; ++c)
+        if (staged[c]) {
+            stage_off[c] = stage_bytes;
+            stage_bytes += ((size_t)tile_vox * elem[c] + 255) & ~(size_t)255;
+        }
+    // scratch: the mask, then two fields of the grown tile (the x pass and the z pass write the first, the y pass the second)
+    const size_t fe = sgn ? 4 : 2, mask_bytes = ((size_t)plan.grown + 255) & ~(size_t)255,
+                 field_bytes = ((size_t)plan.grown * fe + 255) & ~(size_t)255;
+    if ((rc = win_reserve(h, h->d_esdf_scratch, h->esdf_scratch_bytes, mask_bytes + 2 * field_bytes, "mlm_export_esdf"))) return rc;
+    if (stage_bytes && (rc = win_reserve(h, h->d_win_stage, h->win_stage_bytes, stage_bytes, "mlm_export_esdf"))) return rc;
+    uint8_t *mask = (uint8_t *)h->d_esdf_scratch;
+    void *fa = (char *)h->d_esdf_scratch + mask_bytes, *fb = (char *)h->d_esdf_scratch + mask_bytes + field_bytes;
+
+    const int n = h->P.n;
+    const long long H = plan.H;
+    auto floor_div = [n](long long v) { return v >= 0 ? v / n : -((-v + n - 1) / n); };
+    for (long long z0 = 0; z0 < D[2]; z0 += plan.T[2])
+        for (long long y0 = 0; y0 < D[1]; y0 += plan.T[1])
+            for (long long x0 = 0; x0 < D[0]; x0 += plan.T[0]) {
+                MlmEsdf E{};
+                MlmEsdfOut Q{};
+                const long long org[3] = {x0, y0, z0};
+                for (int a = 0; a < 3; ++a) {
+                    Q.t0[a] = org[a];
+                    Q.td[a] = (int)std::min(plan.T[a], D[a] - org[a]);
+                    Q.fd[a] = Q.td[a] + 2 * G;
+                    E.glo[a] = lo[a] + org[a] - H; // (64-bit: the grown box of a window at the int32 edge reaches past it)
+                    E.gd[a] = Q.td[a] + (int)(2 * H);
+                    E.b0[a] = floor_div(E.glo[a]);
+                    E.nb[a] = (int)(floor_div(E.glo[a] + E.gd[a] - 1) - E.b0[a] + 1);
+                }
+                E.flags = flags & 7;
+                E.mask = mask;
+                Q.wd0 = D[0];
+                Q.wd1 = D[1];
+                Q.G = G;
+                Q.out_base = (z0 * D[1] + y0) * D[0] + x0;
+                Q.d = (float)h->cfg.subbox_d_xyz;
+                Q.inv = (float)(0.5 / h->cfg.subbox_d_xyz);
+                void *ch[3];
+                for (int c = 0; c < 3; ++c)
+                    ch[c] = !dst[c] ? nullptr
+                                    : staged[c] ? (void *)((char *)h->d_win_stage + stage_off[c])
+                                                : (void *)((char *)dst[c] + (size_t)Q.out_base * elem[c]);
+                Q.sqdist = (int32_t *)ch[0];
+                Q.dist = (float *)ch[1];
+                Q.grad = (float *)ch[2];
+                if (sgn)
+                    esdf_tile<true>(h, E, C, mask, fa, fb, Q);
+                else
+                    esdf_tile<false>(h, E, C, mask, fa, fb, Q);
+                HIPCHK(h, hipGetLastError());
+                const long long nt = (long long)Q.td[0] * Q.td[1] * Q.td[2];
+                for (int c = 0; c < 3; ++c)
+                    if (staged[c])
+                        HIPCHK(h, hipMemcpyAsync((char *)dst[c] + (size_t)Q.out_base * elem[c], ch[c], (size_t)nt * elem[c], hipMemcpyDefault,
                                                  h->stream));
             }
     HIPCHK(h, hipStreamSynchronize(h->stream));

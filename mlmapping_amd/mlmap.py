@@ -24,6 +24,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MLMAP_HIP_LIB") or os.path.join(_HERE, "lib", "libmlmap_hip.so")  # env: development builds
 
 MLM_OK = 0
+# mlm_export_esdf flags (include/mlmap_hip.h): obstacle predicates (their union) and the signed field
+MLM_ESDF_OCC, MLM_ESDF_INFL, MLM_ESDF_UNKNOWN, MLM_ESDF_SIGNED = 1, 2, 4, 8
 STATUS = {0: "MLM_OK", -1: "MLM_ERR_INVALID", -2: "MLM_ERR_HIP", -3: "MLM_ERR_CAPACITY", -4: "MLM_ERR_UNSUPPORTED"}
 
 # every symbol include/mlmap_hip.h declares
@@ -35,7 +37,7 @@ ABI_SYMBOLS = [
     "mlm_query_odds", "mlm_query_odd_grad", "mlm_query_odds_at", "mlm_export_frontier_points", "mlm_import_blocks",
     "mlm_merge_pack", "mlm_merge_finish",
     "mlm_set_free_in_bound", "mlm_inflate_map", "mlm_block_count",
-    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
+    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
     "mlm_get_awareness_hits",
     "mlm_get_awareness_misses", "mlm_get_T_ls", "mlm_get_odds_table", "mlm_get_kernel_times",
     "mlm_enable_kernel_timing", "mlm_set_timed_kernel", "mlm_host_register", "mlm_host_unregister", "mlm_debug_set", "mlm_debug_reset",
@@ -129,6 +131,7 @@ def load_library(path: Optional[str] = None):
     L.mlm_block_count.argtypes = [vp, vp]
     L.mlm_export_blocks.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     L.mlm_export_window.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
+    L.mlm_export_esdf.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
     L.mlm_export_global_map.argtypes = [vp, i32, vp, vp]
     L.mlm_export_block_flags.argtypes = [vp, i32, vp, vp]
     L.mlm_export_frontier.argtypes = [vp, i32, vp, vp]
@@ -441,6 +444,40 @@ class MLMap:
         lo_a, dims_a = self._window_args(lo, dims)
         ptr = [None if v is None else ctypes.c_void_p(v) for v in (odds, occ, infl, grad)]
         self._chk(self._L.mlm_export_window(self._h, _p(lo_a), _p(dims_a), int(max_iter), *ptr), "mlm_export_window")
+
+    def export_esdf(self, lo, dims, max_dist: int, occ=True, infl=False, unknown=False, signed=False, sqdist=True, dist=False,
+                    grad=False) -> Dict[str, np.ndarray]:
+        """Truncated Euclidean distance field of the voxel box lo <= v < lo + dims (voxel indices as export_window): {"sqdist":
+        int32, "dist": float32 shaped (dz, dy, dx), "grad": float32 (dz, dy, dx, 3)} for the channels asked for.  Obstacles are
+        the union of occ (getOccupancy == OCCUPIED), infl (getInflateOccupancy == OCCUPIED) and unknown (getOccupancy == UNKNOWN);
+        squared index distances to the nearest obstacle of the whole map, clamped at max_dist^2; signed: minus the distance to
+        the nearest non-obstacle on obstacles (mlm_export_esdf)."""
+        lo_a, dims_a = self._window_args(lo, dims)
+        shape = (int(dims_a[2]), int(dims_a[1]), int(dims_a[0]))
+        out = {}
+        if sqdist:
+            out["sqdist"] = np.empty(shape, dtype=np.int32)
+        if dist:
+            out["dist"] = np.empty(shape, dtype=np.float32)
+        if grad:
+            out["grad"] = np.empty(shape + (3,), dtype=np.float32)
+        ptr = [_p(out[k]) if k in out else None for k in ("sqdist", "dist", "grad")]
+        flags = self._esdf_flags(occ, infl, unknown, signed)
+        self._chk(self._L.mlm_export_esdf(self._h, _p(lo_a), _p(dims_a), int(max_dist), flags, *ptr), "mlm_export_esdf")
+        return out
+
+    def export_esdf_dev(self, lo, dims, max_dist: int, occ=True, infl=False, unknown=False, signed=False,
+                        sqdist: Optional[int] = None, dist: Optional[int] = None, grad: Optional[int] = None):
+        """Same into device memory: pointers (ints) to dz*dy*dx int32 / float32 / (x3) float32 elements, None = skipped."""
+        lo_a, dims_a = self._window_args(lo, dims)
+        ptr = [None if v is None else ctypes.c_void_p(v) for v in (sqdist, dist, grad)]
+        flags = self._esdf_flags(occ, infl, unknown, signed)
+        self._chk(self._L.mlm_export_esdf(self._h, _p(lo_a), _p(dims_a), int(max_dist), flags, *ptr), "mlm_export_esdf")
+
+    @staticmethod
+    def _esdf_flags(occ, infl, unknown, signed) -> int:
+        return ((MLM_ESDF_OCC if occ else 0) | (MLM_ESDF_INFL if infl else 0) | (MLM_ESDF_UNKNOWN if unknown else 0)
+                | (MLM_ESDF_SIGNED if signed else 0))
 
     @staticmethod
     def _window_args(lo, dims):

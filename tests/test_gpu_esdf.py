@@ -1,0 +1,422 @@
+"""mlm_export_esdf: the truncated Euclidean distance field of a voxel box (include/mlmap_hip.h), checked bit for bit against plain
+numpy: sqdist as int32, dist and gradients as float32 bits of the header's formulas.
+
+Two numpy forms of the field: the definition taken literally (min over every obstacle voxel of a map built voxel by voxel) for
+small boxes, and a separable truncated transform of the obstacle mask of the box grown by C for any box; both agree where both
+run.  The obstacle masks come from maps built voxel by voxel (import_blocks), from the CPU oracle's getOccupancy /
+getInflateOccupancy at the voxel centres, and from the GPU's own export_window, which must all give the same field."""
+import ctypes
+
+import numpy as np
+import pytest
+
+from mlmapping_amd import synthetic as syn
+from mlmapping_amd.config import S1
+
+pytestmark = pytest.mark.gpu
+
+OCC, INFL, UNKNOWN, SIGNED = 1, 2, 4, 8
+MIN_BOX = 129 ** 3  # smallest esdf_tile_vox (mlm_host.h kEsdfMinBoxVoxels)
+
+
+@pytest.fixture(scope="module")
+def mods():
+    from mlmapping_amd.mlmap import MLMap
+    from oracle.binding import OracleMap
+
+    return MLMap, OracleMap
+
+
+# ---- numpy ground truth -------------------------------------------------------------------------------------------------------
+def edt_separable(mask, C):
+    """min(C^2, squared distance to the nearest True of mask) per voxel, by three 1-D truncated passes; exact wherever every
+    voxel within C - 1 on each axis is inside the array"""
+    C2 = C * C
+    f = np.where(mask, 0, C2).astype(np.uint16)
+    for axis in (2, 1, 0):
+        g = f.copy()
+        for k in range(1, C):
+            a, b = [slice(None)] * 3, [slice(None)] * 3
+            a[axis], b[axis] = slice(0, -k), slice(k, None)
+            a, b = tuple(a), tuple(b)
+            np.minimum(g[a], f[b] + np.uint16(k * k), out=g[a])
+            np.minimum(g[b], f[a] + np.uint16(k * k), out=g[b])
+        f = g
+    return f.astype(np.int32)
+
+
+def edt_brute(obs, lo, dims, C):
+    """the definition literally, over the box lo .. lo + dims ([z][y][x]): min over every obstacle voxel o of the map (obs [K,3],
+    x y z) of |v - o|^2, clamped at C^2"""
+    iz, iy, ix = np.unravel_index(np.arange(dims[0] * dims[1] * dims[2]), (dims[2], dims[1], dims[0]))
+    tgt = np.stack([lo[0] + ix, lo[1] + iy, lo[2] + iz], axis=1).astype(np.int64)
+    obs = np.asarray(obs, dtype=np.int64).reshape(-1, 3)
+    out = np.full(len(tgt), C * C, dtype=np.int64)
+    step = max(1, 20_000_000 // max(1, len(obs)))
+    for i in range(0, len(tgt) if len(obs) else 0, step):
+        d2 = ((tgt[i:i + step, None, :] - obs[None, :, :]) ** 2).sum(-1).min(1)
+        out[i:i + step] = np.minimum(out[i:i + step], d2)
+    return out.reshape(dims[2], dims[1], dims[0]).astype(np.int32)
+
+
+def channels(dout, din, d):
+    """sqdist, dist and gradients of the window from D_out (and D_in: signed) over the window +- 1"""
+    sq = dout if din is None else np.where(dout == 0, -din, dout).astype(np.int32)
+    df = np.float32(d)
+    mag = df * np.sqrt(np.abs(sq).astype(np.float32))
+    dist = np.where(sq < 0, -mag, mag).astype(np.float32)
+    inv = np.float32(0.5 / d)
+    grad = np.stack([(dist[1:-1, 1:-1, 2:] - dist[1:-1, 1:-1, :-2]) * inv, (dist[1:-1, 2:, 1:-1] - dist[1:-1, :-2, 1:-1]) * inv,
+                     (dist[2:, 1:-1, 1:-1] - dist[:-2, 1:-1, 1:-1]) * inv], axis=-1).astype(np.float32)
+    return {"sqdist": sq[1:-1, 1:-1, 1:-1], "dist": dist[1:-1, 1:-1, 1:-1], "grad": grad}
+
+
+def expected(mask, C, signed, d):
+    """channels of the window from the obstacle mask of the window grown by C per side ([z][y][x]), separable form"""
+    crop = tuple(slice(C - 1, s - C + 1) for s in mask.shape)  # window +- 1
+    return channels(edt_separable(mask, C)[crop], edt_separable(~mask, C)[crop] if signed else None, d)
+
+
+def expected_brute(obs, lo, dims, C, d):
+    """channels of an unsigned field from the map's obstacle voxels, the definition literally"""
+    return channels(edt_brute(obs, [v - 1 for v in lo], [v + 2 for v in dims], C), None, d)
+
+
+def check(got, exp, what=""):
+    for k, v in got.items():
+        e = exp[k]
+        assert v.shape == e.shape, (what, k)
+        if k == "sqdist":
+            bad = np.argwhere(v != e)
+        else:
+            bad = np.argwhere(v.view(np.uint32) != e.view(np.uint32))
+        assert len(bad) == 0, f"{what} {k}: {len(bad)} differ, first at {bad[0]}: {v[tuple(bad[0])]} vs {e[tuple(bad[0])]}"
+
+
+def grown(lo, dims, C):
+    return [v - C for v in lo], [v + 2 * C for v in dims]
+
+
+def centres(cfg, lo, dims):
+    n, d = cfg.subbox_n, cfg.subbox_d_xyz
+    iz, iy, ix = np.unravel_index(np.arange(dims[0] * dims[1] * dims[2]), (dims[2], dims[1], dims[0]))
+    v = np.stack([lo[0] + ix, lo[1] + iy, lo[2] + iz], axis=1).astype(np.int64)
+    g = np.floor_divide(v, n)
+    return g.astype(np.float64) * (d * n) + (v - g * n).astype(np.float64) * d + d * 0.5
+
+
+def classes_mask(occ, infl, flags):
+    m = np.zeros(occ.shape, dtype=bool)
+    if flags & OCC:
+        m |= occ == 0
+    if flags & INFL:
+        m |= infl == 0
+    if flags & UNKNOWN:
+        m |= occ == -1
+    return m
+
+
+def oracle_mask(cpu, cfg, lo, dims, flags):
+    """the obstacle mask from the CPU oracle's queries at the voxel centres"""
+    p = centres(cfg, lo, dims)
+    shape = (dims[2], dims[1], dims[0])
+    return classes_mask(cpu.getOccupancy(p).reshape(shape), cpu.getInflateOccupancy(p).reshape(shape), flags)
+
+
+def window_mask(gpu, lo, dims, flags):
+    """the obstacle mask from the GPU's export_window classes"""
+    w = gpu.export_window(lo, dims, odds=False, occ=True, infl=True)
+    return classes_mask(w["occ"].astype(np.int32), w["infl"].astype(np.int32), flags)
+
+
+ALL = dict(sqdist=True, dist=True, grad=True)
+
+
+def esdf(gpu, lo, dims, C, flags, **ch):
+    return gpu.export_esdf(lo, dims, C, occ=bool(flags & OCC), infl=bool(flags & INFL), unknown=bool(flags & UNKNOWN),
+                           signed=bool(flags & SIGNED), **(ch or ALL))
+
+
+# ---- maps built voxel by voxel ------------------------------------------------------------------------------------------------
+class Crafted:
+    """obstacle voxels imported as OCCUPIED cells of otherwise FREE blocks; voxels of blocks not imported are UNKNOWN"""
+
+    def __init__(self, MLMap, obstacles, free_blocks=()):
+        n = S1.subbox_n
+        obs = np.asarray(obstacles, dtype=np.int64).reshape(-1, 3)
+        keys = np.unique(np.concatenate([np.floor_divide(obs, n), np.asarray(free_blocks, dtype=np.int64).reshape(-1, 3)]), axis=0)
+        occ = np.full((len(keys), n ** 3), ord("f"), dtype=np.uint8)
+        kidx = {tuple(k): i for i, k in enumerate(keys.tolist())}
+        for v in obs:
+            g = np.floor_divide(v, n)
+            c = v - g * n
+            occ[kidx[tuple(g.tolist())], c[2] * n * n + c[1] * n + c[0]] = ord("o")
+        self.obs_xyz = obs
+        self.obs, self.keys = _code(obs), _code(keys)
+        self.gpu = MLMap(S1, max_blocks=4096)
+        self.gpu.import_blocks(keys.astype(np.int32), np.zeros(occ.shape, np.float32), occ, np.full(occ.shape, ord("u"), np.uint8),
+                               np.zeros(len(keys), np.uint8))
+
+    def mask(self, lo, dims, flags):
+        n = S1.subbox_n
+        iz, iy, ix = np.unravel_index(np.arange(dims[0] * dims[1] * dims[2]), (dims[2], dims[1], dims[0]))
+        v = np.stack([lo[0] + ix, lo[1] + iy, lo[2] + iz], axis=1).astype(np.int64)
+        is_obs = np.isin(_code(v), self.obs)
+        known = np.isin(_code(np.floor_divide(v, n)), self.keys)
+        occ = np.where(is_obs, 0, np.where(known, 1, -1)).reshape(dims[2], dims[1], dims[0])
+        return classes_mask(occ, np.full(occ.shape, -1), flags)
+
+
+def _code(v):
+    """one int64 per voxel / block index triple (|coordinates| < 2^20)"""
+    v = np.asarray(v, dtype=np.int64).reshape(-1, 3) + (1 << 20)
+    return (v[:, 0] << 42) | (v[:, 1] << 21) | v[:, 2]
+
+
+@pytest.mark.parametrize("C", [1, 5, 64])
+def test_halo_edge(mods, C):
+    """one obstacle k voxels beyond a window face, k = 1 .. C+1: the facing voxel reads min(k^2, C^2); one at offsets (C-1, 1)
+    from a window corner reads min(C^2, (C-1)^2 + 1); every channel of every window equals the definition"""
+    MLMap, _ = mods
+    dims = [5, 4, 3]
+    sp = 3 * C + 20  # windows far enough apart not to see each other's obstacles
+    cases = []
+    for k in range(1, C + 2):
+        lo = [-7 + sp * k, -3, -2]
+        side = k % 2  # beyond the +x face, or beyond the -x face
+        fx = lo[0] + dims[0] - 1 if side else lo[0]
+        cases.append((lo, (fx + k if side else fx - k, lo[1] + 1, lo[2] + 2), (fx, lo[1] + 1, lo[2] + 2), min(k * k, C * C)))
+    lo = [-7 - sp, 11, 4]  # the diagonal one, beyond the (+x, +y) edge
+    cx, cy = lo[0] + dims[0] - 1, lo[1] + dims[1] - 1
+    cases.append((lo, (cx + C - 1, cy + 1, lo[2]), (cx, cy, lo[2]), min(C * C, (C - 1) ** 2 + 1)))
+    m = Crafted(MLMap, [c[1] for c in cases])
+    for i, (lo, ob, face, val) in enumerate(cases):
+        got = esdf(m.gpu, lo, dims, C, OCC)
+        f = tuple(face[a] - lo[a] for a in range(3))
+        assert got["sqdist"][f[2], f[1], f[0]] == val, (C, lo, ob)
+        check(got, expected_brute(m.obs_xyz, lo, dims, C, S1.subbox_d_xyz), f"C={C} {lo}")
+        if i in (0, C - 2, C, len(cases) - 1):
+            glo, gd = grown(lo, dims, C)
+            check(esdf(m.gpu, lo, dims, C, OCC | SIGNED), expected(m.mask(glo, gd, OCC), C, True, S1.subbox_d_xyz), f"signed C={C} {lo}")
+    m.gpu.close()
+
+
+@pytest.mark.parametrize("C", [1, 5, 64])
+def test_sparse_sets_and_planes(mods, C):
+    """random sparse obstacles and a plane, in windows that are not block aligned, negative and one voxel thick; OCC, OCC|SIGNED,
+    UNKNOWN|SIGNED; the brute-force and separable forms agree"""
+    MLMap, _ = mods
+    rng = np.random.default_rng(C)
+    obs = rng.integers([-30, -25, -12], [25, 30, 10], size=(150, 3))
+    plane = np.stack(np.meshgrid(np.arange(-20, 15), np.arange(-18, 12), indexing="ij"), -1).reshape(-1, 2)
+    obs = np.concatenate([obs, np.column_stack([np.full(len(plane), 7), plane])])  # the plane x = 7
+    free = np.stack(np.meshgrid(np.arange(-4, 3), np.arange(-4, 3), np.arange(-2, 2), indexing="ij"), -1).reshape(-1, 3)
+    m = Crafted(MLMap, obs, free)
+    for lo, dims in [([-23, -17, -9], [31, 26, 13]), ([3, -11, 0], [17, 1, 9]), ([-13, -5, 2], [22, 19, 1]), ([-1, -1, -1], [1, 1, 1])]:
+        glo, gd = grown(lo, dims, C)
+        for flags in (OCC, OCC | SIGNED, UNKNOWN | SIGNED):
+            mask = m.mask(glo, gd, flags)
+            assert np.array_equal(mask, window_mask(m.gpu, glo, gd, flags))
+            exp = expected(mask, C, bool(flags & SIGNED), S1.subbox_d_xyz)
+            if flags == OCC:
+                check(exp, expected_brute(m.obs_xyz, lo, dims, C, S1.subbox_d_xyz), "numpy forms")
+            check(esdf(m.gpu, lo, dims, C, flags), exp, f"C={C} {lo} {dims} flags={flags}")
+    m.gpu.close()
+
+
+# ---- real maps ----------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def s1_maps(mods):
+    """S1 after six room_jitter frames, inflate_map after the third and the fifth, on the GPU and in the oracle"""
+    MLMap, OracleMap = mods
+    gpu, cpu = MLMap(S1, max_blocks=8192), OracleMap(S1)
+    for k, (img, (q, t)) in enumerate(syn.stream(S1, "room_jitter", "smooth", 6)):
+        gpu.update_map(img, q, t)
+        cpu.update_depth(img, q, t)
+        if k in (2, 4):
+            gpu.inflate_map(t)
+            cpu.inflate_map(t)
+    yield gpu, cpu
+    gpu.close()
+
+
+def map_window(b, cfg):
+    n = cfg.subbox_n
+    lo = b["keys"].min(0) * n - 7
+    hi = (b["keys"].max(0) + 2) * n - 4
+    return [int(v) for v in lo], [int(v) for v in hi - lo]
+
+
+@pytest.mark.parametrize("flags", [OCC, OCC | INFL, UNKNOWN, OCC | SIGNED, OCC | INFL | SIGNED, UNKNOWN | SIGNED])
+def test_real_map_against_oracle(s1_maps, flags):
+    """C = 16 over a window around the whole map: the field of the oracle's classes at the voxel centres, and the same from the
+    GPU's export_window classes"""
+    gpu, cpu = s1_maps
+    C = 16
+    lo, dims = map_window(cpu.export_blocks(), S1)
+    glo, gd = grown(lo, dims, C)
+    mask = oracle_mask(cpu, S1, glo, gd, flags)
+    assert np.array_equal(mask, window_mask(gpu, glo, gd, flags))
+    assert 0 < mask.sum() < mask.size
+    exp = expected(mask, C, bool(flags & SIGNED), S1.subbox_d_xyz)
+    got = esdf(gpu, lo, dims, C, flags)
+    check(got, exp, f"flags={flags}")
+    if flags & UNKNOWN:  # (observed space is everywhere within C of unknown space)
+        assert (got["sqdist"] > 0).any() and (got["sqdist"] <= 0).any()
+    else:
+        assert (got["sqdist"] == C * C).any() and (got["sqdist"] < C * C).any()
+    if flags & SIGNED:
+        assert (got["sqdist"] < 0).any() == bool((mask[C:-C, C:-C, C:-C]).any())
+
+
+def test_frontier_mode_and_empty_map(mods):
+    """frontier mode (released blocks answer from element 0, infl UNKNOWN) against the oracle's classes; an empty map gives C^2
+    for OCC, 0 for UNKNOWN and -C^2 for UNKNOWN|SIGNED"""
+    MLMap, OracleMap = mods
+    cfg = S1.with_(use_exploration_frontiers=True, subbox_n=5)
+    gpu, cpu = MLMap(cfg, max_blocks=16384, max_batch=2), OracleMap(cfg)
+    for img, (q, t) in syn.stream(cfg, "room_jitter", "smooth", 8):
+        gpu.update_map(img, q, t)
+        cpu.update_depth(img, q, t)
+    b = cpu.export_blocks()
+    assert b["collapsed"].sum() > 20
+    C = 7
+    lo, dims = map_window(b, cfg)
+    glo, gd = grown(lo, dims, C)
+    for flags in (OCC | INFL, UNKNOWN | SIGNED):
+        mask = oracle_mask(cpu, cfg, glo, gd, flags)
+        check(esdf(gpu, lo, dims, C, flags), expected(mask, C, bool(flags & SIGNED), cfg.subbox_d_xyz), f"frontier flags={flags}")
+    gpu.close()
+
+    gpu = MLMap(S1, max_blocks=1024)
+    lo, dims = [-13, -5, -9], [37, 23, 11]
+    for C in (1, 9, 64):
+        w = esdf(gpu, lo, dims, C, OCC)
+        assert (w["sqdist"] == C * C).all() and not w["grad"].any()
+        assert (w["dist"] == np.float32(S1.subbox_d_xyz) * np.sqrt(np.float32(C * C))).all()
+        assert (esdf(gpu, lo, dims, C, UNKNOWN)["sqdist"] == 0).all()
+        w = esdf(gpu, lo, dims, C, UNKNOWN | SIGNED)
+        assert (w["sqdist"] == -C * C).all() and not w["grad"].any()
+    gpu.close()
+
+
+# ---- tiling -------------------------------------------------------------------------------------------------------------------
+def test_forced_tiles_equal_untiled(s1_maps, knobs):
+    """esdf_tile_vox at its smallest cuts a 400 x 60 x 6 window at C = 32 with gradients into dozens of row tiles: the same bytes
+    as one tile, into host and device memory"""
+    import torch
+
+    gpu, cpu = s1_maps
+    b = cpu.export_blocks()
+    n, C = S1.subbox_n, 32
+    mid = ((b["keys"].min(0) + b["keys"].max(0) + 1) * n) // 2
+    dims = [400, 60, 6]
+    lo = [int(mid[0]) - 200, int(mid[1]) - 30, int(mid[2]) - 3]
+    H = C
+    T1 = MIN_BOX // ((dims[0] + 2 * H) * (1 + 2 * H)) - 2 * H  # (mlm_esdf_plan: rows of one plane)
+    assert 1 <= T1 < dims[1] and -(-dims[1] // T1) * dims[2] >= 24
+    ref = {f: esdf(gpu, lo, dims, C, f) for f in (OCC, OCC | INFL | SIGNED)}
+    for f, r in ref.items():
+        assert (r["sqdist"] < C * C).any() and (r["sqdist"] == C * C).any()
+    knobs.set("esdf_tile_vox", MIN_BOX)
+    shape = (dims[2], dims[1], dims[0])
+    for f, r in ref.items():
+        got = esdf(gpu, lo, dims, C, f)
+        for k in r:
+            assert np.array_equal(got[k].view(np.uint8), r[k].view(np.uint8)), (f, k)
+        dev = {"sqdist": torch.empty(shape, dtype=torch.int32, device="cuda"), "dist": torch.empty(shape, dtype=torch.float32, device="cuda"),
+               "grad": torch.empty(shape + (3,), dtype=torch.float32, device="cuda")}
+        gpu.export_esdf_dev(lo, dims, C, occ=True, infl=bool(f & INFL), signed=bool(f & SIGNED), **{k: v.data_ptr() for k, v in dev.items()})
+        for k, v in dev.items():
+            assert np.array_equal(v.cpu().numpy().view(np.uint8), r[k].view(np.uint8)), (f, k)
+
+
+def test_large_window(s1_maps):
+    """512 x 512 x 64 at C = 32 (a grown box past the default voxel cap: two tiles) against the separable numpy field"""
+    gpu, _ = s1_maps
+    C = 32
+    lo, dims = [-250, -240, -20], [512, 512, 64]
+    glo, gd = grown(lo, dims, C)
+    mask = window_mask(gpu, glo, gd, OCC)
+    assert mask.sum() > 1000
+    got = gpu.export_esdf(lo, dims, C, sqdist=True, dist=True)
+    check(got, {k: v for k, v in expected(mask, C, False, S1.subbox_d_xyz).items() if k != "grad"}, "large")
+
+
+# ---- destinations, modes, arguments ------------------------------------------------------------------------------------------
+def test_async_stream_and_device_destinations(mods):
+    """async mode: the field sees every submitted frame; the caller's stream and device tensors give the host result; the scratch
+    grows at the first call and stays"""
+    import torch
+
+    MLMap, OracleMap = mods
+    nf = 8
+    frames = np.stack([img for img, _ in syn.stream(S1, "room_jitter", "smooth", nf)])
+    poses = syn.smooth_trajectory(nf, 42)
+    q, t = np.stack([p[0] for p in poses]), np.stack([p[1] for p in poses])
+    gpu, cpu = MLMap(S1, max_blocks=8192, max_batch=4), OracleMap(S1)
+    for k in range(nf):
+        cpu.update_depth(frames[k], q[k], t[k])
+    before = gpu.frame_stats()["device_bytes"]
+    gpu.set_async(True)
+    gpu.update_map_batch(frames, q, t)  # no sync()
+    C = 12
+    lo, dims = map_window(cpu.export_blocks(), S1)
+    w = esdf(gpu, lo, dims, C, OCC | SIGNED)
+    glo, gd = grown(lo, dims, C)
+    check(w, expected(oracle_mask(cpu, S1, glo, gd, OCC | SIGNED), C, True, S1.subbox_d_xyz), "async")
+    grown_bytes = gpu.frame_stats()["device_bytes"]
+    assert grown_bytes > before
+    esdf(gpu, lo, dims, C, OCC | SIGNED)
+    assert gpu.frame_stats()["device_bytes"] == grown_bytes
+
+    s = torch.cuda.Stream()
+    gpu.set_stream(s.cuda_stream)
+    shape = (dims[2], dims[1], dims[0])
+    dev = {"sqdist": torch.empty(shape, dtype=torch.int32, device="cuda"), "dist": torch.empty(shape, dtype=torch.float32, device="cuda"),
+           "grad": torch.empty(shape + (3,), dtype=torch.float32, device="cuda")}
+    junk = torch.ones(1 << 26, device="cuda")
+    with torch.cuda.stream(s):
+        for _ in range(50):  # (keeps the caller's stream busy: the field is written behind this work)
+            junk.mul_(1.0001)
+        for v in dev.values():
+            v.fill_(7)
+    gpu.export_esdf_dev(lo, dims, C, signed=True, **{k: v.data_ptr() for k, v in dev.items()})
+    for k, v in dev.items():
+        assert np.array_equal(v.cpu().numpy().view(np.uint8), w[k].view(np.uint8)), k
+    assert gpu.frame_stats()["device_bytes"] == grown_bytes
+    gpu.close()
+
+
+def test_invalid_arguments(mods):
+    """each refused argument gives MLM_ERR_INVALID and leaves the handle usable; the int32 extremes are absent blocks"""
+    MLMap, _ = mods
+    gpu = MLMap(S1, max_blocks=1024)
+    L, h = gpu._L, gpu._h
+    buf = np.zeros(1 << 16, dtype=np.int32)
+    p = buf.ctypes.data_as(ctypes.c_void_p)
+
+    def call(lo, dims, C=5, flags=OCC, outs=(p, None, None)):
+        lo_a, dims_a = np.array(lo, dtype=np.int32), np.array(dims, dtype=np.int32)
+        return L.mlm_export_esdf(h, lo_a.ctypes.data_as(ctypes.c_void_p), dims_a.ctypes.data_as(ctypes.c_void_p), C, flags, *outs)
+
+    cases = [([0, 0, 0], [0, 4, 4]), ([0, 0, 0], [4, -1, 4]), ([0, 0, 0], [4, 4, 0]),
+             ([0, 0, 0], [2048, 2048, 1024]), ([0, 0, 0], [65536, 32768, 1]),
+             ([2 ** 31 - 10, 0, 0], [20, 1, 1]), ([0, 0, 2 ** 31 - 1], [1, 1, 1])]
+    for lo, dims in cases:
+        assert call(lo, dims) == -1, (lo, dims)
+        assert call([0, 0, 0], [4, 4, 4]) == 0
+    for C in (0, -1, 65, 1 << 20):
+        assert call([0, 0, 0], [4, 4, 4], C=C) == -1, C
+        assert call([0, 0, 0], [4, 4, 4]) == 0
+    for flags in (0, SIGNED, 16, OCC | 16, OCC | 1 << 30, -1):
+        assert call([0, 0, 0], [4, 4, 4], flags=flags) == -1, flags
+        assert call([0, 0, 0], [4, 4, 4]) == 0
+    assert call([0, 0, 0], [4, 4, 4], outs=(None, None, None)) == -1
+    assert call([0, 0, 0], [4, 4, 4], C=64, flags=OCC | INFL | UNKNOWN | SIGNED) == 0
+    assert (buf[:64] == -64 * 64).all()  # (an empty map: every voxel UNKNOWN, 64 or more from a known one)
+    w = gpu.export_esdf([2 ** 31 - 11, -2 ** 31, 0], [10, 3, 2], 64, **ALL)  # the int32 extremes: absent blocks
+    assert (w["sqdist"] == 64 * 64).all() and not w["grad"].any()
+    w = gpu.export_esdf([2 ** 31 - 11, -2 ** 31, 0], [10, 3, 2], 64, occ=False, unknown=True, signed=True, **ALL)
+    assert (w["sqdist"] == -64 * 64).all() and not w["grad"].any()
+    gpu.close()
