@@ -283,7 +283,8 @@ int mlm_sync(mlm_handle *h);
  * everything that reads the map afterwards is ordered behind it).  Host buffers stay BORROWED FOR THE CALL in both modes: an asynchronous call returns
  * only after its copies out of the caller's buffer have completed (also from a buffer pinned with mlm_host_register, whose
  * copies are truly asynchronous) — the buffer may be refilled as soon as the call returns.  Device inputs of the *_dev entry
- * points are read by the frames' kernels and must stay unmodified until mlm_sync (or until three further batches were submitted). */
+ * points are read by the frames' kernels and must stay unmodified until mlm_sync (or until three further batches were submitted).
+ * A call whose frames leave the sector path (a fall-back, a frame too wide for it) runs them one by one and returns once they are applied. */
 int mlm_set_async(mlm_handle *h, int on);
 /* Small query batches (a planner asking position by position, include/mlmap.h:170-295) are answered from a pinned HOST copy of the
  * block planes (6 bytes per voxel + 13 per block), which grows with the map.  max_bytes bounds that pinned memory (default 1 GiB;
@@ -312,8 +313,8 @@ int mlm_enable_kernel_timing(mlm_handle *h, int on);
 int mlm_set_timed_kernel(mlm_handle *h, const char *name, int every);
 
 /* Test and experiment knobs — NOT part of the drop-in contract.  Named integers read by the NEXT mlm_create of this process:
- * forced fall-backs ("sec_fail_every", "sec_backoff", "sectors"), simulated allocation failures ("debug_fail_slot"), a fixed pool
- * ("pool_grow"), slot layout ("lean_slots", "slot_sets"), launch geometries ("sec_tab", "sec_threads", "rank_grid", ...; the full
+ * forced fall-backs ("sec_fail_every", "sec_backoff", "sectors"), a fixed pool ("pool_grow"), slot layout ("slot_sets"), launch
+ * geometries ("sec_tab", "sec_threads", "rank_grid", ...; the full
  * list is kKnobNames in mlmapping_amd/csrc/mlm_handle.h).  Unknown names: MLM_ERR_INVALID.  mlm_debug_reset forgets them all.  The library reads
  * no environment variable for behaviour; MLM_DEBUG_CREATE / MLM_DEBUG_ALLOC / MLM_DEBUG_DRAIN only print diagnostics. */
 int mlm_debug_set(const char *name, long long value);

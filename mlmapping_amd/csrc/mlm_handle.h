@@ -21,11 +21,11 @@ struct KernelTime {
     hipEvent_t a, b;
 };
 
-// Test and experiment knobs (mlm_debug_set): named integers that mlm_create reads — launch geometries, forced fall-backs,
-// simulated allocation failures.  Process-wide, not part of the drop-in contract; the library reads no environment variable
-// for them (only the three diagnostic switches MLM_DEBUG_CREATE / MLM_DEBUG_ALLOC / MLM_DEBUG_DRAIN, which print).
+// Test and experiment knobs (mlm_debug_set): named integers that mlm_create reads — launch geometries, forced fall-backs.
+// Process-wide, not part of the drop-in contract; the library reads no environment variable for them (only the three diagnostic
+// switches MLM_DEBUG_CREATE / MLM_DEBUG_ALLOC / MLM_DEBUG_DRAIN, which print).
 const char *const kKnobNames[] = {"agg_lds", "big_arm", "big_grid", "bin_block", "chain_grid", "collect_grid", "cu_reserve", "cu_split",
-                                  "debug_fail_slot", "esdf_tile_vox", "ex_spec", "expand_block", "graph", "lean_slots", "logit_exact", "mirror", "mirror_max", "mirror_mb", "need_slots", "node_lds", "pool_grow",
+                                  "esdf_tile_vox", "ex_spec", "expand_block", "graph", "logit_exact", "mirror", "mirror_max", "mirror_mb", "need_slots", "node_lds", "pool_grow",
                                   "rank_grid", "sc_block", "sc_grid", "sec_backoff", "sec_fail_every", "sec_tab", "sec_tab_big", "sec_threads",
                                   "sectors", "single_apply_grid", "single_chain_grid", "single_rank_grid", "slot_sets", "sort_block", "sort_grid", "tile_grid", "tile_sh"};
 struct KnobStore {
@@ -75,9 +75,9 @@ struct MlmSlot {
     bool sector = false;      // the frame it holds went through the sector path (Stage A and the frame-local voxel grid)
     bool keys_exact = false;  // hl_key of the frame it holds was written by order_hits_exact (a replay must not recompute it:
                               // the emulated container's policy state has moved on)
-    MlmDev Pfb{};              // the parameter block a CELL-TABLE Stage A / apply of this slot's frame runs with: the buffers that path shares
-                               // across the slots (lean slots) and, where the slot's own lists are sized by need, the handle's one
-                               // full-size set of them (eff_params)
+    MlmDev Pfb{};              // sector-path handles: the parameter block a CELL-TABLE Stage A / apply of this slot's frame runs with: the
+                               // buffers that path shares across the slots and, where the slot's own lists are sized by need, the handle's
+                               // one full-size set of them (eff_params)
     uint16_t *d_img = nullptr; // staging for host images
     size_t img_cap = 0;
     int32_t *d_pix = nullptr;
@@ -173,11 +173,10 @@ struct mlm_handle {
     unsigned int sort_grid = 256;            // blocks per frame of k_sort_contribs<1024> in a batch
     unsigned int rank_grid = 128;            // blocks per frame of k_rank in a batch (config 2 with two cells per wave: 87.5k frames/s, 64: 87.7k, 256: 86.4k,
                                              // 512: 84.7k; MLM_RANK_GRID)
-    // Lean frame slots (sector-path handles): the three large buffers only the cell-table Stage A uses — the block slices of
-    // contribution nodes sized for its LDS overflow, the (block, cell) pairs and the node lists — exist ONCE per handle instead
-    // of once per slot; a cell-table Stage A (a frame's fall-back, or a batch submitted while the sector path backs off) then
-    // runs one frame at a time, ordered by fb_done across the sets' streams.
-    bool lean = false;
+    // Sector-path handles: the three large buffers only the cell-table Stage A uses — the block slices of contribution nodes sized
+    // for its LDS overflow, the (block, cell) pairs and the node lists — exist ONCE per handle instead of once per slot; a
+    // cell-table Stage A (a frame's fall-back, or a batch submitted while the sector path backs off) then runs one frame at a
+    // time, ordered by fb_done across the sets' streams.
     MlmDev *d_slot_tab_fb = nullptr;         // the slots' constants with those three buffers pointing at the shared ones
     hipEvent_t fb_done = nullptr;
     size_t map_bytes = 0;                    // ... of it the map, its tables and the buffers shared by all frame slots
@@ -278,10 +277,10 @@ struct mlm_handle {
     long long n_pool_grows = 0;
     long long n_big_redos = 0;   // frames whose overflowed columns were redone with the large table at drain time (redo_overflow_columns)
     size_t grow_failed_at = 0;   // a pool of this many blocks did not fit the device (grow_pool does not retry it)
-    MlmNode *fb_bnodes = nullptr, *fb_nodes = nullptr; // lean slots: the cell-table path's shared buffers
+    MlmNode *fb_bnodes = nullptr, *fb_nodes = nullptr; // sector-path handles: the cell-table path's shared buffers
     MlmPair *fb_pairs = nullptr;
     MlmMirror mir;               // host mirror for small query batches (mlm_mirror.h)
-    // Frame slots sized by NEED (sector-path handles with lean slots, not frontier mode): the per-frame lists whose worst case is
+    // Frame slots sized by NEED (sector-path handles, not frontier mode): the per-frame lists whose worst case is
     // "every awareness cell is a multi-kind hit" start at what a camera frame of max_points pixels needs and are doubled at a
     // drained point when a frame's Stage A runs out of room (grow_slots, like grow_pool for the block pool).  The cell-table path,
     // which a frame falls back to one at a time, gets ONE full-size set of those lists per handle, allocated at its first use.
@@ -403,8 +402,8 @@ inline void note_fallback(mlm_handle *h, int frame_no) {
         h->sector_backoff = h->sector_backoff_len; // (it had the pass and gave up all the same)
     }
 }
-// lean slots of a sector-path handle outside frontier mode: the cell-table path's per-frame state exists once (alloc_slot)
-inline bool share_ct(const mlm_handle *h) { return h->lean && !h->P.explore; }
+// a sector-path handle outside frontier mode: the cell-table path's per-frame state exists once (alloc_slot)
+inline bool share_ct(const mlm_handle *h) { return h->use_sectors && !h->P.explore; }
 int drain(mlm_handle *h, bool g_copied = false);
 int grow_pool(mlm_handle *h, size_t want);
 int ensure_free_blocks(mlm_handle *h, size_t need);
@@ -414,7 +413,7 @@ int grow_slots(mlm_handle *h, const MlmCounters &demand);
 int grow_sbkt(mlm_handle *h, size_t buckets);
 int ensure_ct_full(mlm_handle *h);
 // the parameter block the kernels of slot S's frame run with on the path the frame is on (see MlmSlot::Pfb)
-inline const MlmDev &eff_params(const mlm_handle *h, const MlmSlot &S) { return (S.sector || !h->lean) ? S.P : S.Pfb; }
+inline const MlmDev &eff_params(const mlm_handle *h, const MlmSlot &S) { return (S.sector || !h->use_sectors) ? S.P : S.Pfb; }
 void mirror_mark_all(mlm_handle *h);
 void mirror_mark_box(mlm_handle *h, const int lo[3], const int hi[3]);
 void mirror_mark_frames(mlm_handle *h, int n);

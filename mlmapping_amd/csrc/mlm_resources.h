@@ -168,11 +168,10 @@ void free_pool(mlm_handle *h, const MlmDev &P) {
 // least `want` blocks, the blocks copied over, the table rebuilt on the device, every parameter block re-pointed.  Nothing
 // may be in flight (callers drain first).  MLM_ERR_CAPACITY only if the device cannot hold the larger pool.
 // the slots' parameter blocks as the kernels see them (device-resident tables), after the host copies changed
-// MlmSlot::Pfb from MlmSlot::P: the buffers the cell-table path shares across lean slots, and — slots sized by need — the handle's
-// full-size set of the lists that path fills (null until ensure_ct_full has run: no cell-table frame before that)
+// MlmSlot::Pfb from MlmSlot::P (sector-path handles): the buffers the cell-table path shares across the slots, and — slots sized by
+// need — the handle's full-size set of the lists that path fills (null until ensure_ct_full has run: no cell-table frame before that)
 void make_fb_params(mlm_handle *h, MlmSlot &S) {
     S.Pfb = S.P;
-    if (!h->lean) return;
     S.Pfb.bnodes = h->fb_bnodes;
     S.Pfb.pairs = h->fb_pairs;
     S.Pfb.nodes = h->fb_nodes;
@@ -189,9 +188,11 @@ int upload_slot_tab(mlm_handle *h) {
     std::vector<MlmDev> tab(h->slots.size());
     for (size_t i = 0; i < h->slots.size(); ++i) tab[i] = h->slots[i].P;
     HIPCHK(h, hipMemcpy(h->d_slot_tab, tab.data(), tab.size() * sizeof(MlmDev), hipMemcpyHostToDevice));
-    for (auto &S : h->slots) make_fb_params(h, S);
-    if (h->lean && h->d_slot_tab_fb) {
-        for (size_t i = 0; i < tab.size(); ++i) tab[i] = h->slots[i].Pfb;
+    if (h->d_slot_tab_fb) {
+        for (size_t i = 0; i < tab.size(); ++i) {
+            make_fb_params(h, h->slots[i]);
+            tab[i] = h->slots[i].Pfb;
+        }
         HIPCHK(h, hipMemcpy(h->d_slot_tab_fb, tab.data(), tab.size() * sizeof(MlmDev), hipMemcpyHostToDevice));
     }
     return MLM_OK;
@@ -317,12 +318,6 @@ int ensure_free_blocks(mlm_handle *h, size_t need) {
 }
 
 int alloc_slot(mlm_handle *h, MlmSlot &S, size_t index, const std::vector<float> &sigma3) {
-    if (!h->lean) // (test hook: the full slots "do not fit" from slot k on, so that the lean retry of mlm_create runs)
-        if (long long kv; knob("debug_fail_slot", kv))
-            if ((long long)index >= kv) {
-                h->err = "simulated allocation failure (MLM_DEBUG_FAIL_SLOT)";
-                return MLM_ERR_HIP;
-            }
     S.P = h->P;
     MlmDev &P = S.P;
     int rc;
@@ -330,11 +325,11 @@ int alloc_slot(mlm_handle *h, MlmSlot &S, size_t index, const std::vector<float>
     const mlm_handle::SlotCaps &caps = h->caps_now; // (== caps_worst unless the slots are sized by need)
     S.h_ctr = h->h_ctr_all + index;
     P.ctr = h->d_ctr_all + index;
-    // Lean slots of a sector-path handle (not frontier mode, whose own map-dependent part reads them per frame): the per-frame
-    // state only the cell-table path keeps — per-cell records, miss-mask copies, queues, the voxel addresses of its two
-    // map-dependent kernels — exists ONCE, in slot 0's name; a frame that takes that path (a fall-back, a batch submitted while
-    // the sector path backs off, a frame too wide for it) runs alone from its Stage A to the end of its apply kernel.
-    const bool share = h->lean && !P.explore, own = !share || index == 0;
+    // A sector-path handle (not frontier mode, whose own map-dependent part reads them per frame): the per-frame state only the
+    // cell-table path keeps — per-cell records, miss-mask copies, queues, the voxel addresses of its two map-dependent kernels —
+    // exists ONCE, in slot 0's name; a frame that takes that path (a fall-back, a batch submitted while the sector path backs off,
+    // a frame too wide for it) runs alone, confirmed before the next frame's Stage A (submit_batch).
+    const bool own = !share_ct(h) || index == 0;
 #define MLM_CT_ALLOC(field, count)                                                                                    \
     do {                                                                                                              \
         if (!own) P.field = h->slots[0].P.field;                                                                      \
@@ -354,9 +349,9 @@ int alloc_slot(mlm_handle *h, MlmSlot &S, size_t index, const std::vector<float>
     // (256 work items per bin block; image edges and short lists add blocks: twice the quotient + 256)
     P.nb_cap = (unsigned int)((size_t)h->lim.max_points / 128 + 256);
     if ((rc = dev_alloc(h, &P.blk_stats, 4 * (size_t)P.nb_cap))) return rc;
-    // (lean: k_bin_sectors writes at most 256 records per block; the cell-table path's buffers are shared, mlm_create)
-    if ((rc = dev_alloc(h, &P.bnodes, (size_t)P.nb_cap * (h->lean ? 256u : P.node_lds)))) return rc;
-    if (!h->lean && (rc = dev_alloc(h, &P.pairs, (size_t)P.nb_cap * P.agg_lds))) return rc;
+    // (sector path: k_bin_sectors writes at most 256 records per block; the cell-table path's buffers are shared, mlm_create)
+    if ((rc = dev_alloc(h, &P.bnodes, (size_t)P.nb_cap * (h->use_sectors ? 256u : P.node_lds)))) return rc;
+    if (!h->use_sectors && (rc = dev_alloc(h, &P.pairs, (size_t)P.nb_cap * P.agg_lds))) return rc;
     {
         // most contributions one point can make: centre + (+d,-d) while d < 3*sigma(rho) (map_awareness.cpp:149)
         int dmax = 0;
@@ -381,7 +376,7 @@ int alloc_slot(mlm_handle *h, MlmSlot &S, size_t index, const std::vector<float>
         if ((rc = dev_alloc(h, &P.contrib, caps.sub))) return rc;
         if ((rc = dev_alloc(h, &P.subs, caps.sub))) return rc;
         P.node_cap = (unsigned int)(cap / MLM_RAY_LISTS + 4096);
-        if (!h->lean && (rc = dev_alloc(h, &P.nodes, (size_t)MLM_RAY_LISTS * P.node_cap))) return rc;
+        if (!h->use_sectors && (rc = dev_alloc(h, &P.nodes, (size_t)MLM_RAY_LISTS * P.node_cap))) return rc;
     }
     if ((rc = dev_alloc(h, &P.ov_list, (size_t)P.nPhi))) return rc;
     P.chunk_cap = P.nb_cap; // a column can at most get one run from every bin block

@@ -91,10 +91,10 @@ inline unsigned int book_grid(const MlmDev &P, const MlmFrame &F, int mode, int 
 
 // Stage A of a whole batch (slots base..base+n, same mode and image geometry) on stream_a: awareness raycast ->
 // unique hit lists (+odds) and miss masks.  One launch per kernel covers all n frames (blockIdx.z = slot).
-// on_main: on the main stream instead of the slot set's (lean slots whose cell-table state is shared: the frame runs alone,
-// its map-dependent kernels follow on the same stream).
+// on_main: on the main stream instead of the slot set's (a sector-path handle, whose cell-table state is shared: the frame runs
+// alone, its map-dependent kernels follow on the same stream).
 int launch_stage_a_batch(mlm_handle *h, int base, int n, bool on_main = false) {
-    if (h->lean && n > 1) { // the cell-table path's large buffers exist once per handle: one frame at a time
+    if (h->use_sectors && n > 1) { // the cell-table path's large buffers exist once per handle: one frame at a time
         for (int j = 0; j < n; ++j) {
             const int rc = launch_stage_a_batch(h, base + j, 1, on_main);
             if (rc) return rc;
@@ -105,7 +105,7 @@ int launch_stage_a_batch(mlm_handle *h, int base, int n, bool on_main = false) {
         const int rc = ensure_ct_full(h); // (slots sized by need: this path's own full-size lists, at its first use)
         if (rc) return rc;
     }
-    const MlmDev *slot_tab = h->lean ? h->d_slot_tab_fb : h->d_slot_tab;
+    const MlmDev *slot_tab = h->use_sectors ? h->d_slot_tab_fb : h->d_slot_tab;
     const MlmSlot &S0 = h->slots[(size_t)base];
     const MlmDev &P = S0.P;
     const MlmFrame &F = S0.F;
@@ -129,7 +129,7 @@ int launch_stage_a_batch(mlm_handle *h, int base, int n, bool on_main = false) {
     HIPCHK(h, hipMemcpyAsync(h->d_frame_tab + base, h->h_frame_tab + base, (size_t)n * sizeof(MlmFrame),
                              hipMemcpyHostToDevice, st));
     HIPCHK(h, hipMemsetAsync(h->d_ctr_all + base, 0, (size_t)n * sizeof(MlmCounters), st));
-    if (h->lean && !on_main) HIPCHK(h, hipStreamWaitEvent(st, h->fb_done, 0)); // (the previous user of the shared buffers, on whatever stream)
+    if (h->use_sectors && !on_main) HIPCHK(h, hipStreamWaitEvent(st, h->fb_done, 0)); // (the previous user of the shared buffers, on whatever stream)
     unsigned int nb = 0;
     if (F.n > 0) {
         nb = bin_grid(P, F, mode);
@@ -185,7 +185,7 @@ int launch_stage_a_batch(mlm_handle *h, int base, int n, bool on_main = false) {
     }
     if (P.explore)
         tlaunch(h, "k_ex_collect_misses", k_ex_collect_misses, dim3(1024, 1, n), dim3(MLM_BLOCK), 0, st, slot_tab, h->d_frame_tab, base);
-    if (h->lean) HIPCHK(h, hipEventRecord(h->fb_done, st));
+    if (h->use_sectors) HIPCHK(h, hipEventRecord(h->fb_done, st));
     if (!on_main) HIPCHK(h, hipEventRecord(h->stage_a_done[set], st));
     return MLM_OK;
 }

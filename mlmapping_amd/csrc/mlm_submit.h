@@ -71,6 +71,15 @@ int fix_pool_short(mlm_handle *h, MlmSlot &R) {
     return MLM_OK;
 }
 
+// The inputs of a call went up on stream `up`, its Stage A runs on `target`: order it behind them.
+int order_behind_upload(mlm_handle *h, hipStream_t up, hipStream_t target) {
+    if (!up || up == target) return MLM_OK;
+    if (!h->upload_ev) HIPCHK(h, hipEventCreateWithFlags(&h->upload_ev, hipEventDisableTiming));
+    HIPCHK(h, hipEventRecord(h->upload_ev, up));
+    HIPCHK(h, hipStreamWaitEvent(target, h->upload_ev, 0));
+    return MLM_OK;
+}
+
 int submit_batch(mlm_handle *h, int base, int n) {
     if (h->hit_n_bkt > h->max_buckets) {
         h->err = "emulated bucket count exceeds capacity";
@@ -92,41 +101,35 @@ int submit_batch(mlm_handle *h, int base, int n) {
         rc = ensure_free_blocks(h, (h->pending.size() + (size_t)n) * h->frame_block_bound);
         if (rc) return rc;
     }
-    for (int j = 0; j < n; ++j) {
-        MlmSlot &S = h->slots[(size_t)(base + j)];
+    auto stamp = [&](MlmSlot &S) {
         S.seq = h->next_seq++;
         S.F.seq = S.seq;
         S.F.rehash_thr = (unsigned int)std::min<size_t>(h->hit_pol._M_next_resize, 0xFFFFFFFFu);
-    }
-    for (int j = 0; j < n; ++j) {
-        h->slots[(size_t)(base + j)].sector = sectors;
-        h->slots[(size_t)(base + j)].keys_exact = false;
-    }
+        S.sector = sectors;
+        S.keys_exact = false;
+    };
     if (!sectors && share_ct(h)) {
-        // the cell-table path's per-frame state exists once: every frame runs alone, Stage A and the two map-dependent kernels
-        // back to back on the main stream (behind whatever the frames before it left there)
-        HIPCHK(h, hipStreamWaitEvent(h->stream, h->set_free[set], 0));
-        if (h->async_mode) {
-            // (an asynchronous call's inputs — image, pixel list, points — went up on the set's Stage A stream, where its Stage A was
-            // expected to run: run_slots_inner; this one runs on the main stream, which must wait for them.  Found by the recovery fuzzer's
-            // scenario in tests/test_gpu_small_frames.py: a list read before it had arrived, one run in twenty-five.)
-            if (!h->upload_ev) HIPCHK(h, hipEventCreateWithFlags(&h->upload_ev, hipEventDisableTiming));
-            HIPCHK(h, hipEventRecord(h->upload_ev, h->stream_as[set]));
-            HIPCHK(h, hipStreamWaitEvent(h->stream, h->upload_ev, 0));
-        }
-        for (int j = 0; j < n; ++j) {
+        // the cell-table path's per-frame state exists once: with nothing else in flight, frame by frame on the main stream — Stage A,
+        // the two map-dependent kernels, then drain confirms the frame (replaying it if its speculation failed) before the next one's
+        // Stage A reuses the shared buffers.  (An asynchronous call's inputs went up on the set's Stage A stream: run_slots_inner.)
+        rc = drain(h);
+        if (rc == MLM_OK) rc = order_behind_upload(h, h->async_mode ? h->stream_as[set] : h->stream, h->stream);
+        for (int j = 0; j < n && rc == MLM_OK; ++j) {
             MlmSlot &S = h->slots[(size_t)(base + j)];
+            stamp(S); // (here, not up front: a drain may restart the sequence numbers)
             rc = launch_stage_a_batch(h, base + j, 1, true);
             if (rc) return rc;
             launch_stage_bc(h, S, h->hit_n_bkt);
-            HIPCHK(h, hipMemcpyAsync(S.h_ctr, S.P.ctr, sizeof(MlmCounters), hipMemcpyDeviceToHost, h->stream)); // (before the next frame's Stage A
-            h->pending.push_back(&S);                                                                              // reuses nothing of it, but for symmetry)
+            HIPCHK(h, hipMemcpyAsync(S.h_ctr, S.P.ctr, sizeof(MlmCounters), hipMemcpyDeviceToHost, h->stream));
+            h->pending.push_back(&S);
+            rc = drain(h);
         }
-        HIPCHK(h, hipMemcpyAsync(h->h_gb[set], h->P.g, sizeof(MlmGlobal), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipEventRecord(h->batch_done[set], h->stream));
-        HIPCHK(h, hipEventRecord(h->set_free[set], h->stream));
-        h->set_pending[set] = n;
-        return MLM_OK;
+        return rc;
+    }
+    for (int j = 0; j < n; ++j) stamp(h->slots[(size_t)(base + j)]);
+    if (share_ct(h) && !h->pending.empty() && !h->pending.back()->sector) { // (never: such a frame is confirmed before its call returns)
+        h->err = "a sector batch submitted while a frame of the shared cell-table path is pending";
+        return MLM_ERR_UNSUPPORTED;
     }
     {
         // (a synchronous call has nothing to overlap its Stage A with: on the main stream, no dependency between two streams — which
@@ -268,17 +271,12 @@ int drain(mlm_handle *h, bool g_copied) {
                     (size_t)h->hit_pol._M_next_resize, h->hit_n_bkt, h->pending.size(), S.h_ctr->sector_overflow);
         h->h_g->fail_frame = 0x7FFFFFFF;
         HIPCHK(h, hipMemcpyAsync(&h->P.g->fail_frame, &h->h_g->fail_frame, sizeof(int), hipMemcpyHostToDevice, h->stream));
-        bool any_sector = share_ct(h); // (async mode holds up to three batches: a cell-table batch may be followed by sector batches)
-        for (const MlmSlot *R : h->pending) any_sector = any_sector || R->sector;
-        if (any_sector) {
+        if (S.sector) { // (the frames in flight are all on one path: submit_batch)
             // Sector path: the frames in flight were binned into buckets with the bucket count of their submission, which
             // the rehash changes — every pending frame is finished with exact keys, in order (no further speculation).
-            // Cell-table frames among them are finished the same way (k_voxelize would read hl_slot / hl_cid / hl_bkey,
-            // which k_sector never writes for a frame of the sector path).
             for (size_t j = 0; j < h->pending.size(); ++j) {
                 MlmSlot &R = *h->pending[j];
-                // a sector frame whose Stage A gave up, or (shared cell-table state) a cell-table frame: the frames behind it
-                // have run their Stage A over the same buffers since — it takes the cell-table path from its Stage A on, alone
+                // a frame whose Stage A gave up takes the cell-table path from its Stage A on, alone
                 if (j == 0 && !R.h_ctr->sector_overflow) h->n_spec_miss++;
                 if (R.sector && R.h_ctr->sector_overflow == 1u) { // columns wait for the large-table pass (it was not scheduled)
                     rc = redo_overflow_columns(h, R);
@@ -306,7 +304,7 @@ int drain(mlm_handle *h, bool g_copied) {
                         if (rc) return rc;
                     }
                 }
-                if (R.h_ctr->sector_overflow || (!R.sector && share_ct(h))) {
+                if (R.h_ctr->sector_overflow) {
                     if (R.sector) {
                         h->n_sector_fallbacks++;
                         note_fallback(h, R.seq);
@@ -591,19 +589,10 @@ int run_slots_inner(mlm_handle *h, int n) {
     if (h->P.explore) { // frontier mode: exact ordering of both containers, no speculation
         const int K = h->lim.max_batch;
         {
-            // the call's inputs went up on one stream, its Stage A runs on another (synchronous calls: the main stream): order it behind
-            hipStream_t target = h->async_mode ? h->stream_as[h->cur_set] : h->stream;
-            if (h->last_upload && h->last_upload != target) {
-                hipError_t e = hipSuccess;
-                if (!h->upload_ev) e = hipEventCreateWithFlags(&h->upload_ev, hipEventDisableTiming);
-                if (e == hipSuccess) e = hipEventRecord(h->upload_ev, h->last_upload);
-                if (e == hipSuccess) e = hipStreamWaitEvent(target, h->upload_ev, 0);
-                if (e != hipSuccess) {
-                    h->err = std::string("ordering the upload: ") + hipGetErrorString(e);
-                    return MLM_ERR_HIP;
-                }
-            }
+            // (synchronous calls: Stage A on the main stream)
+            const int rc = order_behind_upload(h, h->last_upload, h->async_mode ? h->stream_as[h->cur_set] : h->stream);
             h->last_upload = nullptr;
+            if (rc) return rc;
         }
         {
             size_t in_flight = 0;
@@ -694,21 +683,9 @@ int run_slots_inner(mlm_handle *h, int n) {
     const int set = h->cur_set;
     int rc;
     const bool fast = single_fast_ok(h, n);
-    {
-        // the call's inputs went up on one stream, its Stage A may run on another: order it behind
-        hipStream_t target = (fast || !h->async_mode) ? h->stream : h->stream_as[set];
-        if (h->last_upload && h->last_upload != target) {
-            hipError_t e = hipSuccess;
-            if (!h->upload_ev) e = hipEventCreateWithFlags(&h->upload_ev, hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventRecord(h->upload_ev, h->last_upload);
-            if (e == hipSuccess) e = hipStreamWaitEvent(target, h->upload_ev, 0);
-            if (e != hipSuccess) {
-                h->err = std::string("ordering the upload: ") + hipGetErrorString(e);
-                return MLM_ERR_HIP;
-            }
-        }
-        h->last_upload = nullptr;
-    }
+    rc = order_behind_upload(h, h->last_upload, (fast || !h->async_mode) ? h->stream : h->stream_as[set]);
+    h->last_upload = nullptr;
+    if (rc) return rc;
     if (fast) {
         rc = submit_single_graph(h, set * K);
         if (rc == MLM_OK) rc = drain(h, true); // (the graph ends with the read-back of the map-wide flags)

@@ -373,10 +373,6 @@ int mlm_create(const mlm_config *cfg, const mlm_limits *lim_in, int device, mlm_
                                        // (blocks one tile may overlap: their pool slots live in k_tile's LDS)
                                        P.tile_combos <= MLM_TILE_COMBOS));
         if (knob("sectors", kv)) h->use_sectors = h->use_sectors && (int)kv != 0;
-        // (lean slots cost the worst-case scenes their batching — every frame overflowing its sector tables: 1.3k instead of
-        // 4.4k frames/s on the "scatter" scene — so they are used on request, or when the full slots do not fit the device)
-        h->lean = h->use_sectors;
-        if (knob("lean_slots", kv)) h->lean = h->use_sectors && (int)kv != 0;
         if (getenv("MLM_DEBUG_CREATE"))
             fprintf(stderr, "[create] sector path %d: LDS %u bytes per column (table %u entries), frame-local grid %d x %d x %d in %d tiles of edge %d (%u bytes of LDS each)\n",
                     (int)h->use_sectors, P.sec_lds_bytes, P.sec_tab, P.lv_nx, P.lv_ny, P.lv_nz, P.n_tiles, 1 << P.tile_sh, h->tile_lds_bytes);
@@ -514,34 +510,16 @@ int mlm_create(const mlm_config *cfg, const mlm_limits *lim_in, int device, mlm_
     }
     h->map_bytes = h->alloc_bytes;
     // frame slots sized by need (see mlm_handle::need_sized; knob "need_slots" = 0: every list at its worst case, as up to round 4)
-    h->need_sized = h->lean && h->use_sectors && !P.explore;
+    h->need_sized = h->use_sectors && !P.explore;
     if (knob("need_slots", kv)) h->need_sized = h->need_sized && (int)kv != 0;
     slot_capacities(h, sigma3);
     {
         // the frame slots are most of the footprint (S1 ~1 GB, S3 ~3.8 GB each): three sets of max_batch if they fit the device
-        // memory, else the same with lean slots (sector-path handles), else two sets (a few percent less throughput on config
-        // 2), else the error says what would be needed
+        // memory, else two sets (a few percent less throughput on config 2), else the error says what would be needed
         const size_t mark = h->allocs.size();
         size_t got = 0;
         for (; got < NS; ++got)
             if ((rc = alloc_slot(h, h->slots[got], got, sigma3))) break;
-        if (rc && h->use_sectors && !h->lean) {
-            (void)hipGetLastError();
-            for (size_t a = mark; a < h->allocs.size(); ++a)
-                if (h->allocs[a]) hipFree(h->allocs[a]);
-            h->allocs.resize(mark);
-            h->alloc_bytes = h->map_bytes;
-            for (auto &S : h->slots) // (the image staging buffers are not in `allocs`: ensure_img)
-                if (S.d_img) hipFree(S.d_img);
-            h->slots.assign(NS, MlmSlot{});
-            h->lean = true;
-            h->need_sized = !P.explore && !(knob("need_slots", kv) && (int)kv == 0);
-            slot_capacities(h, sigma3);
-            h->err.clear();
-            rc = MLM_OK;
-            for (got = 0; got < NS; ++got)
-                if ((rc = alloc_slot(h, h->slots[got], got, sigma3))) break;
-        }
         if (rc && got >= 2 * (size_t)h->lim.max_batch && h->n_sets > 2) {
             (void)hipGetLastError();
             // (keep the first two sets; give the partial third one back)
@@ -566,26 +544,15 @@ int mlm_create(const mlm_config *cfg, const mlm_limits *lim_in, int device, mlm_
             return rc;
         }
     }
-    {
-        std::vector<MlmDev> tab(NS);
-        for (size_t i = 0; i < NS; ++i) tab[i] = h->slots[i].P;
-        HIPCHK(h, hipMemcpy(h->d_slot_tab, tab.data(), NS * sizeof(MlmDev), hipMemcpyHostToDevice));
-        if (h->lean) {
-            const MlmDev &P0 = h->slots[0].P;
-            if ((rc = dev_alloc(h, &h->fb_bnodes, (size_t)P0.nb_cap * P0.node_lds))) return rc;
-            if ((rc = dev_alloc(h, &h->fb_pairs, (size_t)P0.nb_cap * P0.agg_lds))) return rc;
-            if ((rc = dev_alloc(h, &h->fb_nodes, (size_t)MLM_RAY_LISTS * P0.node_cap))) return rc;
-            for (size_t i = 0; i < NS; ++i) {
-                make_fb_params(h, h->slots[i]);
-                tab[i] = h->slots[i].Pfb;
-            }
-            if ((rc = dev_alloc(h, &h->d_slot_tab_fb, NS))) return rc;
-            HIPCHK(h, hipMemcpy(h->d_slot_tab_fb, tab.data(), NS * sizeof(MlmDev), hipMemcpyHostToDevice));
-            HIPCHK(h, hipEventCreateWithFlags(&h->fb_done, hipEventDisableTiming));
-        }
+    if (h->use_sectors) { // the cell-table path's buffers that the slots share (alloc_slot)
+        const MlmDev &P0 = h->slots[0].P;
+        if ((rc = dev_alloc(h, &h->fb_bnodes, (size_t)P0.nb_cap * P0.node_lds))) return rc;
+        if ((rc = dev_alloc(h, &h->fb_pairs, (size_t)P0.nb_cap * P0.agg_lds))) return rc;
+        if ((rc = dev_alloc(h, &h->fb_nodes, (size_t)MLM_RAY_LISTS * P0.node_cap))) return rc;
+        if ((rc = dev_alloc(h, &h->d_slot_tab_fb, NS))) return rc;
+        HIPCHK(h, hipEventCreateWithFlags(&h->fb_done, hipEventDisableTiming));
     }
-    if (!h->lean)
-        for (auto &S : h->slots) S.Pfb = S.P;
+    if ((rc = upload_slot_tab(h))) return rc;
     HIPCHK(h, hipDeviceSynchronize());
     if (getenv("MLM_DEBUG_CREATE"))
         fprintf(stderr, "[create] device memory: %.2f GB (%zu frame slots in %d sets of %d, %.3f GB each; the map and the shared tables %.2f GB)\n",

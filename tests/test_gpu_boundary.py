@@ -511,14 +511,10 @@ def test_bench_launcher_contract_two_ranks():
     assert mg["merge_ms"] > 0 and mg["union_blocks"] > mg["own_blocks"] > 0 and mg["merge_bytes_per_rank"] > 0
 
 
-def test_lean_slots_when_the_full_ones_do_not_fit(mods, monkeypatch, knobs):
-    """Full slots (MLM_LEAN_SLOTS=0: every frame slot with cell-table state of its own) are the exception now; mlm_create
-    falls back to lean slots (that state once per handle) when the full ones do not fit the device — simulated here: the first
-    attempt fails at the third slot.  The handle then works as usual, fall-backs to the cell-table path (forced on every
-    second frame) included."""
+def test_fallbacks_in_batches_share_one_cell_table_state(mods, monkeypatch, knobs):
+    """A sector-path handle keeps the cell-table path's per-frame state once, not per frame slot.  Fall-backs to that path
+    (forced on every second frame) in batches of two: each is redone alone on the shared state, and the map matches the oracle."""
     MLMap, OracleMap = mods
-    knobs.set("lean_slots", "0")
-    knobs.set("debug_fail_slot", "2")
     knobs.set("sec_fail_every", "2")
     knobs.set("sec_backoff", "0")
     cfg = S1
@@ -530,6 +526,6 @@ def test_lean_slots_when_the_full_ones_do_not_fit(mods, monkeypatch, knobs):
     gpu.update_map_batch(imgs, q, t)  # 2 + 2 + 2
     for img, (qq, tt) in frames:
         cpu.update_depth(img, qq, tt)
-    compare_maps(gpu.export_blocks(), cpu.export_blocks(), "lean slots")
+    compare_maps(gpu.export_blocks(), cpu.export_blocks(), "fall-backs in batches")
     assert gpu.frame_stats()["n_sector_fallbacks"] == 3
     gpu.close()

@@ -1176,7 +1176,7 @@ def test_callback_query_interleaving(mods):
 
 @pytest.mark.parametrize("env", [{"MLM_SEC_FAIL_EVERY": "1", "MLM_SEC_BACKOFF": "0"}, {"MLM_SEC_FAIL_EVERY": "3", "MLM_SEC_TAB": "512", "MLM_SEC_BACKOFF": "0"},
                                  {"MLM_SEC_FAIL_EVERY": "4", "MLM_SEC_BACKOFF": "2"}, {"MLM_SECTORS": "0"},
-                                 {"MLM_SEC_FAIL_EVERY": "3", "MLM_SEC_BACKOFF": "1", "MLM_LEAN_SLOTS": "0"},
+                                 {"MLM_SEC_FAIL_EVERY": "3", "MLM_SEC_BACKOFF": "1"},
                                  {"MLM_SEC_TAB": "512", "MLM_SEC_TAB_BIG": "1024", "MLM_SEC_BACKOFF": "0"}])
 def test_sector_fallback_and_cell_table_path(mods, monkeypatch, knobs, env):
     """Stage A by azimuth sector falls back to the cell-table path frame by frame when a column overflows its LDS tables
@@ -1203,9 +1203,9 @@ def test_sector_fallback_and_cell_table_path(mods, monkeypatch, knobs, env):
     st = gpu.frame_stats()
     if env.get("MLM_SEC_FAIL_EVERY") == "1":
         assert st["n_sector_fallbacks"] == n, st
-    if env.get("MLM_SEC_FAIL_EVERY") == "3" and "MLM_LEAN_SLOTS" not in env:
+    if env.get("MLM_SEC_FAIL_EVERY") == "3" and env.get("MLM_SEC_BACKOFF") == "0":
         assert st["n_sector_fallbacks"] >= n // 3, st
-    if "MLM_LEAN_SLOTS" in env:  # (full slots: every frame slot keeps cell-table state of its own)
+    if env.get("MLM_SEC_BACKOFF") == "1":  # (the batch after a fall-back goes straight to the cell-table path, frame by frame)
         assert st["n_sector_fallbacks"] >= 1, st
     if env.get("MLM_SEC_FAIL_EVERY") == "4":  # after a fall-back the next batches skip the sector attempt, then it is retried
         assert 1 <= st["n_sector_fallbacks"] < n // 2, st
@@ -1215,8 +1215,7 @@ def test_sector_fallback_and_cell_table_path(mods, monkeypatch, knobs, env):
 
 
 @pytest.mark.parametrize("env", [{}, {"MLM_SEC_FAIL_EVERY": "1", "MLM_SEC_BACKOFF": "0"}, {"MLM_SEC_FAIL_EVERY": "3", "MLM_SEC_BACKOFF": "0"},
-                                 {"MLM_SEC_FAIL_EVERY": "4", "MLM_SEC_BACKOFF": "1"}, {"MLM_SECTORS": "0"},
-                                 {"MLM_SEC_FAIL_EVERY": "3", "MLM_SEC_BACKOFF": "0", "MLM_LEAN_SLOTS": "0"}])
+                                 {"MLM_SEC_FAIL_EVERY": "4", "MLM_SEC_BACKOFF": "1"}, {"MLM_SECTORS": "0"}])
 def test_frontier_mode_sector_path(mods, monkeypatch, knobs, env):
     """Frontier mode runs Stage A by azimuth sector too (insertion times of the miss cells kept in LDS); a frame whose sector
     tables overflow redoes Stage A on the cell-table path before anything that depends on the map is enqueued.  Single
@@ -1263,10 +1262,11 @@ def test_frontier_mode_sector_path(mods, monkeypatch, knobs, env):
 
 def test_async_replay_with_mixed_stage_a_paths(mods, monkeypatch, knobs):
     """Asynchronous submission keeps up to three batches in flight.  Here a cell-table batch (submitted while the sector path
-    backs off after a forced overflow) is followed by sector batches, and a frame of the OLDER, cell-table batch turns out to
-    need a rehash of the emulated hit container (its hit count jumps from ~3 k to ~14 k): the replay must finish every
-    pending frame on the path its Stage A took (round-2 advisor finding: the sector frames were resubmitted through
-    k_voxelize, which reads per-hit fields k_sector never writes)."""
+    backs off after a forced overflow) is followed by sector batches, and a frame of the cell-table batch turns out to need a
+    rehash of the emulated hit container (its hit count jumps from ~3 k to ~14 k).  The cell-table batch runs frame by frame
+    with nothing else in flight, each frame confirmed (and replayed) before the call returns, so the sector batches behind it
+    never share a pending list with it; every replay stays on the path its frame's Stage A took (round-2 advisor finding: the
+    sector frames were resubmitted through k_voxelize, which reads per-hit fields k_sector never writes)."""
     MLMap, OracleMap = mods
     knobs.set("sec_fail_every", "7")
     knobs.set("sec_backoff", "1")

@@ -151,9 +151,10 @@ def test_launches_of_a_lone_frontier_callback(knobs):
 
 
 def test_async_frame_on_the_shared_cell_table_path_waits_for_its_inputs(knobs):
-    """An asynchronous call while the handle backs off from the sector path (a frame's Stage A gave up shortly before) runs its Stage A
-    on the MAIN stream (the cell-table path's per-frame state exists once), while its pixel list went up on the slot set's Stage A
-    stream: the main stream has to wait for it.  Without that wait the list was read before it had arrived in one run in twenty-five of
+    """An asynchronous call while the handle backs off from the sector path (a frame's Stage A gave up shortly before) runs its frames
+    alone on the MAIN stream (the cell-table path's per-frame state exists once), while its pixel list went up on the slot set's Stage A
+    stream: the barrier in front of those frames drains what is in flight and orders the main stream behind that upload before the first
+    Stage A.  Without that wait the list was read before it had arrived in one run in twenty-five of
     the scenario of test_small_frames_between_everything_else[stage_a_gives_up] (a third of the runs with the round-5 library, late in
     a process) — the scenario again, on thirty fresh handles, the map compared after its asynchronous frames.
     Reference: the callback hands over a complete frame, src/mlmap.cpp:463-507."""
