@@ -288,8 +288,9 @@ int mlm_sync(mlm_handle *h);
 int mlm_set_async(mlm_handle *h, int on);
 /* Small query batches (a planner asking position by position, include/mlmap.h:170-295) are answered from a pinned HOST copy of the
  * block planes (6 bytes per voxel + 13 per block), which grows with the map.  max_bytes bounds that pinned memory (default 1 GiB;
- * 0: no host copy at all): a map that needs more is queried by kernels only, as large batches always are — same answers, ~20 us
- * per call instead of ~0.05 us.  Takes effect at the next query; lowering it below what is pinned frees the copy. */
+ * 0, or less than the copy's smallest size of 256 blocks: no host copy at all): a map that needs more is queried by kernels only, as
+ * large batches always are — same answers, ~20 us per call instead of ~0.05 us; the query that finds the map grown beyond the limit
+ * is one of them.  Lowering the limit below what is pinned frees the copy; raising it again brings the copy back at the next query. */
 int mlm_set_host_mirror_limit(mlm_handle *h, size_t max_bytes);
 int mlm_get_frame_stats(mlm_handle *h, mlm_frame_stats *out);
 

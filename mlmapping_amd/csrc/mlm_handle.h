@@ -115,6 +115,9 @@ struct MlmMirror {
     long long q_at_eager = -1;     // n_host_queries when it was launched
     long long n_eager = 0;
 };
+// status of mirror_sync (mlm_mirror.h) when the map has outgrown mlm_set_host_mirror_limit: the query runs as a kernel instead
+// (never returned by an entry point)
+constexpr int kMirrorUnavailable = 1;
 
 // A frame on its own with at most this many strips of 256 points (sampled callbacks, point lists: 4 096 points) runs its cells' float chains
 // inside k_rank<true> instead of launching k_chain_lanes — a launch of its own costs a lone frame the kernel boundary (1.5 us) and the few

@@ -67,6 +67,22 @@ void mirror_free(mlm_handle *h) {
     mirror_mark_all(h);
 }
 constexpr unsigned int kMirrorGrid = 1024;
+constexpr size_t kMirrorMinBlocks = 256; // the smallest planes mirror_reserve allocates
+size_t mirror_bytes(const mlm_handle *h, size_t blocks) { return blocks * ((size_t)h->P.cells * 6 + 13); }
+// After the limit changed (mlm_create: knob "mirror_mb"; mlm_set_host_mirror_limit): a limit below what the planes hold, or below
+// even their smallest size, frees them and sends every query to the kernels; a limit that allows them again brings the host path back.
+void mirror_apply_limit(mlm_handle *h) {
+    MlmMirror &M = h->mir;
+    if (M.alloc_failed || (!M.enabled && !M.over_limit)) return; // (no pinned memory to be had, or the knob "mirror" = 0: kernels)
+    if (mirror_bytes(h, std::max(M.cap, kMirrorMinBlocks)) > M.max_bytes) {
+        if (M.cap) mirror_free(h);
+        M.over_limit = true;
+        M.enabled = false;
+    } else if (M.over_limit) { // (a higher limit: the next small query tries again)
+        M.over_limit = false;
+        M.enabled = true;
+    }
+}
 int mirror_reserve(mlm_handle *h, size_t blocks) {
     MlmMirror &M = h->mir;
     if (!M.stat) {
@@ -74,12 +90,12 @@ int mirror_reserve(mlm_handle *h, size_t blocks) {
         std::memset(M.stat, 0, (2 + kMirrorGrid) * sizeof(unsigned int));
     }
     if (blocks <= M.cap) return MLM_OK;
-    const size_t cap = std::max<size_t>(256, blocks), C = (size_t)h->P.cells;
-    if (cap * (C * 6 + 13) > M.max_bytes) { // (the map has outgrown what the caller lets the mirror pin: small queries run as kernels from now on)
+    const size_t cap = std::max<size_t>(kMirrorMinBlocks, blocks), C = (size_t)h->P.cells;
+    if (mirror_bytes(h, cap) > M.max_bytes) { // (the map has outgrown what the caller lets the mirror pin: small queries run as kernels from now on)
         mirror_free(h);
         M.over_limit = true;
         M.enabled = false;
-        return MLM_OK;
+        return kMirrorUnavailable;
     }
     // New planes; what the old ones hold of blocks [0, n_known) is still valid wherever no box is pending, so it is copied on the
     // host and only new or changed blocks cross the link (the pending boxes stay as they are).
@@ -159,6 +175,7 @@ bool mirror_collect(mlm_handle *h, unsigned int *n_blocks_seen = nullptr) {
     return true;
 }
 // Bring the mirror up to date.  The caller holds the lock and has drained the handle; no eager refresh is pending.
+// kMirrorUnavailable: the map needs more pinned memory than the limit allows (the mirror is now disabled: the caller runs the kernel).
 int mirror_refresh(mlm_handle *h) {
     MlmMirror &M = h->mir;
     // (the geometry first: an empty map has no planes yet, but getOddGrad walks neighbours of absent blocks all the same)

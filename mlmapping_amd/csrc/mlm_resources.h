@@ -53,8 +53,8 @@ int run_query(mlm_handle *h, int mode, const double *pos, int n, float inflate, 
             h->mir.n_host_queries += n;
             return MLM_OK;
         }
-        if (!h->mir.alloc_failed) return rc; // (an error of the frames in flight, reported by the drain)
-        // (no pinned host memory for the mirror: this and all later queries run as kernels)
+        if (!h->mir.alloc_failed && rc != kMirrorUnavailable) return rc; // (an error of the frames in flight, reported by the drain)
+        // (no pinned host memory for the mirror, or more than its limit allows: this and all later queries run as kernels)
     }
     HIPCHK(h, hipSetDevice(h->device));
     int rc = drain(h);

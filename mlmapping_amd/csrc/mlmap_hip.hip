@@ -466,6 +466,7 @@ int mlm_create(const mlm_config *cfg, const mlm_limits *lim_in, int device, mlm_
         if (knob("mirror", kv)) h->mir.enabled = (int)kv != 0;
         if (knob("mirror_mb", kv)) h->mir.max_bytes = (size_t)std::max(0, (int)kv) << 20;
         if (knob("mirror_max", kv)) h->mir.max_clean = std::max(0, (int)kv), h->mir.max_dirty = std::min(h->mir.max_dirty, h->mir.max_clean);
+        mirror_apply_limit(h);
     }
     HIPCHK(h, hipHostMalloc((void **)&h->h_g, sizeof(MlmGlobal), hipHostMallocDefault));
     std::memset(h->h_g, 0, sizeof(MlmGlobal));
@@ -1522,7 +1523,7 @@ int mlm_query_odds_at(mlm_handle *h, const int32_t *glb_id, const int32_t *subbo
             h->mir.n_host_queries += n;
             return MLM_OK;
         }
-        if (!h->mir.alloc_failed) return rc;
+        if (!h->mir.alloc_failed && rc != kMirrorUnavailable) return rc;
     }
     HIPCHK(h, hipSetDevice(h->device));
     int rc = drain(h);
@@ -1558,19 +1559,9 @@ int mlm_set_async(mlm_handle *h, int on) {
 int mlm_set_host_mirror_limit(mlm_handle *h, size_t max_bytes) {
     if (!h) return MLM_ERR_INVALID;
     MLM_LOCK(h);
-    MlmMirror &M = h->mir;
-    M.max_bytes = max_bytes;
-    if (M.alloc_failed) return MLM_OK; // (the planes could not be pinned at all: the kernel path stays)
-    const size_t held = M.cap * ((size_t)h->P.cells * 6 + 13);
-    if (held > max_bytes) {
-        HIPCHK(h, hipSetDevice(h->device));
-        mirror_free(h);
-        M.over_limit = true;
-        M.enabled = false;
-    } else if (M.over_limit && max_bytes > 0) { // (a higher limit: the next small query tries again)
-        M.over_limit = false;
-        M.enabled = true;
-    }
+    h->mir.max_bytes = max_bytes;
+    HIPCHK(h, hipSetDevice(h->device));
+    mirror_apply_limit(h); // (mlm_mirror.h)
     return MLM_OK;
 }
 

@@ -66,6 +66,7 @@ def lib():
         L.mlo_n_z.argtypes = [vp]
         L.mlo_export_blocks.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         L.mlo_export_frontier.argtypes = [vp, vp]
+        L.mlo_import_blocks.argtypes = [vp, i32, vp, vp, vp, vp, vp]
         L.mlo_get_occupancy.argtypes = [vp, vp, i32, vp]
         L.mlo_get_occupancy_inflate.argtypes = [vp, vp, i32, ctypes.c_float, vp]
         L.mlo_get_inflate_occupancy.argtypes = [vp, vp, i32, vp]
@@ -220,6 +221,16 @@ class OracleMap:
         o = np.lexsort((keys[:, 2], keys[:, 1], keys[:, 0]))
         return {"keys": keys[o], "collapsed": collapsed[o], "log_odds": lo[o], "occ": occ[o], "infl": infl[o],
                 "frontier_cnt": fc[o]}
+
+    def import_blocks(self, keys, log_odds=None, occ=None, infl=None, collapsed=None):
+        """Load blocks (layout of export_blocks; None: that plane is left as it is) — MLMap.import_blocks' counterpart."""
+        k = np.ascontiguousarray(keys, dtype=np.int32).reshape(-1, 3)
+        n, C = k.shape[0], self.cells
+        planes = [None if a is None else np.ascontiguousarray(a, dtype=dt).reshape(n, -1)
+                  for a, dt in ((log_odds, np.float32), (occ, np.uint8), (infl, np.uint8), (collapsed, np.uint8))]
+        for a in planes[:3]:
+            assert a is None or a.shape[1] == C, "one row of cells per block"
+        lib().mlo_import_blocks(self._h, n, _p(k), *[None if a is None else _p(a) for a in planes])
 
     def export_frontier(self) -> np.ndarray:
         n = lib().mlo_frontier_total(self._h)

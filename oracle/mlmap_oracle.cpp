@@ -1040,6 +1040,32 @@ void mlo_export_blocks(mlo_handle *h, int32_t *keys, uint8_t *collapsed, float *
         i++;
     }
 }
+void mlo_import_blocks(mlo_handle *h, int n, const int32_t *keys, const float *log_odds, const char *occ, const char *infl,
+                       const uint8_t *collapsed) {
+    LocalMap &lm = h->lm;
+    const size_t C = lm.cell_num_subbox;
+    for (int i = 0; i < n; i++) {
+        Subbox &b = lm.observed_group_map[V3i{keys[3 * i], keys[3 * i + 1], keys[3 * i + 2]}];
+        if (b.occupancy.size() != C) { // a new block (allocate_ram), or a released one taken back to full size
+            const bool fresh = b.occupancy.empty();
+            b.occupancy.resize(C, fresh ? 'u' : b.occupancy[0]);
+            b.inflate_occupancy.resize(C, fresh ? 'u' : b.inflate_occupancy[0]);
+            b.log_odds.resize(C, fresh ? 0.0f : b.log_odds[0]);
+        }
+        const size_t o = (size_t)i * C;
+        if (log_odds) std::copy(log_odds + o, log_odds + o + C, b.log_odds.begin());
+        if (occ) std::copy(occ + o, occ + o + C, b.occupancy.begin());
+        if (infl) std::copy(infl + o, infl + o + C, b.inflate_occupancy.begin());
+        if (collapsed && collapsed[i] && lm.apply_explored_area) { // map_local.cpp:221-226
+            b.occupancy.resize(1);
+            b.occupancy.shrink_to_fit();
+            b.inflate_occupancy.resize(1);
+            b.inflate_occupancy.shrink_to_fit();
+            b.log_odds.resize(1);
+            b.log_odds.shrink_to_fit();
+        }
+    }
+}
 size_t mlo_frontier_total(mlo_handle *h) {
     size_t n = 0;
     for (auto &kv : h->lm.observed_group_map) n += kv.second.frontier.size();

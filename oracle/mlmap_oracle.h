@@ -113,6 +113,11 @@ size_t mlo_block_count(mlo_handle *h);
  * frontier_cnt: n int32.  Collapsed blocks fill element 0 only. Iteration order. */
 void mlo_export_blocks(mlo_handle *h, int32_t *keys, uint8_t *collapsed, float *log_odds, char *occ, char *infl,
                        int32_t *frontier_cnt);
+/* mlm_import_blocks' counterpart (same arrays as mlo_export_blocks writes; any plane may be NULL: a new block keeps allocate_ram's
+ * 0 / 'u' / 'u', map_local.h:215-231, a held one that plane).  In frontier mode a block flagged collapsed keeps element 0 only, as
+ * the release of map_local.cpp:221-226 leaves it.  Frontier sets are not imported. */
+void mlo_import_blocks(mlo_handle *h, int n, const int32_t *keys, const float *log_odds, const char *occ, const char *infl,
+                       const uint8_t *collapsed);
 size_t mlo_frontier_total(mlo_handle *h);
 void mlo_export_frontier(mlo_handle *h, int32_t *keys3_cell /* n*4: gx,gy,gz,cell */);
 

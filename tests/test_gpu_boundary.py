@@ -13,7 +13,7 @@ import pytest
 
 from mlmapping_amd import synthetic as syn
 from mlmapping_amd.config import S1, SDEF, to_c
-from tests.util import ODDS_TOL, compare_maps, voxel_centres
+from tests.util import assert_same_bits, compare_maps, voxel_centres
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -61,13 +61,13 @@ def test_cpp_facade_client_process(mods, tmp_path):
     assert np.array_equal(occ, cpu.getOccupancy(pos))
     assert np.array_equal(occ_i, cpu.getOccupancy(pos, inflate=0.15))
     assert np.array_equal(infl, cpu.getInflateOccupancy(pos))
-    assert np.abs(odd - cpu.getOdd(pos)).max() <= ODDS_TOL
+    assert_same_bits(odd, cpu.getOdd(pos), "getOdd")
     for g, it in ((grad, 5), (grad2, 2)):
         cg = cpu.getOddGrad(pos, it)
-        assert np.abs(g - cg).max() <= 1e-4 * max(1.0, np.abs(cg).max())
+        assert_same_bits(g, cg, f"getOddGrad({it})")
     at = [float.fromhex(x) for x in out[n_pos].split()[1:]]
     want = cpu.getOddAt(np.array([[0, 0, 1], [40, 40, 40]], dtype=np.int32), np.array([7, 0], dtype=np.int32))
-    assert np.abs(np.array(at, dtype=np.float32) - want).max() <= ODDS_TOL and at[1] == 0.5
+    assert_same_bits(np.array(at, dtype=np.float32), want, "getOddAt")
     cpu.setFree_map_in_bound([0.5, -0.5, 1.0], [1.0, 0.5, 1.5])
     o_free = int(cpu.getOccupancy(np.array([[0.75, 0.0, 1.25]]))[0])
     assert out[n_pos + 1].split()[1:] == [str(o_free), str(int(o_free == 1))]

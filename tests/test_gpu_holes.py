@@ -11,7 +11,7 @@ import pytest
 
 from mlmapping_amd import synthetic as syn
 from mlmapping_amd.config import CONFIG2_YAML, CONFIG_SIM_YAML, S1, SDEF
-from tests.util import ODDS_TOL, compare_maps, voxel_centres
+from tests.util import assert_same_bits, compare_maps, voxel_centres
 
 pytestmark = pytest.mark.gpu
 
@@ -84,10 +84,10 @@ def test_id0_quirk_on_queries_and_setfree(mods):
     assert (want[:6000] != -1).sum() > 500, "the quirk positions should fall into observed blocks"
     # the kernel path (large batches) ...
     assert np.array_equal(gpu.getOccupancy(pos), want)
-    assert np.abs(gpu.getOdd(pos) - cpu.getOdd(pos)).max() <= ODDS_TOL
+    assert_same_bits(gpu.getOdd(pos), cpu.getOdd(pos), "getOdd")
     assert np.array_equal(gpu.getOccupancy(pos[:3000], inflate=0.15), cpu.getOccupancy(pos[:3000], inflate=0.15))
     gg, cg = gpu.getOddGrad(pos[:4000]), cpu.getOddGrad(pos[:4000])
-    assert np.array_equal(gg == 0, cg == 0) and np.abs(gg - cg).max() <= 1e-4 * max(1.0, np.abs(cg).max())
+    assert_same_bits(gg, cg, "getOddGrad")
     # ... and the host mirror (one position per call)
     k = 1200
     assert np.array_equal(_one_by_one(gpu.getOccupancy, pos[:k]), want[:k])
@@ -247,7 +247,7 @@ def test_shipped_yaml_configs_verbatim(mods, which, sampled):
     pos = np.concatenate([rng.uniform(-4, 7, size=(4000, 3)), voxel_centres(c, cfg, 6000)])
     assert np.array_equal(gpu.getOccupancy(pos), cpu.getOccupancy(pos))
     assert np.array_equal(gpu.getInflateOccupancy(pos), cpu.getInflateOccupancy(pos))
-    assert np.abs(gpu.getOdd(pos) - cpu.getOdd(pos)).max() <= ODDS_TOL
+    assert_same_bits(gpu.getOdd(pos), cpu.getOdd(pos), "getOdd")
     assert np.array_equal(_one_by_one(gpu.getOccupancy, pos[:500]), cpu.getOccupancy(pos[:500]))
 
 

@@ -8,7 +8,7 @@ import pytest
 
 from mlmapping_amd import synthetic as syn
 from mlmapping_amd.config import S1, SDEF
-from tests.util import ODDS_TOL, compare_maps, voxel_centres
+from tests.util import assert_same_bits, compare_maps, voxel_centres
 
 pytestmark = pytest.mark.gpu
 
@@ -64,7 +64,7 @@ def test_single_position_queries_match_oracle_and_kernel_path(mods, knobs):
     at = np.concatenate([gpu.getOddAt(glb[i:i + 1], sub[i:i + 1]) for i in range(glb.shape[0])])
     assert np.array_equal(at.view(np.uint32), cpu.getOddAt(glb, sub).view(np.uint32))
     assert gpu.frame_stats()["n_mirror_refreshes"] == s1["n_mirror_refreshes"]
-    # the kernel path (mirror off) on the same map: same classes, odds within the tolerance (the device's pow is not the host's)
+    # the kernel path (mirror off) on the same map: the same classes and odds bits (mlm_logit_inv reproduces the host's)
     knobs.set("mirror", 0)
     dev = MLMap(cfg, max_blocks=8192)
     for img, (q, t) in syn.stream(cfg, "room_jitter", "smooth", 5):
@@ -73,7 +73,7 @@ def test_single_position_queries_match_oracle_and_kernel_path(mods, knobs):
     assert np.array_equal(_one_by_one(dev.getOccupancy, pos[:200]), cpu.getOccupancy(pos[:200]))
     assert dev.frame_stats()["n_host_queries"] == 0
     d_odd, h_odd = dev.getOdd(pos), _one_by_one(gpu.getOdd, pos)
-    assert np.abs(d_odd - h_odd).max() <= 2e-7, "kernel path and host mirror disagree beyond an ulp of the float odd"
+    assert_same_bits(d_odd, h_odd, "kernel path vs host mirror")
     assert np.array_equal(dev.getOccupancy(pos), _one_by_one(gpu.getOccupancy, pos))
 
 
@@ -190,11 +190,60 @@ def test_mirror_growth_carries_its_contents_and_respects_the_limit(mods):
     h0 = gpu.frame_stats()["n_host_queries"]
     assert np.array_equal(_one_by_one(gpu.getOccupancy, pos[:40]), cpu.getOccupancy(pos[:40]))
     go, co = _one_by_one(gpu.getOdd, pos[:40]), cpu.getOdd(pos[:40])
-    assert np.max(np.abs(go - co)) <= ODDS_TOL
+    assert_same_bits(go, co, "getOdd on the kernels")
     assert gpu.frame_stats()["n_host_queries"] == h0
     gpu.set_host_mirror_limit(1 << 30)  # raised again: the host path returns
     assert np.array_equal(_one_by_one(gpu.getOdd, pos[:40]).view(np.uint32), co.view(np.uint32))
     assert gpu.frame_stats()["n_host_queries"] > h0
+
+
+@pytest.mark.parametrize("how", ["limit 0", "limit 1 MB", "knob mirror_mb=0", "2 MB, then the map outgrows it"])
+def test_mirror_limit_sends_small_queries_to_the_kernels(mods, knobs, how):
+    """a limit the mirror cannot live with — 0 or 1 MB (less than its smallest planes, 256 blocks) set before the first query, the
+    knob mirror_mb = 0 at create time, 2 MB and a map that walks away until it outgrows them: the next single-position getOdd /
+    getOddAt succeeds on the kernels with the oracle's bits and counts no host query; raising the limit brings the host path back"""
+    MLMap, OracleMap = mods
+    cfg = S1
+    if how.startswith("knob"):
+        knobs.set("mirror_mb", 0)
+    gpu, cpu = MLMap(cfg, max_blocks=2048), OracleMap(cfg)
+    if how.startswith("limit"):
+        gpu.set_host_mirror_limit(0 if how == "limit 0" else 1 << 20)
+    elif how.startswith("2 MB"):
+        gpu.set_host_mirror_limit(2 << 20)
+    img = syn.room_depth(cfg)
+    rng = np.random.default_rng(3)
+    on_host = []
+    for k in range(6 if how.startswith("2 MB") else 1):
+        q, t = syn.static_pose()
+        t = np.array([20.0 * k, 0.0, 0.0]) + t
+        if k == 0:  # (a sparse first frame: few blocks, the planes fit the 2 MB at first)
+            pix = (rng.integers(0, cfg.height, 300) * cfg.width + rng.integers(0, cfg.width, 300)).astype(np.int32)
+            gpu.update_map(img, q, t, pixel_idx=pix)
+            cpu.update_depth_indexed(img, pix, q, t)
+        else:
+            gpu.update_map(img, q, t)
+            cpu.update_depth(img, q, t)
+        b = cpu.export_blocks()
+        pos = voxel_centres(b, cfg, 40, seed=k)
+        glb = b["keys"][rng.integers(0, b["keys"].shape[0], 40)]
+        sub = rng.integers(0, cfg.cells_per_block, 40).astype(np.int32)
+        h0 = gpu.frame_stats()["n_host_queries"]
+        assert_same_bits(_one_by_one(gpu.getOdd, pos), cpu.getOdd(pos), f"{how}, frame {k}: getOdd")
+        assert_same_bits(np.concatenate([gpu.getOddAt(glb[i:i + 1], sub[i:i + 1]) for i in range(40)]), cpu.getOddAt(glb, sub),
+                         f"{how}, frame {k}: getOddAt")
+        on_host.append(gpu.frame_stats()["n_host_queries"] > h0)
+        if b["keys"].shape[0] * (6 * cfg.cells_per_block + 13) > 2 << 20:
+            break
+    if how.startswith("2 MB"):
+        assert on_host[0] and not on_host[-1] and len(on_host) > 1, on_host
+    else:
+        assert not any(on_host), on_host
+    gpu.set_host_mirror_limit(1 << 30)
+    h0 = gpu.frame_stats()["n_host_queries"]
+    assert_same_bits(_one_by_one(gpu.getOdd, pos), cpu.getOdd(pos), f"{how}: getOdd after raising the limit")
+    assert_same_bits(np.concatenate([gpu.getOddAt(glb[i:i + 1], sub[i:i + 1]) for i in range(40)]), cpu.getOddAt(glb, sub))
+    assert gpu.frame_stats()["n_host_queries"] - h0 == 80, "the host path should be back"
 
 
 def test_mirror_in_frontier_mode_released_blocks(mods):

@@ -9,7 +9,7 @@ import pytest
 
 from mlmapping_amd import synthetic as syn
 from mlmapping_amd.config import S1, S1_SIGMA0, S3, SDEF
-from tests.util import ODDS_TOL, compare_maps, fuzz_trial, voxel_centres
+from tests.util import assert_same_bits, compare_maps, fuzz_trial, voxel_centres
 
 pytestmark = pytest.mark.gpu
 
@@ -377,10 +377,10 @@ def test_queries(mods):
     lo, hi = b["keys"].min(0) * 1.0 - 1.0, b["keys"].max(0) * 1.0 + 2.0
     pos = np.concatenate([rng.uniform(lo, hi, size=(50000, 3)), voxel_centres(b, cfg, 100000)])
     assert np.array_equal(gpu.getOccupancy(pos), cpu.getOccupancy(pos))
-    assert np.abs(gpu.getOdd(pos) - cpu.getOdd(pos)).max() <= ODDS_TOL
+    assert_same_bits(gpu.getOdd(pos), cpu.getOdd(pos), "getOdd")
     assert np.array_equal(gpu.getOccupancy(pos[:20000], inflate=0.15), cpu.getOccupancy(pos[:20000], inflate=0.15))
     gg, cg = gpu.getOddGrad(pos[:30000]), cpu.getOddGrad(pos[:30000])
-    assert np.abs(gg - cg).max() <= 1e-4 * max(1.0, np.abs(cg).max())
+    assert_same_bits(gg, cg, "getOddGrad")
     # setFree_map_in_bound: idempotent, then everything must still agree
     bmin, bmax = np.array([0.5, -1.0, 0.3]), np.array([2.5, 1.0, 2.0])
     for _ in range(2):
@@ -480,7 +480,7 @@ def test_exploration_frontiers(mods, name):
         assert b["collapsed"].sum() > 50  # the release path is really exercised
     pos = np.concatenate([np.random.default_rng(3).uniform(-4, 6, size=(40000, 3)), voxel_centres(b, cfg, 60000)])
     assert np.array_equal(gpu.getOccupancy(pos), cpu.getOccupancy(pos))
-    assert np.abs(gpu.getOdd(pos) - cpu.getOdd(pos)).max() <= ODDS_TOL
+    assert_same_bits(gpu.getOdd(pos), cpu.getOdd(pos), "getOdd")
     gpu.setFree_map_in_bound([0.0, -1.0, 0.5], [2.0, 1.0, 1.5])
     cpu.setFree_map_in_bound([0.0, -1.0, 0.5], [2.0, 1.0, 1.5])
     gpu.inflate_map([0.0, 0.0, 1.5])
@@ -1044,7 +1044,7 @@ def test_corridor_substitute(mods):
         b = cpu.export_blocks()
         pos = voxel_centres(b, cfg, 50000)
         assert np.array_equal(gpu.getOccupancy(pos), cpu.getOccupancy(pos))
-        assert np.abs(gpu.getOdd(pos) - cpu.getOdd(pos)).max() <= ODDS_TOL
+        assert_same_bits(gpu.getOdd(pos), cpu.getOdd(pos), "getOdd")
         print("corridor", poses, d)
         gpu.close()
 
@@ -1080,7 +1080,7 @@ def test_odd_grad_iterations(mods, max_iter):
     pos = np.concatenate([voxel_centres(b, cfg, 30000, seed=max_iter), rng.uniform(-3, 6, size=(10000, 3))])
     gg, cg = gpu.getOddGrad(pos, max_iter), cpu.getOddGrad(pos, max_iter)
     assert np.array_equal(gg == 0, cg == 0), "gradient found / not found differs"
-    assert np.abs(gg - cg).max() <= 1e-4 * max(1.0, np.abs(cg).max())
+    assert_same_bits(gg, cg, f"getOddGrad({max_iter})")
     if max_iter == 0:
         assert not gg.any()
 
@@ -1100,7 +1100,7 @@ def test_odds_at_block_and_cell(mods):
         glb = np.concatenate([b["keys"][sel], rng.integers(-60, 60, size=(5000, 3)).astype(np.int32)])
         sub = rng.integers(0, cfg.cells_per_block, glb.shape[0]).astype(np.int32)
         go, co = gpu.getOddAt(glb, sub), cpu.getOddAt(glb, sub)
-        assert np.abs(go - co).max() <= ODDS_TOL
+        assert_same_bits(go, co, "getOddAt")
         assert np.array_equal(go == 0.5, co == 0.5)
         from mlmapping_amd.mlmap import MlmError
         with pytest.raises(MlmError, match="INVALID"):
@@ -1170,7 +1170,7 @@ def test_callback_query_interleaving(mods):
         n = pos.shape[0] if k < 2 else 1000
         sel = pos[: n // (k + 1)] if k else pos[:5000]  # grows on the second round: 5 000 -> 1 000 000 positions
         assert np.array_equal(gpu.getOccupancy(sel), cpu.getOccupancy(sel)), f"queries after callback {k}"
-        assert np.abs(gpu.getOdd(sel[:200000]) - cpu.getOdd(sel[:200000])).max() <= ODDS_TOL
+        assert_same_bits(gpu.getOdd(sel[:200000]), cpu.getOdd(sel[:200000]), "getOdd")
     gpu.close()
 
 

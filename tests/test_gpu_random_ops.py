@@ -7,7 +7,7 @@ import pytest
 
 from mlmapping_amd import synthetic as syn
 from mlmapping_amd.config import SDEF
-from tests.util import ODDS_TOL, compare_maps, voxel_centres
+from tests.util import assert_same_bits, compare_maps, voxel_centres
 
 import os
 
@@ -102,7 +102,7 @@ def test_random_operation_sequences(mods, explore, seed):
             pos = positions(3000)
             assert np.array_equal(gpu.getOccupancy(pos), cpu.getOccupancy(pos)), (step, log)
             assert np.array_equal(gpu.getInflateOccupancy(pos), cpu.getInflateOccupancy(pos)), (step, log)
-            assert np.abs(gpu.getOdd(pos) - cpu.getOdd(pos)).max() <= ODDS_TOL, (step, log)
+            assert_same_bits(gpu.getOdd(pos), cpu.getOdd(pos), f"getOdd, step {step}: {log}")
         elif op == "sync":
             gpu.sync()
         elif op == "mode":
@@ -218,7 +218,7 @@ def test_random_operation_sequences_s1_with_growth(mods, seed):
         elif op == "qbulk":
             pos = positions(4000)
             assert np.array_equal(gpu.getOccupancy(pos), cpu.getOccupancy(pos)), (step, log)
-            assert np.abs(gpu.getOdd(pos) - cpu.getOdd(pos)).max() <= ODDS_TOL, (step, log)
+            assert_same_bits(gpu.getOdd(pos), cpu.getOdd(pos), f"getOdd, step {step}: {log}")
         elif op == "sync":
             gpu.sync()
         elif op == "mode":

@@ -1,6 +1,6 @@
 """mlm_export_window: a dense box of voxels read out in one call — odds, occupancy, inflate occupancy and odds gradients at every
 voxel, which must be what the per-position queries return there (float / double bits, equal int8 classes) and agree with the CPU
-oracle by the project's bars (classes exact, odds within ODDS_TOL, gradient found / not found exact and values within 1e-4)."""
+oracle bit for bit."""
 import ctypes
 import os
 import re
@@ -10,7 +10,7 @@ import pytest
 
 from mlmapping_amd import synthetic as syn
 from mlmapping_amd.config import S1
-from tests.util import ODDS_TOL
+from tests.util import assert_same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -87,17 +87,13 @@ def check_oracle(cpu, w, keys, cid, cen, max_iter, sel=None):
     if sel is not None:
         flat = {k: v[sel] for k, v in flat.items()}
     if "odds" in flat:
-        co = cpu.getOddAt(keys, cid)
-        assert np.abs(flat["odds"] - co).max() <= ODDS_TOL
-        assert np.array_equal(flat["odds"] == 0.5, co == 0.5)
+        assert_same_bits(flat["odds"], cpu.getOddAt(keys, cid), "window odds vs the oracle")
     if "occ" in flat:
         assert np.array_equal(flat["occ"].astype(np.int32), cpu.getOccupancy(cen))
     if "infl" in flat:
         assert np.array_equal(flat["infl"].astype(np.int32), cpu.getInflateOccupancy(cen))
     if "grad" in flat:
-        gg, cg = flat["grad"], cpu.getOddGrad(cen, max_iter)
-        assert np.array_equal(gg == 0, cg == 0), "gradient found / not found differs from the oracle"
-        assert np.abs(gg - cg).max() <= 1e-4 * max(1.0, np.abs(cg).max())
+        assert_same_bits(flat["grad"], cpu.getOddGrad(cen, max_iter), "window gradients vs the oracle")
 
 
 ALL = dict(odds=True, occ=True, infl=True, grad=True)

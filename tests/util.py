@@ -37,6 +37,64 @@ def compare_maps(g: dict, c: dict, what: str = "", exact: bool = True) -> dict:
             "cells": int(g["log_odds"].size)}
 
 
+def assert_same_bits(got, want, what: str = ""):
+    """query answers identical to the oracle's: float odds and double gradients bit for bit (the kernels evaluate logit_inv as
+    the host does), classes exactly"""
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {got.shape} {got.dtype} vs {want.shape} {want.dtype}"
+    if got.dtype.kind == "f":
+        u = {4: np.uint32, 8: np.uint64}[got.dtype.itemsize]
+        bad = (got.view(u) != want.view(u))
+    else:
+        bad = got != want
+    bad = np.flatnonzero(bad.reshape(got.shape[0], -1).any(axis=1)) if got.ndim else np.flatnonzero(bad.reshape(1))
+    if bad.size:
+        i = bad[0]
+        raise AssertionError(f"{what}: {bad.size} of {got.shape[0] if got.ndim else 1} answers differ, first #{i}: {got[i]!r} vs {want[i]!r}")
+
+
+_SCANS = {}
+
+
+def logit_inv_scan(workdir, lo: float = -2.0, hi: float = 4.2, k: int = 1024) -> dict:
+    """tests/cpp/logit_inv_scan.cpp built with g++ and run over every float of [lo, hi] (once per process): {"L", "f": float32 hard
+    cases and the host's odds there, "m": distance to the float midpoint in double ulps, "cr": glibc's pow correctly rounded there,
+    "scanned": floats scanned}"""
+    import os
+    import subprocess
+
+    if (lo, hi, k) not in _SCANS:
+        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        exe = os.path.join(str(workdir), "logit_inv_scan")
+        if not os.path.exists(exe):
+            subprocess.check_call(["g++", "-std=c++17", "-O2", "-pthread", "-ffp-contract=off", "-Wall", "-Werror",
+                                   os.path.join(root, "tests", "cpp", "logit_inv_scan.cpp"), "-o", exe, "-lquadmath"])
+        out = subprocess.run([exe, repr(lo), repr(hi), str(k)], check=True, capture_output=True, text=True).stdout.splitlines()
+        rows = [ln.split() for ln in out if not ln.startswith("#")]
+        tail = out[-1].split()
+        assert tail[:2] == ["#", "scanned"], out[-1]
+        _SCANS[(lo, hi, k)] = {
+            "L": np.array([int(r[0], 16) for r in rows], dtype=np.uint32).view(np.float32),
+            "f": np.array([int(r[1], 16) for r in rows], dtype=np.uint32).view(np.float32),
+            "m": np.array([int(r[2]) for r in rows], dtype=np.int64),
+            "cr": np.array([int(r[3]) for r in rows], dtype=bool),
+            "scanned": int(tail[2]), "threads": int(tail[6])}
+    return _SCANS[(lo, hi, k)]
+
+
+def float_range(lo: float, hi: float, step: int = 1) -> np.ndarray:
+    """every step-th float32 of [lo, hi], in increasing order"""
+    lo32, hi32 = np.float32(lo), np.float32(hi)
+    parts = []
+    if lo32 < 0:  # negative floats: the bit pattern grows as the value falls
+        top = np.float32(min(hi32, -0.0)).view(np.uint32) if hi32 < 0 else np.uint32(0x80000000)
+        parts.append(np.arange(int(lo32.view(np.uint32)), int(top) - 1, -step, dtype=np.int64).astype(np.uint32).view(np.float32))
+    if hi32 >= 0:
+        start = 0 if lo32 < 0 else int(lo32.view(np.uint32))
+        parts.append(np.arange(start, int(hi32.view(np.uint32)) + 1, step, dtype=np.int64).astype(np.uint32).view(np.float32))
+    return np.concatenate(parts)
+
+
 def voxel_centres(b: dict, cfg, limit: int = 200000, seed: int = 0) -> np.ndarray:
     """World centres of (a sample of) the allocated voxels: subbox_id2xyz_glb_vec (map_local.h:208-213)."""
     n = cfg.subbox_n
