@@ -228,6 +228,24 @@ class mlmap {
         check(mlm_export_esdf(h_, lo, dims, max_dist, flags, sqdist, dist, grad3), "mlm_export_esdf");
     }
 
+    // segment casts through the voxel map (mlm_query_rays; flags MLM_RAY_*; n x 3 end points; inputs and outputs host or device
+    // memory, NULL output = skipped)
+    void castRays(const double *p0, const double *p1, int n, int flags, int8_t *status, int32_t *voxel3 = nullptr, double *t = nullptr,
+                  int32_t *n_steps = nullptr, int32_t *n_unknown = nullptr) {
+        check(mlm_query_rays(h_, p0, p1, n, flags, status, voxel3, t, n_steps, n_unknown), "mlm_query_rays");
+    }
+    // one segment (answered from the host mirror: no launch): true if it stops at a voxel that `flags` selects; t_hit the segment
+    // parameter at which that voxel is entered (1 without a stop), voxel3 that voxel (the end voxel without a stop), n_unknown the
+    // UNKNOWN voxels in front of it.  An invalid segment (not finite, longer than 32 768 voxels on an axis) throws.
+    template <class V3>
+    bool castRay(const V3 &p0, const V3 &p1, int flags, double *t_hit = nullptr, int32_t *voxel3 = nullptr, int32_t *n_unknown = nullptr) {
+        const double a[3] = {p0[0], p0[1], p0[2]}, b[3] = {p1[0], p1[1], p1[2]};
+        int8_t st = 0;
+        check(mlm_query_rays(h_, a, b, 1, flags, &st, voxel3, t_hit, nullptr, n_unknown), "mlm_query_rays");
+        if (st < 0) throw std::runtime_error("castRay: invalid segment");
+        return st == 1;
+    }
+
     // planners that query thousands of positions per cycle should use the batched entry points directly
     mlm_handle *handle() { return h_; }
 

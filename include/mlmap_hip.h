@@ -250,6 +250,45 @@ int mlm_export_window(mlm_handle *h, const int32_t lo[3], const int32_t dims[3],
 #define MLM_ESDF_SIGNED 8
 int mlm_export_esdf(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], int max_dist, int flags,
                     int32_t *sqdist, float *dist, float *grad3);
+/* Batched segment casts through the voxel map (no reference counterpart: the reference has no segment query; the classes a ray
+ * meets are those of its point queries, the path is defined here, in integers).  Segment i runs from p0[i] to p1[i] (n x 3 world
+ * positions).  d = subbox_d_xyz, voxel indices are those of mlm_export_window.
+ *   Lattice: a coordinate x becomes q = floor((x / d) * 1024.0) in IEEE double.  A ray is INVALID (status -1, voxel3 0,0,0, t 0.0,
+ *   counts 0) if one of its six q is not finite or |q| >= 2^40, or if |Q1 - Q0| > 2^25 on an axis (32 768 voxels).  Otherwise
+ *   D = Q1 - Q0, start voxel v = Q0 >> 10, end voxel e = Q1 >> 10 (floor), N = sum over the axes of |e - v|.  The start voxel is
+ *   floor(x / d) per axis, the voxel whose mlm_export_window entry is read: at the few positions where the reference's two
+ *   divisions in get_global_idx / get_subbox_id disagree (the id-0 quirk) that is not the cell getOccupancy(pos) reads.
+ *   Steps: per axis with D != 0, s = sign(D) and m = s > 0 ? ((v + 1) << 10) - Q0 : Q0 - (v << 10), so m / |D| is the segment
+ *   parameter at which the ray leaves the current voxel along that axis.  Exactly N times: among the axes with v != e take the
+ *   one with the smallest m / |D| (compared by cross-multiplication in 64 bits), ties to the lowest axis (x before y before z);
+ *   (m, |D|) of that axis is the entry parameter of the next voxel; v += s, m += 1024.  The path is 6-connected, has N + 1 voxels,
+ *   ends at e, and every voxel of it touches the closed segment: a ray through an exact edge or corner also visits the voxels it
+ *   grazes (conservative for collision checks, and deterministic).
+ *   Predicate: O(v) is the union of what `flags` selects — MLM_RAY_OCC getOccupancy(centre) == OCCUPIED, MLM_RAY_INFL
+ *   getInflateOccupancy(centre) == OCCUPIED, MLM_RAY_UNKNOWN getOccupancy(centre) == UNKNOWN — i.e. mlm_export_esdf's predicate on
+ *   what mlm_export_window's occ / infl channels return at v (released frontier-mode blocks, absent blocks and voxels beyond the
+ *   key range included).  flags == 0: nothing stops the ray (a pure count).  Voxels are tested in path order from the start voxel
+ *   (path index 0).  Per ray:
+ *                          stopped at path index k (first voxel with O)          no voxel with O
+ *     status    int8       1                                                      0
+ *     voxel3    int32 x 3  that voxel                                             e
+ *     t         double     (double)m / (double)|D| of the step that entered it;   1.0
+ *                          0.0 for k = 0
+ *     n_steps   int32      k                                                      N + 1
+ *     n_unknown int32      voxels with occ == UNKNOWN among path indices 0..k-1   the same over the whole path
+ *   p0 + t (p1 - p0) is where the segment enters the stopping voxel (up to the 1/1024-voxel lattice); n_unknown is the exploration
+ *   gain of the ray.
+ * Inputs and outputs may be host or device memory, each pointer on its own; any output may be NULL, at least one must not be.  The
+ * call returns when the outputs are written, observes the map as queries do (async mode: waits for everything submitted) and runs
+ * on the stream of mlm_set_stream.  Small batches in host memory are answered from the host mirror like small query batches (same
+ * answers).  MLM_ERR_INVALID: n < 0, a NULL input with n > 0, an unknown flag bit, no output; n == 0 is MLM_OK.  MLM_ERR_CAPACITY:
+ * no device memory for the staging of host inputs / outputs (at most 77 bytes x 2^20 rays, kept by the handle and counted in
+ * mlm_frame_stats.device_bytes; larger batches run in chunks). */
+#define MLM_RAY_OCC 1 /* same bits and same meaning as MLM_ESDF_OCC / _INFL / _UNKNOWN */
+#define MLM_RAY_INFL 2
+#define MLM_RAY_UNKNOWN 4
+int mlm_query_rays(mlm_handle *h, const double *p0, const double *p1, int n, int flags, int8_t *status, int32_t *voxel3, double *t,
+                   int32_t *n_steps, int32_t *n_unknown);
 /* Load blocks into the map (no reference counterpart: the reference never persists or merges maps; this is how a
  * merged global map, mlmapping_amd/merge.py, is put back behind the query interface).  keys [n*3]; log_odds / occ /
  * infl [n*cells] and collapsed [n] as mlm_export_blocks / mlm_export_block_flags write them, any of them may be NULL

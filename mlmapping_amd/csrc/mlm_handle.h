@@ -26,7 +26,7 @@ struct KernelTime {
 // switches MLM_DEBUG_CREATE / MLM_DEBUG_ALLOC / MLM_DEBUG_DRAIN, which print).
 const char *const kKnobNames[] = {"agg_lds", "big_arm", "big_grid", "bin_block", "chain_grid", "collect_grid", "cu_reserve", "cu_split",
                                   "esdf_tile_vox", "ex_spec", "expand_block", "graph", "logit_exact", "mirror", "mirror_max", "mirror_mb", "need_slots", "node_lds", "pool_grow",
-                                  "rank_grid", "sc_block", "sc_grid", "sec_backoff", "sec_fail_every", "sec_tab", "sec_tab_big", "sec_threads",
+                                  "rank_grid", "rays_grid", "sc_block", "sc_grid", "sec_backoff", "sec_fail_every", "sec_tab", "sec_tab_big", "sec_threads",
                                   "sectors", "single_apply_grid", "single_chain_grid", "single_rank_grid", "slot_sets", "sort_block", "sort_grid", "tile_grid", "tile_sh"};
 struct KnobStore {
     std::mutex mu;
@@ -44,7 +44,7 @@ bool knob_value_ok(const char *name, long long v) {
     auto is = [&](const char *k) { return strcmp(name, k) == 0; };
     if (is("expand_block") || is("sort_block") || is("sc_block")) return v >= 64 && v <= 256 && v % 64 == 0;
     if (is("bin_block")) return v == 256 || v == 512 || v == 1024;
-    if (is("big_grid") || is("chain_grid") || is("collect_grid") || is("rank_grid") || is("sc_grid") || is("single_apply_grid") ||
+    if (is("big_grid") || is("chain_grid") || is("collect_grid") || is("rank_grid") || is("rays_grid") || is("sc_grid") || is("single_apply_grid") ||
         is("single_chain_grid") || is("single_rank_grid") || is("sort_grid") || is("tile_grid"))
         return v >= 1 && v <= (1ll << 20);
     if (is("cu_split") || is("cu_reserve")) return v >= 0 && v <= 0x7FFFFFFFll;
@@ -91,6 +91,9 @@ struct MlmMirror {
     bool alloc_failed = false;     // the pinned planes could not be allocated: disabled for good, queries run as kernels
     int max_clean = 256;           // largest batch answered on the host while the mirror is up to date (knob "mirror_max") ...
     int max_dirty = 32;            // ... and while it needs a refresh first (a large batch is then cheaper as one kernel)
+    // mlm_query_rays: a ray costs a walk, not one lookup, so a batch of rays is answered on the host when it has at most a quarter
+    // as many rays as the limits above allow positions (64 / 8 by default; "mirror_max" scales both) AND its paths together have at
+    // most kRayMirrorSteps voxels (known from the end points before anything is walked); everything else is one kernel
     size_t cap = 0;                // blocks the planes hold
     size_t max_bytes = (size_t)1 << 30; // most pinned host memory the planes may take (mlm_set_host_mirror_limit; knob "mirror_mb"): a map
                                    // that needs more is queried by kernels only (over_limit) — nothing is pinned behind the caller's back without bound
@@ -118,6 +121,8 @@ struct MlmMirror {
 // status of mirror_sync (mlm_mirror.h) when the map has outgrown mlm_set_host_mirror_limit: the query runs as a kernel instead
 // (never returned by an entry point)
 constexpr int kMirrorUnavailable = 1;
+constexpr long long kRayMirrorSteps = 16384; // ~50 us of host walking: about what a launch, two copies and a synchronisation cost
+constexpr int kRayChunk = 1 << 20;           // rays per launch of k_rays: bounds the staging of host inputs / outputs (77 bytes per ray)
 
 // A frame on its own with at most this many strips of 256 points (sampled callbacks, point lists: 4 096 points) runs its cells' float chains
 // inside k_rank<true> instead of launching k_chain_lanes — a launch of its own costs a lone frame the kernel boundary (1.5 us) and the few
@@ -147,6 +152,10 @@ struct mlm_handle {
     // mlm_export_esdf: obstacle mask and the two fields of the grown tile (staging shares d_win_stage), kept and enlarged by need
     void *d_esdf_scratch = nullptr;
     size_t esdf_scratch_bytes = 0;
+    // mlm_query_rays: staging of the host inputs / outputs of one chunk of rays, kept and enlarged by need
+    void *d_ray_stage = nullptr;
+    size_t ray_stage_bytes = 0;
+    unsigned int rays_grid = 1024; // most workgroups of k_rays (knob "rays_grid"): 2^20 rays are four per lane
     // sort buffers (rehash frames only)
     unsigned long long *sk_in = nullptr, *sk_out = nullptr;
     uint32_t *sv_in = nullptr, *sv_out = nullptr;

@@ -11,6 +11,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "mlm_raywalk.h"
+
 namespace mlm_host {
 
 struct MapView {
@@ -191,6 +193,43 @@ struct MapView {
                 ((double *)out)[3 * (size_t)i + 1] = r[1];
                 ((double *)out)[3 * (size_t)i + 2] = r[2];
             }
+        }
+    }
+    // mlm_query_rays on the mirrored planes: the walk of mlm_raywalk.h over the classes getOccupancy / getInflateOccupancy return at
+    // the voxels (a released block answers from element 0, its inflated class is UNKNOWN; an absent block is UNKNOWN).  One table
+    // probe per block crossed.
+    struct RayClasses {
+        const MapView &v;
+        int slot = -1, fixed = 4; // fixed: the class of every voxel of an absent or released block
+        bool whole = true;
+        static int occ_bits(uint8_t r) { return r == 'o' ? 1 : (r == 'f' ? 0 : 4); }
+        int operator()(const int g[3], const int c[3], bool new_block) {
+            if (new_block) {
+                slot = v.find(g[0], g[1], g[2]);
+                whole = slot < 0 || v.col[slot];
+                fixed = slot < 0 ? 4 : occ_bits(v.occ[(size_t)slot * v.cells]);
+            }
+            if (whole) return fixed;
+            const size_t at = (size_t)slot * v.cells + (size_t)((c[2] * v.n + c[1]) * v.n + c[0]);
+            return occ_bits(v.occ[at]) | (v.infl[at] == 'o' ? 2 : 0);
+        }
+    };
+    void ray(const double p0[3], const double p1[3], int flags, MlmRayResult &o) const {
+        RayClasses cls{*this};
+        mlm_ray_walk(p0, p1, d_sub, n, flags, cls, o);
+    }
+    // a batch, any output may be null (mlm_query_rays' layout)
+    void rays(const double *p0, const double *p1, int count, int flags, int8_t *status, int32_t *voxel3, double *t, int32_t *n_steps,
+              int32_t *n_unknown) const {
+        for (int i = 0; i < count; ++i) {
+            MlmRayResult o;
+            ray(p0 + 3 * (size_t)i, p1 + 3 * (size_t)i, flags, o);
+            if (status) status[i] = (int8_t)o.status;
+            if (voxel3)
+                for (int a = 0; a < 3; ++a) voxel3[3 * (size_t)i + a] = o.voxel[a];
+            if (t) t[i] = o.t;
+            if (n_steps) n_steps[i] = o.n_steps;
+            if (n_unknown) n_unknown[i] = o.n_unknown;
         }
     }
 };

@@ -262,6 +262,18 @@ bool mirror_wanted(const mlm_handle *h, int mode, int n, int max_iter) {
     if (mode == 4) work *= 1 + 6 * (long long)std::min(max_iter, 64);
     return work <= (M.dirty ? M.max_dirty : M.max_clean);
 }
+// ... and a batch of rays (mlm_query_rays): few rays whose paths are short enough together (MlmMirror, mlm_handle.h)
+bool mirror_rays_wanted(const mlm_handle *h, const double *p0, const double *p1, int n) {
+    const MlmMirror &M = h->mir;
+    if (!M.enabled || (long long)n * 4 > (M.dirty ? M.max_dirty : M.max_clean)) return false;
+    long long steps = 0;
+    for (int i = 0; i < n; ++i) {
+        MlmRayState S;
+        if (!mlm_ray_setup(p0 + 3 * (size_t)i, p1 + 3 * (size_t)i, h->P.d_sub, h->P.n, S)) continue;
+        steps += 1 + S.r[0] + S.r[1] + S.r[2];
+    }
+    return steps <= kRayMirrorSteps;
+}
 // drain + refresh if the map changed since the mirror was filled; the caller holds the lock
 int mirror_sync(mlm_handle *h) {
     if (h->mir.eager_pending) {

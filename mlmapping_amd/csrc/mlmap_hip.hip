@@ -31,6 +31,7 @@
 #include "mlm_kernels_sector.h"
 #include "mlm_kernels_window.h"
 #include "mlm_kernels_esdf.h"
+#include "mlm_kernels_rays.h"
 #include "mlm_host.h"
 #include "mlm_mapview.h"
 
@@ -465,6 +466,7 @@ int mlm_create(const mlm_config *cfg, const mlm_limits *lim_in, int device, mlm_
         if (knob("single_apply_grid", kv)) h->single_apply_grid = (unsigned int)std::max(1, (int)kv);
         if (knob("mirror", kv)) h->mir.enabled = (int)kv != 0;
         if (knob("mirror_mb", kv)) h->mir.max_bytes = (size_t)std::max(0, (int)kv) << 20;
+        if (knob("rays_grid", kv)) h->rays_grid = (unsigned int)kv;
         if (knob("mirror_max", kv)) h->mir.max_clean = std::max(0, (int)kv), h->mir.max_dirty = std::min(h->mir.max_dirty, h->mir.max_clean);
         mirror_apply_limit(h);
     }
@@ -1345,6 +1347,66 @@ int mlm_export_esdf(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], i
                         HIPCHK(h, hipMemcpyAsync((char *)dst[c] + (size_t)Q.out_base * elem[c], ch[c], (size_t)nt * elem[c], hipMemcpyDefault,
                                                  h->stream));
             }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MLM_OK;
+}
+
+int mlm_query_rays(mlm_handle *h, const double *p0, const double *p1, int n, int flags, int8_t *status, int32_t *voxel3, double *t,
+                   int32_t *n_steps, int32_t *n_unknown) {
+    if (!h) return MLM_ERR_INVALID;
+    MLM_LOCK(h);
+    if (n < 0 || (n > 0 && (!p0 || !p1)) || (flags & ~7) || (!status && !voxel3 && !t && !n_steps && !n_unknown)) {
+        h->err = "mlm_query_rays: negative n, a null input, an unknown flag bit or no output";
+        return MLM_ERR_INVALID;
+    }
+    if (n == 0) return MLM_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    // channels: the two inputs, then the five outputs; bytes per ray; in device memory (used in place) or staged
+    void *ch[7] = {(void *)p0, (void *)p1, status, voxel3, t, n_steps, n_unknown};
+    const size_t elem[7] = {3 * sizeof(double), 3 * sizeof(double), 1, 3 * sizeof(int32_t), sizeof(double), sizeof(int32_t), sizeof(int32_t)};
+    bool staged[7];
+    bool all_host = true;
+    for (int c = 0; c < 7; ++c) {
+        staged[c] = ch[c] && !win_in_place(ch[c]);
+        all_host = all_host && (staged[c] || !ch[c]);
+    }
+    // a planner's edge-by-edge calls: answered on the host (mlm_mirror.h), like run_query's small batches
+    if (all_host && mirror_rays_wanted(h, p0, p1, n)) {
+        const int rc = mirror_sync(h);
+        if (rc == MLM_OK) {
+            h->mir.view.rays(p0, p1, n, flags, status, voxel3, t, n_steps, n_unknown);
+            h->mir.n_host_queries += n;
+            return MLM_OK;
+        }
+        if (!h->mir.alloc_failed && rc != kMirrorUnavailable) return rc; // (an error of the frames in flight, reported by the drain)
+        // (no pinned host memory for the mirror, or more than its limit allows: this and all later batches run as kernels)
+    }
+    int rc = drain(h);
+    if (rc) return rc;
+    // chunks: staged channels of a chunk share one kept buffer (at most 77 bytes per ray)
+    const int chunk = std::min(n, kRayChunk);
+    size_t off[7], stage_bytes = 0;
+    for (int c = 0; c < 7; ++c) {
+        off[c] = stage_bytes;
+        if (staged[c]) stage_bytes += ((size_t)chunk * elem[c] + 255) & ~(size_t)255;
+    }
+    if (stage_bytes && (rc = win_reserve(h, h->d_ray_stage, h->ray_stage_bytes, stage_bytes, "mlm_query_rays"))) return rc;
+    for (int i0 = 0; i0 < n; i0 += chunk) {
+        const int m = std::min(chunk, n - i0);
+        void *at[7];
+        for (int c = 0; c < 7; ++c)
+            at[c] = !ch[c] ? nullptr : staged[c] ? (void *)((char *)h->d_ray_stage + off[c]) : (void *)((char *)ch[c] + (size_t)i0 * elem[c]);
+        for (int c = 0; c < 2; ++c)
+            if (staged[c])
+                HIPCHK(h, hipMemcpyAsync(at[c], (const char *)ch[c] + (size_t)i0 * elem[c], (size_t)m * elem[c], hipMemcpyHostToDevice, h->stream));
+        MlmRays R{(const double *)at[0], (const double *)at[1], m, flags, (int8_t *)at[2], (int32_t *)at[3], (double *)at[4], (int32_t *)at[5], (int32_t *)at[6]};
+        const dim3 grid(std::min<unsigned int>(grid_for((size_t)m), h->rays_grid));
+        hipLaunchKernelGGL(k_rays, grid, dim3(MLM_BLOCK), 0, h->stream, h->P, R);
+        HIPCHK(h, hipGetLastError());
+        for (int c = 2; c < 7; ++c)
+            if (staged[c])
+                HIPCHK(h, hipMemcpyAsync((char *)ch[c] + (size_t)i0 * elem[c], at[c], (size_t)m * elem[c], hipMemcpyDeviceToHost, h->stream));
+    }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MLM_OK;
 }

@@ -26,6 +26,8 @@ LIB_PATH = os.environ.get("MLMAP_HIP_LIB") or os.path.join(_HERE, "lib", "libmlm
 MLM_OK = 0
 # mlm_export_esdf flags (include/mlmap_hip.h): obstacle predicates (their union) and the signed field
 MLM_ESDF_OCC, MLM_ESDF_INFL, MLM_ESDF_UNKNOWN, MLM_ESDF_SIGNED = 1, 2, 4, 8
+# mlm_query_rays flags: what stops a ray (their union; 0: nothing, a pure count)
+MLM_RAY_OCC, MLM_RAY_INFL, MLM_RAY_UNKNOWN = 1, 2, 4
 STATUS = {0: "MLM_OK", -1: "MLM_ERR_INVALID", -2: "MLM_ERR_HIP", -3: "MLM_ERR_CAPACITY", -4: "MLM_ERR_UNSUPPORTED"}
 
 # every symbol include/mlmap_hip.h declares
@@ -37,7 +39,7 @@ ABI_SYMBOLS = [
     "mlm_query_odds", "mlm_query_odd_grad", "mlm_query_odds_at", "mlm_export_frontier_points", "mlm_import_blocks",
     "mlm_merge_pack", "mlm_merge_finish",
     "mlm_set_free_in_bound", "mlm_inflate_map", "mlm_block_count",
-    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
+    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_query_rays", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
     "mlm_get_awareness_hits",
     "mlm_get_awareness_misses", "mlm_get_T_ls", "mlm_get_odds_table", "mlm_get_kernel_times",
     "mlm_enable_kernel_timing", "mlm_set_timed_kernel", "mlm_host_register", "mlm_host_unregister", "mlm_debug_set", "mlm_debug_reset",
@@ -132,6 +134,7 @@ def load_library(path: Optional[str] = None):
     L.mlm_export_blocks.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     L.mlm_export_window.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
     L.mlm_export_esdf.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
+    L.mlm_query_rays.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.mlm_export_global_map.argtypes = [vp, i32, vp, vp]
     L.mlm_export_block_flags.argtypes = [vp, i32, vp, vp]
     L.mlm_export_frontier.argtypes = [vp, i32, vp, vp]
@@ -473,6 +476,36 @@ class MLMap:
         ptr = [None if v is None else ctypes.c_void_p(v) for v in (sqdist, dist, grad)]
         flags = self._esdf_flags(occ, infl, unknown, signed)
         self._chk(self._L.mlm_export_esdf(self._h, _p(lo_a), _p(dims_a), int(max_dist), flags, *ptr), "mlm_export_esdf")
+
+    def cast_rays(self, p0, p1, occ=True, infl=False, unknown=False) -> Dict[str, np.ndarray]:
+        """Cast the segments p0[i] -> p1[i] (n x 3 world positions) through the voxel map (mlm_query_rays): {"status": int8 (1
+        stopped, 0 reached the end, -1 invalid ray), "voxel": int32 (n, 3) the stopping or the end voxel, "t": float64 segment
+        parameter at which the stopping voxel is entered (1.0 without a stop), "n_steps": int32 path index of the stopping voxel
+        (voxels visited without a stop), "n_unknown": int32 UNKNOWN voxels in front of it}.  A ray stops at the first voxel that is
+        occ (getOccupancy == OCCUPIED), infl (getInflateOccupancy == OCCUPIED) or unknown (getOccupancy == UNKNOWN), whichever are
+        selected; none selected: a pure count."""
+        a, b = _f64(p0).reshape(-1, 3), _f64(p1).reshape(-1, 3)
+        if a.shape != b.shape:
+            raise MlmError("cast_rays: p0 and p1 differ in shape")
+        n = a.shape[0]
+        out = {"status": np.empty(n, dtype=np.int8), "voxel": np.empty((n, 3), dtype=np.int32), "t": np.empty(n, dtype=np.float64),
+               "n_steps": np.empty(n, dtype=np.int32), "n_unknown": np.empty(n, dtype=np.int32)}
+        self._chk(self._L.mlm_query_rays(self._h, _p(a), _p(b), n, self._ray_flags(occ, infl, unknown),
+                                         *[_p(out[k]) for k in ("status", "voxel", "t", "n_steps", "n_unknown")]), "mlm_query_rays")
+        return out
+
+    def cast_rays_dev(self, p0: int, p1: int, n: int, occ=True, infl=False, unknown=False, status: Optional[int] = None,
+                      voxel: Optional[int] = None, t: Optional[int] = None, n_steps: Optional[int] = None,
+                      n_unknown: Optional[int] = None):
+        """Same on device memory: pointers (ints) to n x 3 float64 end points and to n int8 / n x 3 int32 / n float64 / n int32 /
+        n int32 outputs, None = skipped."""
+        ptr = [None if v is None else ctypes.c_void_p(v) for v in (status, voxel, t, n_steps, n_unknown)]
+        self._chk(self._L.mlm_query_rays(self._h, ctypes.c_void_p(p0), ctypes.c_void_p(p1), int(n),
+                                         self._ray_flags(occ, infl, unknown), *ptr), "mlm_query_rays")
+
+    @staticmethod
+    def _ray_flags(occ, infl, unknown) -> int:
+        return (MLM_RAY_OCC if occ else 0) | (MLM_RAY_INFL if infl else 0) | (MLM_RAY_UNKNOWN if unknown else 0)
 
     @staticmethod
     def _esdf_flags(occ, infl, unknown, signed) -> int:
