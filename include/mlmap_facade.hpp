@@ -228,6 +228,13 @@ class mlmap {
         check(mlm_export_esdf(h_, lo, dims, max_dist, flags, sqdist, dist, grad3), "mlm_export_esdf");
     }
 
+    // cost-to-go field through the free space of a voxel box (mlm_export_reach; flags MLM_REACH_*; seeds3: n_seeds voxel index
+    // triples; steps / parent host or device memory, summary host memory, NULL = skipped)
+    void exportReach(const int32_t lo[3], const int32_t dims[3], const int32_t *seeds3, int n_seeds, int flags, int clearance, int max_steps,
+                     int32_t *steps, uint8_t *parent = nullptr, int64_t summary[4] = nullptr) {
+        check(mlm_export_reach(h_, lo, dims, seeds3, n_seeds, flags, clearance, max_steps, steps, parent, summary), "mlm_export_reach");
+    }
+
     // segment casts through the voxel map (mlm_query_rays; flags MLM_RAY_*; n x 3 end points; inputs and outputs host or device
     // memory, NULL output = skipped)
     void castRays(const double *p0, const double *p1, int n, int flags, int8_t *status, int32_t *voxel3 = nullptr, double *t = nullptr,

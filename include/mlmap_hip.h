@@ -289,6 +289,46 @@ int mlm_export_esdf(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], i
 #define MLM_RAY_UNKNOWN 4
 int mlm_query_rays(mlm_handle *h, const double *p0, const double *p1, int n, int flags, int8_t *status, int32_t *voxel3, double *t,
                    int32_t *n_steps, int32_t *n_unknown);
+/* Cost-to-go field through the free space of a box of voxels (no reference counterpart: the reference has no such field; the
+ * classes behind it are those of its point queries, the field is defined here, in integers).  Voxel indices, window, layout
+ * ([dims[2]][dims[1]][dims[0]], x fastest) and centres are those of mlm_export_window.
+ *   Obstacles: O(v) is the union of what `flags` selects — MLM_REACH_OCC getOccupancy(centre) == OCCUPIED, MLM_REACH_INFL
+ *   getInflateOccupancy(centre) == OCCUPIED, MLM_REACH_UNKNOWN getOccupancy(centre) == UNKNOWN — i.e. mlm_export_esdf's predicate
+ *   on what mlm_export_window's occ / infl channels return at v (released frontier-mode blocks, absent blocks and voxels beyond
+ *   the key range included).  flags == 0: no obstacles (as in mlm_query_rays).
+ *   Clearance r (0..63 voxels, the robot's radius): a voxel v is BLOCKED if some voxel o of the whole map (not only the box) has
+ *   O(o) and |v - o|^2 <= r^2 (integer squared index distance; r = 0: blocked iff O(v)): D_out(v) <= r^2 of mlm_export_esdf at
+ *   max_dist = r + 1, computed by the same passes.
+ *   Traversable: T(v) iff v lies in the box and is not blocked.  The domain is the box: a path never leaves it (obstacles are
+ *   looked up beyond it, paths are not; a caller who wants more context asks for a larger box).
+ *   Seeds: n_seeds >= 1 absolute voxel index triples (host or device memory).  A seed outside the box or not traversable
+ *   contributes nothing and is no error (the voxel that holds the vehicle is UNKNOWN in a fresh map: with MLM_REACH_UNKNOWN seed the
+ *   nearest traversable voxel instead); the others are the effective seeds.  Duplicates are allowed.
+ *   steps  int32  the smallest number of moves of a 6-connected path seed = v0, v1, ..., vk = v whose voxels are all traversable,
+ *                 over all effective seeds; 0 at an effective seed; MLM_REACH_NONE if v is not traversable, if there is no such
+ *                 path, or if that number exceeds max_steps (1 <= max_steps <= 2^31 - 1; values <= max_steps are what they are
+ *                 without the truncation)
+ *   parent uint8  at a reached voxel that is no seed the lowest code c whose neighbour v + e_c lies in the box and has
+ *                 steps == steps(v) - 1, codes 0: -x, 1: +x, 2: -y, 3: +y, 4: -z, 5: +z; MLM_REACH_SEED at effective seeds; 255
+ *                 where steps is MLM_REACH_NONE.  Following parent from a reached voxel walks one shortest path to a seed.
+ *   summary int64 x 4 (host memory): [0] traversable voxels of the box, [1] reached voxels, [2] the largest steps written (-1:
+ *                 none), [3] relaxation sweeps the call needed (informative: depends on the tile geometry).
+ * steps and parent may be host or device memory; any of the three outputs may be NULL, at least one must not be.  The field is
+ * the least fixpoint of steps(v) = min(steps(v), 1 + min over traversable neighbours) from the seeds, so it has exactly one value
+ * whatever the schedule.  The call observes the map as queries do (async mode: waits for everything submitted), runs on the
+ * stream of mlm_set_stream and returns when the outputs are written.  MLM_ERR_INVALID: mlm_export_window's window errors,
+ * n_seeds < 1 or seeds3 == NULL, an unknown flag bit, clearance outside [0, 63], max_steps < 1, no output.  MLM_ERR_CAPACITY:
+ * no device memory for the scratch: this is a global problem that cannot be cut into independent tiles, so the whole box's
+ * field (4 bytes per voxel), one mask byte per voxel and two dirty bytes per tile are resident at once (plus the ESDF scratch
+ * with clearance > 0 and a staging copy of host outputs), kept by the handle and counted in mlm_frame_stats.device_bytes.  The
+ * handle stays usable after either error. */
+#define MLM_REACH_OCC 1 /* same bits and same meaning as MLM_ESDF_OCC / _INFL / _UNKNOWN */
+#define MLM_REACH_INFL 2
+#define MLM_REACH_UNKNOWN 4
+#define MLM_REACH_NONE (-1) /* steps of a voxel that is not reached */
+#define MLM_REACH_SEED 6    /* parent code of a seed */
+int mlm_export_reach(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], const int32_t *seeds3, int n_seeds,
+                     int flags, int clearance, int max_steps, int32_t *steps, uint8_t *parent, int64_t summary[4]);
 /* Load blocks into the map (no reference counterpart: the reference never persists or merges maps; this is how a
  * merged global map, mlmapping_amd/merge.py, is put back behind the query interface).  keys [n*3]; log_odds / occ /
  * infl [n*cells] and collapsed [n] as mlm_export_blocks / mlm_export_block_flags write them, any of them may be NULL

@@ -26,7 +26,7 @@ struct KernelTime {
 // switches MLM_DEBUG_CREATE / MLM_DEBUG_ALLOC / MLM_DEBUG_DRAIN, which print).
 const char *const kKnobNames[] = {"agg_lds", "big_arm", "big_grid", "bin_block", "chain_grid", "collect_grid", "cu_reserve", "cu_split",
                                   "esdf_tile_vox", "ex_spec", "expand_block", "graph", "logit_exact", "mirror", "mirror_max", "mirror_mb", "need_slots", "node_lds", "pool_grow",
-                                  "rank_grid", "rays_grid", "sc_block", "sc_grid", "sec_backoff", "sec_fail_every", "sec_tab", "sec_tab_big", "sec_threads",
+                                  "rank_grid", "rays_grid", "reach_group", "reach_tile", "sc_block", "sc_grid", "sec_backoff", "sec_fail_every", "sec_tab", "sec_tab_big", "sec_threads",
                                   "sectors", "single_apply_grid", "single_chain_grid", "single_rank_grid", "slot_sets", "sort_block", "sort_grid", "tile_grid", "tile_sh"};
 struct KnobStore {
     std::mutex mu;
@@ -49,6 +49,8 @@ bool knob_value_ok(const char *name, long long v) {
         return v >= 1 && v <= (1ll << 20);
     if (is("cu_split") || is("cu_reserve")) return v >= 0 && v <= 0x7FFFFFFFll;
     if (is("esdf_tile_vox")) return v >= kEsdfMinBoxVoxels && v <= kEsdfBoxVoxels; // (mlm_esdf_plan fits every call's tile then)
+    if (is("reach_tile")) return mlm_reach_tile_ok(v);  // (x | y << 8 | z << 16, edges 1..64, tile + halo within k_reach_sweep's LDS)
+    if (is("reach_group")) return v >= 1 && v <= kReachGroupMax; // (sweeps between two looks at the "marked" words)
     return true;
 }
 bool knob(const char *name, long long &out) {
@@ -152,6 +154,11 @@ struct mlm_handle {
     // mlm_export_esdf: obstacle mask and the two fields of the grown tile (staging shares d_win_stage), kept and enlarged by need
     void *d_esdf_scratch = nullptr;
     size_t esdf_scratch_bytes = 0;
+    // mlm_export_reach: field, mask, dirty arrays, control block and seeds of the whole box (mlm_reach_plan), kept and enlarged by
+    // need (the ESDF passes of clearance > 0 use d_esdf_scratch, staged outputs d_win_stage); pinned copy of the control block
+    void *d_reach = nullptr;
+    size_t reach_bytes = 0;
+    unsigned int *h_reach_ctrl = nullptr;
     // mlm_query_rays: staging of the host inputs / outputs of one chunk of rays, kept and enlarged by need
     void *d_ray_stage = nullptr;
     size_t ray_stage_bytes = 0;

@@ -146,6 +146,58 @@ inline MlmEsdfPlan mlm_esdf_plan(const long long D[3], int C, bool grad, long lo
     return p;
 }
 
+// Geometry, scratch and sweep cap of mlm_export_reach (mlm_kernels_reach.h, mlm_reach.h) for a box of D[0] x D[1] x D[2] voxels cut
+// into tiles of T[0] x T[1] x T[2] (knob "reach_tile": T[0] | T[1] << 8 | T[2] << 16; the last tile per axis is cut to the box).
+// A workgroup of k_reach_sweep stages a tile and its one-voxel halo as u32 in LDS: at most kReachHaloVoxels of them (60 KB, two
+// workgroups per CU).  The whole box is resident at once: the field (4 B per voxel), the traversable mask (1 B), two dirty bytes
+// per tile (this sweep's and the next one's), a control block (one "marked something" word per sweep of a group, the summary
+// counters) and the seeds; each part starts on a multiple of 256 bytes.  cap: sweeps after which the field is final whatever
+// the map (mlm_reach.h: a shortest path crosses at most min(max_steps, voxels - 1) tile faces, one sweep per crossing, one for
+// the seeds' tiles, one that marks nothing), rounded up to whole groups by the host loop.  ok == false: a tile edge outside
+// [1, 64] or a halo box beyond kReachHaloVoxels.
+constexpr long long kReachTileDefault = 32 | (8 << 8) | (8 << 16);
+constexpr long long kReachHaloVoxels = 15360;
+constexpr long long kReachGroupDefault = 8, kReachGroupMax = 256;
+constexpr long long kReachCtrlBytes = 2048; // kReachGroupMax words, then the counters
+struct MlmReachPlan {
+    bool ok;
+    long long T[3], n[3], tiles, voxels;
+    long long field_bytes, mask_bytes, dirty_bytes, seed_bytes; // (dirty_bytes: one of the two arrays)
+    long long off_mask, off_dirty, off_ctrl, off_seeds, scratch_bytes;
+    long long cap;
+};
+inline bool mlm_reach_tile_ok(long long packed) {
+    if (packed < 0 || packed >> 24) return false;
+    const long long t[3] = {packed & 255, (packed >> 8) & 255, (packed >> 16) & 255};
+    for (int a = 0; a < 3; ++a)
+        if (t[a] < 1 || t[a] > 64) return false;
+    return (t[0] + 2) * (t[1] + 2) * (t[2] + 2) <= kReachHaloVoxels;
+}
+inline MlmReachPlan mlm_reach_plan(const long long D[3], long long tile_packed, long long n_seeds, long long max_steps) {
+    MlmReachPlan p{};
+    if (!mlm_reach_tile_ok(tile_packed) || D[0] < 1 || D[1] < 1 || D[2] < 1 || n_seeds < 1 || max_steps < 1) return p;
+    auto up = [](long long v) { return (v + 255) & ~255ll; };
+    p.voxels = 1;
+    for (int a = 0; a < 3; ++a) {
+        p.T[a] = (tile_packed >> (8 * a)) & 255;
+        p.n[a] = (D[a] + p.T[a] - 1) / p.T[a];
+        p.voxels *= D[a];
+    }
+    p.tiles = p.n[0] * p.n[1] * p.n[2];
+    p.field_bytes = up(4 * p.voxels);
+    p.mask_bytes = up(p.voxels);
+    p.dirty_bytes = up(p.tiles);
+    p.seed_bytes = up(12 * n_seeds);
+    p.off_mask = p.field_bytes;
+    p.off_dirty = p.off_mask + p.mask_bytes;
+    p.off_ctrl = p.off_dirty + 2 * p.dirty_bytes;
+    p.off_seeds = p.off_ctrl + kReachCtrlBytes;
+    p.scratch_bytes = p.off_seeds + p.seed_bytes;
+    p.cap = std::min(max_steps, p.voxels - 1) + 2;
+    p.ok = true;
+    return p;
+}
+
 namespace mlm_host {
 
 // Does this host's libm log10f (what the reference's logit macro calls) agree with mlm_glibc_log10f?  Checked on the values the

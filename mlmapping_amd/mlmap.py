@@ -26,6 +26,8 @@ LIB_PATH = os.environ.get("MLMAP_HIP_LIB") or os.path.join(_HERE, "lib", "libmlm
 MLM_OK = 0
 # mlm_export_esdf flags (include/mlmap_hip.h): obstacle predicates (their union) and the signed field
 MLM_ESDF_OCC, MLM_ESDF_INFL, MLM_ESDF_UNKNOWN, MLM_ESDF_SIGNED = 1, 2, 4, 8
+# mlm_export_reach: obstacle predicates (their union; none: no obstacles), steps of a voxel not reached, parent code of a seed
+MLM_REACH_OCC, MLM_REACH_INFL, MLM_REACH_UNKNOWN, MLM_REACH_NONE, MLM_REACH_SEED = 1, 2, 4, -1, 6
 # mlm_query_rays flags: what stops a ray (their union; 0: nothing, a pure count)
 MLM_RAY_OCC, MLM_RAY_INFL, MLM_RAY_UNKNOWN = 1, 2, 4
 STATUS = {0: "MLM_OK", -1: "MLM_ERR_INVALID", -2: "MLM_ERR_HIP", -3: "MLM_ERR_CAPACITY", -4: "MLM_ERR_UNSUPPORTED"}
@@ -39,7 +41,7 @@ ABI_SYMBOLS = [
     "mlm_query_odds", "mlm_query_odd_grad", "mlm_query_odds_at", "mlm_export_frontier_points", "mlm_import_blocks",
     "mlm_merge_pack", "mlm_merge_finish",
     "mlm_set_free_in_bound", "mlm_inflate_map", "mlm_block_count",
-    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_query_rays", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
+    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_reach", "mlm_query_rays", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
     "mlm_get_awareness_hits",
     "mlm_get_awareness_misses", "mlm_get_T_ls", "mlm_get_odds_table", "mlm_get_kernel_times",
     "mlm_enable_kernel_timing", "mlm_set_timed_kernel", "mlm_host_register", "mlm_host_unregister", "mlm_debug_set", "mlm_debug_reset",
@@ -134,6 +136,7 @@ def load_library(path: Optional[str] = None):
     L.mlm_export_blocks.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     L.mlm_export_window.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
     L.mlm_export_esdf.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
+    L.mlm_export_reach.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     L.mlm_query_rays.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.mlm_export_global_map.argtypes = [vp, i32, vp, vp]
     L.mlm_export_block_flags.argtypes = [vp, i32, vp, vp]
@@ -476,6 +479,41 @@ class MLMap:
         ptr = [None if v is None else ctypes.c_void_p(v) for v in (sqdist, dist, grad)]
         flags = self._esdf_flags(occ, infl, unknown, signed)
         self._chk(self._L.mlm_export_esdf(self._h, _p(lo_a), _p(dims_a), int(max_dist), flags, *ptr), "mlm_export_esdf")
+
+    def export_reach(self, lo, dims, seeds, occ=True, infl=False, unknown=False, clearance: int = 0, max_steps: Optional[int] = None,
+                     steps=True, parent=False) -> Dict[str, np.ndarray]:
+        """Cost-to-go through the free space of the voxel box lo <= v < lo + dims (voxel indices as export_window) from `seeds`
+        (k x 3 voxel indices): {"steps": int32 (dz, dy, dx), moves of the shortest 6-connected path of traversable voxels from a
+        seed, -1 where there is none (or it is longer than max_steps); "parent": uint8, the neighbour code (0: -x, 1: +x, 2: -y,
+        3: +y, 4: -z, 5: +z) one step nearer a seed, 6 at seeds, 255 where steps is -1; "summary": int64 [traversable, reached,
+        largest steps, sweeps]}.  Obstacles are the union of occ / infl / unknown as in export_esdf (none: no obstacles); a voxel
+        is traversable if no obstacle of the map lies within `clearance` voxels (Euclidean) of it; paths stay inside the box; a
+        seed that is not traversable contributes nothing (mlm_export_reach)."""
+        lo_a, dims_a = self._window_args(lo, dims)
+        shape = (int(dims_a[2]), int(dims_a[1]), int(dims_a[0]))
+        s = np.ascontiguousarray(np.asarray(seeds, dtype=np.int32).reshape(-1, 3))
+        out = {"summary": np.zeros(4, dtype=np.int64)}
+        if steps:
+            out["steps"] = np.empty(shape, dtype=np.int32)
+        if parent:
+            out["parent"] = np.empty(shape, dtype=np.uint8)
+        ptr = [_p(out[k]) if k in out else None for k in ("steps", "parent", "summary")]
+        self._chk(self._L.mlm_export_reach(self._h, _p(lo_a), _p(dims_a), _p(s), len(s), self._ray_flags(occ, infl, unknown), int(clearance),
+                                           2 ** 31 - 1 if max_steps is None else int(max_steps), *ptr), "mlm_export_reach")
+        return out
+
+    def export_reach_dev(self, lo, dims, seeds: int, n_seeds: int, occ=True, infl=False, unknown=False, clearance: int = 0,
+                         max_steps: Optional[int] = None, steps: Optional[int] = None, parent: Optional[int] = None,
+                         summary: bool = False) -> Optional[np.ndarray]:
+        """Same on device memory: `seeds` a pointer (int) to n_seeds x 3 int32, steps / parent pointers to dz*dy*dx int32 / uint8
+        elements, None = skipped; summary=True returns the four int64 counters."""
+        lo_a, dims_a = self._window_args(lo, dims)
+        sm = np.zeros(4, dtype=np.int64) if summary else None
+        ptr = [None if v is None else ctypes.c_void_p(v) for v in (steps, parent)] + [None if sm is None else _p(sm)]
+        self._chk(self._L.mlm_export_reach(self._h, _p(lo_a), _p(dims_a), ctypes.c_void_p(seeds), int(n_seeds),
+                                           self._ray_flags(occ, infl, unknown), int(clearance),
+                                           2 ** 31 - 1 if max_steps is None else int(max_steps), *ptr), "mlm_export_reach")
+        return sm
 
     def cast_rays(self, p0, p1, occ=True, infl=False, unknown=False) -> Dict[str, np.ndarray]:
         """Cast the segments p0[i] -> p1[i] (n x 3 world positions) through the voxel map (mlm_query_rays): {"status": int8 (1
