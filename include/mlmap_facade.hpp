@@ -235,6 +235,13 @@ class mlmap {
         check(mlm_export_reach(h_, lo, dims, seeds3, n_seeds, flags, clearance, max_steps, steps, parent, summary), "mlm_export_reach");
     }
 
+    // connected components of a voxel set of a box with per-component statistics (mlm_export_clusters; flags MLM_CLUSTER_*;
+    // connectivity 6 / 18 / 26; labels / table host or device memory, table [cap][MLM_CLUSTER_ROW], summary host memory, NULL = skipped)
+    void exportClusters(const int32_t lo[3], const int32_t dims[3], int flags, int connectivity, int min_size, int32_t *labels,
+                        int64_t *table = nullptr, int cap = 0, int64_t summary[6] = nullptr) {
+        check(mlm_export_clusters(h_, lo, dims, flags, connectivity, min_size, labels, table, cap, summary), "mlm_export_clusters");
+    }
+
     // segment casts through the voxel map (mlm_query_rays; flags MLM_RAY_*; n x 3 end points; inputs and outputs host or device
     // memory, NULL output = skipped)
     void castRays(const double *p0, const double *p1, int n, int flags, int8_t *status, int32_t *voxel3 = nullptr, double *t = nullptr,

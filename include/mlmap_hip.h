@@ -329,6 +329,51 @@ int mlm_query_rays(mlm_handle *h, const double *p0, const double *p1, int n, int
 #define MLM_REACH_SEED 6    /* parent code of a seed */
 int mlm_export_reach(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], const int32_t *seeds3, int n_seeds,
                      int flags, int clearance, int max_steps, int32_t *steps, uint8_t *parent, int64_t summary[4]);
+/* Connected components of a voxel set of a box, with per-component statistics (no reference counterpart: the reference has no
+ * clustering, its visualiser publishes the frontier cloud raw; the classes behind the set are those of its point queries, set,
+ * components and numbering are defined here, in integers).  Voxel indices, window, layout ([dims[2]][dims[1]][dims[0]], x
+ * fastest) and centres are those of mlm_export_window.
+ *   The set S: `flags` is either MLM_CLUSTER_FRONTIER alone or a non-empty union of MLM_CLUSTER_OCC / _INFL / _UNKNOWN.  The class
+ *   bits: S(v) iff v lies in the box and mlm_export_esdf's obstacle predicate O(v) holds.  FRONTIER: S(v) iff v lies in the box,
+ *   occ(v) == FREE and occ(u) == UNKNOWN for at least one of the six face neighbours u of v, occ being what mlm_export_window's occ
+ *   channel returns; neighbours are looked up in the whole map, also outside the box (released frontier-mode blocks and absent
+ *   blocks included); a neighbour whose index leaves int32 is UNKNOWN (no block can hold it).  Unlike mlm_export_frontier this
+ *   does not need frontier mode and works on any handle (a map loaded with mlm_import_blocks, a merged one).
+ *   Components: connectivity 6, 18 or 26 — moves by the offsets of {-1, 0, 1}^3 with one, at most two, at most three non-zero
+ *   entries.  Two voxels of S are in one component iff a chain of such moves joins them through voxels of S inside the box (the
+ *   domain is the box, as in mlm_export_reach).  The root of a component is its voxel with the smallest linear box index
+ *   (z * dims[1] + y) * dims[0] + x.
+ *   Numbering: components of at least min_size (>= 1) voxels are kept and numbered 0 .. K-1 in ascending order of their roots, so
+ *   every output is a function of the map and the arguments alone.
+ *   labels int32 per voxel: the number of its kept component; MLM_CLUSTER_SMALL in a dropped one; MLM_CLUSTER_NONE off S.
+ *   table  int64 [cap][MLM_CLUSTER_ROW], row k for kept component k < cap (K > cap is no error: the first cap rows are written,
+ *          labels is complete, summary[2] tells; rows from K on are left as they were): [0] voxels; [1..3] root, absolute x, y,
+ *          z; [4..6] / [7..9] smallest / largest absolute index per axis; [10..12] sum over the component of x - lo[0],
+ *          y - lo[1], z - lo[2] (centroid = lo + sum / voxels; < 2^62 by the window limits); [13] bit c set iff the component
+ *          has a voxel on face c of the box (0: -x, 1: +x, 2: -y, 3: +y, 4: -z, 5: +z) — a cluster the box has cut; [14], [15] 0.
+ *   summary int64 x 6 (host memory): [0] voxels of S in the box, [1] components of any size, [2] K, [3] voxels in kept components,
+ *          [4] the largest component (0: none), [5] informative, depends on the tile geometry: the most passes a tile with a
+ *          voxel of S needed to settle its own piece (>= 1 when S is not empty).
+ * labels and table may each be host or device memory; any of the three outputs may be NULL, at least one must not be; cap >= 0,
+ * cap == 0 iff table == NULL.  "Every voxel is labelled with the smallest index of its component" is a least fixpoint of values
+ * that only decrease, so there is exactly one result whatever the schedule.  The call observes the map as queries do (async
+ * mode: waits for everything submitted), runs on the stream of mlm_set_stream and returns when the outputs are written.
+ * MLM_ERR_INVALID: mlm_export_window's window errors, flags that are neither of the two forms, connectivity other than 6 / 18 /
+ * 26, min_size < 1, cap < 0 or at odds with table, no output.  MLM_ERR_CAPACITY: no device memory for the scratch: a global
+ * problem like mlm_export_reach, so the whole box is resident at once — the label word (4 bytes per voxel), one mask byte per
+ * voxel, for the numbering a second word per voxel (the size of a component at its root, then its number) and one count per
+ * 2048 voxels (kept roots, scanned), for FRONTIER the occ class of the box grown by one voxel per side (1 byte each), and for
+ * host destinations min(cap, voxels) rows and a staging copy of labels; kept by the handle and counted in
+ * mlm_frame_stats.device_bytes.  The handle stays usable after either error. */
+#define MLM_CLUSTER_OCC 1       /* same bits and same meaning as MLM_ESDF_OCC / _INFL / _UNKNOWN */
+#define MLM_CLUSTER_INFL 2
+#define MLM_CLUSTER_UNKNOWN 4
+#define MLM_CLUSTER_FRONTIER 16 /* getOccupancy(centre) == FREE and a 6-neighbour's getOccupancy(centre) == UNKNOWN */
+#define MLM_CLUSTER_NONE (-1)   /* label of a voxel outside the set */
+#define MLM_CLUSTER_SMALL (-2)  /* label of a voxel of the set whose component has fewer than min_size voxels */
+#define MLM_CLUSTER_ROW 16      /* int64 per table row */
+int mlm_export_clusters(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], int flags, int connectivity, int min_size,
+                        int32_t *labels, int64_t *table, int cap, int64_t summary[6]);
 /* Load blocks into the map (no reference counterpart: the reference never persists or merges maps; this is how a
  * merged global map, mlmapping_amd/merge.py, is put back behind the query interface).  keys [n*3]; log_odds / occ /
  * infl [n*cells] and collapsed [n] as mlm_export_blocks / mlm_export_block_flags write them, any of them may be NULL

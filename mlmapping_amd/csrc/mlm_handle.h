@@ -24,7 +24,7 @@ struct KernelTime {
 // Test and experiment knobs (mlm_debug_set): named integers that mlm_create reads — launch geometries, forced fall-backs.
 // Process-wide, not part of the drop-in contract; the library reads no environment variable for them (only the three diagnostic
 // switches MLM_DEBUG_CREATE / MLM_DEBUG_ALLOC / MLM_DEBUG_DRAIN, which print).
-const char *const kKnobNames[] = {"agg_lds", "big_arm", "big_grid", "bin_block", "chain_grid", "collect_grid", "cu_reserve", "cu_split",
+const char *const kKnobNames[] = {"agg_lds", "big_arm", "big_grid", "bin_block", "chain_grid", "cluster_tile", "collect_grid", "cu_reserve", "cu_split",
                                   "esdf_tile_vox", "ex_spec", "expand_block", "graph", "logit_exact", "mirror", "mirror_max", "mirror_mb", "need_slots", "node_lds", "pool_grow",
                                   "rank_grid", "rays_grid", "reach_group", "reach_tile", "sc_block", "sc_grid", "sec_backoff", "sec_fail_every", "sec_tab", "sec_tab_big", "sec_threads",
                                   "sectors", "single_apply_grid", "single_chain_grid", "single_rank_grid", "slot_sets", "sort_block", "sort_grid", "tile_grid", "tile_sh"};
@@ -49,6 +49,7 @@ bool knob_value_ok(const char *name, long long v) {
         return v >= 1 && v <= (1ll << 20);
     if (is("cu_split") || is("cu_reserve")) return v >= 0 && v <= 0x7FFFFFFFll;
     if (is("esdf_tile_vox")) return v >= kEsdfMinBoxVoxels && v <= kEsdfBoxVoxels; // (mlm_esdf_plan fits every call's tile then)
+    if (is("cluster_tile")) return mlm_reach_tile_ok(v); // (packed like reach_tile; the tile's labels within k_cluster_local's LDS)
     if (is("reach_tile")) return mlm_reach_tile_ok(v);  // (x | y << 8 | z << 16, edges 1..64, tile + halo within k_reach_sweep's LDS)
     if (is("reach_group")) return v >= 1 && v <= kReachGroupMax; // (sweeps between two looks at the "marked" words)
     return true;
@@ -159,6 +160,10 @@ struct mlm_handle {
     void *d_reach = nullptr;
     size_t reach_bytes = 0;
     unsigned int *h_reach_ctrl = nullptr;
+    // mlm_export_clusters: field, size / number words, mask, grown occ classes, chunk counts, staged rows and counters of the whole
+    // box (mlm_cluster_plan), kept and enlarged by need (staged labels use d_win_stage, the counters' pinned copy h_reach_ctrl)
+    void *d_cluster = nullptr;
+    size_t cluster_bytes = 0;
     // mlm_query_rays: staging of the host inputs / outputs of one chunk of rays, kept and enlarged by need
     void *d_ray_stage = nullptr;
     size_t ray_stage_bytes = 0;

@@ -198,6 +198,52 @@ inline MlmReachPlan mlm_reach_plan(const long long D[3], long long tile_packed, 
     return p;
 }
 
+// Geometry and scratch of mlm_export_clusters (mlm_kernels_cluster.h, mlm_cluster.h) for a box of D voxels cut into tiles as
+// mlm_reach_plan cuts it (knob "cluster_tile", same packing, same validity rule: a workgroup of k_cluster_local keeps a tile's
+// labels as u32 in LDS, fewer than the kReachHaloVoxels k_reach_sweep stages).  The whole box is resident at once: the field (4 B
+// per voxel), the component sizes that become the components' numbers (4 B per voxel, read at the roots only), the mask (1 B),
+// for a frontier the occ classes of the box grown by one voxel per side (1 B each), one count of kept roots per chunk of
+// kClusterChunk voxels (the numbering: chunk counts, an exclusive scan over them, ranks inside each chunk), `cap` table rows of
+// 128 B and a control block (the summary counters); each part starts on a multiple of 256 bytes.  ok == false: what
+// mlm_reach_plan refuses of tile and box, or cap < 0.
+constexpr long long kClusterTileDefault = kReachTileDefault;
+constexpr long long kClusterChunk = 2048;
+constexpr long long kClusterCtrlBytes = 256;
+struct MlmClusterPlan {
+    bool ok;
+    long long T[3], n[3], tiles, voxels, chunks;
+    long long field_bytes, num_bytes, mask_bytes, grown_bytes, chunk_bytes, table_bytes;
+    long long off_num, off_mask, off_grown, off_chunk, off_table, off_ctrl, scratch_bytes;
+};
+inline MlmClusterPlan mlm_cluster_plan(const long long D[3], long long tile_packed, bool frontier, long long cap) {
+    MlmClusterPlan p{};
+    if (!mlm_reach_tile_ok(tile_packed) || D[0] < 1 || D[1] < 1 || D[2] < 1 || cap < 0) return p;
+    auto up = [](long long v) { return (v + 255) & ~255ll; };
+    p.voxels = 1;
+    for (int a = 0; a < 3; ++a) {
+        p.T[a] = (tile_packed >> (8 * a)) & 255;
+        p.n[a] = (D[a] + p.T[a] - 1) / p.T[a];
+        p.voxels *= D[a];
+    }
+    p.tiles = p.n[0] * p.n[1] * p.n[2];
+    p.chunks = (p.voxels + kClusterChunk - 1) / kClusterChunk;
+    p.field_bytes = up(4 * p.voxels);
+    p.num_bytes = up(4 * p.voxels);
+    p.mask_bytes = up(p.voxels);
+    p.grown_bytes = frontier ? up((D[0] + 2) * (D[1] + 2) * (D[2] + 2)) : 0;
+    p.chunk_bytes = up(4 * p.chunks);
+    p.table_bytes = up(128 * cap);
+    p.off_num = p.field_bytes;
+    p.off_mask = p.off_num + p.num_bytes;
+    p.off_grown = p.off_mask + p.mask_bytes;
+    p.off_chunk = p.off_grown + p.grown_bytes;
+    p.off_table = p.off_chunk + p.chunk_bytes;
+    p.off_ctrl = p.off_table + p.table_bytes;
+    p.scratch_bytes = p.off_ctrl + kClusterCtrlBytes;
+    p.ok = true;
+    return p;
+}
+
 namespace mlm_host {
 
 // Does this host's libm log10f (what the reference's logit macro calls) agree with mlm_glibc_log10f?  Checked on the values the

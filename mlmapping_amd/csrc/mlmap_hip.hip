@@ -33,6 +33,7 @@
 #include "mlm_kernels_esdf.h"
 #include "mlm_kernels_rays.h"
 #include "mlm_kernels_reach.h"
+#include "mlm_kernels_cluster.h"
 #include "mlm_host.h"
 #include "mlm_mapview.h"
 
@@ -1528,6 +1529,135 @@ int mlm_export_reach(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], 
         summary[2] = (int64_t)h_cnt[2] - 1;
         summary[3] = (int64_t)needed;
     }
+    return MLM_OK;
+}
+
+int mlm_export_clusters(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], int flags, int connectivity, int min_size, int32_t *labels,
+                        int64_t *table, int cap, int64_t summary[6]) {
+    if (!h) return MLM_ERR_INVALID;
+    MLM_LOCK(h);
+    const bool frontier = flags == MLM_CLUSTER_FRONTIER;
+    const int nfwd = mlm_cluster_nfwd(connectivity);
+    if (!lo || !dims || !(frontier || (flags >= 1 && flags <= 7)) || !nfwd || min_size < 1 || cap < 0 || (cap == 0) != (table == nullptr) ||
+        (!labels && !table && !summary)) {
+        h->err = "mlm_export_clusters: null window, flags neither MLM_CLUSTER_FRONTIER nor a union of the class bits, connectivity not 6 / 18 / 26, "
+                 "min_size < 1, cap < 0, cap == 0 with a table or cap > 0 without one, or no output";
+        return MLM_ERR_INVALID;
+    }
+    long long D[3], nvox = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (dims[a] < 1 || (long long)lo[a] + dims[a] > 0x7FFFFFFFll) {
+            h->err = "mlm_export_clusters: dims must be >= 1 and lo + dims must fit an int32";
+            return MLM_ERR_INVALID;
+        }
+        D[a] = dims[a];
+        nvox *= D[a];
+        if (nvox > 0x7FFFFFFFll) {
+            h->err = "mlm_export_clusters: more than 2^31 - 1 voxels";
+            return MLM_ERR_INVALID;
+        }
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = drain(h);
+    if (rc) return rc;
+
+    long long tile = kClusterTileDefault, kv;
+    if (knob("cluster_tile", kv)) tile = kv;
+    const bool table_staged = table && !win_in_place(table), labels_staged = labels && !win_in_place(labels);
+    const MlmClusterPlan plan = mlm_cluster_plan(D, tile, frontier, table_staged ? std::min<long long>(cap, nvox) : 0); // (K <= voxels)
+    if (!plan.ok) { // (not with the tiles mlm_debug_set admits)
+        h->err = "mlm_export_clusters: no such tile";
+        return MLM_ERR_INVALID;
+    }
+    // labels: written in place, or staged through d_win_stage in ranges of the box; rows: in place, or in the scratch
+    const long long chunk = labels_staged ? std::min(nvox, kEsdfStageVoxels) : nvox;
+    if ((rc = win_reserve(h, h->d_cluster, h->cluster_bytes, (size_t)plan.scratch_bytes, "mlm_export_clusters"))) return rc;
+    if (labels_staged && (rc = win_reserve(h, h->d_win_stage, h->win_stage_bytes, (size_t)chunk * sizeof(int32_t), "mlm_export_clusters")))
+        return rc;
+    if (!h->h_reach_ctrl) HIPCHK(h, hipHostMalloc((void **)&h->h_reach_ctrl, (size_t)kReachCtrlBytes, hipHostMallocDefault));
+    char *base = (char *)h->d_cluster;
+    uint8_t *mask = (uint8_t *)(base + plan.off_mask);
+    unsigned int *chunk_cnt = (unsigned int *)(base + plan.off_chunk);
+    unsigned long long *cnt = (unsigned long long *)(base + plan.off_ctrl);
+    int64_t *rows = !table ? nullptr : table_staged ? (int64_t *)(base + plan.off_table) : table;
+    MlmCluster R{};
+    for (int a = 0; a < 3; ++a) {
+        R.D[a] = D[a];
+        R.lo[a] = lo[a];
+        R.n[a] = plan.n[a];
+        R.T[a] = (int)plan.T[a];
+    }
+    R.tiles = plan.tiles;
+    R.nvox = nvox;
+    R.nfwd = nfwd;
+    R.min_size = (uint32_t)min_size;
+    R.field = (uint32_t *)base;
+    R.num = (uint32_t *)(base + plan.off_num);
+
+    // the mask of the box
+    const int n = h->P.n;
+    auto floor_div = [n](long long v) { return v >= 0 ? v / n : -((-v + n - 1) / n); };
+    const dim3 vgrid(std::min<unsigned int>(grid_for((size_t)nvox), kReachGrid));
+    if (frontier) {
+        MlmClusterOcc E{};
+        for (int a = 0; a < 3; ++a) {
+            E.glo[a] = (long long)lo[a] - 1; // (64-bit: the grown box of a window at the int32 edge reaches past it)
+            E.gd[a] = D[a] + 2;
+            E.b0[a] = floor_div(E.glo[a]);
+            E.nb[a] = (int)(floor_div(E.glo[a] + E.gd[a] - 1) - E.b0[a] + 1);
+        }
+        E.out = (uint8_t *)(base + plan.off_grown);
+        const long long n_bricks = (long long)E.nb[0] * E.nb[1] * E.nb[2];
+        hipLaunchKernelGGL(k_cluster_occ, dim3((unsigned int)std::min<long long>(n_bricks, kEsdfMaskGrid)), dim3(MLM_BLOCK), 0, h->stream, h->P, E);
+        hipLaunchKernelGGL(k_cluster_frontier, vgrid, dim3(MLM_BLOCK), 0, h->stream, (const uint8_t *)E.out, mask, D[0], D[1], nvox);
+    } else {
+        MlmEsdf E{};
+        for (int a = 0; a < 3; ++a) {
+            E.glo[a] = lo[a];
+            E.gd[a] = dims[a];
+            E.b0[a] = floor_div(E.glo[a]);
+            E.nb[a] = (int)(floor_div(E.glo[a] + E.gd[a] - 1) - E.b0[a] + 1);
+        }
+        E.flags = flags;
+        E.mask = mask;
+        const long long n_bricks = (long long)E.nb[0] * E.nb[1] * E.nb[2];
+        hipLaunchKernelGGL(k_esdf_mask, dim3((unsigned int)std::min<long long>(n_bricks, kEsdfMaskGrid)), dim3(MLM_BLOCK), 0, h->stream, h->P, E);
+    }
+    HIPCHK(h, hipGetLastError());
+    // local, merge, flatten and sizes, numbering
+    HIPCHK(h, hipMemsetAsync(cnt, 0, (size_t)kClusterCtrlBytes, h->stream));
+    const size_t lds = (size_t)plan.T[0] * plan.T[1] * plan.T[2] * sizeof(uint32_t);
+    const dim3 cgrid((unsigned int)std::min<long long>(plan.chunks, kReachGrid));
+    hipLaunchKernelGGL(k_cluster_local, dim3((unsigned int)std::min<long long>(plan.tiles, kReachGrid)), dim3(MLM_BLOCK), lds, h->stream, R,
+                       (const uint8_t *)mask, cnt);
+    hipLaunchKernelGGL(k_cluster_merge, vgrid, dim3(MLM_BLOCK), 0, h->stream, R);
+    hipLaunchKernelGGL(k_cluster_flatten, vgrid, dim3(MLM_BLOCK), 0, h->stream, R, cnt);
+    hipLaunchKernelGGL(k_cluster_count, cgrid, dim3(MLM_BLOCK), 0, h->stream, R, plan.chunks, chunk_cnt, cnt);
+    hipLaunchKernelGGL(k_cluster_scan, dim3(1), dim3(MLM_BLOCK), 0, h->stream, chunk_cnt, plan.chunks, cnt);
+    hipLaunchKernelGGL(k_cluster_rank, cgrid, dim3(MLM_BLOCK), 0, h->stream, R, plan.chunks, (const unsigned int *)chunk_cnt, rows, cap);
+    HIPCHK(h, hipGetLastError());
+    // labels and rows
+    if (labels || rows)
+        for (long long j0 = 0; j0 < nvox; j0 += chunk) {
+            const long long j1 = std::min(nvox, j0 + chunk);
+            int32_t *out = !labels ? nullptr : labels_staged ? (int32_t *)h->d_win_stage : labels + j0;
+            hipLaunchKernelGGL(k_cluster_write, dim3(std::min<unsigned int>(grid_for((size_t)(j1 - j0)), kReachGrid)), dim3(MLM_BLOCK), 0, h->stream, R,
+                               j0, j1, out, rows, cap);
+            HIPCHK(h, hipGetLastError());
+            if (labels_staged) HIPCHK(h, hipMemcpyAsync(labels + j0, out, (size_t)(j1 - j0) * sizeof(int32_t), hipMemcpyDefault, h->stream));
+        }
+    unsigned long long *h_cnt = (unsigned long long *)h->h_reach_ctrl;
+    if (summary || table_staged) HIPCHK(h, hipMemcpyAsync(h_cnt, cnt, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (table_staged) { // the rows that exist: min(K, cap)
+        const size_t k = (size_t)std::min<unsigned long long>(h_cnt[2], (unsigned long long)cap);
+        if (k) {
+            HIPCHK(h, hipMemcpyAsync(table, rows, k * MLM_CLUSTER_ROW * sizeof(int64_t), hipMemcpyDefault, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+        }
+    }
+    if (summary)
+        for (int i = 0; i < 6; ++i) summary[i] = (int64_t)h_cnt[i];
     return MLM_OK;
 }
 

@@ -28,6 +28,9 @@ MLM_OK = 0
 MLM_ESDF_OCC, MLM_ESDF_INFL, MLM_ESDF_UNKNOWN, MLM_ESDF_SIGNED = 1, 2, 4, 8
 # mlm_export_reach: obstacle predicates (their union; none: no obstacles), steps of a voxel not reached, parent code of a seed
 MLM_REACH_OCC, MLM_REACH_INFL, MLM_REACH_UNKNOWN, MLM_REACH_NONE, MLM_REACH_SEED = 1, 2, 4, -1, 6
+# mlm_export_clusters: the set (FRONTIER alone, or a union of the class bits), labels off the set / in a dropped component, int64 per row
+MLM_CLUSTER_OCC, MLM_CLUSTER_INFL, MLM_CLUSTER_UNKNOWN, MLM_CLUSTER_FRONTIER = 1, 2, 4, 16
+MLM_CLUSTER_NONE, MLM_CLUSTER_SMALL, MLM_CLUSTER_ROW = -1, -2, 16
 # mlm_query_rays flags: what stops a ray (their union; 0: nothing, a pure count)
 MLM_RAY_OCC, MLM_RAY_INFL, MLM_RAY_UNKNOWN = 1, 2, 4
 STATUS = {0: "MLM_OK", -1: "MLM_ERR_INVALID", -2: "MLM_ERR_HIP", -3: "MLM_ERR_CAPACITY", -4: "MLM_ERR_UNSUPPORTED"}
@@ -41,7 +44,7 @@ ABI_SYMBOLS = [
     "mlm_query_odds", "mlm_query_odd_grad", "mlm_query_odds_at", "mlm_export_frontier_points", "mlm_import_blocks",
     "mlm_merge_pack", "mlm_merge_finish",
     "mlm_set_free_in_bound", "mlm_inflate_map", "mlm_block_count",
-    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_reach", "mlm_query_rays", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
+    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_reach", "mlm_export_clusters", "mlm_query_rays", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
     "mlm_get_awareness_hits",
     "mlm_get_awareness_misses", "mlm_get_T_ls", "mlm_get_odds_table", "mlm_get_kernel_times",
     "mlm_enable_kernel_timing", "mlm_set_timed_kernel", "mlm_host_register", "mlm_host_unregister", "mlm_debug_set", "mlm_debug_reset",
@@ -137,6 +140,7 @@ def load_library(path: Optional[str] = None):
     L.mlm_export_window.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
     L.mlm_export_esdf.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
     L.mlm_export_reach.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
+    L.mlm_export_clusters.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i32, vp]
     L.mlm_query_rays.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.mlm_export_global_map.argtypes = [vp, i32, vp, vp]
     L.mlm_export_block_flags.argtypes = [vp, i32, vp, vp]
@@ -514,6 +518,46 @@ class MLMap:
                                            self._ray_flags(occ, infl, unknown), int(clearance),
                                            2 ** 31 - 1 if max_steps is None else int(max_steps), *ptr), "mlm_export_reach")
         return sm
+
+    def export_clusters(self, lo, dims, frontier=False, occ=False, infl=False, unknown=False, connectivity: int = 26, min_size: int = 1,
+                        labels=True, cap: int = 4096) -> Dict[str, np.ndarray]:
+        """Connected components of a voxel set of the box lo <= v < lo + dims (voxel indices as export_window): the frontier (FREE
+        voxels with an UNKNOWN face neighbour anywhere in the map; works without frontier mode) or the union of occ / infl /
+        unknown as in export_esdf.  connectivity 6, 18 or 26; components of at least min_size voxels are numbered 0 .. K-1 by
+        their smallest voxel.  {"labels": int32 (dz, dy, dx), the component's number, -2 in a dropped component, -1 off the set;
+        "table": int64 (min(K, cap), 16): voxels, root x y z, smallest x y z, largest x y z, sums of x - lo[0], y - lo[1],
+        z - lo[2], box-face bits, 0, 0; "summary": int64 [voxels of the set, components, K, voxels in kept components, largest
+        component, local passes]} (mlm_export_clusters)."""
+        lo_a, dims_a = self._window_args(lo, dims)
+        shape = (int(dims_a[2]), int(dims_a[1]), int(dims_a[0]))
+        out = {"summary": np.zeros(6, dtype=np.int64)}
+        if labels:
+            out["labels"] = np.empty(shape, dtype=np.int32)
+        if cap > 0:
+            out["table"] = np.zeros((int(cap), MLM_CLUSTER_ROW), dtype=np.int64)
+        ptr = [_p(out[k]) if k in out else None for k in ("labels", "table")]
+        self._chk(self._L.mlm_export_clusters(self._h, _p(lo_a), _p(dims_a), self._cluster_flags(frontier, occ, infl, unknown), int(connectivity),
+                                              int(min_size), *ptr, int(cap), _p(out["summary"])), "mlm_export_clusters")
+        if cap > 0:
+            out["table"] = out["table"][:min(int(out["summary"][2]), int(cap))]
+        return out
+
+    def export_clusters_dev(self, lo, dims, frontier=False, occ=False, infl=False, unknown=False, connectivity: int = 26, min_size: int = 1,
+                            labels: Optional[int] = None, table: Optional[int] = None, cap: int = 0,
+                            summary: bool = False) -> Optional[np.ndarray]:
+        """Same on device memory: labels a pointer (int) to dz*dy*dx int32, table a pointer to cap x 16 int64, None = skipped;
+        summary=True returns the six int64 counters."""
+        lo_a, dims_a = self._window_args(lo, dims)
+        sm = np.zeros(6, dtype=np.int64) if summary else None
+        ptr = [None if v is None else ctypes.c_void_p(v) for v in (labels, table)]
+        self._chk(self._L.mlm_export_clusters(self._h, _p(lo_a), _p(dims_a), self._cluster_flags(frontier, occ, infl, unknown), int(connectivity),
+                                              int(min_size), *ptr, int(cap), None if sm is None else _p(sm)), "mlm_export_clusters")
+        return sm
+
+    @staticmethod
+    def _cluster_flags(frontier, occ, infl, unknown) -> int:
+        return ((MLM_CLUSTER_FRONTIER if frontier else 0) | (MLM_CLUSTER_OCC if occ else 0) | (MLM_CLUSTER_INFL if infl else 0) |
+                (MLM_CLUSTER_UNKNOWN if unknown else 0))
 
     def cast_rays(self, p0, p1, occ=True, infl=False, unknown=False) -> Dict[str, np.ndarray]:
         """Cast the segments p0[i] -> p1[i] (n x 3 world positions) through the voxel map (mlm_query_rays): {"status": int8 (1
