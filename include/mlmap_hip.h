@@ -145,7 +145,10 @@ int mlm_abi_version(void);
 int mlm_set_stream(mlm_handle *h, void *hip_stream);
 
 /* replaces mlmap::project_depth + update_map (src/mlmap.cpp:311-349,382-386).
- * img: uint16 millimetres (the 16UC1 image of mlmap.cpp:477-484), row_stride in pixels.
+ * img: uint16 millimetres (the 16UC1 image of mlmap.cpp:477-484), row_stride in pixels (>= width, else MLM_ERR_INVALID):
+ * pixel (u, v) is img[v*row_stride + u].  An image is (height-1)*row_stride + width pixels long: the padding of a row is
+ * never interpreted, and the LAST row need not be padded — no entry point reads a host image beyond its last pixel
+ * (of a batch: beyond the last pixel of its last frame, (n_frames-1)*frame_stride + (height-1)*row_stride + width).
  * pixel_idx == NULL: dense — every pixel with raw != 0 in row-major order (v outer).
  * pixel_idx != NULL: exactly those pixels (v*width+u) in list order, raw == 0 skipped — lets a host reproduce
  * the reference's rand() sampler (mlmap.cpp:322-327) outside and keep parity. */

@@ -34,6 +34,19 @@ MLM_HD inline int mlm_cv_f32_to_u16(float v) {
     return r > 65535.0f ? 65535 : (int)r;
 }
 
+// Pixels of a host depth image that the host entry points read (and upload): `height` rows of `width` pixels, `row_stride` pixels
+// apart, from the first pixel of the first row to the LAST PIXEL of the last row — the padding behind the last row is not part of
+// the image (include/mlmap_hip.h), so a buffer may end with its last pixel.  0 for arguments the entry points refuse.
+inline size_t mlm_image_span(int width, int height, int row_stride) {
+    if (width <= 0 || height <= 0 || row_stride < width) return 0;
+    return (size_t)(height - 1) * (size_t)row_stride + (size_t)width;
+}
+// Same for `n_frames` images `frame_stride` pixels apart: up to the last pixel of the last frame.
+inline size_t mlm_batch_span(int n_frames, size_t frame_stride, int width, int height, int row_stride) {
+    const size_t one = mlm_image_span(width, height, row_stride);
+    return n_frames <= 0 || !one ? 0 : (size_t)(n_frames - 1) * frame_stride + one;
+}
+
 // log10f of glibc 2.35 (Ubuntu 22.04: sysdeps/ieee754/flt-32/e_log10f.c on top of the table-driven logf of
 // sysdeps/ieee754/flt-32/e_logf.c + logf_data.c), restated operation by operation: the hit increment of the reference is
 // `logit(odd)` = log10f(odd / (1 - odd)) evaluated by the HOST's libm (map_local.h:8, map_local.cpp:159), and the log-odds

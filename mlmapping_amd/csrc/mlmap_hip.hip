@@ -678,6 +678,7 @@ int mlm_integrate_depth_batch(mlm_handle *h, const uint16_t *img_host, int n_fra
     HIPCHK(h, hipSetDevice(h->device));
     const int K = h->lim.max_batch;
     const size_t n_px = (size_t)row_stride * height;
+    const size_t span = mlm_image_span(width, height, row_stride); // (what is read of one frame: the last row is not padded)
     for (int k0 = 0; k0 < n_frames; k0 += K) {
         const int n = std::min(K, n_frames - k0);
         // frames that lie back to back in host memory go up in ONE copy into the slot set's batch buffer (64 copies of 0.6 MB each
@@ -696,14 +697,14 @@ int mlm_integrate_depth_batch(mlm_handle *h, const uint16_t *img_host, int n_fra
                 HIPCHK(h, hipMalloc((void **)&h->d_img_set[set], (size_t)K * n_px * sizeof(uint16_t)));
                 h->img_set_cap[set] = (size_t)K * n_px;
             }
-            HIPCHK(h, hipMemcpyAsync(h->d_img_set[set], img_host + (size_t)k0 * frame_stride, (size_t)n * n_px * sizeof(uint16_t), hipMemcpyHostToDevice, up));
+            HIPCHK(h, hipMemcpyAsync(h->d_img_set[set], img_host + (size_t)k0 * frame_stride, mlm_batch_span(n, n_px, width, height, row_stride) * sizeof(uint16_t), hipMemcpyHostToDevice, up));
         }
         for (int j = 0; j < n; ++j) {
             MlmSlot &S = cur_slot(h, j);
             if (!packed) {
                 int rc = ensure_img(h, S, n_px);
                 if (rc) return rc;
-                HIPCHK(h, hipMemcpyAsync(S.d_img, img_host + (size_t)(k0 + j) * frame_stride, n_px * sizeof(uint16_t), hipMemcpyHostToDevice, up));
+                HIPCHK(h, hipMemcpyAsync(S.d_img, img_host + (size_t)(k0 + j) * frame_stride, span * sizeof(uint16_t), hipMemcpyHostToDevice, up));
             }
             S.F = MlmFrame{};
             frame_setup(h, q_wb + 4 * (size_t)(k0 + j), t_wb + 3 * (size_t)(k0 + j), S.F);
@@ -770,7 +771,7 @@ int mlm_integrate_depth_u16(mlm_handle *h, const uint16_t *img, int width, int h
     if (rc) return rc;
     hipStream_t up = upload_stream(h);
     h->last_upload = up;
-    HIPCHK(h, hipMemcpyAsync(S.d_img, img, n_px * sizeof(uint16_t), hipMemcpyHostToDevice, up));
+    HIPCHK(h, hipMemcpyAsync(S.d_img, img, mlm_image_span(width, height, row_stride) * sizeof(uint16_t), hipMemcpyHostToDevice, up));
     if (pixel_idx) {
         if (n_idx < 0 || n_idx > h->lim.max_points) return MLM_ERR_CAPACITY;
         if ((rc = ensure_pix(h, S))) return rc;

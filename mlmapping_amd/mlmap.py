@@ -286,7 +286,7 @@ class MLMap:
         q = _f64(q_wb).reshape(n_frames, 4)
         t = _f64(t_wb).reshape(n_frames, 3)
         self._chk(self._L.mlm_integrate_depth_batch_dev(self._h, ctypes.c_void_p(img_dev_ptr), n_frames,
-                                                        frame_stride or width * height, width, height,
+                                                        frame_stride or (row_stride or width) * height, width, height,
                                                         row_stride or width, _p(q), _p(t)),
                   "mlm_integrate_depth_batch_dev")
 

@@ -2,6 +2,7 @@
 // torch: only the C ABI) and run as a fresh child process: it integrates frames read from a file through the facade's
 // reference-named methods and prints its answers, which the test compares with the ctypes path and the oracle.
 // Vec3 below stands for Eigen::Vector3d (anything with operator[](int) -> double works with the facade's templates).
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -37,7 +38,14 @@ int main(int argc, char **argv) {
         for (int k = 0; k < n_frames; ++k) {
             double pose[7];
             if (!read_exact(f, pose, sizeof pose) || !read_exact(f, img.data(), img.size() * 2)) return 2;
-            map.set_depth_image(img.data(), W, H);
+            std::vector<uint16_t> padded;
+            if (k % 2) { // every other frame as a padded image: rows W + 5 apart, the padding valid depth, the last row not padded
+                padded.assign((size_t)(H - 1) * (W + 5) + W, 1234);
+                for (int v = 0; v < H; ++v) std::copy(img.begin() + (size_t)v * W, img.begin() + (size_t)(v + 1) * W, padded.begin() + (size_t)v * (W + 5));
+                map.set_depth_image(padded.data(), W, H, W + 5);
+            } else {
+                map.set_depth_image(img.data(), W, H);
+            }
             map.set_pose(pose, pose + 4);
             map.project_depth();
             map.update_map();

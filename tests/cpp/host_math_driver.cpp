@@ -119,6 +119,36 @@ int main() {
         for (float v : in) out.push_back((double)mlm_cv_f32_to_u16(v));
         rec("cvt", 0, out.data(), (int)out.size());
     }
+    // ---- pixels of a padded image / batch that the host entry points read (mlm_image_span, mlm_batch_span): a buffer of exactly
+    //      that many pixels holds every pixel (u, v) of every frame, its last element is the last pixel of the last frame (the
+    //      sanitizer sees a read beyond it), and refused arguments give 0
+    {
+        const int cases[][5] = {{333, 7, 333, 1, 0}, {333, 7, 334, 1, 0}, {333, 7, 340, 3, 0}, {640, 5, 1280, 2, 0}, {1, 1, 1, 1, 0},
+                                {1, 9, 5, 4, 7}, {640, 480, 647, 3, 1000}, {8, 1, 100, 5, 3}, {5, 4, 4, 1, 0}, {0, 4, 4, 1, 0},
+                                {4, 0, 4, 1, 0}, {4, 4, 4, 0, 0}, {4, -1, 4, 2, 0}};
+        int i = 0;
+        for (const auto &c : cases) {
+            const int W = c[0], H = c[1], rs = c[2], n = c[3];
+            const size_t fs = (size_t)rs * (H > 0 ? H : 0) + (size_t)c[4];
+            const size_t one = mlm_image_span(W, H, rs), all = mlm_batch_span(n, fs, W, H, rs);
+            std::vector<uint16_t> buf(all, 0);
+            unsigned long long touched = 0, last = 0;
+            if (all)
+                for (int k = 0; k < n; ++k)
+                    for (int v = 0; v < H; ++v)
+                        for (int u = 0; u < W; ++u) {
+                            const size_t at = (size_t)k * fs + (size_t)v * rs + u;
+                            touched += ++buf.data()[at]; // (a heap overflow here is what the sanitizer reports)
+                            last = at;
+                        }
+            if (all && (last + 1 != all || touched != (unsigned long long)n * W * H)) {
+                std::fprintf(stderr, "image span wrong for case %d: %zu pixels, last pixel at %llu\n", i, all, last);
+                return 1;
+            }
+            const double v[7] = {(double)W, (double)H, (double)rs, (double)n, (double)fs, (double)one, (double)all};
+            rec("span", i++, v, 7);
+        }
+    }
     // ---- mlm_glibc_log10f against this host's libm log10f (what the reference's logit macro calls, map_local.h:8): every
     //      317th positive finite float (6.7 M inputs; the full 2^31 sweep was run once, zero mismatches), every float of the
     //      logit's usual argument range [0.5, 2), subnormals, zero, infinity

@@ -3,7 +3,7 @@
 reach(T, seeds, max_steps): `steps` by a wavefront breadth-first search over index arrays of the traversable mask T ([z][y][x],
 seeds as (x, y, z) relative to the box), `parent` by the header's rule applied literally to that field, and the summary counters.
 blocked(obstacles_grown, r): the blocked mask of clearance r from the obstacle mask of the box grown by r + 1 per side, by the
-separable truncated transform (edt_separable, the form tests/test_gpu_esdf.py checks against the definition).
+separable truncated transform (edt_separable, the form of tests/esdf_ref.py that tests/test_gpu_esdf.py checks against the definition).
 Mask builders for the crafted cases: serpentine slabs and the layered 3-D maze."""
 import numpy as np
 

@@ -429,6 +429,8 @@ def test_invalid_arguments_are_refused(mods):
     """Every entry point answers bad arguments with a status (MLM_ERR_INVALID / MLM_ERR_CAPACITY), never with a crash, and the handle
     keeps working: null buffers, null handle, non-positive sizes, a row stride below the width, negative counts, a frame above
     mlm_limits.max_points, export buffers that are too small — followed by a frame that must still equal the oracle's."""
+    import torch
+
     from mlmapping_amd import mlmap as mm
 
     MLMap, OracleMap = mods
@@ -439,6 +441,8 @@ def test_invalid_arguments_are_refused(mods):
     q, t = np.ascontiguousarray(q, np.float64), np.ascontiguousarray(t, np.float64)
     pq, pt, pimg = q.ctypes.data, t.ctypes.data, img.ctypes.data
     W, H = cfg.width, cfg.height
+    dev_img = torch.zeros(W * H, dtype=torch.int16, device="cuda")
+    pdev = ctypes.c_void_p(dev_img.data_ptr())
     ERR_INVALID, ERR_CAPACITY = -1, -3  # (mlmap_hip.h)
     bad = (ERR_INVALID, ERR_CAPACITY)
     out = np.zeros(16, np.int8)
@@ -450,6 +454,9 @@ def test_invalid_arguments_are_refused(mods):
         lambda: L.mlm_integrate_depth_u16(h, pimg, 0, H, W, None, 0, pq, pt),
         lambda: L.mlm_integrate_depth_u16(h, pimg, W, -3, W, None, 0, pq, pt),
         lambda: L.mlm_integrate_depth_u16(h, pimg, W, H, W - 1, None, 0, pq, pt),
+        lambda: L.mlm_integrate_depth_u16_dev(h, pdev, W, H, W - 1, None, 0, pq, pt),          # a row stride below the width, on the
+        lambda: L.mlm_integrate_depth_batch(h, pimg, 1, W * H, W, H, W - 1, pq, pt),          # other three depth entry points
+        lambda: L.mlm_integrate_depth_batch_dev(h, pdev, 1, W * H, W, H, W - 1, pq, pt),
         lambda: L.mlm_integrate_depth_u16(h, pimg, W, H, W, pimg, -5, pq, pt),
         lambda: L.mlm_integrate_depth_u16(h, pimg, W, H, W, None, 0, None, pt),
         lambda: L.mlm_integrate_depth_u16(h, pimg, 4 * W, H, 4 * W, None, 0, pq, pt),   # above max_points

@@ -160,3 +160,18 @@ def test_log10f_restatement_matches_host_libm(rec):
     with an error on any mismatch); reference: logit macro map_local.h:8 evaluated by the host libm, map_local.cpp:159."""
     n, bad = rec["log10f"][0]
     assert n > 8e6 and bad == 0
+
+
+def test_image_span(rec):
+    """mlm_image_span / mlm_batch_span (what the host entry points read of a padded image and of a batch): (height - 1) * row_stride +
+    width, plus (n_frames - 1) * frame_stride for a batch, and 0 for refused arguments; the driver touches every pixel of a buffer
+    of exactly that size under the sanitizers and exits with an error unless the last pixel is the last element"""
+    assert len(rec["span"]) == 13
+    refused = 0
+    for i, (W, H, rs, n, fs, one, total) in sorted((i, [int(x) for x in v]) for i, v in rec["span"].items()):
+        ok = W > 0 and H > 0 and rs >= W
+        assert one == ((H - 1) * rs + W if ok else 0), (i, W, H, rs)
+        assert total == ((n - 1) * fs + one if ok and n > 0 else 0), (i, W, H, rs, n, fs)
+        assert not ok or one <= rs * H
+        refused += total == 0
+    assert refused == 5

@@ -43,7 +43,7 @@ def timed(fn, reps, warmup, sync):
 
 
 def numpy_edt(mask, C):
-    """the separable truncated transform (tests/test_gpu_esdf.py::edt_separable)"""
+    """the separable truncated transform (tests/esdf_ref.py::edt_separable)"""
     f = np.where(mask, 0, C * C).astype(np.uint16)
     for axis in (2, 1, 0):
         g = f.copy()
