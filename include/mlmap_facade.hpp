@@ -260,6 +260,14 @@ class mlmap {
         return st == 1;
     }
 
+    // distinct-voxel gain of grouped ray fans (mlm_query_views; view k = segments view_begin[k] .. view_begin[k + 1]; flags MLM_RAY_*;
+    // lo / dims the accounting box or both NULL; exclude / mark uint8 per voxel of the box; table [n_views][MLM_VIEW_ROW]; every
+    // pointer host or device memory, NULL = skipped, mark or table must be given)
+    void queryViews(const double *p0, const double *p1, const int32_t *view_begin, int n_views, int flags, int64_t *table,
+                    const int32_t *lo = nullptr, const int32_t *dims = nullptr, const uint8_t *exclude = nullptr, uint8_t *mark = nullptr) {
+        check(mlm_query_views(h_, p0, p1, view_begin, n_views, flags, lo, dims, exclude, mark, table), "mlm_query_views");
+    }
+
     // planners that query thousands of positions per cycle should use the batched entry points directly
     mlm_handle *handle() { return h_; }
 

@@ -292,6 +292,47 @@ int mlm_export_esdf(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], i
 #define MLM_RAY_UNKNOWN 4
 int mlm_query_rays(mlm_handle *h, const double *p0, const double *p1, int n, int flags, int8_t *status, int32_t *voxel3, double *t,
                    int32_t *n_steps, int32_t *n_unknown);
+/* Distinct-voxel gain of grouped ray fans: from which candidate pose is the most unknown space seen?  (No reference counterpart:
+ * the reference has no view query.)  The sum of mlm_query_rays' n_unknown over a fan is not that number: the rays of a fan share
+ * voxels near the origin (a 64 x 48 fan of 4 m at d = 0.1 visits each of its voxels 3.5 times on average).  This call counts sets.
+ *   Views and rays: view k is the group of segments view_begin[k] <= i < view_begin[k + 1] of p0 / p1 (n x 3 world positions,
+ *   n = view_begin[n_views]); view_begin[0] >= 0, non-decreasing.  The rays of a view need not share an origin (the swept volume
+ *   of a trajectory is a view).  Each ray is walked exactly as mlm_query_rays walks it with the same `flags` (MLM_RAY_OCC | _INFL |
+ *   _UNKNOWN, 0: nothing stops it): lattice, path, tie rule, stop predicate and validity are the ones stated there.  For ray i with
+ *   mlm_query_rays' (status, n_steps = k_i): its traversed voxels are path indices 0 .. k_i - 1 (the whole path without a stop), its
+ *   stop voxel is path index k_i if status == 1; an invalid ray contributes no voxel.
+ *   Box: lo and dims are both NULL (B = all voxels) or both given (B = the window lo <= v < lo + dims, mlm_export_window's rules and
+ *   errors).  Rays walk and stop outside B as usual; only the accounting is restricted to B.
+ *   Sets: A_k = the union of the traversed voxels of view k, cut to B; S_k = the union of its stop voxels, cut to B.  The stop
+ *   predicate is a function of the voxel alone, so A_k and S_k are disjoint.
+ *   exclude (optional, needs the box): uint8 per voxel of the box, window layout ([dims[2]][dims[1]][dims[0]], x fastest);
+ *   E = the voxels with a non-zero byte, counted in none of the words [0..3].
+ *   mark (optional, needs the box): same layout; for every view mark[v] |= 1 for v in A_k and mark[v] |= 2 for v in S_k,
+ *   independent of exclude; all other bytes are left as they were.  An OR over views, so schedule-independent.
+ *   table (optional): int64 [n_views][MLM_VIEW_ROW]:
+ *     [0] |A_k \ E|                                   [4] rays with status 1
+ *     [1] of those, voxels whose occ class is UNKNOWN   [5] invalid rays
+ *         (the gain of the view)                        [6] sum of n_steps over the valid rays (visits with multiplicity,
+ *     [2] of those, voxels whose occ class is FREE          regardless of B and E); [6] / ([0] + [3]) is the overlap factor
+ *     [3] |S_k \ E| (visible surface voxels)           [7] 0, or 1 if the view was refused
+ *   Classes are what mlm_export_window's occ / infl channels return (released blocks, absent blocks and voxels beyond the key
+ *   range included), as for mlm_query_rays.
+ *   Refused views: the bounding box of a view is the box spanned by the start and end voxels of its valid rays, cut to B (the set
+ *   is kept as one bit per voxel of it).  If it holds more than 2^31 - 1 voxels the view is refused: words [0..6] are 0, [7] is 1,
+ *   nothing is marked for it, and the call still returns MLM_OK.
+ * Greedy view selection: score all candidates, mark the winner into a zeroed box, pass that box as exclude and score again.
+ * Each pointer on its own may be host or device memory; at least one of mark / table must be given.  Every value is a set
+ * cardinality or a sum, so it has exactly one value whatever the schedule.  The call observes the map as queries do (async mode:
+ * waits for everything submitted), runs on the stream of mlm_set_stream and returns when the outputs are written.
+ * MLM_ERR_INVALID: n_views < 0, view_begin NULL, negative at [0] or decreasing, p0 / p1 NULL with rays, an unknown flag bit, lo
+ * without dims, the window errors, exclude or mark without a box, mark == exclude, no output; n_views == 0 is MLM_OK.
+ * MLM_ERR_CAPACITY: no device memory for the scratch (bounding boxes, work lists, the bitsets of views too large for on-chip
+ * memory: at most 256 MiB at a time, which is also the most one view can need) or the staging of host inputs / outputs (rays in chunks of views
+ * of about 2^20 rays — a longer view whole —, a host exclude / mark the whole box), kept by the handle and counted in
+ * mlm_frame_stats.device_bytes.  The handle stays usable after either error. */
+#define MLM_VIEW_ROW 8
+int mlm_query_views(mlm_handle *h, const double *p0, const double *p1, const int32_t *view_begin, int n_views, int flags,
+                    const int32_t lo[3], const int32_t dims[3], const uint8_t *exclude, uint8_t *mark, int64_t *table);
 /* Cost-to-go field through the free space of a box of voxels (no reference counterpart: the reference has no such field; the
  * classes behind it are those of its point queries, the field is defined here, in integers).  Voxel indices, window, layout
  * ([dims[2]][dims[1]][dims[0]], x fastest) and centres are those of mlm_export_window.

@@ -27,7 +27,7 @@ struct KernelTime {
 const char *const kKnobNames[] = {"agg_lds", "big_arm", "big_grid", "bin_block", "chain_grid", "cluster_tile", "collect_grid", "cu_reserve", "cu_split",
                                   "esdf_tile_vox", "ex_spec", "expand_block", "graph", "logit_exact", "mirror", "mirror_max", "mirror_mb", "need_slots", "node_lds", "pool_grow",
                                   "rank_grid", "rays_grid", "reach_group", "reach_tile", "sc_block", "sc_grid", "sec_backoff", "sec_fail_every", "sec_tab", "sec_tab_big", "sec_threads",
-                                  "sectors", "single_apply_grid", "single_chain_grid", "single_rank_grid", "slot_sets", "sort_block", "sort_grid", "tile_grid", "tile_sh"};
+                                  "sectors", "single_apply_grid", "single_chain_grid", "single_rank_grid", "slot_sets", "sort_block", "sort_grid", "tile_grid", "tile_sh", "view_lds_bits"};
 struct KnobStore {
     std::mutex mu;
     std::unordered_map<std::string, long long> v;
@@ -51,6 +51,7 @@ bool knob_value_ok(const char *name, long long v) {
     if (is("esdf_tile_vox")) return v >= kEsdfMinBoxVoxels && v <= kEsdfBoxVoxels; // (mlm_esdf_plan fits every call's tile then)
     if (is("cluster_tile")) return mlm_reach_tile_ok(v); // (packed like reach_tile; the tile's labels within k_cluster_local's LDS)
     if (is("reach_tile")) return mlm_reach_tile_ok(v);  // (x | y << 8 | z << 16, edges 1..64, tile + halo within k_reach_sweep's LDS)
+    if (is("view_lds_bits")) return v >= 0 && v <= kViewLdsBits; // (larger bitsets go to global scratch; 0: all of them)
     if (is("reach_group")) return v >= 1 && v <= kReachGroupMax; // (sweeps between two looks at the "marked" words)
     return true;
 }
@@ -167,6 +168,10 @@ struct mlm_handle {
     // mlm_query_rays: staging of the host inputs / outputs of one chunk of rays, kept and enlarged by need
     void *d_ray_stage = nullptr;
     size_t ray_stage_bytes = 0;
+    // mlm_query_views: per-view boxes, job lists, staged rows and the global path's bitsets of one chunk of views, kept and enlarged by
+    // need (staged rays use d_ray_stage, a staged exclude / mark d_win_stage)
+    void *d_views = nullptr;
+    size_t views_bytes = 0;
     unsigned int rays_grid = 1024; // most workgroups of k_rays (knob "rays_grid"): 2^20 rays are four per lane
     // sort buffers (rehash frames only)
     unsigned long long *sk_in = nullptr, *sk_out = nullptr;

@@ -32,6 +32,7 @@
 #include "mlm_kernels_window.h"
 #include "mlm_kernels_esdf.h"
 #include "mlm_kernels_rays.h"
+#include "mlm_kernels_views.h"
 #include "mlm_kernels_reach.h"
 #include "mlm_kernels_cluster.h"
 #include "mlm_host.h"
@@ -1719,6 +1720,182 @@ int mlm_query_rays(mlm_handle *h, const double *p0, const double *p1, int n, int
                 HIPCHK(h, hipMemcpyAsync((char *)ch[c] + (size_t)i0 * elem[c], at[c], (size_t)m * elem[c], hipMemcpyDeviceToHost, h->stream));
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MLM_OK;
+}
+
+namespace {
+constexpr int kViewChunkViews = 1 << 16;    // views per pass: bounds the job lists and the staged rows (64 bytes per view)
+constexpr unsigned int kViewGrid = 1 << 16; // most workgroups of a launch (grid-stride over the jobs)
+inline size_t view_align(size_t b) { return (b + 255) & ~(size_t)255; }
+} // namespace
+
+int mlm_query_views(mlm_handle *h, const double *p0, const double *p1, const int32_t *view_begin, int n_views, int flags, const int32_t lo[3],
+                    const int32_t dims[3], const uint8_t *exclude, uint8_t *mark, int64_t *table) {
+    if (!h) return MLM_ERR_INVALID;
+    MLM_LOCK(h);
+    const bool boxed = lo && dims;
+    if (n_views < 0 || (n_views > 0 && !view_begin) || (flags & ~7) || (!mark && !table) || (!lo != !dims) || ((exclude || mark) && !boxed) ||
+        (mark && mark == exclude)) {
+        h->err = "mlm_query_views: negative n_views, a null view_begin, an unknown flag bit, no output, lo without dims, exclude or mark without "
+                 "a box, or mark == exclude";
+        return MLM_ERR_INVALID;
+    }
+    MlmViewWindow B{};
+    long long nvox = 0;
+    if (boxed) {
+        B.on = 1;
+        nvox = 1;
+        for (int a = 0; a < 3; ++a) {
+            if (dims[a] < 1 || (long long)lo[a] + dims[a] > 0x7FFFFFFFll) {
+                h->err = "mlm_query_views: dims must be >= 1 and lo + dims must fit an int32";
+                return MLM_ERR_INVALID;
+            }
+            B.lo[a] = lo[a];
+            B.d[a] = dims[a];
+            nvox *= dims[a];
+            if (nvox > 0x7FFFFFFFll) {
+                h->err = "mlm_query_views: more than 2^31 - 1 voxels";
+                return MLM_ERR_INVALID;
+            }
+        }
+    }
+    if (n_views == 0) return MLM_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    // view_begin: validated on the host (copied back when it is device memory, behind the caller's work on the stream)
+    std::vector<int32_t> vb_copy;
+    const int32_t *vb = view_begin;
+    if (win_in_place(view_begin)) {
+        vb_copy.resize((size_t)n_views + 1);
+        HIPCHK(h, hipMemcpyAsync(vb_copy.data(), view_begin, vb_copy.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        vb = vb_copy.data();
+    }
+    bool vb_ok = vb[0] >= 0;
+    for (int k = 0; k < n_views && vb_ok; ++k) vb_ok = vb[k + 1] >= vb[k];
+    if (!vb_ok || (vb[n_views] > vb[0] && (!p0 || !p1))) {
+        h->err = "mlm_query_views: view_begin must start at >= 0 and must not decrease; rays need p0 and p1";
+        return MLM_ERR_INVALID;
+    }
+    int rc = drain(h);
+    if (rc) return rc;
+
+    long long lds_bits = kViewLdsBits, kv;
+    if (knob("view_lds_bits", kv)) lds_bits = kv;
+    const bool p_staged[2] = {p0 && !win_in_place(p0), p1 && !win_in_place(p1)};
+    const bool ex_staged = exclude && !win_in_place(exclude), mark_staged = mark && !win_in_place(mark), table_staged = table && !win_in_place(table);
+    // a host exclude / mark: the whole box once (mark with its contents: bytes no view touches stay as they were)
+    const size_t box_bytes = view_align((size_t)nvox);
+    if ((ex_staged || mark_staged) &&
+        (rc = win_reserve(h, h->d_win_stage, h->win_stage_bytes, box_bytes * ((ex_staged ? 1 : 0) + (mark_staged ? 1 : 0)), "mlm_query_views")))
+        return rc;
+    const uint8_t *d_exclude = exclude;
+    uint8_t *d_mark = mark;
+    if (ex_staged) {
+        d_exclude = (const uint8_t *)h->d_win_stage;
+        HIPCHK(h, hipMemcpyAsync(h->d_win_stage, exclude, (size_t)nvox, hipMemcpyHostToDevice, h->stream));
+    }
+    if (mark_staged) {
+        d_mark = (uint8_t *)h->d_win_stage + (ex_staged ? box_bytes : 0);
+        HIPCHK(h, hipMemcpyAsync(d_mark, mark, (size_t)nvox, hipMemcpyHostToDevice, h->stream));
+    }
+
+    std::vector<long long> begin;
+    std::vector<MlmViewJob> jobs;
+    std::vector<MlmViewBox> raw;
+    for (int k0 = 0; k0 < n_views;) {
+        // a chunk of views: at most kViewChunkViews, and with staged rays at most kRayChunk rays (a longer view on its own)
+        int k1 = k0 + 1;
+        while (k1 < n_views && k1 - k0 < kViewChunkViews && (!(p_staged[0] || p_staged[1]) || (long long)vb[k1 + 1] - vb[k0] <= kRayChunk)) ++k1;
+        const int nv = k1 - k0;
+        const long long r0 = vb[k0], nr = (long long)vb[k1] - r0;
+        begin.resize((size_t)nv + 1);
+        for (int k = 0; k <= nv; ++k) begin[(size_t)k] = (long long)vb[k0 + k] - r0;
+        const double *ray[2] = {p0, p1};
+        const size_t ray_bytes = view_align((size_t)nr * 3 * sizeof(double));
+        if (nr && (p_staged[0] || p_staged[1]) &&
+            (rc = win_reserve(h, h->d_ray_stage, h->ray_stage_bytes, ray_bytes * ((p_staged[0] ? 1 : 0) + (p_staged[1] ? 1 : 0)), "mlm_query_views")))
+            return rc;
+        for (int c = 0; c < 2; ++c) {
+            if (!nr) continue;
+            if (p_staged[c]) {
+                double *at = (double *)((char *)h->d_ray_stage + (c && p_staged[0] ? ray_bytes : 0));
+                HIPCHK(h, hipMemcpyAsync(at, ray[c] + 3 * (size_t)r0, (size_t)nr * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+                ray[c] = at;
+            } else {
+                ray[c] += 3 * (size_t)r0;
+            }
+        }
+        // the views' bounding boxes
+        jobs.clear();
+        for (int k = 0; k < nv; ++k)
+            for (long long i = begin[(size_t)k]; i < begin[(size_t)k + 1]; i += kViewBoxRays)
+                jobs.push_back(MlmViewJob{k, (int)i, (int)std::min(i + kViewBoxRays, begin[(size_t)k + 1]), 0, 1, 0, 0});
+        const size_t raw_bytes = view_align((size_t)nv * sizeof(MlmViewBox));
+        if ((rc = win_reserve(h, h->d_views, h->views_bytes, raw_bytes + view_align(jobs.size() * sizeof(MlmViewJob)), "mlm_query_views"))) return rc;
+        MlmViewBox *d_raw = (MlmViewBox *)h->d_views;
+        MlmViewJob *d_jobs = (MlmViewJob *)((char *)h->d_views + raw_bytes);
+        hipLaunchKernelGGL(k_views_box_init, dim3((unsigned int)((nv + 255) / 256)), dim3(256), 0, h->stream, d_raw, nv);
+        if (!jobs.empty()) {
+            HIPCHK(h, hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * sizeof(MlmViewJob), hipMemcpyHostToDevice, h->stream));
+            hipLaunchKernelGGL(k_views_box, dim3((unsigned int)std::min<size_t>(jobs.size(), kViewGrid)), dim3(256), 0, h->stream, h->P, ray[0], ray[1],
+                               (const MlmViewJob *)d_jobs, (int)jobs.size(), d_raw);
+        }
+        HIPCHK(h, hipGetLastError());
+        raw.resize((size_t)nv);
+        HIPCHK(h, hipMemcpyAsync(raw.data(), d_raw, (size_t)nv * sizeof(MlmViewBox), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        // the plan, its lists and the scratch (the kept buffer may move: the boxes go up again)
+        const MlmViewPlan plan = mlm_view_plan(raw.data(), begin.data(), nv, B, lds_bits);
+        jobs.clear();
+        size_t first[kViewLdsClasses + 1];
+        for (int c = 0; c < kViewLdsClasses; ++c) {
+            first[c] = jobs.size();
+            jobs.insert(jobs.end(), plan.lds[c].begin(), plan.lds[c].end());
+        }
+        first[kViewGlobal] = jobs.size();
+        jobs.insert(jobs.end(), plan.global.begin(), plan.global.end());
+        const size_t jobs_bytes = view_align(jobs.size() * sizeof(MlmViewJob)), ref_bytes = view_align(plan.refused.size() * sizeof(int)),
+                     rows_bytes = table_staged ? view_align((size_t)nv * kViewRow * sizeof(int64_t)) : 0;
+        if ((rc = win_reserve(h, h->d_views, h->views_bytes, raw_bytes + jobs_bytes + ref_bytes + rows_bytes + (size_t)plan.scratch_words * 4, "mlm_query_views")))
+            return rc;
+        char *base = (char *)h->d_views;
+        d_raw = (MlmViewBox *)base;
+        d_jobs = (MlmViewJob *)(base + raw_bytes);
+        int *d_ref = (int *)(base + raw_bytes + jobs_bytes);
+        int64_t *rows = !table ? nullptr : table_staged ? (int64_t *)(base + raw_bytes + jobs_bytes + ref_bytes) : table + (size_t)k0 * kViewRow;
+        HIPCHK(h, hipMemcpyAsync(d_raw, raw.data(), (size_t)nv * sizeof(MlmViewBox), hipMemcpyHostToDevice, h->stream));
+        if (!jobs.empty()) HIPCHK(h, hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * sizeof(MlmViewJob), hipMemcpyHostToDevice, h->stream));
+        if (rows) HIPCHK(h, hipMemsetAsync(rows, 0, (size_t)nv * kViewRow * sizeof(int64_t), h->stream));
+        MlmViews V{ray[0], ray[1], flags, B, d_exclude, d_mark, d_raw, rows, (uint32_t *)(base + raw_bytes + jobs_bytes + ref_bytes + rows_bytes)};
+        for (int c = 0; c < kViewLdsClasses; ++c) {
+            const size_t nj = first[c + 1] - first[c];
+            if (!nj) continue;
+            hipLaunchKernelGGL(k_views_lds, dim3((unsigned int)std::min<size_t>(nj, kViewGrid)), dim3(kViewLdsThreads), (size_t)mlm_view_class_bytes(c),
+                               h->stream, h->P, V, (const MlmViewJob *)(d_jobs + first[c]), (int)nj);
+        }
+        HIPCHK(h, hipGetLastError());
+        for (const MlmViewPlan::Batch &b : plan.batches) {
+            HIPCHK(h, hipMemsetAsync(V.scratch, 0, (size_t)b.words * 4, h->stream));
+            const size_t nj = b.job1 - b.job0;
+            hipLaunchKernelGGL(k_views_global, dim3((unsigned int)std::min<size_t>(nj, kViewGrid)), dim3(kViewGlobalThreads), 0, h->stream, h->P, V,
+                               (const MlmViewJob *)(d_jobs + first[kViewGlobal] + b.job0), (int)nj);
+            HIPCHK(h, hipGetLastError());
+        }
+        if (rows && !plan.refused.empty()) {
+            HIPCHK(h, hipMemcpyAsync(d_ref, plan.refused.data(), plan.refused.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+            hipLaunchKernelGGL(k_views_refused, dim3((unsigned int)((plan.refused.size() + 255) / 256)), dim3(256), 0, h->stream, rows,
+                               (const int *)d_ref, (int)plan.refused.size());
+            HIPCHK(h, hipGetLastError());
+        }
+        if (table_staged)
+            HIPCHK(h, hipMemcpyAsync(table + (size_t)k0 * kViewRow, rows, (size_t)nv * kViewRow * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream)); // (the lists above are reused by the next chunk)
+        k0 = k1;
+    }
+    if (mark_staged) {
+        HIPCHK(h, hipMemcpyAsync(mark, d_mark, (size_t)nvox, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
     return MLM_OK;
 }
 

@@ -33,6 +33,8 @@ MLM_CLUSTER_OCC, MLM_CLUSTER_INFL, MLM_CLUSTER_UNKNOWN, MLM_CLUSTER_FRONTIER = 1
 MLM_CLUSTER_NONE, MLM_CLUSTER_SMALL, MLM_CLUSTER_ROW = -1, -2, 16
 # mlm_query_rays flags: what stops a ray (their union; 0: nothing, a pure count)
 MLM_RAY_OCC, MLM_RAY_INFL, MLM_RAY_UNKNOWN = 1, 2, 4
+# mlm_query_views: int64 per row of the table
+MLM_VIEW_ROW = 8
 STATUS = {0: "MLM_OK", -1: "MLM_ERR_INVALID", -2: "MLM_ERR_HIP", -3: "MLM_ERR_CAPACITY", -4: "MLM_ERR_UNSUPPORTED"}
 
 # every symbol include/mlmap_hip.h declares
@@ -44,7 +46,7 @@ ABI_SYMBOLS = [
     "mlm_query_odds", "mlm_query_odd_grad", "mlm_query_odds_at", "mlm_export_frontier_points", "mlm_import_blocks",
     "mlm_merge_pack", "mlm_merge_finish",
     "mlm_set_free_in_bound", "mlm_inflate_map", "mlm_block_count",
-    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_reach", "mlm_export_clusters", "mlm_query_rays", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
+    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_reach", "mlm_export_clusters", "mlm_query_rays", "mlm_query_views", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
     "mlm_get_awareness_hits",
     "mlm_get_awareness_misses", "mlm_get_T_ls", "mlm_get_odds_table", "mlm_get_kernel_times",
     "mlm_enable_kernel_timing", "mlm_set_timed_kernel", "mlm_host_register", "mlm_host_unregister", "mlm_debug_set", "mlm_debug_reset",
@@ -142,6 +144,7 @@ def load_library(path: Optional[str] = None):
     L.mlm_export_reach.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     L.mlm_export_clusters.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i32, vp]
     L.mlm_query_rays.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
+    L.mlm_query_views.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.mlm_export_global_map.argtypes = [vp, i32, vp, vp]
     L.mlm_export_block_flags.argtypes = [vp, i32, vp, vp]
     L.mlm_export_frontier.argtypes = [vp, i32, vp, vp]
@@ -585,6 +588,52 @@ class MLMap:
         self._chk(self._L.mlm_query_rays(self._h, ctypes.c_void_p(p0), ctypes.c_void_p(p1), int(n),
                                          self._ray_flags(occ, infl, unknown), *ptr), "mlm_query_rays")
 
+    def query_views(self, p0, p1, view_begin, occ=True, infl=False, unknown=False, box=None, exclude=None, mark=False) -> Dict[str, np.ndarray]:
+        """Distinct-voxel accounting of grouped ray fans (mlm_query_views): view k is the segments view_begin[k] .. view_begin[k + 1]
+        of p0 / p1 (n x 3 world positions), walked as cast_rays walks them.  {"table": int64 (n_views, 8): distinct traversed
+        voxels, of those UNKNOWN (the gain), of those FREE, distinct stop voxels, stopped rays, invalid rays, visits with
+        multiplicity, refused; "mark": uint8 (dz, dy, dx) or absent}.  box = (lo, dims) restricts the accounting to a window (voxel
+        indices as export_window); exclude: uint8 (dz, dy, dx), voxels with a non-zero byte are not counted; mark: True for a
+        zeroed array, or a uint8 (dz, dy, dx) array that is updated in place (|= 1 traversed, |= 2 stop voxel) and returned."""
+        a, b = _f64(p0).reshape(-1, 3), _f64(p1).reshape(-1, 3)
+        vb = np.ascontiguousarray(view_begin, dtype=np.int32).reshape(-1)
+        if a.shape != b.shape or vb.size < 1 or (vb.size > 1 and int(vb[-1]) > a.shape[0]):
+            raise MlmError("query_views: p0 and p1 differ in shape, or view_begin is empty or reaches past the rays")
+        lo_p = dims_p = ex_p = mk_p = None
+        out = {"table": np.zeros((vb.size - 1, MLM_VIEW_ROW), dtype=np.int64)}
+        if box is not None:
+            lo_a, dims_a = self._window_args(*box)
+            lo_p, dims_p = _p(lo_a), _p(dims_a)
+            shape = (int(dims_a[2]), int(dims_a[1]), int(dims_a[0]))
+            if exclude is not None:
+                ex = np.ascontiguousarray(exclude, dtype=np.uint8)
+                if ex.shape != shape:
+                    raise MlmError("query_views: exclude must have the box's shape (dz, dy, dx)")
+                ex_p = _p(ex)
+            if mark is not False and mark is not None:
+                mk = np.zeros(shape, dtype=np.uint8) if mark is True else mark
+                if not (isinstance(mk, np.ndarray) and mk.dtype == np.uint8 and mk.shape == shape and mk.flags["C_CONTIGUOUS"]):
+                    raise MlmError("query_views: mark must be a contiguous uint8 array of the box's shape (dz, dy, dx)")
+                out["mark"] = mk
+                mk_p = _p(mk)
+        elif exclude is not None or (mark is not False and mark is not None):
+            raise MlmError("query_views: exclude and mark need a box")
+        self._chk(self._L.mlm_query_views(self._h, _p(a), _p(b), _p(vb), vb.size - 1, self._ray_flags(occ, infl, unknown), lo_p, dims_p, ex_p,
+                                          mk_p, _p(out["table"])), "mlm_query_views")
+        return out
+
+    def query_views_dev(self, p0: int, p1: int, view_begin: int, n_views: int, occ=True, infl=False, unknown=False, box=None,
+                        exclude: Optional[int] = None, mark: Optional[int] = None, table: Optional[int] = None):
+        """Same on pointers (ints; device or host memory, each on its own): n x 3 float64 end points, n_views + 1 int32 view_begin,
+        uint8 exclude / mark of the box, int64 n_views x 8 table; None = skipped."""
+        lo_p = dims_p = None
+        if box is not None:
+            lo_a, dims_a = self._window_args(*box)
+            lo_p, dims_p = _p(lo_a), _p(dims_a)
+        ptr = [None if v is None else ctypes.c_void_p(v) for v in (exclude, mark, table)]
+        self._chk(self._L.mlm_query_views(self._h, ctypes.c_void_p(p0), ctypes.c_void_p(p1), ctypes.c_void_p(view_begin), int(n_views),
+                                          self._ray_flags(occ, infl, unknown), lo_p, dims_p, *ptr), "mlm_query_views")
+
     @staticmethod
     def _ray_flags(occ, infl, unknown) -> int:
         return (MLM_RAY_OCC if occ else 0) | (MLM_RAY_INFL if infl else 0) | (MLM_RAY_UNKNOWN if unknown else 0)
@@ -673,3 +722,26 @@ class MLMap:
         n = ctypes.c_int32()
         self._chk(self._L.mlm_get_kernel_times(self._h, cap, names, _p(ms), ctypes.byref(n)), "mlm_get_kernel_times")
         return [(names[i].decode(), float(ms[i])) for i in range(min(n.value, cap))]
+
+
+def pinhole_fan(width: int, height: int, fx: float, fy: float, cx: float, cy: float, max_range: float) -> np.ndarray:
+    """The ray grid of a pinhole camera for query_views: (height * width, 3) float64 end points in the camera frame (x right, y down,
+    z forward), one per pixel centre (u + 0.5, v + 0.5), each at distance max_range from the optical centre along its pixel's
+    ray.  A convenience: nothing of it is part of mlm_query_views' contract, which starts at the end points it is given."""
+    u, v = np.meshgrid(np.arange(width, dtype=np.float64) + 0.5, np.arange(height, dtype=np.float64) + 0.5)
+    dirs = np.stack([(u - cx) / fx, (v - cy) / fy, np.ones_like(u)], axis=-1).reshape(-1, 3)
+    return dirs / np.linalg.norm(dirs, axis=1, keepdims=True) * float(max_range)
+
+
+def fan_views(origins, rotations, fan):
+    """(p0, p1, view_begin) of one view per pose for query_views: view k casts the end points `fan` (m x 3, sensor frame, e.g.
+    pinhole_fan's) from origins[k] (world) turned by rotations[k] (3 x 3, sensor to world).  A convenience like pinhole_fan."""
+    o = _f64(origins).reshape(-1, 3)
+    R = _f64(rotations).reshape(-1, 3, 3)
+    f = _f64(fan).reshape(-1, 3)
+    if len(o) != len(R):
+        raise MlmError("fan_views: one rotation per origin")
+    p1 = o[:, None, :] + np.einsum("kij,mj->kmi", R, f)
+    p0 = np.broadcast_to(o[:, None, :], p1.shape)
+    return (np.ascontiguousarray(p0).reshape(-1, 3), np.ascontiguousarray(p1).reshape(-1, 3),
+            (np.arange(len(o) + 1, dtype=np.int64) * len(f)).astype(np.int32))
