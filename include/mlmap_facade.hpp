@@ -268,6 +268,24 @@ class mlmap {
         check(mlm_query_views(h_, p0, p1, view_begin, n_views, flags, lo, dims, exclude, mark, table), "mlm_query_views");
     }
 
+    // class counts and free-space growth of axis-aligned voxel boxes (mlm_query_boxes; flags MLM_BOX_*; box6 n x 6 inclusive voxel
+    // indices lo then hi; max_grow six layer counts in host memory or NULL = a pure count; lo / dims the limit window or both NULL;
+    // table [n][MLM_BOX_ROW]; box6 and every output host or device memory, NULL output = skipped)
+    void queryBoxes(const int32_t *box6, int n, int flags, const int32_t max_grow[6], int8_t *status, int32_t *out6 = nullptr,
+                    uint8_t *closed = nullptr, int64_t *table = nullptr, const int32_t *lo = nullptr, const int32_t *dims = nullptr) {
+        check(mlm_query_boxes(h_, box6, n, flags, max_grow, lo, dims, status, out6, closed, table), "mlm_query_boxes");
+    }
+    // one box (answered from the host mirror when its limit volume is small: no launch): the largest box the growth of
+    // mlm_query_boxes reaches from [a, b]; false if [a, b] itself holds a voxel that `flags` selects.  An invalid box throws.
+    bool growBox(const int32_t a[3], const int32_t b[3], int flags, const int32_t max_grow[6], int32_t out6[6], uint8_t *closed = nullptr,
+                 int64_t *row = nullptr) {
+        const int32_t in[6] = {a[0], a[1], a[2], b[0], b[1], b[2]};
+        int8_t st = 0;
+        check(mlm_query_boxes(h_, in, 1, flags, max_grow, nullptr, nullptr, &st, out6, closed, row), "mlm_query_boxes");
+        if (st < 0) throw std::runtime_error("growBox: invalid box");
+        return st == 1;
+    }
+
     // planners that query thousands of positions per cycle should use the batched entry points directly
     mlm_handle *handle() { return h_; }
 

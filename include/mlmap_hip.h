@@ -333,6 +333,52 @@ int mlm_query_rays(mlm_handle *h, const double *p0, const double *p1, int n, int
 #define MLM_VIEW_ROW 8
 int mlm_query_views(mlm_handle *h, const double *p0, const double *p1, const int32_t *view_begin, int n_views, int flags,
                     const int32_t lo[3], const int32_t dims[3], const uint8_t *exclude, uint8_t *mark, int64_t *table);
+/* Class counts and exact free-space growth of axis-aligned voxel boxes: is this box free, how much of it is unknown, and how far
+ * can it be grown before it touches an obstacle?  (No reference counterpart: the reference has no volume query; the classes are
+ * those of its point queries, the growth is defined here, in integers, with exactly one answer.)  Voxel indices and classes are
+ * those of mlm_export_window (released frontier-mode blocks, absent blocks and voxels beyond the key range, which are UNKNOWN,
+ * included).
+ *   Faces: 0 -x, 1 +x, 2 -y, 3 +y, 4 -z, 5 +z (the parent codes of mlm_export_reach).
+ *   Items: item i is the box B0 = [a, b], box6[6i .. 6i+2] = a, box6[6i+3 .. 6i+5] = b, inclusive voxel indices.  It is INVALID if
+ *   a > b on an axis, b - a >= 2^15 on an axis, or a limit window is given and B0 does not lie inside it: status -1, out6 = the
+ *   six input words, closed 0, a table row of zeros.
+ *   Predicate: O(v) is the union of what `flags` selects (MLM_BOX_OCC getOccupancy(centre) == OCCUPIED, MLM_BOX_INFL
+ *   getInflateOccupancy(centre) == OCCUPIED, MLM_BOX_UNKNOWN getOccupancy(centre) == UNKNOWN), exactly as in mlm_query_rays;
+ *   flags == 0: nothing blocks.
+ *   Limits: max_grow[c] in 0 .. 4096 (host memory) is the most layers face c may move outward from B0; NULL: all zero, the call is
+ *   a pure count of B0.  lo / dims are both NULL or both given: W is then a window under mlm_export_window's rules and errors, and
+ *   the box never leaves W.  A face whose next layer would leave W, exceed max_grow[c] or leave int32 is closed by limit.
+ *   Blocked start: if B0 holds a voxel with O: status 0, out6 = B0, closed 0, no growth; table word [2] counts the O voxels of B0
+ *   in full.
+ *   Growth: otherwise status 1, all six faces start open.  Rounds are repeated until no face is open; a round visits the faces in
+ *   order c = 0 .. 5 and skips closed ones: (1) a face at a limit is closed by limit; (2) otherwise its slab is the one-voxel layer
+ *   adjacent to the current box on face c, spanning the box's current extent on the other two axes (what faces earlier in the same
+ *   round have added included); (3) if a slab voxel has O the face is closed by obstacle; (4) otherwise the box absorbs the slab.
+ *   Closing is permanent (exact: the slabs of a face only ever grow, so a blocked slab stays blocked).
+ *   Per item:
+ *     status  int8       1 grown, 0 blocked start, -1 invalid
+ *     out6    int32 x 6  the final box, lo then hi, inclusive
+ *     closed  uint8      bit c set iff face c was closed by an obstacle (clear: closed by limit)
+ *     table   int64 x MLM_BOX_ROW  [0] voxels of the final box  [1] of those, voxels whose occ class is UNKNOWN
+ *                                  [2] of those, voxels with O (non-zero only at status 0)  [3] slabs absorbed
+ *   A slab has fewer than 40 960^2 < 2^31 voxels, a box fewer than 2^48.  Every word is a function of the map and the arguments
+ *   alone.
+ * Any output may be NULL, at least one must not be; box6 and each output on its own may be host or device memory.  The call
+ * observes the map as queries do (async mode: waits for everything submitted), runs on the stream of mlm_set_stream and returns
+ * when the outputs are written.  A batch in host memory of at most 64 boxes (8 while the host mirror needs a refresh; a quarter
+ * of the mirror's batch limits) whose limit volumes — B0 plus max_grow per face, cut to W — sum to at most 16 384 voxels is
+ * answered from the host mirror without a launch (same answers); everything else, and every batch after
+ * mlm_set_host_mirror_limit(h, 0), runs as a kernel.  MLM_ERR_INVALID: n < 0, box6 NULL with n > 0, an unknown flag bit, a max_grow
+ * entry outside [0, 4096], lo without dims or the reverse, the window errors, no output; n == 0 is MLM_OK.  MLM_ERR_CAPACITY: no
+ * device memory for the staging of host inputs / outputs (at most 82 bytes x 2^18 boxes, kept by the handle and counted in
+ * mlm_frame_stats.device_bytes; larger batches run in chunks).  The handle stays usable after either error. */
+#define MLM_BOX_OCC 1 /* same bits and same meaning as MLM_RAY_OCC / _INFL / _UNKNOWN */
+#define MLM_BOX_INFL 2
+#define MLM_BOX_UNKNOWN 4
+#define MLM_BOX_ROW 4
+int mlm_query_boxes(mlm_handle *h, const int32_t *box6, int n, int flags, const int32_t max_grow[6],
+                    const int32_t lo[3], const int32_t dims[3],
+                    int8_t *status, int32_t *out6, uint8_t *closed, int64_t *table);
 /* Cost-to-go field through the free space of a box of voxels (no reference counterpart: the reference has no such field; the
  * classes behind it are those of its point queries, the field is defined here, in integers).  Voxel indices, window, layout
  * ([dims[2]][dims[1]][dims[0]], x fastest) and centres are those of mlm_export_window.

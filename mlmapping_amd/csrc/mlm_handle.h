@@ -127,6 +127,12 @@ struct MlmMirror {
 constexpr int kMirrorUnavailable = 1;
 constexpr long long kRayMirrorSteps = 16384; // ~50 us of host walking: about what a launch, two copies and a synchronisation cost
 constexpr int kRayChunk = 1 << 20;           // rays per launch of k_rays: bounds the staging of host inputs / outputs (77 bytes per ray)
+// mlm_query_boxes: a batch in host memory is answered on the host when it has at most a quarter as many boxes as the mirror's limits
+// allow positions (64 / 8 by default, as for rays) AND the limit volumes of its valid boxes — B0 plus max_grow per face, cut to the
+// window: the most voxels the growth can read, known before anything is read — sum to at most kBoxMirrorVoxels
+constexpr long long kBoxMirrorVoxels = 16384;
+constexpr int kBoxChunk = 1 << 18;           // boxes per launch of k_boxes: bounds the staging of host inputs / outputs (82 bytes per box)
+constexpr unsigned int kBoxGrid = 8192;      // most workgroups of k_boxes (a wave per box, grid-stride): 32 768 waves, four times what the chip holds
 
 // A frame on its own with at most this many strips of 256 points (sampled callbacks, point lists: 4 096 points) runs its cells' float chains
 // inside k_rank<true> instead of launching k_chain_lanes — a launch of its own costs a lone frame the kernel boundary (1.5 us) and the few
@@ -172,6 +178,7 @@ struct mlm_handle {
     // need (staged rays use d_ray_stage, a staged exclude / mark d_win_stage)
     void *d_views = nullptr;
     size_t views_bytes = 0;
+    // mlm_query_boxes stages the host inputs / outputs of one chunk of boxes in d_ray_stage too
     unsigned int rays_grid = 1024; // most workgroups of k_rays (knob "rays_grid"): 2^20 rays are four per lane
     // sort buffers (rehash frames only)
     unsigned long long *sk_in = nullptr, *sk_out = nullptr;

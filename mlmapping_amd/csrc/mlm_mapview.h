@@ -6,11 +6,13 @@
 // marks a released block (vectors of size 1 in the reference: element 0 answers, mlmap.h:183-184,221-222); block keys are packed
 // like the device's (three 21-bit biased indices) into an open-addressed table.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <vector>
 
+#include "mlm_boxgrow.h"
 #include "mlm_raywalk.h"
 
 namespace mlm_host {
@@ -230,6 +232,64 @@ struct MapView {
             if (t) t[i] = o.t;
             if (n_steps) n_steps[i] = o.n_steps;
             if (n_unknown) n_unknown[i] = o.n_unknown;
+        }
+    }
+    // mlm_query_boxes on the mirrored planes: the growth of mlm_boxgrow.h over the same classes.  The scan walks the box block by
+    // block: one table probe per block touched, no plane memory for an absent or released block.
+    struct BoxScan {
+        const MapView &v;
+        static long long fdiv(long long a, long long n) { return a >= 0 ? a / n : -((-a + n - 1) / n); }
+        void operator()(const int32_t lo[3], const int32_t hi[3], int flags, bool full, long long &n_unknown, long long &n_obstacle) const {
+            const long long n = v.n;
+            long long g0[3], g1[3];
+            for (int a = 0; a < 3; ++a) {
+                g0[a] = fdiv(lo[a], n);
+                g1[a] = fdiv(hi[a], n);
+            }
+            for (long long gz = g0[2]; gz <= g1[2]; ++gz)
+                for (long long gy = g0[1]; gy <= g1[1]; ++gy)
+                    for (long long gx = g0[0]; gx <= g1[0]; ++gx) {
+                        const long long g[3] = {gx, gy, gz};
+                        long long c0[3], c1[3], cnt = 1; // the cells of this block inside the box
+                        for (int a = 0; a < 3; ++a) {
+                            c0[a] = std::max<long long>(lo[a], g[a] * n) - g[a] * n;
+                            c1[a] = std::min<long long>(hi[a], g[a] * n + n - 1) - g[a] * n;
+                            cnt *= c1[a] - c0[a] + 1;
+                        }
+                        const int slot = v.find((int)gx, (int)gy, (int)gz);
+                        if (slot < 0 || v.col[slot]) {
+                            const int bits = slot < 0 ? 4 : RayClasses::occ_bits(v.occ[(size_t)slot * v.cells]);
+                            if (bits & 4) n_unknown += cnt;
+                            if (bits & flags) n_obstacle += cnt;
+                        } else {
+                            for (long long cz = c0[2]; cz <= c1[2]; ++cz)
+                                for (long long cy = c0[1]; cy <= c1[1]; ++cy)
+                                    for (long long cx = c0[0]; cx <= c1[0]; ++cx) {
+                                        const size_t at = (size_t)slot * v.cells + (size_t)((cz * n + cy) * n + cx);
+                                        const int bits = RayClasses::occ_bits(v.occ[at]) | (v.infl[at] == 'o' ? 2 : 0);
+                                        n_unknown += (bits >> 2) & 1;
+                                        n_obstacle += (bits & flags) ? 1 : 0;
+                                    }
+                        }
+                        if (!full && n_obstacle) return;
+                    }
+        }
+    };
+    void box(const int32_t b6[6], int flags, const MlmBoxLimits &L, MlmBoxResult &o) const {
+        BoxScan scan{*this};
+        mlm_box_grow(b6, flags, L, scan, o);
+    }
+    // a batch, any output may be null (mlm_query_boxes' layout)
+    void boxes(const int32_t *box6, int count, int flags, const MlmBoxLimits &L, int8_t *status, int32_t *out6, uint8_t *closed, int64_t *table) const {
+        for (int i = 0; i < count; ++i) {
+            MlmBoxResult o;
+            box(box6 + 6 * (size_t)i, flags, L, o);
+            if (status) status[i] = (int8_t)o.status;
+            if (out6)
+                for (int k = 0; k < 6; ++k) out6[6 * (size_t)i + k] = o.box[k];
+            if (closed) closed[i] = (uint8_t)o.closed;
+            if (table)
+                for (int k = 0; k < 4; ++k) table[4 * (size_t)i + k] = o.row[k];
         }
     }
 };

@@ -274,6 +274,18 @@ bool mirror_rays_wanted(const mlm_handle *h, const double *p0, const double *p1,
     }
     return steps <= kRayMirrorSteps;
 }
+// ... and a batch of boxes (mlm_query_boxes): few boxes whose limit volumes are small enough together (kBoxMirrorVoxels, mlm_handle.h)
+bool mirror_boxes_wanted(const mlm_handle *h, const int32_t *box6, int n, const MlmBoxLimits &L) {
+    const MlmMirror &M = h->mir;
+    if (!M.enabled || (long long)n * 4 > (M.dirty ? M.max_dirty : M.max_clean)) return false;
+    long long vox = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!mlm_box_valid(box6 + 6 * (size_t)i, L)) continue;
+        vox += mlm_box_limit_volume(box6 + 6 * (size_t)i, L);
+        if (vox > kBoxMirrorVoxels) return false;
+    }
+    return true;
+}
 // drain + refresh if the map changed since the mirror was filled; the caller holds the lock
 int mirror_sync(mlm_handle *h) {
     if (h->mir.eager_pending) {

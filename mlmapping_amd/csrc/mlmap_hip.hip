@@ -32,6 +32,7 @@
 #include "mlm_kernels_window.h"
 #include "mlm_kernels_esdf.h"
 #include "mlm_kernels_rays.h"
+#include "mlm_kernels_boxes.h"
 #include "mlm_kernels_views.h"
 #include "mlm_kernels_reach.h"
 #include "mlm_kernels_cluster.h"
@@ -1716,6 +1717,89 @@ int mlm_query_rays(mlm_handle *h, const double *p0, const double *p1, int n, int
         hipLaunchKernelGGL(k_rays, grid, dim3(MLM_BLOCK), 0, h->stream, h->P, R);
         HIPCHK(h, hipGetLastError());
         for (int c = 2; c < 7; ++c)
+            if (staged[c])
+                HIPCHK(h, hipMemcpyAsync((char *)ch[c] + (size_t)i0 * elem[c], at[c], (size_t)m * elem[c], hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MLM_OK;
+}
+
+int mlm_query_boxes(mlm_handle *h, const int32_t *box6, int n, int flags, const int32_t max_grow[6], const int32_t lo[3], const int32_t dims[3],
+                    int8_t *status, int32_t *out6, uint8_t *closed, int64_t *table) {
+    if (!h) return MLM_ERR_INVALID;
+    MLM_LOCK(h);
+    if (n < 0 || (n > 0 && !box6) || (flags & ~7) || (!lo != !dims) || (!status && !out6 && !closed && !table)) {
+        h->err = "mlm_query_boxes: negative n, a null box6, an unknown flag bit, lo without dims or no output";
+        return MLM_ERR_INVALID;
+    }
+    MlmBoxLimits L{};
+    for (int c = 0; c < 6; ++c) {
+        L.grow[c] = max_grow ? max_grow[c] : 0;
+        if (L.grow[c] < 0 || L.grow[c] > MLM_BOX_MAX_GROW) {
+            h->err = "mlm_query_boxes: max_grow must lie in [0, 4096]";
+            return MLM_ERR_INVALID;
+        }
+    }
+    if (lo) {
+        L.on = 1;
+        long long nvox = 1;
+        for (int a = 0; a < 3; ++a) {
+            if (dims[a] < 1 || (long long)lo[a] + dims[a] > 0x7FFFFFFFll) {
+                h->err = "mlm_query_boxes: dims must be >= 1 and lo + dims must fit an int32";
+                return MLM_ERR_INVALID;
+            }
+            nvox *= dims[a];
+            if (nvox > 0x7FFFFFFFll) {
+                h->err = "mlm_query_boxes: more than 2^31 - 1 voxels";
+                return MLM_ERR_INVALID;
+            }
+            L.wlo[a] = lo[a];
+            L.whi[a] = lo[a] + (dims[a] - 1);
+        }
+    }
+    if (n == 0) return MLM_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    // channels: the input, then the four outputs; bytes per box; in device memory (used in place) or staged
+    void *ch[5] = {(void *)box6, status, out6, closed, table};
+    const size_t elem[5] = {6 * sizeof(int32_t), 1, 6 * sizeof(int32_t), 1, MLM_BOX_ROW * sizeof(int64_t)};
+    bool staged[5];
+    bool all_host = true;
+    for (int c = 0; c < 5; ++c) {
+        staged[c] = ch[c] && !win_in_place(ch[c]);
+        all_host = all_host && (staged[c] || !ch[c]);
+    }
+    // a planner's waypoint-by-waypoint calls: answered on the host (mlm_mirror.h), like mlm_query_rays' small batches
+    if (all_host && mirror_boxes_wanted(h, box6, n, L)) {
+        const int rc = mirror_sync(h);
+        if (rc == MLM_OK) {
+            h->mir.view.boxes(box6, n, flags, L, status, out6, closed, table);
+            h->mir.n_host_queries += n;
+            return MLM_OK;
+        }
+        if (!h->mir.alloc_failed && rc != kMirrorUnavailable) return rc; // (an error of the frames in flight, reported by the drain)
+    }
+    int rc = drain(h);
+    if (rc) return rc;
+    // chunks: staged channels of a chunk share one kept buffer (at most 82 bytes per box)
+    const int chunk = std::min(n, kBoxChunk);
+    size_t off[5], stage_bytes = 0;
+    for (int c = 0; c < 5; ++c) {
+        off[c] = stage_bytes;
+        if (staged[c]) stage_bytes += ((size_t)chunk * elem[c] + 255) & ~(size_t)255;
+    }
+    if (stage_bytes && (rc = win_reserve(h, h->d_ray_stage, h->ray_stage_bytes, stage_bytes, "mlm_query_boxes"))) return rc;
+    for (int i0 = 0; i0 < n; i0 += chunk) {
+        const int m = std::min(chunk, n - i0);
+        void *at[5];
+        for (int c = 0; c < 5; ++c)
+            at[c] = !ch[c] ? nullptr : staged[c] ? (void *)((char *)h->d_ray_stage + off[c]) : (void *)((char *)ch[c] + (size_t)i0 * elem[c]);
+        if (staged[0]) HIPCHK(h, hipMemcpyAsync(at[0], (const char *)ch[0] + (size_t)i0 * elem[0], (size_t)m * elem[0], hipMemcpyHostToDevice, h->stream));
+        MlmBoxes B{(const int32_t *)at[0], m, flags, L, (int8_t *)at[1], (int32_t *)at[2], (uint8_t *)at[3], (int64_t *)at[4]};
+        // one wave per box, four to a workgroup; at most kBoxGrid workgroups (grid-stride)
+        const dim3 grid(std::min<unsigned int>(((unsigned int)m + MLM_BLOCK / 64 - 1) / (MLM_BLOCK / 64), kBoxGrid));
+        hipLaunchKernelGGL(k_boxes, grid, dim3(MLM_BLOCK), 0, h->stream, h->P, B);
+        HIPCHK(h, hipGetLastError());
+        for (int c = 1; c < 5; ++c)
             if (staged[c])
                 HIPCHK(h, hipMemcpyAsync((char *)ch[c] + (size_t)i0 * elem[c], at[c], (size_t)m * elem[c], hipMemcpyDeviceToHost, h->stream));
     }

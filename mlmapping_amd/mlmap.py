@@ -35,6 +35,8 @@ MLM_CLUSTER_NONE, MLM_CLUSTER_SMALL, MLM_CLUSTER_ROW = -1, -2, 16
 MLM_RAY_OCC, MLM_RAY_INFL, MLM_RAY_UNKNOWN = 1, 2, 4
 # mlm_query_views: int64 per row of the table
 MLM_VIEW_ROW = 8
+# mlm_query_boxes flags: what blocks a box (their union; 0: nothing), int64 per row of the table
+MLM_BOX_OCC, MLM_BOX_INFL, MLM_BOX_UNKNOWN, MLM_BOX_ROW = 1, 2, 4, 4
 STATUS = {0: "MLM_OK", -1: "MLM_ERR_INVALID", -2: "MLM_ERR_HIP", -3: "MLM_ERR_CAPACITY", -4: "MLM_ERR_UNSUPPORTED"}
 
 # every symbol include/mlmap_hip.h declares
@@ -46,7 +48,7 @@ ABI_SYMBOLS = [
     "mlm_query_odds", "mlm_query_odd_grad", "mlm_query_odds_at", "mlm_export_frontier_points", "mlm_import_blocks",
     "mlm_merge_pack", "mlm_merge_finish",
     "mlm_set_free_in_bound", "mlm_inflate_map", "mlm_block_count",
-    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_reach", "mlm_export_clusters", "mlm_query_rays", "mlm_query_views", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
+    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_reach", "mlm_export_clusters", "mlm_query_rays", "mlm_query_views", "mlm_query_boxes", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
     "mlm_get_awareness_hits",
     "mlm_get_awareness_misses", "mlm_get_T_ls", "mlm_get_odds_table", "mlm_get_kernel_times",
     "mlm_enable_kernel_timing", "mlm_set_timed_kernel", "mlm_host_register", "mlm_host_unregister", "mlm_debug_set", "mlm_debug_reset",
@@ -145,6 +147,7 @@ def load_library(path: Optional[str] = None):
     L.mlm_export_clusters.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i32, vp]
     L.mlm_query_rays.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.mlm_query_views.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
+    L.mlm_query_boxes.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.mlm_export_global_map.argtypes = [vp, i32, vp, vp]
     L.mlm_export_block_flags.argtypes = [vp, i32, vp, vp]
     L.mlm_export_frontier.argtypes = [vp, i32, vp, vp]
@@ -633,6 +636,60 @@ class MLMap:
         ptr = [None if v is None else ctypes.c_void_p(v) for v in (exclude, mark, table)]
         self._chk(self._L.mlm_query_views(self._h, ctypes.c_void_p(p0), ctypes.c_void_p(p1), ctypes.c_void_p(view_begin), int(n_views),
                                           self._ray_flags(occ, infl, unknown), lo_p, dims_p, *ptr), "mlm_query_views")
+
+    def query_boxes(self, boxes, occ=True, infl=False, unknown=False, max_grow=None, window=None):
+        """Class counts and free-space growth of axis-aligned voxel boxes (mlm_query_boxes).  boxes: n x 6 int32, lo then hi,
+        inclusive voxel indices as export_window — a numpy array (numpy results) or a torch device tensor (torch device results).
+        A box is blocked by voxels that are occ (getOccupancy == OCCUPIED), infl (getInflateOccupancy == OCCUPIED) or unknown
+        (getOccupancy == UNKNOWN), whichever are selected; none selected: nothing blocks.  max_grow: the most layers per face
+        (-x, +x, -y, +y, -z, +z; one int for all six; None: a pure count of the boxes); window = (lo, dims): the box never leaves it.
+        {"status": int8 (1 grown, 0 the box itself is blocked, -1 invalid), "box": int32 (n, 6) the final box, "closed": uint8, bit c
+        set iff face c was closed by an obstacle (clear: by a limit), "table": int64 (n, 4): voxels of the final box, of those
+        UNKNOWN, of those blocking (only at status 0), slabs absorbed}."""
+        mg_p = lo_p = dims_p = None
+        if max_grow is not None:
+            mg = np.ascontiguousarray(np.broadcast_to(np.asarray(max_grow, dtype=np.int64), (6,)))
+            if ((mg < -2 ** 31) | (mg >= 2 ** 31)).any():
+                raise MlmError("query_boxes: max_grow does not fit an int32")
+            mg = mg.astype(np.int32)
+            mg_p = _p(mg)
+        if window is not None:
+            lo_a, dims_a = self._window_args(*window)
+            lo_p, dims_p = _p(lo_a), _p(dims_a)
+        flags = self._ray_flags(occ, infl, unknown)
+        if isinstance(boxes, np.ndarray) or not hasattr(boxes, "data_ptr"):
+            b = np.ascontiguousarray(np.asarray(boxes, dtype=np.int32).reshape(-1, 6))
+            n = b.shape[0]
+            out = {"status": np.empty(n, dtype=np.int8), "box": np.empty((n, 6), dtype=np.int32), "closed": np.empty(n, dtype=np.uint8),
+                   "table": np.empty((n, MLM_BOX_ROW), dtype=np.int64)}
+            ptr = [_p(b)] + [_p(out[k]) for k in ("status", "box", "closed", "table")]
+        else:
+            import torch
+
+            if boxes.dtype != torch.int32 or boxes.numel() % 6 or not boxes.is_contiguous():
+                raise MlmError("query_boxes: a tensor of boxes must be contiguous int32 with 6 words per box")
+            n = boxes.numel() // 6
+            dev = boxes.device
+            out = {"status": torch.empty(n, dtype=torch.int8, device=dev), "box": torch.empty((n, 6), dtype=torch.int32, device=dev),
+                   "closed": torch.empty(n, dtype=torch.uint8, device=dev), "table": torch.empty((n, MLM_BOX_ROW), dtype=torch.int64, device=dev)}
+            ptr = [ctypes.c_void_p(boxes.data_ptr())] + [ctypes.c_void_p(out[k].data_ptr()) for k in ("status", "box", "closed", "table")]
+        self._chk(self._L.mlm_query_boxes(self._h, ptr[0], n, flags, mg_p, lo_p, dims_p, *ptr[1:]), "mlm_query_boxes")
+        return out
+
+    def query_boxes_dev(self, boxes: int, n: int, occ=True, infl=False, unknown=False, max_grow=None, window=None,
+                        status: Optional[int] = None, box: Optional[int] = None, closed: Optional[int] = None, table: Optional[int] = None):
+        """Same on pointers (ints; device or host memory, each on its own): n x 6 int32 boxes, n int8 / n x 6 int32 / n uint8 /
+        n x 4 int64 outputs, None = skipped."""
+        mg_p = lo_p = dims_p = None
+        if max_grow is not None:
+            mg = np.ascontiguousarray(np.broadcast_to(np.asarray(max_grow, dtype=np.int32), (6,)))
+            mg_p = _p(mg)
+        if window is not None:
+            lo_a, dims_a = self._window_args(*window)
+            lo_p, dims_p = _p(lo_a), _p(dims_a)
+        ptr = [None if v is None else ctypes.c_void_p(v) for v in (status, box, closed, table)]
+        self._chk(self._L.mlm_query_boxes(self._h, ctypes.c_void_p(boxes), int(n), self._ray_flags(occ, infl, unknown), mg_p, lo_p, dims_p, *ptr),
+                  "mlm_query_boxes")
 
     @staticmethod
     def _ray_flags(occ, infl, unknown) -> int:

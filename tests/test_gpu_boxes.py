@@ -1,0 +1,314 @@
+"""mlm_query_boxes: class counts and exact free-space growth of voxel boxes (include/mlmap_hip.h), every output held byte for byte to
+the contract written in plain Python integers (tests/box_ref.py) over classes that do not come from the code under test: maps built
+voxel by voxel, and the CPU oracle's block dumps.  Every case runs three ways — a small batch in host memory (the host mirror),
+device tensors for every pointer (the kernel k_boxes), and host memory again after set_host_mirror_limit(0) (the kernel, staged) —
+and all three must give the same bytes."""
+import ctypes
+
+import numpy as np
+import pytest
+
+from mlmapping_amd import synthetic as syn
+from mlmapping_amd.config import S1
+from tests import box_ref as br
+from tests import raywalk_ref as rw
+
+pytestmark = pytest.mark.gpu
+
+OCC, INFL, UNKNOWN = br.OCC, br.INFL, br.UNKNOWN
+D, N = S1.subbox_d_xyz, S1.subbox_n
+BOX_CHUNK = 1 << 18  # boxes per launch when host memory is staged (include/mlmap_hip.h: "82 bytes x 2^18 boxes")
+
+
+@pytest.fixture(scope="module")
+def mods():
+    from mlmapping_amd.mlmap import MLMap
+    from oracle.binding import OracleMap
+
+    return MLMap, OracleMap
+
+
+def crafted(MLMap, obstacles, free_blocks, inflated=()):
+    """obstacle voxels OCCUPIED (and `inflated` voxels inflated-OCCUPIED) in otherwise FREE blocks; everything else UNKNOWN"""
+    obs = np.asarray(obstacles, dtype=np.int64).reshape(-1, 3)
+    inf = np.asarray(inflated, dtype=np.int64).reshape(-1, 3)
+    keys = np.unique(np.concatenate([np.floor_divide(obs, N), np.floor_divide(inf, N), np.asarray(free_blocks, dtype=np.int64).reshape(-1, 3)]), axis=0)
+    occ = np.full((len(keys), N ** 3), ord("f"), dtype=np.uint8)
+    infl = np.full((len(keys), N ** 3), ord("u"), dtype=np.uint8)
+    kidx = {tuple(k): i for i, k in enumerate(keys.tolist())}
+    for arr, plane in ((obs, occ), (inf, infl)):
+        for v in arr:
+            g = np.floor_divide(v, N)
+            c = v - g * N
+            plane[kidx[tuple(g.tolist())], (c[2] * N + c[1]) * N + c[0]] = ord("o")
+    b = {"keys": keys.astype(np.int32), "occ": occ, "infl": infl, "collapsed": np.zeros(len(keys), np.uint8)}
+    gpu = MLMap(S1, max_blocks=4096)
+    gpu.import_blocks(b["keys"], np.zeros(occ.shape, np.float32), occ, infl, b["collapsed"])
+    return gpu, b
+
+
+def kw(flags):
+    return {"occ": bool(flags & OCC), "infl": bool(flags & INFL), "unknown": bool(flags & UNKNOWN)}
+
+
+def to_numpy(out):
+    return {k: (v if isinstance(v, np.ndarray) else v.cpu().numpy()) for k, v in out.items()}
+
+
+def same_bytes(a, b, what=""):
+    for k in br.OUTPUTS:
+        assert np.array_equal(np.ascontiguousarray(a[k]).view(np.uint8), np.ascontiguousarray(b[k]).view(np.uint8)), (what, k)
+
+
+def host_and_device(gpu, boxes, flags, mg, window, expect_mirror=None):
+    """the batch from host memory and from device tensors: the same bytes; returns the host answer"""
+    import torch
+
+    boxes = np.ascontiguousarray(boxes, dtype=np.int32).reshape(-1, 6)
+    before = gpu.frame_stats()["n_host_queries"]
+    host = gpu.query_boxes(boxes, max_grow=mg, window=window, **kw(flags))
+    if expect_mirror is not None:
+        assert (gpu.frame_stats()["n_host_queries"] > before) == expect_mirror, "the batch did not take the expected path"
+    dev = to_numpy(gpu.query_boxes(torch.from_numpy(boxes).cuda(), max_grow=mg, window=window, **kw(flags)))
+    same_bytes(host, dev, ("host / device", flags, mg, window))
+    return host
+
+
+def three_ways(make, cases):
+    """cases: [(boxes, flags, max_grow, window)] on the map make() builds -> (gpu, block dump): mirror and device tensors on one
+    handle, then the kernel with staged host memory on a handle after set_host_mirror_limit(0); everything equal to box_ref.
+    Returns the answers."""
+    gpu, b = make()
+    classes = rw.block_classes(b, N)
+    exp = [br.grow_all(bx, f, classes, mg, w) for bx, f, mg, w in cases]
+    got = []
+    for (bx, f, mg, w), e in zip(cases, exp):
+        g = host_and_device(gpu, bx, f, mg, w, expect_mirror=True)
+        br.assert_equal(g, e, f"mirror flags={f} max_grow={mg} window={w}")
+        got.append(g)
+    gpu.close()
+    gpu, _ = make()
+    gpu.set_host_mirror_limit(0)
+    for (bx, f, mg, w), e in zip(cases, exp):
+        g = host_and_device(gpu, bx, f, mg, w, expect_mirror=False)
+        br.assert_equal(g, e, f"kernel flags={f} max_grow={mg} window={w}")
+    assert gpu.frame_stats()["n_host_queries"] == 0
+    gpu.close()
+    return got
+
+
+def one(res, i=0):
+    return int(res["status"][i]), tuple(int(v) for v in res["box"][i]), int(res["closed"][i]), tuple(int(v) for v in res["table"][i])
+
+
+# ---- answers written by hand --------------------------------------------------------------------------------------------------
+def test_order_dependence_by_hand(mods):
+    """B0 = {(0,0,0)}, the only obstacle at (-1,-1,0), max_grow 3: -x absorbs (-1,0,0) first, then -y is closed by that obstacle"""
+    MLMap, _ = mods
+    free = [(gx, gy, gz) for gx in (-1, 0) for gy in (-1, 0) for gz in (-1, 0)]  # voxels -10 .. 9 on every axis
+    got = three_ways(lambda: crafted(MLMap, [(-1, -1, 0)], free), [([[0, 0, 0, 0, 0, 0]], OCC, [3] * 6, None)])
+    assert one(got[0]) == (1, (-3, 0, -3, 3, 3, 3), 1 << 2, (7 * 4 * 7, 0, 0, 15))
+
+
+ROOM_OBS = [(4, 4, 4), (5, 4, 4), (11, 12, 5)]
+
+
+def room(MLMap):
+    """a FREE room of 20 x 20 x 10 voxels (0 .. 19, 0 .. 19, 0 .. 9) in UNKNOWN (absent) space, three occupied voxels and one inflated"""
+    return crafted(MLMap, ROOM_OBS, [(gx, gy, 0) for gx in (0, 1) for gy in (0, 1)], inflated=[(15, 15, 5)])
+
+
+def test_room_by_hand(mods):
+    MLMap, _ = mods
+    cases = [([[5, 6, 3, 6, 6, 4]], UNKNOWN, [6, 14, 7, 14, 4, 6], None),                      # free room: every face closes at a wall
+             ([[1, 3, 8, 1, 3, 8]], 0, [2, 0, 5, 1, 0, 3], None),               # limits only, into unknown space
+             ([[3, 3, 3, 12, 13, 6]], OCC, [5] * 6, None),                      # blocked start: three occupied voxels, far apart in scan order
+             ([[15, 14, 5, 15, 14, 5]], INFL, 1, None),                         # the inflated voxel blocks with INFL ...
+             ([[15, 14, 5, 15, 14, 5]], OCC, 1, None)]                          # ... and not with OCC
+    got = three_ways(lambda: room(MLMap), cases)
+    assert one(got[0]) == (1, (0, 0, 0, 19, 19, 9), 63, (4000, 0, 0, 5 + 13 + 6 + 13 + 3 + 5))
+    assert one(got[1]) == (1, (-1, -2, 8, 1, 4, 11), 0, (3 * 7 * 4, 3 * 7 * 4 - 2 * 5 * 2, 0, 11))
+    assert one(got[2]) == (0, (3, 3, 3, 12, 13, 6), 0, (10 * 11 * 4, 0, 3, 0))
+    assert one(got[3]) == (1, (14, 13, 4, 16, 14, 6), 1 << 3, (18, 0, 0, 5))
+    assert one(got[4]) == (1, (14, 13, 4, 16, 15, 6), 0, (27, 0, 0, 6))
+
+
+# ---- what the kernel can get wrong ----------------------------------------------------------------------------------------------
+TRAP_OBS = [(3, 3, 2), (-4, -4, -3),       # 8 x 8 slabs (64 voxels) across block edges at 0: the last voxel of the +z slab at z 2, the first of the -z slab at z -3
+            (12, 5, 7), (8, -7, 3),        # 5 x 13 slabs (65): last of +z at z 7, first of -z at z 3; x 8 .. 12 crosses the block edge at 10, y -7 .. 5 the one at 0
+            (-9, 15, 4), (-17, 10, -4)]    # 9 x 9 slabs (81) in x, z: last of +y at y 15, first of -y at y 10; x -17 .. -9 crosses -10, z -4 .. 4 crosses 0
+TRAP_FREE = [(gx, gy, gz) for gx in range(-2, 3) for gy in range(-2, 3) for gz in range(-1, 2)]  # voxels -20 .. 29, -20 .. 29, -10 .. 19
+
+
+def test_slab_sizes_block_edges_negative_coordinates_and_absent_blocks(mods):
+    MLMap, _ = mods
+    make = lambda: crafted(MLMap, TRAP_OBS, TRAP_FREE)
+    z_only, y_only = [0, 0, 0, 0, 3, 3], [0, 0, 3, 3, 0, 0]
+    cases = [([[-4, -4, 0, 3, 3, 0], [8, -7, 5, 12, 5, 5]], OCC, z_only, None),
+             ([[-17, 12, -4, -9, 12, 4]], OCC, y_only, None),
+             ([[-11, -1, -1, -9, 1, 1], [-11, -11, -11, -9, -9, -9]], OCC, 2, None),       # voxels -11 .. -9: across 0 and across the block edge at -10
+             ([[25, 25, -15, 35, 33, -5]], 0, 1, None),                                      # B0 over blocks 2 .. 3, 2 .. 3, -2 .. -1, most of them absent
+             ([[25, 25, -15, 35, 33, -5]], UNKNOWN, 1, None),
+             ([[-4, -4, 0, 3, 3, 0], [-17, 12, -4, -9, 12, 4], [0, 0, 0, 0, 0, 0]], OCC | UNKNOWN, 6, None)]
+    got = three_ways(make, cases)
+    assert one(got[0], 0) == (1, (-4, -4, -2, 3, 3, 1), (1 << 4) | (1 << 5), (8 * 8 * 4, 0, 0, 3))
+    assert one(got[0], 1) == (1, (8, -7, 4, 12, 5, 6), (1 << 4) | (1 << 5), (5 * 13 * 3, 0, 0, 2))
+    assert one(got[1], 0) == (1, (-17, 11, -4, -9, 14, 4), (1 << 2) | (1 << 3), (9 * 4 * 9, 0, 0, 3))
+    assert one(got[3])[3][1] == 13 * 11 * 13 - 6 * 6 * 7 and one(got[3])[0] == 1  # (grown by one: 24 .. 36, 24 .. 34, -16 .. -4; FREE: 24 .. 29, 24 .. 29, -10 .. -4)
+    assert one(got[4]) == (0, (25, 25, -15, 35, 33, -5), 0, (11 * 9 * 11, 11 * 9 * 11 - 5 * 5 * 6, 11 * 9 * 11 - 5 * 5 * 6, 0))
+
+
+COUNT_OBS = [(x, y, z) for x in range(-20, 30, 3) for y in range(-19, 30, 4) for z in range(-10, 20, 3)]  # an occupied voxel every 3 x 4 x 3
+
+
+def test_pure_counts_of_2000_random_boxes(mods):
+    """max_grow NULL on 2 000 small boxes in and around the map (one launch, many boxes per wave), and the first 8 through the mirror"""
+    MLMap, _ = mods
+    gpu, b = crafted(MLMap, TRAP_OBS + COUNT_OBS, TRAP_FREE, inflated=[(1, 2, 3), (-5, -6, -7)])
+    rng = np.random.default_rng(5)
+    a = rng.integers(-26, 32, size=(2000, 3))
+    boxes = np.concatenate([a, a + rng.integers(0, 6, size=(2000, 3))], axis=1).astype(np.int32)
+    classes = rw.block_classes(b, N)
+    for f in (OCC, OCC | INFL | UNKNOWN):
+        exp = br.grow_all(boxes, f, classes)
+        assert (exp["status"] == 0).sum() > 200 and (exp["status"] == 1).sum() > 200 and (exp["table"][:, 1] > 0).sum() > 200
+        br.assert_equal(host_and_device(gpu, boxes, f, None, None, expect_mirror=False), exp, f"pure counts flags={f}")
+        br.assert_equal(host_and_device(gpu, boxes[:8], f, None, None, expect_mirror=True), {k: v[:8] for k, v in exp.items()}, "mirror")
+    long = [[0, 0, 0, 0, 2 ** 15 - 1, 0]]  # the longest valid side: y 0 .. 29 FREE, the rest UNKNOWN
+    exp = br.grow_all(long, 0, classes)
+    assert one(exp) == (1, (0, 0, 0, 0, 2 ** 15 - 1, 0), 0, (2 ** 15, 2 ** 15 - 30, 0, 0))
+    br.assert_equal(host_and_device(gpu, long, 0, None, None), exp, "longest side")
+    gpu.close()
+
+
+# ---- limits -------------------------------------------------------------------------------------------------------------------
+def test_window_int32_edges_and_invalid_items(mods):
+    MLMap, _ = mods
+    lo, hi = br.I32_MIN, br.I32_MAX
+    W = ([-6, -3, -2], [14, 9, 7])  # voxels -6 .. 7, -3 .. 5, -2 .. 4
+    cases = [([[0, 0, 0, 1, 1, 1], [-6, -3, -2, 7, 5, 4], [-7, 0, 0, -6, 0, 0], [0, 0, 0, 0, 6, 0], [20, 20, 20, 20, 20, 20]], OCC, 4096, W),
+             ([[lo, 0, 0, lo + 1, 0, 0], [0, hi, 0, 0, hi, 0], [lo, lo, lo, lo, lo, lo], [hi - 2, hi - 1, hi, hi - 1, hi, hi]], OCC, 2, None),
+             ([[3, 0, 0, 2, 0, 0], [0, 0, 5, 0, 0, 4], [0, 0, 0, 2 ** 15, 0, 0], [0, 0, 0, 0, 0, 0]], 0, None, None)]
+    got = three_ways(lambda: crafted(MLMap, [(30, 30, 30)], TRAP_FREE), cases)
+    assert one(got[0], 0) == (1, (-6, -3, -2, 7, 5, 4), 0, (14 * 9 * 7, 0, 0, 6 + 6 + 3 + 4 + 2 + 3))  # growth stops at each face of W
+    assert one(got[0], 1) == (1, (-6, -3, -2, 7, 5, 4), 0, (14 * 9 * 7, 0, 0, 0))
+    assert [one(got[0], i)[0] for i in (2, 3, 4)] == [-1, -1, -1]  # B0 not inside W
+    assert one(got[0], 2) == (-1, (-7, 0, 0, -6, 0, 0), 0, (0, 0, 0, 0))
+    assert one(got[1], 0) == (1, (lo, -2, -2, lo + 3, 2, 2), 0, (4 * 5 * 5, 4 * 5 * 5, 0, 2 + 4 * 2))  # no wrap at the int32 edges
+    assert one(got[1], 1) == (1, (-2, hi - 2, -2, 2, hi, 2), 0, (5 * 3 * 5, 5 * 3 * 5, 0, 2 + 4 * 2))
+    assert one(got[1], 2) == (1, (lo, lo, lo, lo + 2, lo + 2, lo + 2), 0, (27, 27, 0, 6))
+    assert one(got[1], 3) == (1, (hi - 4, hi - 3, hi - 2, hi, hi, hi), 0, (5 * 4 * 3, 5 * 4 * 3, 0, 2 + 1 + 2 + 2))
+    assert [one(got[2], i)[0] for i in range(4)] == [-1, -1, -1, 1]
+    assert one(got[2], 0) == (-1, (3, 0, 0, 2, 0, 0), 0, (0, 0, 0, 0)) and one(got[2], 2) == (-1, (0, 0, 0, 2 ** 15, 0, 0), 0, (0, 0, 0, 0))
+
+
+# ---- map forms ----------------------------------------------------------------------------------------------------------------
+def seeds_and_boxes(b, n, seed, n_seeds, n_boxes):
+    rng = np.random.default_rng(seed)
+    lo, hi = b["keys"].min(0) * n - 3, (b["keys"].max(0) + 1) * n + 3
+    vox = rng.integers(lo, hi, size=(60000, 3))
+    free = vox[rw.block_classes(b, n)(vox) == 0][:n_seeds]
+    assert len(free) == n_seeds
+    a = rng.integers(lo, hi, size=(n_boxes, 3))
+    return np.concatenate([np.concatenate([free, free], axis=1), np.concatenate([a, a + rng.integers(0, 4, size=(n_boxes, 3))], axis=1)]).astype(np.int32)
+
+
+def test_frontier_map_with_released_blocks_against_the_oracle(mods):
+    MLMap, OracleMap = mods
+    cfg = S1.with_(use_exploration_frontiers=True, subbox_n=5)
+    gpu, cpu = MLMap(cfg, max_blocks=16384, max_batch=2), OracleMap(cfg)
+    for img, (q, t) in syn.stream(cfg, "room_jitter", "smooth", 8):
+        gpu.update_map(img, q, t)
+        cpu.update_depth(img, q, t)
+    b = cpu.export_blocks()
+    assert b["collapsed"].sum() > 20
+    classes = rw.block_classes(b, cfg.subbox_n)
+    boxes = seeds_and_boxes(b, cfg.subbox_n, 7, 120, 80)
+    grown = 0
+    for f in br.FLAG_SETS:
+        exp = br.grow_all(boxes, f, classes, [8] * 6)
+        grown += int(exp["table"][:, 3].sum())
+        br.assert_equal(host_and_device(gpu, boxes, f, 8, None, expect_mirror=False), exp, f"frontier flags={f}")
+        br.assert_equal(host_and_device(gpu, boxes[:3], f, 8, None), {k: v[:3] for k, v in exp.items()}, f"frontier, small batch flags={f}")
+    assert grown > 5000
+    gpu.close()
+
+
+def test_async_mode_observes_the_map(mods):
+    """after mlm_integrate_depth_batch in async mode, without sync(): the boxes see every submitted frame"""
+    MLMap, OracleMap = mods
+    nf = 8
+    frames = np.stack([img for img, _ in syn.stream(S1, "room_jitter", "smooth", nf)])
+    poses = syn.smooth_trajectory(nf, 42)
+    q, t = np.stack([p[0] for p in poses]), np.stack([p[1] for p in poses])
+    gpu, cpu = MLMap(S1, max_blocks=8192, max_batch=4), OracleMap(S1)
+    for k in range(nf):
+        cpu.update_depth(frames[k], q[k], t[k])
+    b = cpu.export_blocks()
+    boxes = seeds_and_boxes(b, N, 3, 60, 40)
+    exp = br.grow_all(boxes, OCC | UNKNOWN, rw.block_classes(b, N), [5] * 6)
+    assert exp["table"][:, 3].sum() > 500
+    gpu.set_async(True)
+    gpu.update_map_batch(frames, q, t)  # no sync()
+    before = gpu.frame_stats()["device_bytes"]
+    br.assert_equal(gpu.query_boxes(boxes, occ=True, unknown=True, max_grow=5), exp, "async")
+    grown = gpu.frame_stats()["device_bytes"]
+    assert grown >= before
+    br.assert_equal(host_and_device(gpu, boxes, OCC | UNKNOWN, 5, None), exp, "async, again")
+    assert gpu.frame_stats()["device_bytes"] == grown  # (the staging is kept)
+    gpu.close()
+
+
+# ---- chunks -------------------------------------------------------------------------------------------------------------------
+def test_chunk_seam(mods):
+    """chunk size + 3 single-voxel boxes from host memory, max_grow NULL: the rows around the seam and the last rows"""
+    MLMap, _ = mods
+    gpu, b = room(MLMap)
+    n = BOX_CHUNK + 3
+    rng = np.random.default_rng(9)
+    a = rng.integers(-4, 24, size=(n, 3)).astype(np.int32)
+    boxes = np.concatenate([a, a], axis=1)
+    before = gpu.frame_stats()["device_bytes"]
+    got = gpu.query_boxes(boxes, occ=True, unknown=True)
+    assert gpu.frame_stats()["device_bytes"] - before >= 82 * BOX_CHUNK  # (the staging of one chunk is counted)
+    pick = np.r_[0:4, BOX_CHUNK - 4:n]  # the first rows, the last four of the first chunk, the three of the second
+    exp = br.grow_all(boxes[pick], OCC | UNKNOWN, rw.block_classes(b, N))
+    br.assert_equal({k: v[pick] for k, v in got.items()}, exp, "seam")
+    inside = ((a >= 0) & (a < [20, 20, 10])).all(axis=1)  # every row: outside the room UNKNOWN blocks, inside only the three occupied voxels
+    blocked = ~inside | (a[:, None, :] == np.array(ROOM_OBS)[None]).all(axis=2).any(axis=1)
+    assert np.array_equal(got["status"], np.where(blocked, 0, 1).astype(np.int8)) and np.array_equal(got["box"], boxes)
+    gpu.close()
+
+
+# ---- arguments ----------------------------------------------------------------------------------------------------------------
+def test_arguments_and_single_outputs(mods, knobs):
+    MLMap, _ = mods
+    for mirror in (1, 0):
+        knobs.set("mirror", mirror)
+        gpu, _ = room(MLMap)
+        L, h = gpu._L, gpu._h
+        P = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+        boxes = np.array([[5, 6, 3, 6, 6, 4], [3, 0, 0, 2, 0, 0], [3, 3, 3, 12, 13, 6]], dtype=np.int32)
+        mg, wlo, wd = np.full(6, 3, np.int32), np.array([0, 0, 0], np.int32), np.array([20, 20, 10], np.int32)
+        outs = [np.zeros(3, np.int8), np.zeros((3, 6), np.int32), np.zeros(3, np.uint8), np.zeros((3, 4), np.int64)]
+        call = lambda bx=boxes, n=3, f=OCC, g=mg, l=wlo, d=wd, o=outs: L.mlm_query_boxes(h, P(bx), n, f, P(g), P(l), P(d), *[P(x) for x in o])
+        bad_grow = [mg.copy(), mg.copy()]
+        bad_grow[0][2], bad_grow[1][5] = -1, 4097
+        for bad in (lambda: call(n=-1), lambda: call(bx=None), lambda: call(f=8), lambda: call(f=-1), lambda: call(f=OCC | 1 << 20),
+                    lambda: call(g=bad_grow[0]), lambda: call(g=bad_grow[1]), lambda: call(l=None), lambda: call(d=None),
+                    lambda: call(d=np.array([20, 0, 10], np.int32)), lambda: call(l=np.array([2 ** 31 - 5, 0, 0], np.int32)),
+                    lambda: call(d=np.array([2048, 2048, 1024], np.int32)), lambda: call(o=[None] * 4)):
+            assert bad() == -1
+            assert call() == 0  # (the handle is usable afterwards)
+        assert call(bx=None, n=0) == 0  # n == 0
+        assert call() == 0
+        assert outs[0].tolist() == [1, -1, 0] and outs[1].tolist() == [[2, 5, 0, 9, 9, 7], [3, 0, 0, 2, 0, 0], [3, 3, 3, 12, 13, 6]]  # (-y stops in front of (4,4,4))
+        assert outs[2].tolist() == [1 << 2, 0, 0] and outs[3].tolist() == [[8 * 5 * 8, 0, 0, 16], [0, 0, 0, 0], [440, 0, 3, 0]]
+        full = [o.copy() for o in outs]
+        for k in range(4):  # only one output, each in turn
+            outs[k][...] = 9
+            assert call(o=[outs[j] if j == k else None for j in range(4)]) == 0
+            assert np.array_equal(outs[k], full[k]), k
+        assert call(g=None, l=None, d=None) == 0  # max_grow NULL, no window: a pure count
+        assert outs[1].tolist() == boxes.tolist() and outs[3][0].tolist() == [4, 0, 0, 0]
+        gpu.close()
