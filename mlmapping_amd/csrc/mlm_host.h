@@ -474,6 +474,17 @@ inline void div_magic(unsigned int d, unsigned long long &m, int &s) {
     m = ((1ull << s) + d - 1) / d;
 }
 
+// exact floor(i / d) for i < 2^20 (STRIP_MAGIC_MAX_I) and 1 <= d <= 2^11 (STRIP_MAGIC_MAX_D) as the high 32 bits of (2 i) * m,
+// m = ceil(2^31 / d) <= 2^31: with m d = 2^31 + e, 0 <= e < d, and i = q d + r, (i m) / 2^31 = q + (r + i e / 2^31) / d, and
+// i e < 2^20 * 2^11 = 2^31 keeps the bracket below r + 1 <= d.  (k_bin_sectors: a strip's row in the image, d = strips per row — a dense
+// image of the sector path is at most MLM_SEC_MAX_WIDTH = 65 528 pixels wide, 2 048 strips, and has fewer than 2^15 strips,
+// MlmDev::nb_cap with mlm_limits.max_points < 2^21.)  0: d is out of range.
+constexpr unsigned int STRIP_MAGIC_MAX_I = 1u << 20, STRIP_MAGIC_MAX_D = 1u << 11;
+inline uint32_t strip_magic(unsigned int d) {
+    if (d < 1u || d > STRIP_MAGIC_MAX_D) return 0u;
+    return (uint32_t)(((1ull << 31) + d - 1) / d);
+}
+
 // Replay the rehash policy of libstdc++'s _Hashtable for `U` unique insertions into a cleared container.
 // Returns the epochs: (number of elements present when the epoch ends, bucket count during the epoch).
 // Uses the very policy object std::unordered_map uses, so it follows whatever libstdc++ this library is linked to.

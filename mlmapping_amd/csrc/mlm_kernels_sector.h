@@ -140,20 +140,29 @@ __device__ __forceinline__ void mlm_sector_fail(const MlmDev &P, const MlmFrame 
 
 // work item of thread `threadIdx.x` in strip `strip` of the frame (mlm_tile_item with the strip index instead of blockIdx.x):
 // dense images are cut into strips of 32 x 8 pixels (a wave = an 8x8 tile), lists into runs of 256 items
-template <int MODE> __device__ __forceinline__ MlmTile mlm_strip_item(const MlmFrame &F, unsigned int strip) {
-    MlmTile t;
+struct MlmStripItem {
+    int i;           // work item (pixel index py * width + px / list position / point index)
+    bool valid;
+    int px, py;      // dense images: the pixel's column and row
+    uint32_t by, bx; // dense images: the strip's row and column in the image (the same for the whole workgroup)
+};
+template <int MODE> __device__ __forceinline__ MlmStripItem mlm_strip_item(const MlmFrame &F, unsigned int strip) {
+    MlmStripItem t;
     if (MODE == 0) {
-        const int tiles_x = (F.width + 31) >> 5;
-        const int by = (int)strip / tiles_x;
-        const int bx = (int)strip - by * tiles_x;
+        // strip / tiles_x without a division: the high word of (2 strip) * tx_m (mlm_host.h: strip_magic; strip < 2^20, tiles_x <= 2^11)
+        const uint32_t tiles_x = ((uint32_t)F.width + 31u) >> 5;
+        t.by = __umulhi(strip << 1, F.tx_m);
+        t.bx = strip - t.by * tiles_x;
         const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-        const int px = bx * 32 + (w & 3) * 8 + (l & 7);
-        const int py = by * 8 + (l >> 3);
-        t.valid = px < F.width && py < F.height;
-        t.i = py * F.width + px;
+        t.px = (int)t.bx * 32 + (w & 3) * 8 + (l & 7);
+        t.py = (int)t.by * 8 + (l >> 3);
+        t.valid = t.px < F.width && t.py < F.height;
+        t.i = t.py * F.width + t.px;
     } else {
         t.i = (int)(strip * 256u + threadIdx.x);
         t.valid = t.i < F.n;
+        t.px = t.py = 0;
+        t.by = t.bx = 0u;
     }
     return t;
 }
@@ -183,9 +192,11 @@ __device__ __forceinline__ void mlm_bin_sectors_body(const MlmDev &P, const MlmF
     bool have[S];
     double xs[S], ys[S], zs[S];
     uint16_t raw[S];
+    uint32_t tile_yx[S]; // dense images: the strip's row << MLM_REC_XT_BITS | 8-pixel column of its first wave (a record's tile origin)
 #pragma unroll
     for (int j = 0; j < S; ++j) {
-        MlmTile T = mlm_strip_item<MODE>(F, strip0 + (unsigned int)j);
+        MlmStripItem T = mlm_strip_item<MODE>(F, strip0 + (unsigned int)j);
+        tile_yx[j] = (T.by << MLM_REC_XT_BITS) | (T.bx * 4u);
         if (strip0 + (unsigned int)j >= n_strips) T.valid = false;
         item[j] = T.i;
         have[j] = T.valid;
@@ -197,9 +208,10 @@ __device__ __forceinline__ void mlm_bin_sectors_body(const MlmDev &P, const MlmF
                 ys[j] = mlm_gp(F.pts)[3 * (size_t)T.i + 1];
                 zs[j] = mlm_gp(F.pts)[3 * (size_t)T.i + 2];
             } else {
+                // (dense images: column and row come from the strip's place in the image; a list's pixel index has to be divided)
                 const int pix = (MODE == 1) ? (pre ? pre_pix : mlm_gp(F.pix)[T.i]) : T.i;
-                const int v = pix / F.width;
-                const int u = pix - v * F.width;
+                const int v = MODE == 0 ? T.py : pix / F.width;
+                const int u = MODE == 0 ? T.px : pix - v * F.width;
                 raw[j] = (MODE == 1 && pre) ? (uint16_t)pre_raw : (MODE == 1 && F.raw) ? (uint16_t)mlm_gp(F.raw)[T.i] : mlm_gp(F.img)[(size_t)v * F.row_stride + u];
                 // mlmap.cpp:329,344-346: (size_t u - float cx_) is a float subtraction, the rest is double (the depth factor below)
                 xs[j] = (double)((float)u - P.cx);
@@ -278,11 +290,7 @@ __device__ __forceinline__ void mlm_bin_sectors_body(const MlmDev &P, const MlmF
         rec_cell[j] = leader ? (uint32_t)zi << 16 | (uint32_t)rho : (MLM_SEC_OUTER | (uint32_t)rho); // (hit records: z and rho of the centre cell, nRho * nZ < 65 536)
         // hit records carry their tile's origin (MLM_REC_XT_BITS; list modes: 64 items = one row) for k_rank
         uint32_t yx = i00 >> 6 << 11;
-        if (MODE == 0) { // (from the strip's place in the image: nothing is divided per wave)
-            const uint32_t tiles_x = ((uint32_t)F.width + 31u) >> 5, strip = strip0 + (uint32_t)j;
-            const uint32_t by = strip / tiles_x, bx = strip - by * tiles_x;
-            yx = (by << MLM_REC_XT_BITS) | (bx * 4u + (uint32_t)wid);
-        }
+        if (MODE == 0) yx = tile_yx[j] + (uint32_t)wid; // (from the strip's place in the image, mlm_strip_item: bx * 4 + wid < 2^MLM_REC_XT_BITS)
         // a record is 16 bytes (MlmSecRec).  Hit: centre cell z << 16 | rho, tile origin yx, lane mask (the wave's first work item
         // follows from yx: y0 * width + x0, lists (yx >> 11) << 6).  Ray of a point outside the map: MLM_SEC_OUTER | rho, z, and in the
         // mask's place its first point (the leader's own work item: frontier mode orders miss cells by it)

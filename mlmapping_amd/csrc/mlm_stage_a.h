@@ -30,6 +30,18 @@ void frame_setup(const mlm_handle *h, const double q_wb_in[4], const double t_wb
     F.lv_o[2] = (int)std::floor((F.t_wa[2] + P.z_border_min) / P.d_sub) - 4;
 }
 
+// the image of a depth frame: its geometry and what the kernels derive from it once per frame instead of once per workgroup
+// (tx_m's range: a frame takes the sector path only if its image is at most MLM_SEC_MAX_WIDTH wide — submit_batch, single_fast_ok,
+// explore_submit — and has at most MlmDev::nb_cap = max_points / 128 + 256 strips, max_points < 2^MLM_SEC_CNT_BITS on that path)
+static_assert((MLM_SEC_MAX_WIDTH + 31) / 32 <= (int)STRIP_MAGIC_MAX_D, "strips per row of the widest image of the sector path");
+static_assert((1u << MLM_SEC_CNT_BITS) / 128u + 256u <= STRIP_MAGIC_MAX_I, "strips of the largest frame of the sector path");
+void frame_image(MlmFrame &F, int width, int height, int row_stride) {
+    F.width = width;
+    F.height = height;
+    F.row_stride = row_stride;
+    F.tx_m = strip_magic(((unsigned int)width + 31u) / 32u); // (0 for an image wider than the sector path takes: launch_stage_a_sector)
+}
+
 std::vector<std::pair<size_t, size_t>> plan_epochs(mlm_handle *h, size_t U) {
     return plan_epochs_for(h->hit_pol, h->hit_n_bkt, U);
 }

@@ -304,7 +304,8 @@ struct MlmFrame {
     int lv_o[3];           // origin of the frame-local voxel grid (MlmDev::lv_state) in voxel coordinates
     int pad2;                  // frontier mode: running frame number (test hook MLM_SEC_FAIL_EVERY; seq stays 0 there)
     int flags;                 // sector path, k_apply_tiles: MLM_FRAME_EXACT_KEYS | MLM_FRAME_SKIP
-    int pad3;
+    uint32_t tx_m;             // dense images, k_bin_sectors: strip / tiles_x (tiles_x = ceil(width / 32)) is the high word of (2 strip) * tx_m,
+                               // exact for strip < 2^20 and tiles_x <= 2^11 (mlm_host.h: strip_magic; 0: no such multiplier, wider image)
     // k_bin_sectors' cheap evaluation (mlm_bin_point_fast): the linear map of QuaternionBase::_transformVector for q_ls as a matrix
     // (I + 2 w [q]x + 2 [q]x^2, row major; exact for any q, unit or not), its gain 1 + 2 |w| |q_v|_1 + 2 |q_v|_1^2 (bound of the
     // intermediates per unit |v|), and |t_ls|_1 + 1

@@ -656,9 +656,7 @@ int mlm_integrate_depth_batch_dev(mlm_handle *h, const uint16_t *img_dev, int n_
             S.F = MlmFrame{};
             frame_setup(h, q_wb + 4 * (size_t)(k0 + j), t_wb + 3 * (size_t)(k0 + j), S.F);
             S.F.img = img_dev + (size_t)(k0 + j) * frame_stride;
-            S.F.width = width;
-            S.F.height = height;
-            S.F.row_stride = row_stride;
+            frame_image(S.F, width, height, row_stride);
             S.F.n = width * height;
             S.mode = 0;
         }
@@ -711,9 +709,7 @@ int mlm_integrate_depth_batch(mlm_handle *h, const uint16_t *img_host, int n_fra
             S.F = MlmFrame{};
             frame_setup(h, q_wb + 4 * (size_t)(k0 + j), t_wb + 3 * (size_t)(k0 + j), S.F);
             S.F.img = packed ? h->d_img_set[set] + (size_t)j * n_px : S.d_img;
-            S.F.width = width;
-            S.F.height = height;
-            S.F.row_stride = row_stride;
+            frame_image(S.F, width, height, row_stride);
             S.F.n = width * height;
             S.mode = 0;
         }
@@ -754,9 +750,7 @@ static int integrate_u16_dev(mlm_handle *h, const uint16_t *img_dev, int width, 
     S.F.img = img_dev;
     S.F.pix = pixel_idx_dev;
     S.F.raw = pixel_idx_dev ? raw_dev : nullptr;
-    S.F.width = width;
-    S.F.height = height;
-    S.F.row_stride = row_stride;
+    frame_image(S.F, width, height, row_stride);
     S.F.n = (int)n;
     S.mode = pixel_idx_dev ? 1 : 0;
     return run_slots(h, 1);
