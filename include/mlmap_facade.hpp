@@ -235,6 +235,17 @@ class mlmap {
         check(mlm_export_reach(h_, lo, dims, seeds3, n_seeds, flags, clearance, max_steps, steps, parent, summary), "mlm_export_reach");
     }
 
+    // clearance-weighted cost field with face / edge / corner moves through the free space of a voxel box (mlm_export_route; flags
+    // MLM_ROUTE_*; connectivity 6 / 18 / 26; move_cost[3] and penalty[n_penalty] host memory; cost / parent host or device memory,
+    // summary host memory, NULL = skipped)
+    void exportRoute(const int32_t lo[3], const int32_t dims[3], const int32_t *seeds3, int n_seeds, int flags, int clearance, int connectivity,
+                     const int32_t move_cost[3], const int32_t *penalty, int n_penalty, int max_cost, int32_t *cost, uint8_t *parent = nullptr,
+                     int64_t summary[4] = nullptr) {
+        check(mlm_export_route(h_, lo, dims, seeds3, n_seeds, flags, clearance, connectivity, move_cost, penalty, n_penalty, max_cost, cost, parent,
+                               summary),
+              "mlm_export_route");
+    }
+
     // connected components of a voxel set of a box with per-component statistics (mlm_export_clusters; flags MLM_CLUSTER_*;
     // connectivity 6 / 18 / 26; labels / table host or device memory, table [cap][MLM_CLUSTER_ROW], summary host memory, NULL = skipped)
     void exportClusters(const int32_t lo[3], const int32_t dims[3], int flags, int connectivity, int min_size, int32_t *labels,

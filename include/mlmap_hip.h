@@ -419,6 +419,55 @@ int mlm_query_boxes(mlm_handle *h, const int32_t *box6, int n, int flags, const 
 #define MLM_REACH_SEED 6    /* parent code of a seed */
 int mlm_export_reach(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], const int32_t *seeds3, int n_seeds,
                      int flags, int clearance, int max_steps, int32_t *steps, uint8_t *parent, int64_t summary[4]);
+/* Clearance-weighted cost field through the free space of a box of voxels, with face, edge and corner moves (no reference
+ * counterpart: the reference has no such field; it is defined here, in integers).  What a planner with diagonal moves and a soft
+ * clearance cost searches on: mlm_export_reach's paths are Manhattan staircases that hug obstacles at exactly `clearance` voxels.
+ * Window, layout, voxel indices, the obstacle predicate O(v) of `flags`, the clearance r (v is BLOCKED iff D_out(v) <= r^2, looked
+ * up in the whole map), traversable voxels, the domain (the box: a path never leaves it) and the seeds (host or device memory; one
+ * outside the box or on a blocked voxel contributes nothing; duplicates allowed) are those of mlm_export_reach.
+ *   Moves: connectivity 6, 18 or 26 — the offsets of {-1, 0, 1}^3 with one, at most two, at most three non-zero entries, as in
+ *   mlm_export_clusters.  A move by offset o from u to v = u + o costs move_cost[nnz(o) - 1] (host memory, each entry in 1..65535;
+ *   entries of move kinds the connectivity excludes are ignored).  It is permitted iff u and v are traversable voxels of the box
+ *   and so is u + o' for every o' obtained from o by zeroing a non-empty proper subset of its non-zero entries: an edge move needs
+ *   its two face-adjacent intermediates, a corner move its six intermediates (no corner cutting; that is the whole rule, and it is
+ *   symmetric in u and v).  Voxels outside the box count as blocked.
+ *   Soft clearance: penalty (host memory) has n_penalty >= 0 entries, each in 0..65535, clearance + n_penalty <= 63; NULL iff
+ *   n_penalty == 0.  The ring k(v) of a traversable v is the smallest k >= 0 with D_out(v) <= (r + 1 + k)^2; pen(v) = penalty[k(v)]
+ *   if k(v) < n_penalty, else 0.  D_out is mlm_export_esdf's, computed by the same passes at max_dist = r + n_penalty + 1, so every
+ *   threshold lies strictly below the truncation; with n_penalty == 0 the blocked mask is obtained exactly as mlm_export_reach
+ *   obtains it.
+ *   cost   int32  the cost of a path v0 ... vk of permitted moves from an effective seed v0 is the sum over i = 1..k of
+ *                 move_cost(move i) + pen(v_i) (a seed costs 0 and pays no penalty for its own voxel); cost(v) is the minimum over
+ *                 all such paths from all effective seeds; MLM_ROUTE_NONE if v is not traversable, if there is no path, or if
+ *                 the minimum exceeds max_cost (1 <= max_cost <= 2^31 - 1; values <= max_cost are what they are without the
+ *                 truncation)
+ *   parent uint8  at a reached voxel that is no seed the lowest code c such that the move from u = v + o_c to v is permitted and
+ *                 cost(u) + move_cost + pen(v) == cost(v); MLM_ROUTE_SEED at effective seeds; 255 where cost is MLM_ROUTE_NONE.
+ *                 Codes 0..5 are mlm_export_reach's (-x, +x, -y, +y, -z, +z); 6..17 the twelve offsets with two non-zero entries
+ *                 in ascending lexicographic order of (dz, dy, dx): 6 is (dx, dy, dz) = (0, -1, -1), 10 is (-1, -1, 0), 17 is
+ *                 (0, 1, 1); 18..25 the eight corners in the same order: 18 is (-1, -1, -1), 25 is (1, 1, 1).  Face moves win ties.
+ *                 Following parent from a reached voxel walks one optimal path to a seed.
+ *   summary int64 x 4 (host memory): [0] traversable voxels of the box, [1] reached voxels, [2] the largest cost written (-1:
+ *                 none), [3] relaxation sweeps the call needed (informative: depends on the tile geometry).
+ * cost and parent may be host or device memory; any of the three outputs may be NULL, at least one must not be.  The field is the
+ * least fixpoint of cost(v) = min(cost(v), cost(u) + move_cost + pen(v)) over permitted moves, so it has exactly one value
+ * whatever the schedule.  With connectivity 6, move_cost[0] == 1, n_penalty == 0 and max_cost == max_steps, cost and parent equal
+ * mlm_export_reach's steps and parent, with the seed code MLM_ROUTE_SEED (26) in place of MLM_REACH_SEED (6).  Streams, async
+ * mode and mlm_frame_stats.device_bytes as for mlm_export_reach, whose scratch the call shares.  MLM_ERR_INVALID:
+ * mlm_export_reach's window, seed and flag errors, clearance outside [0, 63], connectivity other than 6 / 18 / 26, move_cost NULL
+ * or an entry out of range, n_penalty < 0, clearance + n_penalty > 63, penalty NULL with n_penalty > 0 or an entry out of range,
+ * max_cost < 1, no output.  MLM_ERR_CAPACITY: as for mlm_export_reach — the whole box is resident, 4 bytes of cost and one class
+ * byte per voxel, two dirty bytes per tile (plus the ESDF scratch with clearance + n_penalty > 0 and a staging copy of host
+ * outputs).  The handle stays usable after either error. */
+#define MLM_ROUTE_OCC 1 /* same bits and meaning as MLM_REACH_* */
+#define MLM_ROUTE_INFL 2
+#define MLM_ROUTE_UNKNOWN 4
+#define MLM_ROUTE_NONE (-1) /* cost of a voxel that is not reached */
+#define MLM_ROUTE_SEED 26   /* parent code of an effective seed */
+int mlm_export_route(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], const int32_t *seeds3, int n_seeds,
+                     int flags, int clearance, int connectivity, const int32_t move_cost[3],
+                     const int32_t *penalty, int n_penalty, int max_cost,
+                     int32_t *cost, uint8_t *parent, int64_t summary[4]);
 /* Connected components of a voxel set of a box, with per-component statistics (no reference counterpart: the reference has no
  * clustering, its visualiser publishes the frontier cloud raw; the classes behind the set are those of its point queries, set,
  * components and numbering are defined here, in integers).  Voxel indices, window, layout ([dims[2]][dims[1]][dims[0]], x

@@ -26,7 +26,7 @@ struct KernelTime {
 // switches MLM_DEBUG_CREATE / MLM_DEBUG_ALLOC / MLM_DEBUG_DRAIN, which print).
 const char *const kKnobNames[] = {"agg_lds", "big_arm", "big_grid", "bin_block", "chain_grid", "cluster_tile", "collect_grid", "cu_reserve", "cu_split",
                                   "esdf_tile_vox", "ex_spec", "expand_block", "graph", "logit_exact", "mirror", "mirror_max", "mirror_mb", "need_slots", "node_lds", "pool_grow",
-                                  "rank_grid", "rays_grid", "reach_group", "reach_tile", "sc_block", "sc_grid", "sec_backoff", "sec_fail_every", "sec_tab", "sec_tab_big", "sec_threads",
+                                  "rank_grid", "rays_grid", "reach_group", "reach_tile", "route_group", "route_tile", "sc_block", "sc_grid", "sec_backoff", "sec_fail_every", "sec_tab", "sec_tab_big", "sec_threads",
                                   "sectors", "single_apply_grid", "single_chain_grid", "single_rank_grid", "slot_sets", "sort_block", "sort_grid", "tile_grid", "tile_sh", "view_lds_bits"};
 struct KnobStore {
     std::mutex mu;
@@ -51,6 +51,8 @@ bool knob_value_ok(const char *name, long long v) {
     if (is("esdf_tile_vox")) return v >= kEsdfMinBoxVoxels && v <= kEsdfBoxVoxels; // (mlm_esdf_plan fits every call's tile then)
     if (is("cluster_tile")) return mlm_reach_tile_ok(v); // (packed like reach_tile; the tile's labels within k_cluster_local's LDS)
     if (is("reach_tile")) return mlm_reach_tile_ok(v);  // (x | y << 8 | z << 16, edges 1..64, tile + halo within k_reach_sweep's LDS)
+    if (is("route_tile")) return mlm_reach_tile_ok(v);  // (packed like reach_tile; mlm_route_plan: the LDS of k_route_sweep)
+    if (is("route_group")) return v >= 1 && v <= kReachGroupMax; // (as reach_group)
     if (is("view_lds_bits")) return v >= 0 && v <= kViewLdsBits; // (larger bitsets go to global scratch; 0: all of them)
     if (is("reach_group")) return v >= 1 && v <= kReachGroupMax; // (sweeps between two looks at the "marked" words)
     return true;

@@ -211,6 +211,51 @@ inline MlmReachPlan mlm_reach_plan(const long long D[3], long long tile_packed, 
     return p;
 }
 
+// Geometry, scratch and sweep cap of mlm_export_route (mlm_kernels_route.h, mlm_route.h): the box is cut as mlm_reach_plan cuts it
+// (knob "route_tile", same packing, same validity rule; knob "route_group": sweeps between two looks at the "marked" words, as
+// "reach_group") and the scratch is laid out as mlm_reach_plan lays it out, the mask byte being the voxel's class byte (its ring,
+// 255: blocked) and the control block holding, behind the "marked" words and the counters, the 64 words of the penalty table at
+// kRoutePenOffset.  A workgroup of k_route_sweep stages the tile and its full one-voxel halo as u32 in LDS and, beside it, the
+// entry penalty of every voxel of the tile as u16: lds_bytes = 4 * (T0 + 2)(T1 + 2)(T2 + 2) + 2 * T0 T1 T2, 17 696 B for the
+// default tile (nine workgroups per CU by LDS), below 61 440 + 30 720 B for every valid tile (the tile holds fewer voxels than
+// its halo box; beyond 64 KB the host raises the kernel's dynamic LDS limit, one workgroup per CU then).  cap: voxels + 1
+// sweeps (mlm_route.h: an optimal path crosses at most voxels - 1 tile boundaries, one sweep per crossing, one for the seeds'
+// tiles, one that marks nothing), rounded up to whole groups by the host loop.  ok == false: what mlm_reach_plan refuses of tile,
+// box and seeds.
+constexpr long long kRouteTileDefault = kReachTileDefault, kRouteGroupDefault = kReachGroupDefault;
+constexpr long long kRoutePenOffset = 1280, kRoutePenWords = 64; // (within kReachCtrlBytes, behind kReachGroupMax words and the counters)
+struct MlmRoutePlan {
+    bool ok;
+    long long T[3], n[3], tiles, voxels;
+    long long field_bytes, class_bytes, dirty_bytes, seed_bytes; // (dirty_bytes: one of the two arrays)
+    long long off_class, off_dirty, off_ctrl, off_seeds, scratch_bytes;
+    long long lds_bytes, cap;
+};
+inline MlmRoutePlan mlm_route_plan(const long long D[3], long long tile_packed, long long n_seeds) {
+    MlmRoutePlan p{};
+    const MlmReachPlan q = mlm_reach_plan(D, tile_packed, n_seeds, 1);
+    if (!q.ok) return p;
+    for (int a = 0; a < 3; ++a) {
+        p.T[a] = q.T[a];
+        p.n[a] = q.n[a];
+    }
+    p.tiles = q.tiles;
+    p.voxels = q.voxels;
+    p.field_bytes = q.field_bytes;
+    p.class_bytes = q.mask_bytes;
+    p.dirty_bytes = q.dirty_bytes;
+    p.seed_bytes = q.seed_bytes;
+    p.off_class = q.off_mask;
+    p.off_dirty = q.off_dirty;
+    p.off_ctrl = q.off_ctrl;
+    p.off_seeds = q.off_seeds;
+    p.scratch_bytes = q.scratch_bytes;
+    p.lds_bytes = 4 * (p.T[0] + 2) * (p.T[1] + 2) * (p.T[2] + 2) + 2 * p.T[0] * p.T[1] * p.T[2];
+    p.cap = p.voxels + 1;
+    p.ok = true;
+    return p;
+}
+
 // Geometry and scratch of mlm_export_clusters (mlm_kernels_cluster.h, mlm_cluster.h) for a box of D voxels cut into tiles as
 // mlm_reach_plan cuts it (knob "cluster_tile", same packing, same validity rule: a workgroup of k_cluster_local keeps a tile's
 // labels as u32 in LDS, fewer than the kReachHaloVoxels k_reach_sweep stages).  The whole box is resident at once: the field (4 B

@@ -35,6 +35,7 @@
 #include "mlm_kernels_boxes.h"
 #include "mlm_kernels_views.h"
 #include "mlm_kernels_reach.h"
+#include "mlm_kernels_route.h"
 #include "mlm_kernels_cluster.h"
 #include "mlm_host.h"
 #include "mlm_mapview.h"
@@ -1511,6 +1512,193 @@ int mlm_export_reach(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], 
         for (int c = 0; c < 2; ++c)
             ch[c] = !dst[c] ? nullptr : staged[c] ? (void *)((char *)h->d_win_stage + stage_off[c]) : (void *)((char *)dst[c] + (size_t)j0 * elem[c]);
         hipLaunchKernelGGL(k_reach_out, dim3(std::min<unsigned int>(grid_for((size_t)(j1 - j0)), kReachGrid)), dim3(MLM_BLOCK), 0, h->stream, R, j0, j1,
+                           (int32_t *)ch[0], (uint8_t *)ch[1], cnt);
+        HIPCHK(h, hipGetLastError());
+        for (int c = 0; c < 2; ++c)
+            if (staged[c])
+                HIPCHK(h, hipMemcpyAsync((char *)dst[c] + (size_t)j0 * elem[c], ch[c], (size_t)(j1 - j0) * elem[c], hipMemcpyDefault, h->stream));
+    }
+    unsigned long long *h_cnt = (unsigned long long *)h->h_reach_ctrl;
+    if (summary) HIPCHK(h, hipMemcpyAsync(h_cnt, cnt, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (summary) {
+        summary[0] = (int64_t)h_cnt[0];
+        summary[1] = (int64_t)h_cnt[1];
+        summary[2] = (int64_t)h_cnt[2] - 1;
+        summary[3] = (int64_t)needed;
+    }
+    return MLM_OK;
+}
+
+int mlm_export_route(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], const int32_t *seeds3, int n_seeds, int flags, int clearance,
+                     int connectivity, const int32_t move_cost[3], const int32_t *penalty, int n_penalty, int max_cost, int32_t *cost,
+                     uint8_t *parent, int64_t summary[4]) {
+    if (!h) return MLM_ERR_INVALID;
+    MLM_LOCK(h);
+    bool ok = lo && dims && seeds3 && n_seeds >= 1 && !(flags & ~7) && clearance >= 0 && clearance <= 63 && mlm_route_connectivity_ok(connectivity) &&
+              move_cost && n_penalty >= 0 && clearance + n_penalty <= 63 && (penalty || n_penalty == 0) && max_cost >= 1 && (cost || parent || summary);
+    const int kinds = connectivity == 6 ? 1 : connectivity == 18 ? 2 : 3; // (entries of move kinds the connectivity excludes are ignored)
+    for (int k = 0; ok && k < kinds; ++k) ok = move_cost[k] >= 1 && move_cost[k] <= 65535;
+    for (int k = 0; ok && k < n_penalty; ++k) ok = penalty[k] >= 0 && penalty[k] <= 65535;
+    if (!ok) {
+        h->err = "mlm_export_route: null window or seeds, n_seeds < 1, an unknown flag bit, clearance outside [0, 63], connectivity not 6 / 18 / 26, "
+                 "move_cost NULL or an entry outside [1, 65535], n_penalty < 0, clearance + n_penalty > 63, penalty NULL with n_penalty > 0 or an "
+                 "entry outside [0, 65535], max_cost < 1 or no output";
+        return MLM_ERR_INVALID;
+    }
+    long long D[3], nvox = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (dims[a] < 1 || (long long)lo[a] + dims[a] > 0x7FFFFFFFll) {
+            h->err = "mlm_export_route: dims must be >= 1 and lo + dims must fit an int32";
+            return MLM_ERR_INVALID;
+        }
+        D[a] = dims[a];
+        nvox *= D[a];
+        if (nvox > 0x7FFFFFFFll) {
+            h->err = "mlm_export_route: more than 2^31 - 1 voxels";
+            return MLM_ERR_INVALID;
+        }
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = drain(h);
+    if (rc) return rc;
+
+    long long tile = kRouteTileDefault, group = kRouteGroupDefault, kv;
+    if (knob("route_tile", kv)) tile = kv;
+    if (knob("route_group", kv)) group = kv;
+    const MlmRoutePlan plan = mlm_route_plan(D, tile, n_seeds);
+    if (!plan.ok) { // (not with the tiles mlm_debug_set admits)
+        h->err = "mlm_export_route: no such tile";
+        return MLM_ERR_INVALID;
+    }
+    // outputs: written in place, or staged through d_win_stage in ranges of the box
+    void *dst[2] = {cost, parent};
+    const size_t elem[2] = {sizeof(int32_t), 1};
+    bool staged[2];
+    bool any_staged = false;
+    for (int c = 0; c < 2; ++c) {
+        staged[c] = dst[c] && !win_in_place(dst[c]);
+        any_staged |= staged[c];
+    }
+    const long long chunk = any_staged ? std::min(nvox, kEsdfStageVoxels) : nvox;
+    size_t stage_off[2] = {0, 0}, stage_bytes = 0;
+    for (int c = 0; c < 2; ++c)
+        if (staged[c]) {
+            stage_off[c] = stage_bytes;
+            stage_bytes += ((size_t)chunk * elem[c] + 255) & ~(size_t)255;
+        }
+    if ((rc = win_reserve(h, h->d_reach, h->reach_bytes, (size_t)plan.scratch_bytes, "mlm_export_route"))) return rc;
+    if (stage_bytes && (rc = win_reserve(h, h->d_win_stage, h->win_stage_bytes, stage_bytes, "mlm_export_route"))) return rc;
+    if (!h->h_reach_ctrl) HIPCHK(h, hipHostMalloc((void **)&h->h_reach_ctrl, (size_t)kReachCtrlBytes, hipHostMallocDefault));
+    char *base = (char *)h->d_reach;
+    uint8_t *cls = (uint8_t *)(base + plan.off_class), *dirty[2] = {(uint8_t *)(base + plan.off_dirty), (uint8_t *)(base + plan.off_dirty + plan.dirty_bytes)};
+    unsigned int *marked = (unsigned int *)(base + plan.off_ctrl);
+    unsigned long long *cnt = (unsigned long long *)(base + plan.off_ctrl + kReachGroupMax * 4);
+    uint32_t *pen = (uint32_t *)(base + plan.off_ctrl + kRoutePenOffset);
+    int32_t *seeds = (int32_t *)(base + plan.off_seeds);
+    MlmRoute R{};
+    for (int a = 0; a < 3; ++a) {
+        R.D[a] = D[a];
+        R.n[a] = plan.n[a];
+        R.T[a] = (int)plan.T[a];
+        R.move_cost[a] = a < kinds ? (uint32_t)move_cost[a] : 1u;
+    }
+    R.tiles = plan.tiles;
+    R.connectivity = connectivity;
+    R.max_cost = (uint32_t)max_cost;
+    R.field = (uint32_t *)base;
+    R.cls = cls;
+    R.pen = pen;
+
+    // the class bytes of the box
+    const int n = h->P.n;
+    auto floor_div = [n](long long v) { return v >= 0 ? v / n : -((-v + n - 1) / n); };
+    if (clearance == 0 && n_penalty == 0) {
+        MlmEsdf E{};
+        for (int a = 0; a < 3; ++a) {
+            E.glo[a] = lo[a];
+            E.gd[a] = dims[a];
+            E.b0[a] = floor_div(E.glo[a]);
+            E.nb[a] = (int)(floor_div(E.glo[a] + E.gd[a] - 1) - E.b0[a] + 1);
+        }
+        E.flags = flags;
+        E.mask = cls;
+        const long long n_bricks = (long long)E.nb[0] * E.nb[1] * E.nb[2];
+        hipLaunchKernelGGL(k_esdf_mask, dim3((unsigned int)std::min<long long>(n_bricks, kEsdfMaskGrid)), dim3(MLM_BLOCK), 0, h->stream, h->P, E);
+    } else {
+        // the rings of D_out of mlm_export_esdf at max_dist = clearance + n_penalty + 1, tile by tile (each a contiguous range of the box)
+        const int C = clearance + n_penalty + 1;
+        long long box_cap = kEsdfBoxVoxels;
+        if (knob("esdf_tile_vox", kv)) box_cap = kv;
+        const MlmEsdfPlan ep = mlm_esdf_plan(D, C, false, box_cap, 1ll << 62);
+        if (ep.T[0] < 1) { // (not with the caps mlm_debug_set admits)
+            h->err = "mlm_export_route: no ESDF tile fits the voxel cap";
+            return MLM_ERR_INVALID;
+        }
+        const size_t mask_bytes = ((size_t)ep.grown + 255) & ~(size_t)255, field_bytes = ((size_t)ep.grown * 2 + 255) & ~(size_t)255;
+        if ((rc = win_reserve(h, h->d_esdf_scratch, h->esdf_scratch_bytes, mask_bytes + 2 * field_bytes, "mlm_export_route"))) return rc;
+        uint8_t *emask = (uint8_t *)h->d_esdf_scratch;
+        void *fa = (char *)h->d_esdf_scratch + mask_bytes, *fb = (char *)h->d_esdf_scratch + mask_bytes + field_bytes;
+        for (long long z0 = 0; z0 < D[2]; z0 += ep.T[2])
+            for (long long y0 = 0; y0 < D[1]; y0 += ep.T[1])
+                for (long long x0 = 0; x0 < D[0]; x0 += ep.T[0]) {
+                    MlmEsdf E{};
+                    const long long org[3] = {x0, y0, z0};
+                    int td[3];
+                    for (int a = 0; a < 3; ++a) {
+                        td[a] = (int)std::min(ep.T[a], D[a] - org[a]);
+                        E.glo[a] = lo[a] + org[a] - ep.H;
+                        E.gd[a] = td[a] + (int)(2 * ep.H);
+                        E.b0[a] = floor_div(E.glo[a]);
+                        E.nb[a] = (int)(floor_div(E.glo[a] + E.gd[a] - 1) - E.b0[a] + 1);
+                    }
+                    E.flags = flags;
+                    E.mask = emask;
+                    esdf_passes<false>(h, E, C, emask, fa, fb, td[0], td[1], td[2]);
+                    const long long nt = (long long)td[0] * td[1] * td[2];
+                    hipLaunchKernelGGL(k_route_class, dim3(std::min<unsigned int>(grid_for((size_t)nt), kEsdfPassGrid)), dim3(MLM_BLOCK), 0, h->stream,
+                                       (const uint16_t *)fa, cls + (z0 * D[1] + y0) * D[0] + x0, nt, clearance, n_penalty);
+                    HIPCHK(h, hipGetLastError());
+                }
+    }
+    // field, seeds, dirty arrays, control block with the penalty table (staged in the pinned block behind what the host reads back)
+    uint32_t *h_pen = (uint32_t *)((char *)h->h_reach_ctrl + kRoutePenOffset);
+    for (int k = 0; k < kRoutePenWords; ++k) h_pen[k] = k < n_penalty ? (uint32_t)penalty[k] : 0u;
+    HIPCHK(h, hipMemsetAsync(base + plan.off_dirty, 0, (size_t)(2 * plan.dirty_bytes + kReachCtrlBytes), h->stream));
+    HIPCHK(h, hipMemcpyAsync(pen, h_pen, (size_t)kRoutePenWords * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(seeds, seeds3, (size_t)n_seeds * 12, hipMemcpyDefault, h->stream));
+    hipLaunchKernelGGL(k_route_init, dim3(std::min<unsigned int>(grid_for((size_t)nvox), kReachGrid)), dim3(MLM_BLOCK), 0, h->stream, (const uint8_t *)cls,
+                       R.field, nvox, n_penalty);
+    hipLaunchKernelGGL(k_route_seed, dim3(std::min<unsigned int>(grid_for((size_t)n_seeds), 1024u)), dim3(MLM_BLOCK), 0, h->stream, R,
+                       (const int32_t *)seeds, n_seeds, (long long)lo[0], (long long)lo[1], (long long)lo[2], dirty[0]);
+    HIPCHK(h, hipGetLastError());
+    // sweeps in groups, as mlm_export_reach runs them
+    auto sweep = connectivity == 6 ? k_route_sweep<6> : connectivity == 18 ? k_route_sweep<18> : k_route_sweep<26>;
+    const size_t lds = (size_t)plan.lds_bytes;
+    if (lds > 65536) HIPCHK(h, hipFuncSetAttribute((const void *)sweep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const dim3 sgrid((unsigned int)std::min<long long>(plan.tiles, kReachGrid));
+    long long sweeps = 0, needed = -1;
+    while (needed < 0) {
+        if (sweeps >= plan.cap) { // (mlm_route.h: cannot happen; an endless loop otherwise)
+            h->err = "mlm_export_route: the field did not settle within " + std::to_string(sweeps) + " sweeps";
+            return MLM_ERR_HIP;
+        }
+        if (sweeps) HIPCHK(h, hipMemsetAsync(marked, 0, (size_t)group * sizeof(unsigned int), h->stream));
+        for (long long g = 0; g < group; ++g, ++sweeps)
+            hipLaunchKernelGGL(sweep, sgrid, dim3(MLM_BLOCK), lds, h->stream, R, dirty[sweeps & 1], dirty[(sweeps & 1) ^ 1], marked + g);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(h->h_reach_ctrl, marked, (size_t)group * sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        for (long long g = 0; g < group && needed < 0; ++g)
+            if (h->h_reach_ctrl[g] == 0) needed = sweeps - group + g + 1;
+    }
+    // outputs and counters
+    for (long long j0 = 0; j0 < nvox; j0 += chunk) {
+        const long long j1 = std::min(nvox, j0 + chunk);
+        void *ch[2];
+        for (int c = 0; c < 2; ++c)
+            ch[c] = !dst[c] ? nullptr : staged[c] ? (void *)((char *)h->d_win_stage + stage_off[c]) : (void *)((char *)dst[c] + (size_t)j0 * elem[c]);
+        hipLaunchKernelGGL(k_route_out, dim3(std::min<unsigned int>(grid_for((size_t)(j1 - j0)), kReachGrid)), dim3(MLM_BLOCK), 0, h->stream, R, j0, j1,
                            (int32_t *)ch[0], (uint8_t *)ch[1], cnt);
         HIPCHK(h, hipGetLastError());
         for (int c = 0; c < 2; ++c)

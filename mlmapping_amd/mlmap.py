@@ -28,6 +28,8 @@ MLM_OK = 0
 MLM_ESDF_OCC, MLM_ESDF_INFL, MLM_ESDF_UNKNOWN, MLM_ESDF_SIGNED = 1, 2, 4, 8
 # mlm_export_reach: obstacle predicates (their union; none: no obstacles), steps of a voxel not reached, parent code of a seed
 MLM_REACH_OCC, MLM_REACH_INFL, MLM_REACH_UNKNOWN, MLM_REACH_NONE, MLM_REACH_SEED = 1, 2, 4, -1, 6
+# mlm_export_route: the same predicates, cost of a voxel not reached, parent code of a seed (0..25 are the moves' codes)
+MLM_ROUTE_OCC, MLM_ROUTE_INFL, MLM_ROUTE_UNKNOWN, MLM_ROUTE_NONE, MLM_ROUTE_SEED = 1, 2, 4, -1, 26
 # mlm_export_clusters: the set (FRONTIER alone, or a union of the class bits), labels off the set / in a dropped component, int64 per row
 MLM_CLUSTER_OCC, MLM_CLUSTER_INFL, MLM_CLUSTER_UNKNOWN, MLM_CLUSTER_FRONTIER = 1, 2, 4, 16
 MLM_CLUSTER_NONE, MLM_CLUSTER_SMALL, MLM_CLUSTER_ROW = -1, -2, 16
@@ -48,7 +50,7 @@ ABI_SYMBOLS = [
     "mlm_query_odds", "mlm_query_odd_grad", "mlm_query_odds_at", "mlm_export_frontier_points", "mlm_import_blocks",
     "mlm_merge_pack", "mlm_merge_finish",
     "mlm_set_free_in_bound", "mlm_inflate_map", "mlm_block_count",
-    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_reach", "mlm_export_clusters", "mlm_query_rays", "mlm_query_views", "mlm_query_boxes", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
+    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_reach", "mlm_export_route", "mlm_export_clusters", "mlm_query_rays", "mlm_query_views", "mlm_query_boxes", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
     "mlm_get_awareness_hits",
     "mlm_get_awareness_misses", "mlm_get_T_ls", "mlm_get_odds_table", "mlm_get_kernel_times",
     "mlm_enable_kernel_timing", "mlm_set_timed_kernel", "mlm_host_register", "mlm_host_unregister", "mlm_debug_set", "mlm_debug_reset",
@@ -144,6 +146,7 @@ def load_library(path: Optional[str] = None):
     L.mlm_export_window.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
     L.mlm_export_esdf.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
     L.mlm_export_reach.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
+    L.mlm_export_route.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp]
     L.mlm_export_clusters.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i32, vp]
     L.mlm_query_rays.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.mlm_query_views.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
@@ -524,6 +527,48 @@ class MLMap:
                                            self._ray_flags(occ, infl, unknown), int(clearance),
                                            2 ** 31 - 1 if max_steps is None else int(max_steps), *ptr), "mlm_export_reach")
         return sm
+
+    def export_route(self, lo, dims, seeds, occ=True, infl=False, unknown=False, clearance: int = 0, connectivity: int = 26,
+                     move_cost=(10, 14, 17), penalty=(), max_cost: Optional[int] = None, cost=True, parent=False) -> Dict[str, np.ndarray]:
+        """Clearance-weighted cost field through the free space of the voxel box lo <= v < lo + dims from `seeds` (k x 3 voxel
+        indices), window, obstacles, clearance and seeds as export_reach: {"cost": int32 (dz, dy, dx), the cheapest path of
+        permitted moves from a seed, -1 where there is none (or it costs more than max_cost); "parent": uint8, the code (0..25)
+        of the offset towards the voxel before on one cheapest path, 26 at seeds, 255 where cost is -1; "summary": int64
+        [traversable, reached, largest cost, sweeps]}.  connectivity 6, 18 or 26: face, edge and corner moves at move_cost[0 / 1
+        / 2], a diagonal move only where all the voxels it brushes are traversable; entering a voxel in ring k around the blocked
+        voxels (obstacle distance within clearance + 1 + k) adds penalty[k] (mlm_export_route)."""
+        lo_a, dims_a = self._window_args(lo, dims)
+        shape = (int(dims_a[2]), int(dims_a[1]), int(dims_a[0]))
+        s = np.ascontiguousarray(np.asarray(seeds, dtype=np.int32).reshape(-1, 3))
+        out = {"summary": np.zeros(4, dtype=np.int64)}
+        if cost:
+            out["cost"] = np.empty(shape, dtype=np.int32)
+        if parent:
+            out["parent"] = np.empty(shape, dtype=np.uint8)
+        ptr = [_p(out[k]) if k in out else None for k in ("cost", "parent", "summary")]
+        self._chk(self._L.mlm_export_route(self._h, _p(lo_a), _p(dims_a), _p(s), len(s), self._ray_flags(occ, infl, unknown),
+                                           *self._route_args(clearance, connectivity, move_cost, penalty, max_cost), *ptr), "mlm_export_route")
+        return out
+
+    def export_route_dev(self, lo, dims, seeds: int, n_seeds: int, occ=True, infl=False, unknown=False, clearance: int = 0,
+                         connectivity: int = 26, move_cost=(10, 14, 17), penalty=(), max_cost: Optional[int] = None,
+                         cost: Optional[int] = None, parent: Optional[int] = None, summary: bool = False) -> Optional[np.ndarray]:
+        """Same on device memory: `seeds` a pointer (int) to n_seeds x 3 int32, cost / parent pointers to dz*dy*dx int32 / uint8
+        elements, None = skipped; summary=True returns the four int64 counters."""
+        lo_a, dims_a = self._window_args(lo, dims)
+        sm = np.zeros(4, dtype=np.int64) if summary else None
+        ptr = [None if v is None else ctypes.c_void_p(v) for v in (cost, parent)] + [None if sm is None else _p(sm)]
+        self._chk(self._L.mlm_export_route(self._h, _p(lo_a), _p(dims_a), ctypes.c_void_p(seeds), int(n_seeds), self._ray_flags(occ, infl, unknown),
+                                           *self._route_args(clearance, connectivity, move_cost, penalty, max_cost), *ptr), "mlm_export_route")
+        return sm
+
+    @staticmethod
+    def _route_args(clearance, connectivity, move_cost, penalty, max_cost):
+        """clearance, connectivity, move_cost[3], penalty, n_penalty, max_cost as mlm_export_route takes them (the arrays are kept
+        alive by the returned list until the call is over)"""
+        mc = np.ascontiguousarray(np.asarray(move_cost, dtype=np.int32).reshape(3))
+        pen = np.ascontiguousarray(np.asarray(penalty, dtype=np.int32).reshape(-1))
+        return [int(clearance), int(connectivity), _p(mc), _p(pen) if len(pen) else None, len(pen), 2 ** 31 - 1 if max_cost is None else int(max_cost)]
 
     def export_clusters(self, lo, dims, frontier=False, occ=False, infl=False, unknown=False, connectivity: int = 26, min_size: int = 1,
                         labels=True, cap: int = 4096) -> Dict[str, np.ndarray]:
