@@ -6,6 +6,7 @@
 // Not part of the hot path: every method is a thin forward to one mlm_* call.
 #pragma once
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <memory>
 #include <stdexcept>
@@ -269,6 +270,36 @@ class mlmap {
         check(mlm_query_rays(h_, a, b, 1, flags, &st, voxel3, t_hit, nullptr, n_unknown), "mlm_query_rays");
         if (st < 0) throw std::runtime_error("castRay: invalid segment");
         return st == 1;
+    }
+
+    // the depth images the map predicts for a pinhole camera (mlm_render_depth; flags MLM_RAY_*; T_ws n_poses x 12: R sensor -> world
+    // row major, then the optical centre; K = fx, fy, cx, cy in host memory or NULL = the configuration's camera; outputs
+    // [n_poses][height][width], depth uint16 mm as the integrate calls read it, 0 = nothing stopped the ray; table
+    // [n_poses][MLM_RENDER_ROW]; T_ws and every output host or device memory, NULL output = skipped)
+    void renderDepth(const double *T_ws, int n_poses, int width, int height, const double K[4], int max_depth_mm, int flags, uint16_t *depth,
+                     int8_t *status = nullptr, int32_t *voxel3 = nullptr, int32_t *n_unknown = nullptr, int64_t *table = nullptr) {
+        check(mlm_render_depth(h_, T_ws, n_poses, width, height, K, max_depth_mm, flags, depth, status, voxel3, n_unknown, table), "mlm_render_depth");
+    }
+    // one image from a body pose, as the integrate calls take it: q_wb (w, x, y, z), t_wb, composed with the configuration's T_bs
+    // (a convenience outside mlm_render_depth's contract, which starts at R and o: plain double arithmetic, q_wb normalised here).
+    // Compare it with the frame just received at that pose: pixels much nearer than rendered are something new.
+    void renderDepthAt(const double q_wb[4], const double t_wb[3], int width, int height, int max_depth_mm, int flags, uint16_t *depth,
+                       int8_t *status = nullptr) {
+        double T[12];
+        composeTws(q_wb, t_wb, cfg_.T_bs, T);
+        renderDepth(T, 1, width, height, nullptr, max_depth_mm, flags, depth, status);
+    }
+    static void composeTws(const double q_wb[4], const double t_wb[3], const double T_bs[16], double T_ws[12]) {
+        double n = 0.0;
+        for (int i = 0; i < 4; ++i) n += q_wb[i] * q_wb[i];
+        n = std::sqrt(n);
+        const double w = q_wb[0] / n, x = q_wb[1] / n, y = q_wb[2] / n, z = q_wb[3] / n;
+        const double R[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - w * z),     2 * (x * z + w * y),     2 * (x * y + w * z),    1 - 2 * (x * x + z * z),
+                             2 * (y * z - w * x),     2 * (x * z - w * y),     2 * (y * z + w * x),     1 - 2 * (x * x + y * y)};
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 3; ++c) T_ws[3 * r + c] = R[3 * r] * T_bs[c] + R[3 * r + 1] * T_bs[4 + c] + R[3 * r + 2] * T_bs[8 + c];
+            T_ws[9 + r] = t_wb[r] + (R[3 * r] * T_bs[3] + R[3 * r + 1] * T_bs[7] + R[3 * r + 2] * T_bs[11]);
+        }
     }
 
     // distinct-voxel gain of grouped ray fans (mlm_query_views; view k = segments view_begin[k] .. view_begin[k + 1]; flags MLM_RAY_*;

@@ -292,6 +292,40 @@ int mlm_export_esdf(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], i
 #define MLM_RAY_UNKNOWN 4
 int mlm_query_rays(mlm_handle *h, const double *p0, const double *p1, int n, int flags, int8_t *status, int32_t *voxel3, double *t,
                    int32_t *n_steps, int32_t *n_unknown);
+/* Expected depth images of the map: what should a pinhole camera see from this pose?  (No reference counterpart: the reference
+ * projects depth images into the map, project_depth, mlmap.cpp:338-349, and has no inverse.)  Per pose and pixel one segment is
+ * made on the device — its end points never exist in memory — and walked exactly as mlm_query_rays walks it.
+ *   Poses: T_ws is [n_poses][12] doubles, per pose R (3 x 3, sensor to world, row major) followed by the optical centre o in the
+ *   world: the caller composes T_wb * T_bs (the Python binding and the facade have a convenience for it).  K = fx, fy, cx, cy in
+ *   host memory, NULL: the handle's cam_fx, cam_fy, cam_cx, cam_cy.  Z = (double)max_depth_mm / 1000.0.
+ *   The segment of pixel (u, v), integers as in project_depth (0 <= u < width, 0 <= v < height): xs = (((double)u - cx) * Z) / fx,
+ *   ys = (((double)v - cy) * Z) / fy, zs = Z; p0 = o; p1[a] = ((R[a][0] * xs + R[a][1] * ys) + R[a][2] * zs) + o[a] — every
+ *   operation one IEEE double operation in that order, nothing fused.  It ends on the plane of z-depth Z in front of the camera.
+ *   The walk: lattice, validity, path, tie rule, predicate and classes are mlm_query_rays'; flags are the MLM_RAY_* bits with their
+ *   meaning there (0: nothing stops a ray).  A non-finite entry of T_ws is no error: the pixels of that pose are invalid rays, as
+ *   are all pixels when Z / subbox_d_xyz exceeds 32 768 voxels on an axis.
+ *   Outputs, [n_poses][height][width] with u fastest:
+ *     depth     uint16     millimetres of z-depth, the 16UC1 format the integrate calls read.  status 1: z = t * (double)max_depth_mm
+ *                          (one multiply), depth = min(65535, max(1, (long long)floor(z + 0.5))); status 0 or -1: 0.  So depth == 0
+ *                          iff nothing stopped the ray: a sensor's "no return", which the integrate calls skip.
+ *     status    int8       \
+ *     voxel3    int32 x 3   > mlm_query_rays' values for that segment
+ *     n_unknown int32      /
+ *   table (optional): int64 [n_poses][MLM_RENDER_ROW]: [0] pixels with status 1, [1] pixels with status 0, [2] invalid pixels,
+ *   [3] the sum of n_unknown over the pose.  Sums of integers: one value whatever the schedule.
+ * T_ws and every output may be host or device memory, each pointer on its own; any output may be NULL, at least one must not be.
+ * The call returns when the outputs are written, observes the map as queries do (async mode: waits for everything submitted) and
+ * runs on the stream of mlm_set_stream.  There is no host-mirror shortcut: every call is a kernel launch (an image is thousands of
+ * rays).  MLM_ERR_INVALID: n_poses < 0, T_ws NULL with n_poses > 0, width or height outside 1..8192, more than 2^31 - 1 pixels in
+ * all, fx or fy not finite or not > 0, cx or cy not finite, max_depth_mm outside 1..65535, an unknown flag bit, no output;
+ * n_poses == 0 is MLM_OK.  MLM_ERR_CAPACITY: no device memory for the staging of what lies in host memory: 96 bytes per pose
+ * for T_ws and 32 bytes per pose for table (the whole call), and for the per-pixel outputs at most 19 bytes (2 depth, 1 status,
+ * 12 voxel3, 4 n_unknown) x the pixels of one chunk — the call runs in chunks of whole rows of tiles, at most 2^20 pixels each;
+ * a call of at most 2^20 pixels is one chunk —, each part rounded up to 256 bytes; the staging is kept by the handle (it shares
+ * mlm_query_rays' buffer) and counted in mlm_frame_stats.device_bytes.  The handle stays usable after either error. */
+#define MLM_RENDER_ROW 4
+int mlm_render_depth(mlm_handle *h, const double *T_ws, int n_poses, int width, int height, const double K[4], int max_depth_mm,
+                     int flags, uint16_t *depth, int8_t *status, int32_t *voxel3, int32_t *n_unknown, int64_t *table);
 /* Distinct-voxel gain of grouped ray fans: from which candidate pose is the most unknown space seen?  (No reference counterpart:
  * the reference has no view query.)  The sum of mlm_query_rays' n_unknown over a fan is not that number: the rays of a fan share
  * voxels near the origin (a 64 x 48 fan of 4 m at d = 0.1 visits each of its voxels 3.5 times on average).  This call counts sets.

@@ -26,7 +26,7 @@ struct KernelTime {
 // switches MLM_DEBUG_CREATE / MLM_DEBUG_ALLOC / MLM_DEBUG_DRAIN, which print).
 const char *const kKnobNames[] = {"agg_lds", "big_arm", "big_grid", "bin_block", "chain_grid", "cluster_tile", "collect_grid", "cu_reserve", "cu_split",
                                   "esdf_tile_vox", "ex_spec", "expand_block", "graph", "logit_exact", "mirror", "mirror_max", "mirror_mb", "need_slots", "node_lds", "pool_grow",
-                                  "rank_grid", "rays_grid", "reach_group", "reach_tile", "route_group", "route_tile", "sc_block", "sc_grid", "sec_backoff", "sec_fail_every", "sec_tab", "sec_tab_big", "sec_threads",
+                                  "rank_grid", "rays_grid", "reach_group", "reach_tile", "render_tile", "route_group", "route_tile", "sc_block", "sc_grid", "sec_backoff", "sec_fail_every", "sec_tab", "sec_tab_big", "sec_threads",
                                   "sectors", "single_apply_grid", "single_chain_grid", "single_rank_grid", "slot_sets", "sort_block", "sort_grid", "tile_grid", "tile_sh", "view_lds_bits"};
 struct KnobStore {
     std::mutex mu;
@@ -55,6 +55,7 @@ bool knob_value_ok(const char *name, long long v) {
     if (is("route_group")) return v >= 1 && v <= kReachGroupMax; // (as reach_group)
     if (is("view_lds_bits")) return v >= 0 && v <= kViewLdsBits; // (larger bitsets go to global scratch; 0: all of them)
     if (is("reach_group")) return v >= 1 && v <= kReachGroupMax; // (sweeps between two looks at the "marked" words)
+    if (is("render_tile")) return v >= 0 && v <= 2; // (k_render has three instantiations: 64 x 1, 16 x 4, 8 x 8)
     return true;
 }
 bool knob(const char *name, long long &out) {
@@ -133,6 +134,8 @@ constexpr int kRayChunk = 1 << 20;           // rays per launch of k_rays: bound
 // allow positions (64 / 8 by default, as for rays) AND the limit volumes of its valid boxes — B0 plus max_grow per face, cut to the
 // window: the most voxels the growth can read, known before anything is read — sum to at most kBoxMirrorVoxels
 constexpr long long kBoxMirrorVoxels = 16384;
+constexpr int kRenderChunk = 1 << 20;        // most pixels per launch of k_render: bounds the staging of host outputs (19 bytes per pixel)
+constexpr int kRenderTileDefault = 2;        // k_render's tile: 0 64 x 1, 1 16 x 4, 2 8 x 8 (profiles/render_rate.json)
 constexpr int kBoxChunk = 1 << 18;           // boxes per launch of k_boxes: bounds the staging of host inputs / outputs (82 bytes per box)
 constexpr unsigned int kBoxGrid = 8192;      // most workgroups of k_boxes (a wave per box, grid-stride): 32 768 waves, four times what the chip holds
 
@@ -182,6 +185,8 @@ struct mlm_handle {
     size_t views_bytes = 0;
     // mlm_query_boxes stages the host inputs / outputs of one chunk of boxes in d_ray_stage too
     unsigned int rays_grid = 1024; // most workgroups of k_rays (knob "rays_grid"): 2^20 rays are four per lane
+    // mlm_render_depth stages host poses, one chunk of host per-pixel outputs and a host table in d_ray_stage too
+    int render_tile = kRenderTileDefault; // (knob "render_tile")
     // sort buffers (rehash frames only)
     unsigned long long *sk_in = nullptr, *sk_out = nullptr;
     uint32_t *sv_in = nullptr, *sv_out = nullptr;

@@ -32,6 +32,7 @@
 #include "mlm_kernels_window.h"
 #include "mlm_kernels_esdf.h"
 #include "mlm_kernels_rays.h"
+#include "mlm_kernels_render.h"
 #include "mlm_kernels_boxes.h"
 #include "mlm_kernels_views.h"
 #include "mlm_kernels_reach.h"
@@ -472,6 +473,7 @@ int mlm_create(const mlm_config *cfg, const mlm_limits *lim_in, int device, mlm_
         if (knob("mirror", kv)) h->mir.enabled = (int)kv != 0;
         if (knob("mirror_mb", kv)) h->mir.max_bytes = (size_t)std::max(0, (int)kv) << 20;
         if (knob("rays_grid", kv)) h->rays_grid = (unsigned int)kv;
+        if (knob("render_tile", kv)) h->render_tile = (int)kv;
         if (knob("mirror_max", kv)) h->mir.max_clean = std::max(0, (int)kv), h->mir.max_dirty = std::min(h->mir.max_dirty, h->mir.max_clean);
         mirror_apply_limit(h);
     }
@@ -1902,6 +1904,71 @@ int mlm_query_rays(mlm_handle *h, const double *p0, const double *p1, int n, int
             if (staged[c])
                 HIPCHK(h, hipMemcpyAsync((char *)ch[c] + (size_t)i0 * elem[c], at[c], (size_t)m * elem[c], hipMemcpyDeviceToHost, h->stream));
     }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MLM_OK;
+}
+
+int mlm_render_depth(mlm_handle *h, const double *T_ws, int n_poses, int width, int height, const double K[4], int max_depth_mm, int flags,
+                     uint16_t *depth, int8_t *status, int32_t *voxel3, int32_t *n_unknown, int64_t *table) {
+    if (!h) return MLM_ERR_INVALID;
+    MLM_LOCK(h);
+    const double k4[4] = {K ? K[0] : h->cfg.cam_fx, K ? K[1] : h->cfg.cam_fy, K ? K[2] : h->cfg.cam_cx, K ? K[3] : h->cfg.cam_cy};
+    const bool dims_ok = width >= 1 && width <= 8192 && height >= 1 && height <= 8192;
+    const long long pixels = dims_ok && n_poses > 0 ? (long long)n_poses * width * height : 0;
+    if (n_poses < 0 || (n_poses > 0 && !T_ws) || !dims_ok || pixels > 0x7FFFFFFFll || !(std::isfinite(k4[0]) && k4[0] > 0.0) ||
+        !(std::isfinite(k4[1]) && k4[1] > 0.0) || !std::isfinite(k4[2]) || !std::isfinite(k4[3]) || max_depth_mm < 1 || max_depth_mm > 65535 ||
+        (flags & ~7) || (!depth && !status && !voxel3 && !n_unknown && !table)) {
+        h->err = "mlm_render_depth: negative n_poses, null poses, width or height outside 1..8192, more than 2^31 - 1 pixels, intrinsics not finite "
+                 "or a focal length <= 0, max_depth_mm outside 1..65535, an unknown flag bit or no output";
+        return MLM_ERR_INVALID;
+    }
+    if (n_poses == 0) return MLM_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = drain(h);
+    if (rc) return rc;
+    // tiles; chunks of whole tile rows (counted over all poses: pose * tiles_y + ty), whose pixels are one contiguous range of the outputs
+    const int TW = h->render_tile == 0 ? 64 : (h->render_tile == 1 ? 16 : 8), TH = 64 / TW;
+    void (*const kern)(const MlmDev, const MlmRender) = TW == 64 ? k_render<64, 1> : (TW == 16 ? k_render<16, 4> : k_render<8, 8>);
+    const int tiles_x = (width + TW - 1) / TW, tiles_y = (height + TH - 1) / TH;
+    const long long q_total = (long long)n_poses * tiles_y; // (<= pixels)
+    const long long q_chunk = std::max(1, kRenderChunk / (TH * width));
+    const long long chunk_pixels = std::min(pixels, q_chunk * TH * width);
+    auto first_pixel = [&](long long q) { return ((q / tiles_y) * height + (q % tiles_y) * TH) * width; };
+    // channels: the poses, the four per-pixel outputs, the table; in device memory (used in place) or staged — poses and table for the
+    // whole call, the per-pixel outputs chunk by chunk (at most 19 bytes per pixel)
+    void *ch[6] = {(void *)T_ws, depth, status, voxel3, n_unknown, table};
+    const size_t elem[6] = {12 * sizeof(double), sizeof(uint16_t), 1, 3 * sizeof(int32_t), sizeof(int32_t), MLM_RENDER_ROW * sizeof(int64_t)};
+    bool staged[6];
+    size_t off[6], stage_bytes = 0;
+    for (int c = 0; c < 6; ++c) {
+        staged[c] = ch[c] && !win_in_place(ch[c]);
+        off[c] = stage_bytes;
+        if (staged[c]) stage_bytes += ((size_t)(c == 0 || c == 5 ? n_poses : chunk_pixels) * elem[c] + 255) & ~(size_t)255;
+    }
+    if (stage_bytes && (rc = win_reserve(h, h->d_ray_stage, h->ray_stage_bytes, stage_bytes, "mlm_render_depth"))) return rc;
+    auto dev = [&](int c) { return !ch[c] ? nullptr : staged[c] ? (void *)((char *)h->d_ray_stage + off[c]) : ch[c]; };
+    if (staged[0]) HIPCHK(h, hipMemcpyAsync(dev(0), T_ws, (size_t)n_poses * elem[0], hipMemcpyHostToDevice, h->stream));
+    if (table) HIPCHK(h, hipMemsetAsync(dev(5), 0, (size_t)n_poses * elem[5], h->stream));
+    MlmRender R{};
+    R.T = (const double *)dev(0);
+    for (int k = 0; k < 4; ++k) R.K[k] = k4[k];
+    R.Z = (double)max_depth_mm / 1000.0;
+    R.width = width, R.height = height, R.max_mm = max_depth_mm, R.flags = flags;
+    R.tiles_x = tiles_x, R.tiles_y = tiles_y;
+    R.table = (unsigned long long *)dev(5);
+    for (long long q0 = 0; q0 < q_total; q0 += q_chunk) {
+        const long long q1 = std::min(q_total, q0 + q_chunk), i0 = first_pixel(q0), m = first_pixel(q1) - i0;
+        void *at[5];
+        for (int c = 1; c < 5; ++c) at[c] = !ch[c] ? nullptr : staged[c] ? dev(c) : (void *)((char *)ch[c] + (size_t)i0 * elem[c]);
+        R.q0 = (int)q0, R.n_tiles = (int)((q1 - q0) * tiles_x), R.pix0 = i0;
+        R.depth = (uint16_t *)at[1], R.status = (int8_t *)at[2], R.voxel3 = (int32_t *)at[3], R.n_unknown = (int32_t *)at[4];
+        // one wave per tile, four to a workgroup
+        hipLaunchKernelGGL(kern, dim3(((unsigned int)R.n_tiles + MLM_BLOCK / 64 - 1) / (MLM_BLOCK / 64)), dim3(MLM_BLOCK), 0, h->stream, h->P, R);
+        HIPCHK(h, hipGetLastError());
+        for (int c = 1; c < 5; ++c)
+            if (staged[c]) HIPCHK(h, hipMemcpyAsync((char *)ch[c] + (size_t)i0 * elem[c], at[c], (size_t)m * elem[c], hipMemcpyDeviceToHost, h->stream));
+    }
+    if (staged[5]) HIPCHK(h, hipMemcpyAsync(table, dev(5), (size_t)n_poses * elem[5], hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MLM_OK;
 }

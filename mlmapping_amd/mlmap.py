@@ -37,6 +37,8 @@ MLM_CLUSTER_NONE, MLM_CLUSTER_SMALL, MLM_CLUSTER_ROW = -1, -2, 16
 MLM_RAY_OCC, MLM_RAY_INFL, MLM_RAY_UNKNOWN = 1, 2, 4
 # mlm_query_views: int64 per row of the table
 MLM_VIEW_ROW = 8
+# mlm_render_depth: int64 per row of the table
+MLM_RENDER_ROW = 4
 # mlm_query_boxes flags: what blocks a box (their union; 0: nothing), int64 per row of the table
 MLM_BOX_OCC, MLM_BOX_INFL, MLM_BOX_UNKNOWN, MLM_BOX_ROW = 1, 2, 4, 4
 STATUS = {0: "MLM_OK", -1: "MLM_ERR_INVALID", -2: "MLM_ERR_HIP", -3: "MLM_ERR_CAPACITY", -4: "MLM_ERR_UNSUPPORTED"}
@@ -50,7 +52,7 @@ ABI_SYMBOLS = [
     "mlm_query_odds", "mlm_query_odd_grad", "mlm_query_odds_at", "mlm_export_frontier_points", "mlm_import_blocks",
     "mlm_merge_pack", "mlm_merge_finish",
     "mlm_set_free_in_bound", "mlm_inflate_map", "mlm_block_count",
-    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_reach", "mlm_export_route", "mlm_export_clusters", "mlm_query_rays", "mlm_query_views", "mlm_query_boxes", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
+    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_reach", "mlm_export_route", "mlm_export_clusters", "mlm_query_rays", "mlm_render_depth", "mlm_query_views", "mlm_query_boxes", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
     "mlm_get_awareness_hits",
     "mlm_get_awareness_misses", "mlm_get_T_ls", "mlm_get_odds_table", "mlm_get_kernel_times",
     "mlm_enable_kernel_timing", "mlm_set_timed_kernel", "mlm_host_register", "mlm_host_unregister", "mlm_debug_set", "mlm_debug_reset",
@@ -149,6 +151,7 @@ def load_library(path: Optional[str] = None):
     L.mlm_export_route.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp]
     L.mlm_export_clusters.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i32, vp]
     L.mlm_query_rays.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
+    L.mlm_render_depth.argtypes = [vp, vp, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp]
     L.mlm_query_views.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.mlm_query_boxes.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.mlm_export_global_map.argtypes = [vp, i32, vp, vp]
@@ -636,6 +639,50 @@ class MLMap:
         self._chk(self._L.mlm_query_rays(self._h, ctypes.c_void_p(p0), ctypes.c_void_p(p1), int(n),
                                          self._ray_flags(occ, infl, unknown), *ptr), "mlm_query_rays")
 
+    def render_depth(self, T_ws=None, q_wb=None, t_wb=None, width: int = 0, height: int = 0, K=None, max_depth: float = 8.0, occ=True, infl=False,
+                     unknown=False) -> Dict[str, np.ndarray]:
+        """The depth images the map predicts for a pinhole camera (mlm_render_depth), one per pose.  Poses: T_ws (n, 12) float64 — R
+        (3 x 3, sensor to world, row major) then the optical centre in the world — or q_wb (n, 4; w, x, y, z) and t_wb (n, 3), which
+        compose_T_ws turns into T_ws with the configuration's T_bs (the poses update_map takes).  K = (fx, fy, cx, cy), None: the
+        configuration's camera.  max_depth in metres (1 mm .. 65.535 m): where the pixels' rays end.  A ray stops as in cast_rays
+        (occ / infl / unknown).  {"depth": uint16 (n, height, width) millimetres of z-depth as update_map reads them, 0 where
+        nothing stopped the ray; "status": int8, "voxel": int32 (n, height, width, 3), "n_unknown": int32 as cast_rays' for the
+        pixel's segment; "table": int64 (n, 4): stopped, not stopped, invalid pixels and the sum of n_unknown per pose}."""
+        if T_ws is None:
+            if q_wb is None or t_wb is None:
+                raise MlmError("render_depth: give T_ws, or q_wb and t_wb")
+            T = compose_T_ws(q_wb, t_wb, self.cfg.T_B_S)
+        else:
+            T = _f64(T_ws).reshape(-1, 12)
+        n, w, hgt = T.shape[0], int(width), int(height)
+        if w < 1 or hgt < 1:
+            raise MlmError("render_depth: width and height must be >= 1")
+        k = None if K is None else _f64(K).reshape(4)
+        out = {"depth": np.empty((n, hgt, w), dtype=np.uint16), "status": np.empty((n, hgt, w), dtype=np.int8),
+               "voxel": np.empty((n, hgt, w, 3), dtype=np.int32), "n_unknown": np.empty((n, hgt, w), dtype=np.int32),
+               "table": np.empty((n, MLM_RENDER_ROW), dtype=np.int64)}
+        self._chk(self._L.mlm_render_depth(self._h, _p(T), n, w, hgt, None if k is None else _p(k), self._depth_mm(max_depth),
+                                           self._ray_flags(occ, infl, unknown), *[_p(out[c]) for c in ("depth", "status", "voxel", "n_unknown", "table")]),
+                  "mlm_render_depth")
+        return out
+
+    def render_depth_dev(self, T_ws: int, n_poses: int, width: int, height: int, K=None, max_depth: float = 8.0, occ=True, infl=False,
+                         unknown=False, depth: Optional[int] = None, status: Optional[int] = None, voxel: Optional[int] = None,
+                         n_unknown: Optional[int] = None, table: Optional[int] = None):
+        """Same on pointers (ints; device or host memory, each on its own): n_poses x 12 float64 poses, n_poses x height x width
+        uint16 / int8 / 3 x int32 / int32 outputs, n_poses x 4 int64 table; None = skipped."""
+        k = None if K is None else _f64(K).reshape(4)
+        ptr = [None if v is None else ctypes.c_void_p(v) for v in (depth, status, voxel, n_unknown, table)]
+        self._chk(self._L.mlm_render_depth(self._h, ctypes.c_void_p(T_ws), int(n_poses), int(width), int(height), None if k is None else _p(k),
+                                           self._depth_mm(max_depth), self._ray_flags(occ, infl, unknown), *ptr), "mlm_render_depth")
+
+    @staticmethod
+    def _depth_mm(max_depth) -> int:
+        mm = int(round(float(max_depth) * 1000.0))
+        if not 1 <= mm <= 65535:
+            raise MlmError("render_depth: max_depth must lie in 0.001 .. 65.535 m")
+        return mm
+
     def query_views(self, p0, p1, view_begin, occ=True, infl=False, unknown=False, box=None, exclude=None, mark=False) -> Dict[str, np.ndarray]:
         """Distinct-voxel accounting of grouped ray fans (mlm_query_views): view k is the segments view_begin[k] .. view_begin[k + 1]
         of p0 / p1 (n x 3 world positions), walked as cast_rays walks them.  {"table": int64 (n_views, 8): distinct traversed
@@ -847,3 +894,24 @@ def fan_views(origins, rotations, fan):
     p0 = np.broadcast_to(o[:, None, :], p1.shape)
     return (np.ascontiguousarray(p0).reshape(-1, 3), np.ascontiguousarray(p1).reshape(-1, 3),
             (np.arange(len(o) + 1, dtype=np.int64) * len(f)).astype(np.int32))
+
+
+def compose_T_ws(q_wb, t_wb, T_bs) -> np.ndarray:
+    """(n, 12) float64 poses for render_depth from body poses: q_wb (n, 4; w, x, y, z, normalised here), t_wb (n, 3) and the
+    body-to-sensor transform T_bs (4 x 4, row major: MapConfig.T_B_S): per pose the rotation R_wb R_bs (row major) followed by the
+    optical centre t_wb + R_wb t_bs.  Plain numpy and a convenience: mlm_render_depth's contract starts at R and o as given, and
+    this is not the operation order of the integrate calls' quaternion composition (the two agree to rounding)."""
+    q = _f64(q_wb).reshape(-1, 4)
+    t = _f64(t_wb).reshape(-1, 3)
+    if len(q) != len(t):
+        raise MlmError("compose_T_ws: one translation per quaternion")
+    B = _f64(T_bs).reshape(4, 4)
+    q = q / np.linalg.norm(q, axis=1, keepdims=True)
+    w, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    R = np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+                  2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                  2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], axis=1).reshape(-1, 3, 3)
+    out = np.empty((len(q), 12), dtype=np.float64)
+    out[:, :9] = (R @ B[:3, :3]).reshape(-1, 9)
+    out[:, 9:] = t + R @ B[:3, 3]
+    return out
