@@ -229,6 +229,13 @@ class mlmap {
         check(mlm_export_esdf(h_, lo, dims, max_dist, flags, sqdist, dist, grad3), "mlm_export_esdf");
     }
 
+    // the slab lo .. lo + dims projected onto the ground plane: occupancy grid, column statistics, plane distances
+    // (mlm_export_grid2d; flags MLM_GRID_*; grid / cols / sqdist / dist host or device memory, summary host memory, NULL = skipped)
+    void export_grid2d(const int32_t lo[3], const int32_t dims[3], int flags, int min_free, int z_ref, int max_dist, int8_t *grid,
+                       int32_t *cols = nullptr, int32_t *sqdist = nullptr, float *dist = nullptr, int64_t summary[6] = nullptr) {
+        check(mlm_export_grid2d(h_, lo, dims, flags, min_free, z_ref, max_dist, grid, cols, sqdist, dist, summary), "mlm_export_grid2d");
+    }
+
     // cost-to-go field through the free space of a voxel box (mlm_export_reach; flags MLM_REACH_*; seeds3: n_seeds voxel index
     // triples; steps / parent host or device memory, summary host memory, NULL = skipped)
     void exportReach(const int32_t lo[3], const int32_t dims[3], const int32_t *seeds3, int n_seeds, int flags, int clearance, int max_steps,

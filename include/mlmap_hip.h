@@ -253,6 +253,58 @@ int mlm_export_window(mlm_handle *h, const int32_t lo[3], const int32_t dims[3],
 #define MLM_ESDF_SIGNED 8
 int mlm_export_esdf(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], int max_dist, int flags,
                     int32_t *sqdist, float *dist, float *grad3);
+/* The map projected onto the ground plane: an occupancy grid of a height band, per-column statistics and the plane distance to the
+ * nearest blocked cell.  (Takes the place of the reference's Local2OccupancyGrid2D, include/independent_modules/l2grid2d.{h,cpp},
+ * the /occupancy_map publisher behind use_projected_2d_map: it is written against a dense array the reference no longer allocates
+ * and is disabled upstream, mlmap.cpp:102-109.  The classes are those of the reference's point queries, exactly as
+ * mlm_export_window returns them; everything else is defined here, in integers.)
+ *   Slab: lo / dims form a window under mlm_export_window's rules and errors, and lo[2] > INT32_MIN.  The cell (x, y) of the plane
+ *   stands for the column of voxels (x, y, z), lo[2] <= z < lo[2] + dims[2].  The 2-D outputs are laid out [dims[1]][dims[0]], x
+ *   fastest: nav_msgs/OccupancyGrid's data order with width = dims[0], height = dims[1], resolution = subbox_d_xyz and origin
+ *   lo * subbox_d_xyz.
+ *   Predicate: O(v) is mlm_export_esdf's — the union of what MLM_GRID_OCC / _INFL / _UNKNOWN select on what mlm_export_window's
+ *   occ / infl channels return at v (released frontier-mode blocks, absent blocks and voxels beyond the key range included); at
+ *   least one of the three bits.
+ *   Column counts: n_obs voxels with O, n_unk voxels with occ == UNKNOWN, n_free voxels with occ == FREE.  The sets may overlap
+ *   (an unknown voxel counts in n_obs too with MLM_GRID_UNKNOWN; an inflated voxel may be FREE).
+ *   grid  int8   100 if n_obs > 0; otherwise -1 if n_free < min_free; otherwise 0.  0 <= min_free <= dims[2].  With min_free == 0 and
+ *                flags == MLM_GRID_OCC this is the reference's rule: 0 unless an occupied cell lies in the band, then 100
+ *                (l2grid2d.cpp:46-69).
+ *   cols  int32 x MLM_GRID_COL per cell; z_ref is an absolute voxel index, lo[2] <= z_ref < lo[2] + dims[2] (validated only when
+ *                cols is given):
+ *                  [0] n_obs   [1] n_unk   [2] n_free
+ *                  [3] the smallest z with O                          (none: lo[2] + dims[2])
+ *                  [4] the largest z with O                           (none: lo[2] - 1)
+ *                  [5] below: the largest z <= z_ref with O           (none: lo[2] - 1)
+ *                  [6] above: the smallest z >= z_ref with O          (none: lo[2] + dims[2])
+ *                  [7] UNKNOWN voxels with below < z < above
+ *                so above - below - 1 is the obstacle-free height around z_ref: the whole slab if the column has no obstacle, -1
+ *                if z_ref itself is one.
+ *   Distance: P(x, y), defined for every cell of the plane and not only the box, is grid == 100 of that column over the same z
+ *   range, or grid != 0 with MLM_GRID_DIST_UNOBSERVED.  C = max_dist, 1 <= C <= 64, required when sqdist or dist is given and
+ *   ignored otherwise.
+ *   sqdist int32  D = min(C^2, min over the cells (x', y') with P of (x - x')^2 + (y - y')^2)
+ *   dist   float  d * sqrtf((float)D), d = (float)subbox_d_xyz (sqrtf correctly rounded, one multiply: mlm_export_esdf's formula).
+ *                 There is no signed form and no gradient.
+ *   summary int64 x 6 (host memory): [0], [1], [2] the cells with grid 100, 0 and -1; [3], [4], [5] the sums of n_obs, n_unk and
+ *                 n_free over the box.
+ * grid, cols, sqdist and dist may each be host or device memory; any of the five outputs may be NULL, at least one must not be.
+ * Every word is a count, an extremum or an exact integer transform, so it has one value whatever the schedule.  The call observes the
+ * map as queries do (async mode: waits for everything submitted), runs on the stream of mlm_set_stream and returns when the outputs
+ * are written.  There is no host-mirror shortcut.  MLM_ERR_INVALID: the window errors, lo[2] == INT32_MIN, no class bit or an
+ * unknown bit in flags, min_free outside [0, dims[2]], z_ref outside the slab with cols, max_dist outside [1, 64] with sqdist /
+ * dist, no output.  MLM_ERR_CAPACITY: no device memory for the scratch — 256 bytes of counters and, with sqdist / dist, a mask byte
+ * and two u16 fields per cell of the tile grown by max_dist - 1 per side (the plane is processed in tiles of whole rows, a grown
+ * tile has at most 2^24 cells: 80 MB), sharing mlm_export_esdf's buffer — or for the staging of host outputs (at most 41 bytes x
+ * 2^20 cells, each channel rounded up to 256 bytes, sharing mlm_export_window's buffer); both are kept by the handle and counted in
+ * mlm_frame_stats.device_bytes.  The handle stays usable after either error. */
+#define MLM_GRID_OCC 1              /* same bits and meaning as MLM_ESDF_OCC / _INFL / _UNKNOWN */
+#define MLM_GRID_INFL 2
+#define MLM_GRID_UNKNOWN 4
+#define MLM_GRID_DIST_UNOBSERVED 16 /* cells with grid == -1 are obstacles of the distance field too */
+#define MLM_GRID_COL 8              /* int32 per column row */
+int mlm_export_grid2d(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], int flags, int min_free, int z_ref,
+                      int max_dist, int8_t *grid, int32_t *cols, int32_t *sqdist, float *dist, int64_t summary[6]);
 /* Batched segment casts through the voxel map (no reference counterpart: the reference has no segment query; the classes a ray
  * meets are those of its point queries, the path is defined here, in integers).  Segment i runs from p0[i] to p1[i] (n x 3 world
  * positions).  d = subbox_d_xyz, voxel indices are those of mlm_export_window.

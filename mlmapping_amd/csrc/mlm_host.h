@@ -159,6 +159,39 @@ inline MlmEsdfPlan mlm_esdf_plan(const long long D[3], int C, bool grad, long lo
     return p;
 }
 
+// Tiles of mlm_export_grid2d (mlm_kernels_grid.h) for a plane of D[0] x D[1] cells, truncation C (cells), distances asked for or
+// not: mlm_esdf_plan's rule in two dimensions.  A tile is whole rows of the plane, else a piece of one row, so that its outputs
+// are one contiguous range of the plane's [D1][D0] layout.  The grown tile (the tile plus H = C - 1 cells per side with distances,
+// H = 0 without) holds at most box_cap cells, the tile itself at most out_cap (the staging of host destinations; knob
+// "grid_tile": any cap from one cell up, for the tests).  Tile origins are the multiples of T per axis, n[a] = ceil(D[a] / T[a])
+// of them, the last one cut to the plane.  T[0] == 0: box_cap < (2H + 1)^2 or out_cap < 1, no tile fits.
+constexpr long long kGridBoxCells = 1ll << 24;       // grown tile: mask (1 B) + two u16 fields per cell, 80 MB
+constexpr long long kGridMinBoxCells = 127ll * 127;  // the smallest box every call fits: one cell grown by H = 63
+constexpr long long kGridStageCells = 1ll << 20;     // staged tile: <= 41 bytes per cell
+struct MlmGridPlan {
+    long long T[2], n[2];
+    long long H, grown; // grown: cells of a full grown tile
+};
+inline MlmGridPlan mlm_grid_plan(const long long D[2], int C, bool dist, long long box_cap, long long out_cap) {
+    MlmGridPlan p{};
+    const long long H = dist ? C - 1 : 0, h2 = 2 * H;
+    p.H = H;
+    auto fits = [&](long long tx, long long ty) { return (tx + h2) * (ty + h2) <= box_cap && tx * ty <= out_cap; };
+    if (fits(D[0], 1)) {
+        p.T[0] = D[0];
+        p.T[1] = std::min({D[1], box_cap / (D[0] + h2) - h2, out_cap / D[0]});
+    } else if (fits(1, 1)) {
+        p.T[0] = std::min({D[0], box_cap / (1 + h2) - h2, out_cap});
+        p.T[1] = 1;
+    } else {
+        return p;
+    }
+    for (int a = 0; a < 2; ++a) p.n[a] = (D[a] + p.T[a] - 1) / p.T[a];
+    p.grown = (p.T[0] + h2) * (p.T[1] + h2);
+    return p;
+}
+inline bool mlm_grid_tile_ok(long long cells) { return cells >= 1 && cells <= kGridStageCells; }
+
 // Geometry, scratch and sweep cap of mlm_export_reach (mlm_kernels_reach.h, mlm_reach.h) for a box of D[0] x D[1] x D[2] voxels cut
 // into tiles of T[0] x T[1] x T[2] (knob "reach_tile": T[0] | T[1] << 8 | T[2] << 16; the last tile per axis is cut to the box).
 // A workgroup of k_reach_sweep stages a tile and its one-voxel halo as u32 in LDS: at most kReachHaloVoxels of them (60 KB, two

@@ -31,6 +31,7 @@
 #include "mlm_kernels_sector.h"
 #include "mlm_kernels_window.h"
 #include "mlm_kernels_esdf.h"
+#include "mlm_kernels_grid.h"
 #include "mlm_kernels_rays.h"
 #include "mlm_kernels_render.h"
 #include "mlm_kernels_boxes.h"
@@ -1218,6 +1219,7 @@ int mlm_export_window(mlm_handle *h, const int32_t lo[3], const int32_t dims[3],
 extern "C++" {
 namespace {
 constexpr unsigned int kEsdfMaskGrid = 2048, kEsdfPassGrid = 4096;
+constexpr unsigned int kGridColGrid = 1u << 16; // most workgroups of k_grid_columns (a brick stack each, grid-stride)
 constexpr unsigned int kReachGrid = 1u << 16; // most workgroups of the mlm_export_reach kernels (grid-stride loops over voxels / tiles)
 
 // the mask and the three passes of one tile of mlm_export_esdf (mlm_kernels_esdf.h) into fa [ez][ey][ex]; T: u16 (unsigned) or
@@ -1358,6 +1360,139 @@ int mlm_export_esdf(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], i
                                                  h->stream));
             }
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MLM_OK;
+}
+
+int mlm_export_grid2d(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], int flags, int min_free, int z_ref, int max_dist,
+                      int8_t *grid, int32_t *cols, int32_t *sqdist, float *dist, int64_t summary[6]) {
+    if (!h) return MLM_ERR_INVALID;
+    MLM_LOCK(h);
+    const bool want_dist = sqdist || dist;
+    if (!lo || !dims || (flags & 7) == 0 || (flags & ~(7 | MLM_GRID_DIST_UNOBSERVED)) || (!grid && !cols && !sqdist && !dist && !summary)) {
+        h->err = "mlm_export_grid2d: null window, no class bit or an unknown bit in flags, or no output";
+        return MLM_ERR_INVALID;
+    }
+    long long D[3], nvox = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (dims[a] < 1 || (long long)lo[a] + dims[a] > 0x7FFFFFFFll) {
+            h->err = "mlm_export_grid2d: dims must be >= 1 and lo + dims must fit an int32";
+            return MLM_ERR_INVALID;
+        }
+        D[a] = dims[a];
+        nvox *= D[a];
+        if (nvox > 0x7FFFFFFFll) {
+            h->err = "mlm_export_grid2d: more than 2^31 - 1 voxels";
+            return MLM_ERR_INVALID;
+        }
+    }
+    if (lo[2] == INT32_MIN || min_free < 0 || min_free > dims[2] || (cols && (z_ref < lo[2] || z_ref >= lo[2] + dims[2])) ||
+        (want_dist && (max_dist < 1 || max_dist > 64))) {
+        h->err = "mlm_export_grid2d: lo[2] == INT32_MIN, min_free outside [0, dims[2]], z_ref outside the slab or max_dist outside [1, 64]";
+        return MLM_ERR_INVALID;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = drain(h);
+    if (rc) return rc;
+
+    // channels: destination, bytes per cell, written in place or staged
+    void *dst[4] = {grid, cols, sqdist, dist};
+    const size_t elem[4] = {1, MLM_GRID_COL * sizeof(int32_t), sizeof(int32_t), sizeof(float)};
+    bool staged[4];
+    bool any_staged = false;
+    for (int c = 0; c < 4; ++c) {
+        staged[c] = dst[c] && !win_in_place(dst[c]);
+        any_staged |= staged[c];
+    }
+    const int C = want_dist ? max_dist : 1;
+    long long out_cap = any_staged ? kGridStageCells : (1ll << 62), kv;
+    if (knob("grid_tile", kv)) out_cap = std::min(out_cap, kv);
+    const MlmGridPlan plan = mlm_grid_plan(D, C, want_dist, kGridBoxCells, out_cap);
+    if (plan.T[0] < 1) { // (not with the caps mlm_debug_set admits)
+        h->err = "mlm_export_grid2d: no tile fits the cell cap";
+        return MLM_ERR_INVALID;
+    }
+    const long long tile_cells = plan.T[0] * plan.T[1];
+    size_t stage_off[4] = {0, 0, 0, 0}, stage_bytes = 0;
+    for (int c = 0; c < 4; ++c)
+        if (staged[c]) {
+            stage_off[c] = stage_bytes;
+            stage_bytes += ((size_t)tile_cells * elem[c] + 255) & ~(size_t)255;
+        }
+    // scratch: the summary counters, then (with distances) the mask and two u16 fields of the grown tile
+    const size_t ctrl_bytes = 256, mask_bytes = want_dist ? ((size_t)plan.grown + 255) & ~(size_t)255 : 0,
+                 field_bytes = want_dist ? ((size_t)plan.grown * 2 + 255) & ~(size_t)255 : 0;
+    if ((rc = win_reserve(h, h->d_esdf_scratch, h->esdf_scratch_bytes, ctrl_bytes + mask_bytes + 2 * field_bytes, "mlm_export_grid2d"))) return rc;
+    if (stage_bytes && (rc = win_reserve(h, h->d_win_stage, h->win_stage_bytes, stage_bytes, "mlm_export_grid2d"))) return rc;
+    if (summary && !h->h_reach_ctrl) HIPCHK(h, hipHostMalloc((void **)&h->h_reach_ctrl, (size_t)kReachCtrlBytes, hipHostMallocDefault));
+    unsigned long long *sums = summary ? (unsigned long long *)h->d_esdf_scratch : nullptr;
+    uint8_t *mask = want_dist ? (uint8_t *)h->d_esdf_scratch + ctrl_bytes : nullptr;
+    uint16_t *fa = (uint16_t *)((char *)h->d_esdf_scratch + ctrl_bytes + mask_bytes), *fb = (uint16_t *)((char *)fa + field_bytes);
+    if (sums) HIPCHK(h, hipMemsetAsync(sums, 0, 6 * sizeof(unsigned long long), h->stream));
+
+    const int n = h->P.n;
+    const long long H = plan.H;
+    auto floor_div = [n](long long v) { return v >= 0 ? v / n : -((-v + n - 1) / n); };
+    // a workgroup has one lane per column of a brick stack: whole waves, as many as a full brick's n^2 columns need
+    const unsigned int block = (unsigned int)std::min<long long>(MLM_BLOCK, (((long long)n * n + 63) / 64) * 64);
+    for (long long y0 = 0; y0 < D[1]; y0 += plan.T[1])
+        for (long long x0 = 0; x0 < D[0]; x0 += plan.T[0]) {
+            MlmGrid G{};
+            const long long org[2] = {x0, y0};
+            for (int a = 0; a < 2; ++a) {
+                G.tlo[a] = lo[a] + org[a];
+                G.td[a] = (int)std::min(plan.T[a], D[a] - org[a]);
+                G.glo[a] = G.tlo[a] - H; // (64-bit: the grown tile of a window at the int32 edge reaches past it)
+                G.gd[a] = G.td[a] + (int)(2 * H);
+                G.b0[a] = floor_div(G.glo[a]);
+                G.nb[a] = (int)(floor_div(G.glo[a] + G.gd[a] - 1) - G.b0[a] + 1);
+            }
+            G.zlo = lo[2];
+            G.zhi = lo[2] + dims[2];
+            G.b0[2] = floor_div(G.zlo);
+            G.nb[2] = (int)(floor_div((long long)G.zhi - 1) - G.b0[2] + 1);
+            G.flags = flags;
+            G.min_free = min_free;
+            G.z_ref = z_ref;
+            const long long out_base = y0 * D[0] + x0; // (every channel pointer is where the tile's first cell goes)
+            void *ch[4];
+            for (int c = 0; c < 4; ++c)
+                ch[c] = !dst[c] ? nullptr
+                                : staged[c] ? (void *)((char *)h->d_win_stage + stage_off[c])
+                                            : (void *)((char *)dst[c] + (size_t)out_base * elem[c]);
+            G.grid = (int8_t *)ch[0];
+            G.cols = (int32_t *)ch[1];
+            G.mask = mask;
+            G.sums = sums;
+            const long long stacks = (long long)G.nb[0] * G.nb[1];
+            const dim3 cgrid((unsigned int)std::min<long long>(stacks, kGridColGrid));
+            if (cols)
+                hipLaunchKernelGGL(k_grid_columns<true>, cgrid, dim3(block), 0, h->stream, h->P, G);
+            else
+                hipLaunchKernelGGL(k_grid_columns<false>, cgrid, dim3(block), 0, h->stream, h->P, G);
+            const long long nt = (long long)G.td[0] * G.td[1];
+            if (want_dist) {
+                // x: mask [gd1][gd0] -> fa [gd1][td0];  y: fa -> fb [td1][td0]
+                const long long rows = G.gd[1], xtasks = rows * ((G.td[0] + 63) / 64);
+                hipLaunchKernelGGL(k_esdf_x<false>, dim3((unsigned int)std::min<long long>((xtasks + 3) / 4, kEsdfPassGrid)), dim3(MLM_BLOCK), 0,
+                                   h->stream, (const uint8_t *)mask, (void *)fa, rows, G.gd[0], G.td[0], C);
+                const int lc = (G.td[1] + MLM_ESDF_LINE_TL - 1) / MLM_ESDF_LINE_TL, TL = (G.td[1] + lc - 1) / lc;
+                const long long ltiles = (long long)lc * ((G.td[0] + 63) / 64);
+                hipLaunchKernelGGL(k_esdf_line<uint16_t>, dim3((unsigned int)std::min<long long>(ltiles, kEsdfPassGrid)), dim3(MLM_BLOCK),
+                                   (size_t)(TL + 2 * C - 2) * 64 * sizeof(uint16_t), h->stream, (const uint16_t *)fa, fb, (long long)G.td[0], G.td[1],
+                                   1, C, TL);
+                hipLaunchKernelGGL(k_grid_dist_out, dim3(std::min<unsigned int>(grid_for((size_t)nt), kEsdfPassGrid)), dim3(MLM_BLOCK), 0, h->stream,
+                                   (const uint16_t *)fb, nt, (float)h->cfg.subbox_d_xyz, (int32_t *)ch[2], (float *)ch[3]);
+            }
+            HIPCHK(h, hipGetLastError());
+            for (int c = 0; c < 4; ++c)
+                if (staged[c])
+                    HIPCHK(h, hipMemcpyAsync((char *)dst[c] + (size_t)out_base * elem[c], ch[c], (size_t)nt * elem[c], hipMemcpyDefault, h->stream));
+        }
+    unsigned long long *h_cnt = (unsigned long long *)h->h_reach_ctrl;
+    if (summary) HIPCHK(h, hipMemcpyAsync(h_cnt, sums, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (summary)
+        for (int i = 0; i < 6; ++i) summary[i] = (int64_t)h_cnt[i];
     return MLM_OK;
 }
 

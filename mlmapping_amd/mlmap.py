@@ -26,6 +26,8 @@ LIB_PATH = os.environ.get("MLMAP_HIP_LIB") or os.path.join(_HERE, "lib", "libmlm
 MLM_OK = 0
 # mlm_export_esdf flags (include/mlmap_hip.h): obstacle predicates (their union) and the signed field
 MLM_ESDF_OCC, MLM_ESDF_INFL, MLM_ESDF_UNKNOWN, MLM_ESDF_SIGNED = 1, 2, 4, 8
+# mlm_export_grid2d: the class bits (their union), "unobserved cells are obstacles of the distance too", int32 per column row
+MLM_GRID_OCC, MLM_GRID_INFL, MLM_GRID_UNKNOWN, MLM_GRID_DIST_UNOBSERVED, MLM_GRID_COL = 1, 2, 4, 16, 8
 # mlm_export_reach: obstacle predicates (their union; none: no obstacles), steps of a voxel not reached, parent code of a seed
 MLM_REACH_OCC, MLM_REACH_INFL, MLM_REACH_UNKNOWN, MLM_REACH_NONE, MLM_REACH_SEED = 1, 2, 4, -1, 6
 # mlm_export_route: the same predicates, cost of a voxel not reached, parent code of a seed (0..25 are the moves' codes)
@@ -52,7 +54,7 @@ ABI_SYMBOLS = [
     "mlm_query_odds", "mlm_query_odd_grad", "mlm_query_odds_at", "mlm_export_frontier_points", "mlm_import_blocks",
     "mlm_merge_pack", "mlm_merge_finish",
     "mlm_set_free_in_bound", "mlm_inflate_map", "mlm_block_count",
-    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_reach", "mlm_export_route", "mlm_export_clusters", "mlm_query_rays", "mlm_render_depth", "mlm_query_views", "mlm_query_boxes", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
+    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_grid2d", "mlm_export_reach", "mlm_export_route", "mlm_export_clusters", "mlm_query_rays", "mlm_render_depth", "mlm_query_views", "mlm_query_boxes", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
     "mlm_get_awareness_hits",
     "mlm_get_awareness_misses", "mlm_get_T_ls", "mlm_get_odds_table", "mlm_get_kernel_times",
     "mlm_enable_kernel_timing", "mlm_set_timed_kernel", "mlm_host_register", "mlm_host_unregister", "mlm_debug_set", "mlm_debug_reset",
@@ -147,6 +149,7 @@ def load_library(path: Optional[str] = None):
     L.mlm_export_blocks.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     L.mlm_export_window.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
     L.mlm_export_esdf.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
+    L.mlm_export_grid2d.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     L.mlm_export_reach.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     L.mlm_export_route.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp]
     L.mlm_export_clusters.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i32, vp]
@@ -495,6 +498,72 @@ class MLMap:
         ptr = [None if v is None else ctypes.c_void_p(v) for v in (sqdist, dist, grad)]
         flags = self._esdf_flags(occ, infl, unknown, signed)
         self._chk(self._L.mlm_export_esdf(self._h, _p(lo_a), _p(dims_a), int(max_dist), flags, *ptr), "mlm_export_esdf")
+
+    def export_grid2d(self, lo, dims, occ=True, infl=False, unknown=False, min_free: int = 0, z_ref: Optional[int] = None,
+                      max_dist: Optional[int] = None, dist_unobserved=False, grid=True, cols=False, sqdist=False, dist=False) -> Dict[str, np.ndarray]:
+        """The slab lo <= v < lo + dims (voxel indices as export_window) projected onto the ground plane: {"grid": int8 (dy, dx),
+        100 where the column lo[2] <= z < lo[2] + dims[2] holds an obstacle, else -1 where it holds fewer than min_free FREE voxels,
+        else 0 — nav_msgs/OccupancyGrid's data order; "cols": int32 (dy, dx, 8): n_obs, n_unk, n_free, lowest and highest obstacle z,
+        the nearest obstacle z at or below and at or above z_ref (none: lo[2] - 1 / lo[2] + dims[2]), the UNKNOWN voxels strictly
+        between those two; "sqdist": int32 and "dist": float32 (dy, dx), the plane distance to the nearest cell with grid == 100
+        (dist_unobserved: grid != 0) anywhere in the plane, squared in cells and clamped at max_dist^2, and in metres; "summary":
+        int64 [cells with 100, 0, -1, sum of n_obs, n_unk, n_free]}.  Obstacles are the union of occ / infl / unknown as in
+        export_esdf; z_ref=None is the middle layer lo[2] + dims[2] // 2; max_dist (1..64) is needed for sqdist / dist
+        (mlm_export_grid2d; grid2d_band turns a height band in metres into lo[2], dims[2] and z_ref)."""
+        lo_a, dims_a = self._window_args(lo, dims)
+        shape = (int(dims_a[1]), int(dims_a[0]))
+        out = {}
+        if grid:
+            out["grid"] = np.empty(shape, dtype=np.int8)
+        if cols:
+            out["cols"] = np.empty(shape + (MLM_GRID_COL,), dtype=np.int32)
+        if sqdist:
+            out["sqdist"] = np.empty(shape, dtype=np.int32)
+        if dist:
+            out["dist"] = np.empty(shape, dtype=np.float32)
+        out["summary"] = np.zeros(6, dtype=np.int64)
+        ptr = [_p(out[k]) if k in out else None for k in ("grid", "cols", "sqdist", "dist", "summary")]
+        self._chk(self._L.mlm_export_grid2d(self._h, _p(lo_a), _p(dims_a), self._grid_flags(occ, infl, unknown, dist_unobserved), int(min_free),
+                                            self._grid_z_ref(lo_a, dims_a, z_ref), int(max_dist or 0), *ptr), "mlm_export_grid2d")
+        return out
+
+    def export_grid2d_dev(self, lo, dims, occ=True, infl=False, unknown=False, min_free: int = 0, z_ref: Optional[int] = None,
+                          max_dist: Optional[int] = None, dist_unobserved=False, grid: Optional[int] = None, cols: Optional[int] = None,
+                          sqdist: Optional[int] = None, dist: Optional[int] = None) -> np.ndarray:
+        """Same into device memory: pointers (ints) to dy*dx int8 / (x8) int32 / int32 / float32 elements, None = skipped; returns
+        the summary."""
+        lo_a, dims_a = self._window_args(lo, dims)
+        summary = np.zeros(6, dtype=np.int64)
+        ptr = [None if v is None else ctypes.c_void_p(v) for v in (grid, cols, sqdist, dist)]
+        self._chk(self._L.mlm_export_grid2d(self._h, _p(lo_a), _p(dims_a), self._grid_flags(occ, infl, unknown, dist_unobserved), int(min_free),
+                                            self._grid_z_ref(lo_a, dims_a, z_ref), int(max_dist or 0), *ptr, _p(summary)), "mlm_export_grid2d")
+        return summary
+
+    @staticmethod
+    def grid2d_band(min_z: float, max_z: float, d: float, z_vehicle: Optional[float] = None) -> Tuple[int, int, int]:
+        """(lo_z, dims_z, z_ref) of export_grid2d for the height band min_z .. max_z in metres at voxel size d — the reference's keys
+        projected_2d_map_min_z / projected_2d_map_max_z and subbox_d_xyz.  With z_vehicle (use_relative_height) the band is min_z +
+        z_vehicle .. max_z + z_vehicle.  The slab covers the layers floor(zmin / d) .. floor(zmax / d) inclusive; z_ref is
+        floor(z_vehicle / d) clamped into the slab, without z_vehicle the slab's middle layer lo_z + dims_z // 2.  Plain double
+        arithmetic (Python floats): one addition, one division and one floor per bound."""
+        zmin, zmax = float(min_z), float(max_z)
+        if z_vehicle is not None:
+            zmin, zmax = zmin + float(z_vehicle), zmax + float(z_vehicle)
+        if not zmin <= zmax or not d > 0:
+            raise MlmError("grid2d_band: needs min_z <= max_z and d > 0")
+        lo_z, hi_z = int(np.floor(zmin / float(d))), int(np.floor(zmax / float(d)))
+        dims_z = hi_z - lo_z + 1
+        z_ref = lo_z + dims_z // 2 if z_vehicle is None else min(max(int(np.floor(float(z_vehicle) / float(d))), lo_z), hi_z)
+        return lo_z, dims_z, z_ref
+
+    @staticmethod
+    def _grid_flags(occ, infl, unknown, dist_unobserved) -> int:
+        return ((MLM_GRID_OCC if occ else 0) | (MLM_GRID_INFL if infl else 0) | (MLM_GRID_UNKNOWN if unknown else 0)
+                | (MLM_GRID_DIST_UNOBSERVED if dist_unobserved else 0))
+
+    @staticmethod
+    def _grid_z_ref(lo_a, dims_a, z_ref) -> int:
+        return int(lo_a[2]) + int(dims_a[2]) // 2 if z_ref is None else int(z_ref)
 
     def export_reach(self, lo, dims, seeds, occ=True, infl=False, unknown=False, clearance: int = 0, max_steps: Optional[int] = None,
                      steps=True, parent=False) -> Dict[str, np.ndarray]:
