@@ -334,6 +334,24 @@ class mlmap {
         if (st < 0) throw std::runtime_error("growBox: invalid box");
         return st == 1;
     }
+    // exact nearest obstacle voxel of batched positions (mlm_query_nearest; flags MLM_NEAR_*, max_dist 1 .. 64 voxels; pos and outputs
+    // host or device memory, NULL = skipped)
+    void queryNearest(const double *pos, int n, int max_dist, int flags, int8_t *status, int32_t *voxel3 = nullptr, int32_t *delta3 = nullptr,
+                      int64_t *sq = nullptr, double *dist = nullptr) {
+        check(mlm_query_nearest(h_, pos, n, max_dist, flags, status, voxel3, delta3, sq, dist), "mlm_query_nearest");
+    }
+    // one position (answered from the host mirror while (2 max_dist + 1)^3 <= 2^18: no launch): the nearest voxel that `flags`
+    // selects within max_dist voxels, its distance in metres, and optionally the vector to its centre in 1/1024 voxel; false if
+    // there is none.  A position that is not finite or beyond the lattice throws.
+    template <class V3> bool nearestObstacle(const V3 &pos_w, int max_dist, int flags, Vec3I &voxel, double &dist, int32_t *delta3 = nullptr) {
+        const double p[3] = {pos_w[0], pos_w[1], pos_w[2]};
+        int8_t st = 0;
+        int32_t v[3] = {0, 0, 0};
+        check(mlm_query_nearest(h_, p, 1, max_dist, flags, &st, v, delta3, nullptr, &dist), "mlm_query_nearest");
+        if (st < 0) throw std::runtime_error("nearestObstacle: invalid position");
+        voxel = Vec3I{{v[0], v[1], v[2]}};
+        return st == 1;
+    }
 
     // planners that query thousands of positions per cycle should use the batched entry points directly
     mlm_handle *handle() { return h_; }

@@ -465,6 +465,47 @@ int mlm_query_views(mlm_handle *h, const double *p0, const double *p1, const int
 int mlm_query_boxes(mlm_handle *h, const int32_t *box6, int n, int flags, const int32_t max_grow[6],
                     const int32_t lo[3], const int32_t dims[3],
                     int8_t *status, int32_t *out6, uint8_t *closed, int64_t *table);
+/* Exact nearest obstacle voxel of batched points: for each position the obstacle voxel closest to it and the vector to that voxel's
+ * centre, with a sub-voxel part — the {point, obstacle} pair gradient-based trajectory optimisers push away from.  (No reference
+ * counterpart: the reference has no such query; the classes are those of its point queries, the metric and the tie rule are defined
+ * here, in integers, with exactly one answer.)  Voxel indices and classes are those of mlm_export_window.
+ *   Lattice: position i is pos[3i .. 3i+2], world frame.  Per axis Q = floor((x / d) * 1024.0) (IEEE double, d = subbox_d_xyz):
+ *   mlm_query_rays' lattice, 1024 units per voxel.  The point is INVALID if a Q is not finite or |Q| >= 2^40: status -1, voxel3
+ *   0,0,0, delta3 0,0,0, sq MLM_NEAR_NONE, dist -1.0.  v = Q >> 10 (floor) is the point's voxel; |v| <= 2^30, so no index below
+ *   leaves int32.
+ *   Predicate: O(o) is the union of what `flags` selects (MLM_NEAR_OCC getOccupancy(centre) == OCCUPIED, MLM_NEAR_INFL
+ *   getInflateOccupancy(centre) == OCCUPIED, MLM_NEAR_UNKNOWN getOccupancy(centre) == UNKNOWN), exactly as in mlm_query_rays
+ *   (released frontier-mode blocks, absent blocks and voxels beyond the key range, which are UNKNOWN, included); at least one of the
+ *   three bits must be set.
+ *   Metric: C = max_dist, 1 .. 64 voxels.  For a voxel o, delta_a(o) = 1024 * o_a + 512 - Q_a is the vector from the point to the
+ *   centre of o in 1/1024 voxel, E(o) = sum over the axes of delta_a^2 (int64, below 2^34).  The candidates are the voxels of the
+ *   whole map with O(o) and E(o) <= (1024 * C)^2: a ball, not a cube; every candidate has |o_a - v_a| <= C.
+ *   Answer: the candidate with the smallest key = E * 2^24 + (o_z - v_z + 64) * 2^16 + (o_y - v_y + 64) * 2^8 + (o_x - v_x + 64):
+ *   the smallest E, ties to the smallest z, then y, then x.
+ *   Per point:                        candidate found                         no candidate
+ *     status  int8                    1                                       0
+ *     voxel3  int32 x 3               o                                       v
+ *     delta3  int32 x 3               delta(o)                                0,0,0
+ *     sq      int64                   E(o)                                    MLM_NEAR_NONE
+ *     dist    double                  ((double)(float)d * sqrt((double)E)) / 1024.0   -1.0
+ *   dist is three IEEE double operations in that order (sqrt correctly rounded, nothing fused); -delta3 / |delta3| is the direction
+ *   that gains clearance fastest.  For a point on a voxel centre sq == 2^20 * |v - o|^2, mlm_export_esdf's sqdist wherever
+ *   sqdist < C^2.  Every word is a function of the map and the arguments alone.
+ * Any output may be NULL, at least one must not be; pos and each output on its own may be host or device memory.  The call observes
+ * the map as queries do (async mode: waits for everything submitted), runs on the stream of mlm_set_stream and returns when the
+ * outputs are written.  A batch in host memory of at most 64 points (8 while the host mirror needs a refresh: mlm_query_boxes' rule)
+ * with n * (2C + 1)^3 <= 2^18 is answered from the host mirror without a launch (same answers); everything else, and every batch
+ * after mlm_set_host_mirror_limit(h, 0), runs as a kernel.  MLM_ERR_INVALID: n < 0, pos NULL with n > 0, no class bit set or an
+ * unknown flag bit, max_dist outside [1, 64], no output; n == 0 is MLM_OK.  MLM_ERR_CAPACITY: no device memory for the staging of
+ * host inputs / outputs (at most 65 bytes x 2^18 points, each part rounded up to 256 bytes, in the buffer mlm_query_rays stages in,
+ * kept by the handle and counted in mlm_frame_stats.device_bytes; larger batches run in chunks).  The handle stays usable after
+ * either error. */
+#define MLM_NEAR_OCC 1 /* same bits and same meaning as MLM_RAY_OCC / _INFL / _UNKNOWN */
+#define MLM_NEAR_INFL 2
+#define MLM_NEAR_UNKNOWN 4
+#define MLM_NEAR_NONE (-1) /* sq of a point with no obstacle in range */
+int mlm_query_nearest(mlm_handle *h, const double *pos, int n, int max_dist, int flags,
+                      int8_t *status, int32_t *voxel3, int32_t *delta3, int64_t *sq, double *dist);
 /* Cost-to-go field through the free space of a box of voxels (no reference counterpart: the reference has no such field; the
  * classes behind it are those of its point queries, the field is defined here, in integers).  Voxel indices, window, layout
  * ([dims[2]][dims[1]][dims[0]], x fastest) and centres are those of mlm_export_window.

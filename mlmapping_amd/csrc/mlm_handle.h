@@ -139,6 +139,12 @@ constexpr int kRenderChunk = 1 << 20;        // most pixels per launch of k_rend
 constexpr int kRenderTileDefault = 2;        // k_render's tile: 0 64 x 1, 1 16 x 4, 2 8 x 8 (profiles/render_rate.json)
 constexpr int kBoxChunk = 1 << 18;           // boxes per launch of k_boxes: bounds the staging of host inputs / outputs (82 bytes per box)
 constexpr unsigned int kBoxGrid = 8192;      // most workgroups of k_boxes (a wave per box, grid-stride): 32 768 waves, four times what the chip holds
+// mlm_query_nearest: a batch in host memory is answered on the host when it has at most as many points as mlm_query_boxes allows
+// boxes (64 / 8 by default) AND the cubes v +- max_dist of its points — the most voxels the search can read, known from the
+// arguments alone — hold at most kNearMirrorVoxels voxels together
+constexpr long long kNearMirrorVoxels = 1ll << 18;
+constexpr int kNearChunk = 1 << 18;          // points per launch of k_nearest: bounds the staging of host inputs / outputs (65 bytes per point)
+constexpr unsigned int kNearGrid = 8192;     // most workgroups of k_nearest (a wave per point, grid-stride), as kBoxGrid
 
 // A frame on its own with at most this many strips of 256 points (sampled callbacks, point lists: 4 096 points) runs its cells' float chains
 // inside k_rank<true> instead of launching k_chain_lanes — a launch of its own costs a lone frame the kernel boundary (1.5 us) and the few
@@ -184,7 +190,7 @@ struct mlm_handle {
     // need (staged rays use d_ray_stage, a staged exclude / mark d_win_stage)
     void *d_views = nullptr;
     size_t views_bytes = 0;
-    // mlm_query_boxes stages the host inputs / outputs of one chunk of boxes in d_ray_stage too
+    // mlm_query_boxes stages the host inputs / outputs of one chunk of boxes in d_ray_stage too, mlm_query_nearest those of one chunk of points
     unsigned int rays_grid = 1024; // most workgroups of k_rays (knob "rays_grid"): 2^20 rays are four per lane
     // mlm_render_depth stages host poses, one chunk of host per-pixel outputs and a host table in d_ray_stage too
     int render_tile = kRenderTileDefault; // (knob "render_tile")

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "mlm_boxgrow.h"
+#include "mlm_nearest.h"
 #include "mlm_raywalk.h"
 
 namespace mlm_host {
@@ -290,6 +291,51 @@ struct MapView {
             if (closed) closed[i] = (uint8_t)o.closed;
             if (table)
                 for (int k = 0; k < 4; ++k) table[4 * (size_t)i + k] = o.row[k];
+        }
+    }
+    // mlm_query_nearest on the mirrored planes: the search of mlm_nearest.h over the same classes.  One table probe per block that the
+    // bounds let through, no plane memory for an absent or released block.
+    struct NearScan {
+        const MapView &v;
+        int slot = -1;
+        int probe(const int g[3]) {
+            slot = v.find(g[0], g[1], g[2]);
+            if (slot < 0) return 4;
+            if (v.col[slot]) return RayClasses::occ_bits(v.occ[(size_t)slot * v.cells]);
+            return -1;
+        }
+        unsigned long long scan(const MlmNearPoint &p, const int g[3], const int c0[3], const int c1[3], int flags) const {
+            unsigned long long best = MLM_NEAR_NOKEY;
+            for (int cz = c0[2]; cz <= c1[2]; ++cz)
+                for (int cy = c0[1]; cy <= c1[1]; ++cy)
+                    for (int cx = c0[0]; cx <= c1[0]; ++cx) {
+                        const size_t at = (size_t)slot * v.cells + (size_t)((cz * v.n + cy) * v.n + cx);
+                        int bits = RayClasses::occ_bits(v.occ[at]);
+                        if (flags & 2) bits |= v.infl[at] == 'o' ? 2 : 0; // (infl is read only when INFL is selected, as in k_nearest)
+                        if (!(bits & flags)) continue;
+                        const int32_t o[3] = {g[0] * v.n + cx, g[1] * v.n + cy, g[2] * v.n + cz};
+                        best = std::min(best, mlm_near_voxel_key(p, o));
+                    }
+            return best;
+        }
+    };
+    void nearest_one(const double pos[3], int max_dist, int flags, MlmNearResult &o) const {
+        NearScan vox{*this};
+        mlm_near_search(pos, d_sub, n, max_dist, flags, vox, o);
+    }
+    // a batch, any output may be null (mlm_query_nearest's layout)
+    void nearest(const double *pos, int count, int max_dist, int flags, int8_t *status, int32_t *voxel3, int32_t *delta3, int64_t *sq,
+                 double *dist) const {
+        for (int i = 0; i < count; ++i) {
+            MlmNearResult o;
+            nearest_one(pos + 3 * (size_t)i, max_dist, flags, o);
+            if (status) status[i] = (int8_t)o.status;
+            for (int a = 0; a < 3; ++a) {
+                if (voxel3) voxel3[3 * (size_t)i + a] = o.voxel[a];
+                if (delta3) delta3[3 * (size_t)i + a] = o.delta[a];
+            }
+            if (sq) sq[i] = o.sq;
+            if (dist) dist[i] = o.dist;
         }
     }
 };

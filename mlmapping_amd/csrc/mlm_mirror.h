@@ -286,6 +286,13 @@ bool mirror_boxes_wanted(const mlm_handle *h, const int32_t *box6, int n, const 
     }
     return true;
 }
+// ... and a batch of points of mlm_query_nearest: few points whose cubes v +- C are small enough together (kNearMirrorVoxels, mlm_handle.h)
+bool mirror_nearest_wanted(const mlm_handle *h, int n, int max_dist) {
+    const MlmMirror &M = h->mir;
+    if (!M.enabled || (long long)n * 4 > (M.dirty ? M.max_dirty : M.max_clean)) return false;
+    const long long side = 2 * (long long)max_dist + 1;
+    return n * side * side * side <= kNearMirrorVoxels;
+}
 // drain + refresh if the map changed since the mirror was filled; the caller holds the lock
 int mirror_sync(mlm_handle *h) {
     if (h->mir.eager_pending) {

@@ -35,6 +35,7 @@
 #include "mlm_kernels_rays.h"
 #include "mlm_kernels_render.h"
 #include "mlm_kernels_boxes.h"
+#include "mlm_kernels_nearest.h"
 #include "mlm_kernels_views.h"
 #include "mlm_kernels_reach.h"
 #include "mlm_kernels_route.h"
@@ -2184,6 +2185,65 @@ int mlm_query_boxes(mlm_handle *h, const int32_t *box6, int n, int flags, const 
         hipLaunchKernelGGL(k_boxes, grid, dim3(MLM_BLOCK), 0, h->stream, h->P, B);
         HIPCHK(h, hipGetLastError());
         for (int c = 1; c < 5; ++c)
+            if (staged[c])
+                HIPCHK(h, hipMemcpyAsync((char *)ch[c] + (size_t)i0 * elem[c], at[c], (size_t)m * elem[c], hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MLM_OK;
+}
+
+int mlm_query_nearest(mlm_handle *h, const double *pos, int n, int max_dist, int flags, int8_t *status, int32_t *voxel3, int32_t *delta3,
+                      int64_t *sq, double *dist) {
+    if (!h) return MLM_ERR_INVALID;
+    MLM_LOCK(h);
+    if (n < 0 || (n > 0 && !pos) || (flags & ~7) || !(flags & 7) || max_dist < 1 || max_dist > MLM_NEAR_MAX_DIST ||
+        (!status && !voxel3 && !delta3 && !sq && !dist)) {
+        h->err = "mlm_query_nearest: negative n, a null pos, no class bit or an unknown flag bit, max_dist outside [1, 64] or no output";
+        return MLM_ERR_INVALID;
+    }
+    if (n == 0) return MLM_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    // channels: the input, then the five outputs; bytes per point; in device memory (used in place) or staged
+    void *ch[6] = {(void *)pos, status, voxel3, delta3, sq, dist};
+    const size_t elem[6] = {3 * sizeof(double), 1, 3 * sizeof(int32_t), 3 * sizeof(int32_t), sizeof(int64_t), sizeof(double)};
+    bool staged[6];
+    bool all_host = true;
+    for (int c = 0; c < 6; ++c) {
+        staged[c] = ch[c] && !win_in_place(ch[c]);
+        all_host = all_host && (staged[c] || !ch[c]);
+    }
+    // an optimiser's few control points: answered on the host (mlm_mirror.h), like mlm_query_boxes' small batches
+    if (all_host && mirror_nearest_wanted(h, n, max_dist)) {
+        const int rc = mirror_sync(h);
+        if (rc == MLM_OK) {
+            h->mir.view.nearest(pos, n, max_dist, flags, status, voxel3, delta3, sq, dist);
+            h->mir.n_host_queries += n;
+            return MLM_OK;
+        }
+        if (!h->mir.alloc_failed && rc != kMirrorUnavailable) return rc; // (an error of the frames in flight, reported by the drain)
+    }
+    int rc = drain(h);
+    if (rc) return rc;
+    // chunks: staged channels of a chunk share one kept buffer (at most 65 bytes per point)
+    const int chunk = std::min(n, kNearChunk);
+    size_t off[6], stage_bytes = 0;
+    for (int c = 0; c < 6; ++c) {
+        off[c] = stage_bytes;
+        if (staged[c]) stage_bytes += ((size_t)chunk * elem[c] + 255) & ~(size_t)255;
+    }
+    if (stage_bytes && (rc = win_reserve(h, h->d_ray_stage, h->ray_stage_bytes, stage_bytes, "mlm_query_nearest"))) return rc;
+    for (int i0 = 0; i0 < n; i0 += chunk) {
+        const int m = std::min(chunk, n - i0);
+        void *at[6];
+        for (int c = 0; c < 6; ++c)
+            at[c] = !ch[c] ? nullptr : staged[c] ? (void *)((char *)h->d_ray_stage + off[c]) : (void *)((char *)ch[c] + (size_t)i0 * elem[c]);
+        if (staged[0]) HIPCHK(h, hipMemcpyAsync(at[0], (const char *)ch[0] + (size_t)i0 * elem[0], (size_t)m * elem[0], hipMemcpyHostToDevice, h->stream));
+        MlmNearest Q{(const double *)at[0], m, max_dist, flags, (int8_t *)at[1], (int32_t *)at[2], (int32_t *)at[3], (int64_t *)at[4], (double *)at[5]};
+        // one wave per point, four to a workgroup; at most kNearGrid workgroups (grid-stride)
+        const dim3 grid(std::min<unsigned int>(((unsigned int)m + MLM_BLOCK / 64 - 1) / (MLM_BLOCK / 64), kNearGrid));
+        hipLaunchKernelGGL(k_nearest, grid, dim3(MLM_BLOCK), 0, h->stream, h->P, Q);
+        HIPCHK(h, hipGetLastError());
+        for (int c = 1; c < 6; ++c)
             if (staged[c])
                 HIPCHK(h, hipMemcpyAsync((char *)ch[c] + (size_t)i0 * elem[c], at[c], (size_t)m * elem[c], hipMemcpyDeviceToHost, h->stream));
     }

@@ -54,7 +54,7 @@ ABI_SYMBOLS = [
     "mlm_query_odds", "mlm_query_odd_grad", "mlm_query_odds_at", "mlm_export_frontier_points", "mlm_import_blocks",
     "mlm_merge_pack", "mlm_merge_finish",
     "mlm_set_free_in_bound", "mlm_inflate_map", "mlm_block_count",
-    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_grid2d", "mlm_export_reach", "mlm_export_route", "mlm_export_clusters", "mlm_query_rays", "mlm_render_depth", "mlm_query_views", "mlm_query_boxes", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
+    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_grid2d", "mlm_export_reach", "mlm_export_route", "mlm_export_clusters", "mlm_query_rays", "mlm_render_depth", "mlm_query_views", "mlm_query_boxes", "mlm_query_nearest", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
     "mlm_get_awareness_hits",
     "mlm_get_awareness_misses", "mlm_get_T_ls", "mlm_get_odds_table", "mlm_get_kernel_times",
     "mlm_enable_kernel_timing", "mlm_set_timed_kernel", "mlm_host_register", "mlm_host_unregister", "mlm_debug_set", "mlm_debug_reset",
@@ -157,6 +157,7 @@ def load_library(path: Optional[str] = None):
     L.mlm_render_depth.argtypes = [vp, vp, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp]
     L.mlm_query_views.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.mlm_query_boxes.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.mlm_query_nearest.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
     L.mlm_export_global_map.argtypes = [vp, i32, vp, vp]
     L.mlm_export_block_flags.argtypes = [vp, i32, vp, vp]
     L.mlm_export_frontier.argtypes = [vp, i32, vp, vp]
@@ -851,6 +852,49 @@ class MLMap:
         ptr = [None if v is None else ctypes.c_void_p(v) for v in (status, box, closed, table)]
         self._chk(self._L.mlm_query_boxes(self._h, ctypes.c_void_p(boxes), int(n), self._ray_flags(occ, infl, unknown), mg_p, lo_p, dims_p, *ptr),
                   "mlm_query_boxes")
+
+    NEAREST_OUTPUTS = ("status", "voxel", "delta", "sq", "dist")
+
+    def query_nearest(self, pos, max_dist, occ=True, infl=False, unknown=False, outputs=None):
+        """The exact nearest obstacle voxel of each position (mlm_query_nearest).  pos: n x 3 float64 world positions — a numpy array
+        (numpy results) or a torch device tensor (torch device results).  max_dist: 1 .. 64 voxels, the radius of the ball that is
+        searched.  An obstacle is a voxel that is occ (getOccupancy == OCCUPIED), infl (getInflateOccupancy == OCCUPIED) or unknown
+        (getOccupancy == UNKNOWN), whichever are selected (at least one).  outputs: the names wanted (None: all five).
+        {"status": int8 (1 found, 0 nothing in range, -1 invalid position), "voxel": int32 (n, 3) the obstacle voxel (the
+        position's own without one), "delta": int32 (n, 3) the vector from the position to that voxel's centre in 1/1024 voxel,
+        "sq": int64 its squared length (-1 without an obstacle), "dist": float64 its length in metres (-1.0 without one)}."""
+        names = self.NEAREST_OUTPUTS if outputs is None else tuple(outputs)
+        if not names or any(k not in self.NEAREST_OUTPUTS for k in names):
+            raise MlmError("query_nearest: outputs must name at least one of " + ", ".join(self.NEAREST_OUTPUTS))
+        flags = self._ray_flags(occ, infl, unknown)
+        if isinstance(pos, np.ndarray) or not hasattr(pos, "data_ptr"):
+            p = _f64(pos).reshape(-1, 3)
+            n = p.shape[0]
+            shapes = {"status": ((n,), np.int8), "voxel": ((n, 3), np.int32), "delta": ((n, 3), np.int32), "sq": ((n,), np.int64),
+                      "dist": ((n,), np.float64)}
+            out = {k: np.empty(*shapes[k]) for k in names}
+            ptr = [_p(p)] + [_p(out[k]) if k in out else None for k in self.NEAREST_OUTPUTS]
+        else:
+            import torch
+
+            if pos.dtype != torch.float64 or pos.numel() % 3 or not pos.is_contiguous():
+                raise MlmError("query_nearest: a tensor of positions must be contiguous float64 with 3 values per position")
+            n = pos.numel() // 3
+            dev = pos.device
+            shapes = {"status": ((n,), torch.int8), "voxel": ((n, 3), torch.int32), "delta": ((n, 3), torch.int32), "sq": ((n,), torch.int64),
+                      "dist": ((n,), torch.float64)}
+            out = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev) for k in names}
+            ptr = [ctypes.c_void_p(pos.data_ptr())] + [ctypes.c_void_p(out[k].data_ptr()) if k in out else None for k in self.NEAREST_OUTPUTS]
+        self._chk(self._L.mlm_query_nearest(self._h, ptr[0], n, int(max_dist), flags, *ptr[1:]), "mlm_query_nearest")
+        return out
+
+    def query_nearest_dev(self, pos: int, n: int, max_dist: int, occ=True, infl=False, unknown=False, status: Optional[int] = None,
+                          voxel: Optional[int] = None, delta: Optional[int] = None, sq: Optional[int] = None, dist: Optional[int] = None):
+        """Same on pointers (ints; device or host memory, each on its own): n x 3 float64 positions, n int8 / n x 3 int32 /
+        n x 3 int32 / n int64 / n float64 outputs, None = skipped."""
+        ptr = [None if v is None else ctypes.c_void_p(v) for v in (status, voxel, delta, sq, dist)]
+        self._chk(self._L.mlm_query_nearest(self._h, ctypes.c_void_p(pos), int(n), int(max_dist), self._ray_flags(occ, infl, unknown), *ptr),
+                  "mlm_query_nearest")
 
     @staticmethod
     def _ray_flags(occ, infl, unknown) -> int:
