@@ -25,7 +25,7 @@ struct KernelTime {
 // Process-wide, not part of the drop-in contract; the library reads no environment variable for them (only the three diagnostic
 // switches MLM_DEBUG_CREATE / MLM_DEBUG_ALLOC / MLM_DEBUG_DRAIN, which print).
 const char *const kKnobNames[] = {"agg_lds", "big_arm", "big_grid", "bin_block", "chain_grid", "cluster_tile", "collect_grid", "cu_reserve", "cu_split",
-                                  "esdf_tile_vox", "ex_spec", "expand_block", "graph", "grid_tile", "logit_exact", "mirror", "mirror_max", "mirror_mb", "need_slots", "node_lds", "pool_grow",
+                                  "esdf_tile_vox", "ex_spec", "expand_block", "graph", "grid_tile", "hit_tab_n", "logit_exact", "mirror", "mirror_max", "mirror_mb", "need_slots", "node_lds", "pool_grow",
                                   "rank_grid", "rays_grid", "reach_group", "reach_tile", "render_tile", "route_group", "route_tile", "sc_block", "sc_grid", "sec_backoff", "sec_fail_every", "sec_tab", "sec_tab_big", "sec_threads",
                                   "sectors", "single_apply_grid", "single_chain_grid", "single_rank_grid", "slot_sets", "sort_block", "sort_grid", "tile_grid", "tile_sh", "view_lds_bits"};
 struct KnobStore {
@@ -56,6 +56,7 @@ bool knob_value_ok(const char *name, long long v) {
     if (is("route_group")) return v >= 1 && v <= kReachGroupMax; // (as reach_group)
     if (is("view_lds_bits")) return v >= 0 && v <= kViewLdsBits; // (larger bitsets go to global scratch; 0: all of them)
     if (is("reach_group")) return v >= 1 && v <= kReachGroupMax; // (sweeps between two looks at the "marked" words)
+    if (is("hit_tab_n")) return v >= 0 && v <= 65536 && (v & (v - 1)) == 0; // (entries per chain of MlmDev::hit_p / hit_inc: a power of two, 0 = no tables)
     if (is("render_tile")) return v >= 0 && v <= 2; // (k_render has three instantiations: 64 x 1, 16 x 4, 8 x 8)
     return true;
 }

@@ -563,6 +563,44 @@ inline uint32_t strip_magic(unsigned int d) {
     return (uint32_t)(((1ull << 31) + d - 1) / d);
 }
 
+// Bucket of a hit in the emulated container without a 64-bit remainder (k_sector).  The hash code is a 32-bit value sign-extended to
+// size_t (VectorHasher, mlm_hash_rpz), the bucket `code % n` with n the container's bucket count.  For n < 2^32:
+//   code >= 0   a 32-bit remainder, as Lemire's fastmod: with m = floor((2^64 - 1) / n) + 1 (mod 2^64: 0 for n = 1) the remainder of any
+//               x < 2^32 is the high 64 bits of ((m * x) mod 2^64) * n — exact for all 2^32 operands and every n < 2^32 (Lemire, Kaser,
+//               Kurz, "Faster remainder by direct computation", 2019, theorem 1 with N = 32, F = 64).  div_magic does not do: it
+//               covers operands below 2^27 only.
+//   code <  0   code = 2^64 - x with x = -(int32) code in [1, 2^31]: with c = 2^64 mod n and t = x mod n the bucket is
+//               c - t (c >= t) or c + n - t (the sum may wrap 32 bits; the result, below n, does not).
+// fast == 0 (n >= 2^32; a cylinder of more than 2^31 cells): the kernel keeps the 64-bit remainder.
+// tests/test_bucket_mod.py checks both forms against 128-bit arithmetic.
+struct MlmBktMod {
+    unsigned long long n; // the bucket count
+    unsigned long long m; // fastmod multiplier
+    uint32_t c;           // 2^64 mod n
+    uint32_t fast;        // 1: n < 2^32, the two forms above apply
+};
+inline MlmBktMod bkt_mod(unsigned long long n) {
+    MlmBktMod B{n, 0ull, 0u, 0u};
+    if (n == 0ull || n >= (1ull << 32)) return B;
+    B.m = 0xFFFFFFFFFFFFFFFFull / n + 1ull;
+    B.c = (uint32_t)((0xFFFFFFFFFFFFFFFFull % n + 1ull) % n);
+    B.fast = 1u;
+    return B;
+}
+MLM_HD inline uint32_t mlm_mod_u32(uint32_t x, const MlmBktMod &B) {
+    const unsigned long long low = B.m * x; // (mod 2^64)
+    const uint32_t n = (uint32_t)B.n;
+    const unsigned long long lo = (low & 0xFFFFFFFFull) * n, hi = (low >> 32) * n + (lo >> 32); // high 64 bits of low * n: hi >> 32
+    return (uint32_t)(hi >> 32);
+}
+// code: the sign-extended hash (mlm_hash_rpz); B.fast must be set
+MLM_HD inline uint32_t mlm_bucket_fast(unsigned long long code, const MlmBktMod &B) {
+    const uint32_t h = (uint32_t)code;
+    if ((int32_t)h >= 0) return mlm_mod_u32(h, B);
+    const uint32_t t = mlm_mod_u32(0u - h, B);
+    return B.c >= t ? B.c - t : B.c + (uint32_t)B.n - t;
+}
+
 // Replay the rehash policy of libstdc++'s _Hashtable for `U` unique insertions into a cleared container.
 // Returns the epochs: (number of elements present when the epoch ends, bucket count during the epoch).
 // Uses the very policy object std::unordered_map uses, so it follows whatever libstdc++ this library is linked to.

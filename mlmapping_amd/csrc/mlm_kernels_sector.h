@@ -43,6 +43,16 @@
 #pragma once
 #include "mlm_kernels.h"
 
+// Wave votes on a bool.  HIP's __ballot / __any / __all take an int: the predicate is materialised as 0 / 1 in a register and compared
+// with zero again (v_cndmask + v_cmp per vote); the builtin takes the compare's lane mask as it stands.
+__device__ __forceinline__ unsigned long long mlm_ballot(bool b) { return __builtin_amdgcn_ballot_w64(b); }
+__device__ __forceinline__ bool mlm_any(bool b) { return mlm_ballot(b) != 0ull; }
+__device__ __forceinline__ bool mlm_all(bool b) { return mlm_ballot(!b) == 0ull; }
+// is this lane the lowest one of lane mask m?  (no bit of m below it: v_mbcnt; the lane itself has to be in m)
+__device__ __forceinline__ bool mlm_lowest_lane_of(unsigned long long m) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)) == 0u;
+}
+
 #define MLM_SEC_THREADS 512 // threads of a column's workgroup (k_sector also exists with 256: MlmDev::sec_tab <= 1024)
 #define MLM_SEC_WAVES (MLM_SEC_THREADS / 64)
 #define MLM_SEC_COLS 256    // distinct columns one k_bin_sectors block can feed in the list modes: one per record at most (a pixel list
@@ -249,7 +259,7 @@ __device__ __forceinline__ void mlm_bin_sectors_body(const MlmDev &P, const MlmF
 #else
         sure = !have[j];
 #endif
-        if (!__all(sure)) { // ... and, for a wave with a lane too close to a cell boundary to be sure, by the reference's own sequence
+        if (!mlm_all(sure)) { // ... and, for a wave with a lane too close to a cell boundary to be sure, by the reference's own sequence
             if (lane == 0) g_atomic_add(&mlm_gp(P.ctr)->bin_exact, 1u); // (statistic: mlm_frame_stats.n_bin_exact_waves)
             if (have[j]) {
                 // p_l = T_ls * p_s (map_awareness.cpp:222; se3.cpp:91-95)
@@ -263,29 +273,34 @@ __device__ __forceinline__ void mlm_bin_sectors_body(const MlmDev &P, const MlmF
         }
         if (inside) c0 = zi * P.nRhoPhi + phi * P.nRho + rho;
         const uint32_t i00 = (uint32_t)mlm_readlane(item[j], 0); // work item of lane 0 of this wave (see MlmNode)
-        // lanes of one centre cell -> one record, held by their lowest lane (= earliest insertion time)
+        // lanes of one centre cell -> one record, held by their lowest lane (= earliest insertion time).  The lanes of a group take the
+        // group's mask inside the branch on the very compare the vote was made from — there the active lanes ARE the group, so the mask is
+        // a copy of exec (one v_mov_b64), and no lane compares itself with the leader per iteration; who leads follows once, after the
+        // loops: the lane below which its mask has no bit.  (c0 = -1 off the map: the compare alone is the predicate.)
         unsigned long long my_mask = 0;
-        bool leader = false;
-        mlm_wave_groups(c0, inside, [&](int, unsigned long long m) {
-            leader = true;
-            my_mask = m;
-        });
+        {
+            unsigned long long todo = mlm_ballot(c0 >= 0);
+            while (todo) {
+                const int k = mlm_readlane(c0, __ffsll((long long)todo) - 1);
+                const bool mine = c0 == k;
+                todo &= ~mlm_ballot(mine);
+                if (mine) my_mask = mlm_ballot(true);
+            }
+        }
         // points outside the map that can still cast (map_awareness.cpp:241,249-265): identical starts merged per wave
         const bool outer = have[j] && !inside && can_do_cast && P.visibility;
-        bool ray_leader = false;
         {
-            unsigned long long todo = __ballot(outer);
+            unsigned long long todo = mlm_ballot(outer);
             while (todo) {
                 const int ld = __ffsll((long long)todo) - 1;
                 const int kr = mlm_readlane(rho, ld), kp = mlm_readlane(phi, ld), kz = mlm_readlane(zi, ld);
-                const unsigned long long m = __ballot(outer && rho == kr && phi == kp && zi == kz);
-                if (lane == ld) {
-                    ray_leader = true;
-                    my_mask = m;
-                }
-                todo &= ~m;
+                const bool mine = outer && rho == kr && phi == kp && zi == kz;
+                todo &= ~mlm_ballot(mine);
+                if (mine) my_mask = mlm_ballot(true);
             }
         }
+        const bool first = mlm_lowest_lane_of(my_mask); // (inside and outer exclude each other: my_mask is the lane's own group's, or 0)
+        const bool leader = inside && first, ray_leader = outer && first;
         rec_place[j] = MLM_NIL;
         rec_cell[j] = leader ? (uint32_t)zi << 16 | (uint32_t)rho : (MLM_SEC_OUTER | (uint32_t)rho); // (hit records: z and rho of the centre cell, nRho * nZ < 65 536)
         // hit records carry their tile's origin (MLM_REC_XT_BITS; list modes: 64 items = one row) for k_rank
@@ -311,8 +326,8 @@ __device__ __forceinline__ void mlm_bin_sectors_body(const MlmDev &P, const MlmF
             if (placed) rec_place[j] = e | (atomicAdd(&s_col_cnt[j][e], 1u) << 16);
             else s_over = 1; // (dense tiles only: more than 64 columns in one 32x8 pixel strip)
         }
-        const unsigned int n_pts = (unsigned int)__popcll(__ballot(have[j]));
-        const unsigned int n_oor = (unsigned int)__popcll(__ballot(have[j] && !(can_do_cast && P.visibility)));
+        const unsigned int n_pts = (unsigned int)__popcll(mlm_ballot(have[j]));
+        const unsigned int n_oor = (unsigned int)__popcll(mlm_ballot(have[j] && !(can_do_cast && P.visibility)));
         if (lane == 0) s_cnt[j][wid] = n_pts | (n_oor << 10);
     }
     __syncthreads();
@@ -402,6 +417,22 @@ __global__ __launch_bounds__(256) void k_bin_sectors_hostf(const MlmDev *__restr
     __syncthreads();
     pre = pre && s_F.pix == list_pix && s_F.raw == list_raw;
     mlm_bin_sectors_body<MODE, 1>(P, s_F, n_strips, pre, pre_pix, pre_raw);
+}
+
+// MlmDev::hit_p / hit_inc / logit_one (mlm_types.h): one thread per entry of the odds table runs the hit-list loop's own chain and
+// mlm_logit for n = 1 .. P.hit_tab_n; thread 0 also leaves mlm_logit(1.0f) in *logit_one.  Run once per handle (mlm_create).
+__global__ __launch_bounds__(256) void k_fill_hit_tables(const MlmDev P, float *hit_p, float *hit_inc, float *logit_one) {
+    const uint32_t e = blockIdx.x * 256u + threadIdx.x;
+    if (e == 0u) *logit_one = mlm_logit(P, 1.0f);
+    if (e >= (uint32_t)((2 * MLM_DIFF_RANGE + 1) * P.nRho)) return;
+    const float a = P.odds_table[e];
+    float p = a;
+    for (uint32_t n = 1;; ++n) {
+        hit_p[(size_t)e * P.hit_tab_n + (n - 1u)] = p;
+        hit_inc[(size_t)e * P.hit_tab_n + (n - 1u)] = mlm_logit(P, p);
+        if (n == P.hit_tab_n) break;
+        if (p != 1.0f) p = 1 - (1 - p) * (1 - a);
+    }
 }
 
 // find (or with INSERT create) the table entry of a column-local cell key; -1: table full
@@ -541,7 +572,7 @@ __device__ __forceinline__ void mlm_fold_bin_stats(const MlmDev &P, int n_bin_bl
 // alone is 10 % slower).
 template <bool EX, bool BIG, int NT>
 __device__ __forceinline__ void mlm_sector_column(const MlmDev &P, const MlmFrame &F, const int phi, int tile_w, int n_bin_blocks, unsigned long long rho_m,
-                                                  int rho_s, unsigned long long n_bkt, int col_flags, unsigned long long row_m, int row_s) {
+                                                  int rho_s, const mlm_host::MlmBktMod bkt, int col_flags, unsigned long long row_m, int row_s) {
     // col_flags: bit 0 — k_sector_big follows this launch; bits 4-7 — lanes per ray = 4 << that (a lone frame's columns have the lanes)
     const int big_armed = col_flags & 1;
     const uint32_t ray_sh = 2u + (((uint32_t)col_flags >> 4) & 15u);
@@ -693,7 +724,7 @@ __device__ __forceinline__ void mlm_sector_column(const MlmDev &P, const MlmFram
         for (int i0 = 0; i0 < P.nRho; i0 += 64) {
             const int i = i0 + lane;
             const bool change = i < P.nRho && (i == 0 || s_vr[i].x != s_vr[i - 1].x);
-            const unsigned long long m = __ballot(change);
+            const unsigned long long m = mlm_ballot(change);
             const int id = carry + (int)__popcll(m & ((2ull << lane) - 1ull)) - 1;
             if (i < P.nRho) {
                 s_vr[i].w = id;
@@ -1084,7 +1115,7 @@ __device__ __forceinline__ void mlm_sector_column(const MlmDev &P, const MlmFram
             cur_bits |= 1u << (r & 31);
         }
         if (!EX && cur_w >= 0) atomicOr(&s_miss[cur_w], cur_bits);
-        if (__any(ties != 0)) {
+        if (mlm_any(ties != 0)) {
             const double slope = (rho > 0) ? dz / (rho * 1.0) : 0.0;
             while (ties) {
                 const int k = k_lo + __ffsll((long long)ties) - 1;
@@ -1113,22 +1144,38 @@ __device__ __forceinline__ void mlm_sector_column(const MlmDev &P, const MlmFram
         mlm_gp(P.hl_vt)[pos] = c.tmin; // (the replay kernels re-rank it: k_assign_rank)
         if (!mlm_sec_needs_order(c)) {
             // one kind: cnt applications of one value (update_odds_hashmap, map_awareness.h:147-154), 1.0f is absorbing;
-            // several kinds with enough strong contributions: 1.0f in any order; two contributions: their product (mlm_sec_needs_order)
-            const float a = mlm_gp(P.odds_table)[mlm_contribution_index(P, rho, __ffs((int)(c.kg & MLM_SEC_KIND_MASK)) - 1)]; // (one value per hit cell: from memory)
-            float p = a;
-            if (__popc(c.kg & MLM_SEC_KIND_MASK) > 1) {
+            // several kinds with enough strong contributions: 1.0f in any order; two contributions: their product (mlm_sec_needs_order).
+            // n applications of one value and their logit are constants of the handle: from MlmDev::hit_p / hit_inc (one load instead
+            // of a serial float chain as long as the wave's longest lane's, the FP64 log10f and a division); counts beyond the table
+            // continue the chain from its last entry.
+            const uint32_t kinds = c.kg & MLM_SEC_KIND_MASK, cnt = c.cnt & MLM_SEC_CNT_MASK, TN = P.hit_tab_n;
+            const int ai = mlm_contribution_index(P, rho, __ffs((int)kinds) - 1);
+            const bool want_p = EX || P.record_awareness; // (the odd itself is only read back by mlm_get_awareness_hits)
+            float p = 0.0f, inc = 0.0f;
+            bool have_inc = false;
+            if (__popc(kinds) > 1) {
                 if ((c.cnt >> MLM_SEC_CNT_BITS) >= MLM_SEC_STRONG_ENOUGH) {
                     p = 1.0f;
+                    inc = P.logit_one;
+                    have_inc = TN != 0u;
                 } else { // two contributions of two kinds: the same value in either order
-                    const uint32_t rest = c.kg & MLM_SEC_KIND_MASK & ((c.kg & MLM_SEC_KIND_MASK) - 1u);
+                    const float a = mlm_gp(P.odds_table)[ai];
+                    const uint32_t rest = kinds & (kinds - 1u);
                     const float b = mlm_gp(P.odds_table)[mlm_contribution_index(P, rho, __ffs((int)rest) - 1)];
                     p = 1 - (1 - a) * (1 - b);
                 }
+            } else if (cnt - 1u < TN) { // (1 <= cnt <= TN)
+                const size_t at = (size_t)ai * TN + (cnt - 1u);
+                inc = mlm_gp(P.hit_inc)[at];
+                have_inc = true;
+                if (want_p) p = mlm_gp(P.hit_p)[at];
             } else {
-                for (uint32_t j = 1; j < (c.cnt & MLM_SEC_CNT_MASK) && p != 1.0f; ++j) p = 1 - (1 - p) * (1 - a);
+                const float a = mlm_gp(P.odds_table)[ai]; // (one value per hit cell: from memory)
+                p = TN ? mlm_gp(P.hit_p)[(size_t)ai * TN + (TN - 1u)] : a;
+                for (uint32_t j = TN ? TN : 1u; j < cnt && p != 1.0f; ++j) p = 1 - (1 - p) * (1 - a);
             }
-            if (EX || P.record_awareness) mlm_gp(P.hl_odd)[pos] = p; // (the odd itself is only read back by mlm_get_awareness_hits)
-            mlm_gp(P.hl_inc)[pos] = mlm_logit(P, p);
+            if (want_p) mlm_gp(P.hl_odd)[pos] = p;
+            mlm_gp(P.hl_inc)[pos] = have_inc ? inc : mlm_logit(P, p);
         }
         if (EX) { // frontier mode: the hit's world voxel (its kernels look the block up themselves)
             int gx, gy, gz, cid;
@@ -1143,7 +1190,9 @@ __device__ __forceinline__ void mlm_sector_column(const MlmDev &P, const MlmFram
         mlm_gp(P.hl_vt16)[pos] = (uint16_t)(s_vr[rho].y * P.lv_nz + s_vz[z].x);
         // (a fire-and-forget atomic: measured 32-byte transactions, 1.2 MB per VGA frame with k_rank's read-back — walking the hit
         // list once per class of buckets with the minima in LDS instead, profiles/r4c, cost 4.6 MB of re-reads and 2.5 us per frame)
-        const unsigned long long b = mlm_hash_rpz(rho, phi, z) % n_bkt;
+        // (the 64-bit remainder as two 32-bit forms with host-made constants, mlm_host.h: MlmBktMod; a uniform branch)
+        const unsigned long long code = mlm_hash_rpz(rho, phi, z);
+        const unsigned long long b = bkt.fast ? (unsigned long long)mlm_host::mlm_bucket_fast(code, bkt) : code % bkt.n;
         mlm_gp(P.hl_bkt)[pos] = (uint32_t)b;
         if (b < P.sbkt_cap) g_atomic_min(&mlm_gp(P.sbkt)[b], mlm_bkt_entry(F.seq, c.tmin));
     }
@@ -1262,12 +1311,12 @@ template <bool EX, int NT>
 // (256 threads: eight workgroups per CU = eight waves per SIMD, 64 VGPRs; 512 threads — tables above 1 024 entries: at most three
 // workgroups per CU by LDS, or a frame on its own — six waves per SIMD, 80 VGPRs)
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == 256 ? 8 : 6))) void k_sector(MLM_SLOT_ARGS, int tile_w, int n_bin_blocks, unsigned long long rho_m,
-                                                                                       int rho_s, unsigned long long n_bkt, int big_armed, unsigned long long row_m, int row_s) {
+                                                                                       int rho_s, const mlm_host::MlmBktMod bkt, int big_armed, unsigned long long row_m, int row_s) {
     // (row_m, row_s: exact division of a pixel index by the image width — the row of a cell's first pixel, mlm_ref_pack)
     MLM_SLOT_SETUP
     MLM_SPAN_BEGIN(0)
     if (blockIdx.x == 0 && threadIdx.x < 64) mlm_fold_bin_stats(P, n_bin_blocks);
-    mlm_sector_column<EX, false, NT>(P, F, (int)blockIdx.x, tile_w, n_bin_blocks, rho_m, rho_s, n_bkt, big_armed, row_m, row_s);
+    mlm_sector_column<EX, false, NT>(P, F, (int)blockIdx.x, tile_w, n_bin_blocks, rho_m, rho_s, bkt, big_armed, row_m, row_s);
     MLM_SPAN_END(0)
 }
 // The columns on the overflow lists of a batch's frames, with the large cell table (dynamic LDS of MlmDev::sec_big_lds_bytes:
@@ -1280,7 +1329,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == 256 ? 
 template <bool EX>
 __global__ __launch_bounds__(MLM_SEC_THREADS) void k_sector_big(const MlmDev *__restrict__ slot_tab, const MlmFrame *__restrict__ frame_tab, int slot_base,
                                                                 int n_frames, int tile_w, int n_bin_blocks, unsigned long long rho_m, int rho_s,
-                                                                unsigned long long n_bkt, unsigned long long row_m, int row_s) {
+                                                                const mlm_host::MlmBktMod bkt, unsigned long long row_m, int row_s) {
     __shared__ unsigned int s_first[65]; // exclusive prefix of the frames' overflow counts (n_frames <= 64)
     if (threadIdx.x < 64) {
         const int j = (int)threadIdx.x;
@@ -1305,7 +1354,7 @@ __global__ __launch_bounds__(MLM_SEC_THREADS) void k_sector_big(const MlmDev *__
         while (j + 1 < n_frames && s_first[j + 1] <= t) ++j;
         const MlmDev &P = slot_tab[slot_base + j];
         const MlmFrame &F = frame_tab[slot_base + j];
-        mlm_sector_column<EX, true, MLM_SEC_THREADS>(P, F, (int)mlm_gp(P.ov_list)[t - s_first[j]], tile_w, n_bin_blocks, rho_m, rho_s, n_bkt, 0, row_m, row_s);
+        mlm_sector_column<EX, true, MLM_SEC_THREADS>(P, F, (int)mlm_gp(P.ov_list)[t - s_first[j]], tile_w, n_bin_blocks, rho_m, rho_s, bkt, 0, row_m, row_s);
     }
 }
 
@@ -1451,7 +1500,7 @@ __global__ __launch_bounds__(MLM_BLOCK) MLM_RANK_ATTR void k_rank(MLM_SLOT_ARGS,
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        bad = __any(bad);
+        bad = mlm_any(bad);
         uint32_t carry = 0;
         int used = MLM_SEC_RANK_WORDS;
         if (!bad) {
@@ -1615,7 +1664,7 @@ __global__ __launch_bounds__(MLM_BLOCK) MLM_RANK_ATTR void k_rank(MLM_SLOT_ARGS,
                     out64 = out64 || dxs < 0 || dxs > 56;
                     row32 = row32 || (yx_ >> 11) >= 32u;
                 }
-            const unsigned long long o_l = __ballot(valid && out64), r_l = __ballot(valid && row32);
+            const unsigned long long o_l = mlm_ballot(valid && out64), r_l = mlm_ballot(valid && row32);
             if (valid && hl == 0) {
                 if ((uint32_t)(o_l >> (32 * half))) atomicAdd(&g_mlm_span[29], 1ull);
                 if ((uint32_t)(r_l >> (32 * half))) atomicAdd(&g_mlm_span[31], 1ull);
@@ -1658,12 +1707,12 @@ __global__ __launch_bounds__(MLM_BLOCK) MLM_RANK_ATTR void k_rank(MLM_SLOT_ARGS,
             }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        const unsigned long long bad_lanes = __ballot(bad);
+        const unsigned long long bad_lanes = mlm_ballot(bad);
         bool ok = act && ((uint32_t)(bad_lanes >> (32 * half)) == 0u);
         uint32_t carry = 0, used = MLM_SEC_RANK_WORDS / 2;
         for (uint32_t j0 = 0; j0 < MLM_SEC_RANK_WORDS / 2; j0 += 32) {
             const bool need = ok && carry < n;
-            if (!__any(need)) break;
+            if (!mlm_any(need)) break;
             const uint32_t cw = need ? (uint32_t)__popcll(((volatile MLM_LDS unsigned long long *)rows_h)[j0 + hl]) : 0u;
             const uint32_t incl = half_incl_scan(cw);
             const uint32_t t0 = mlm_readlane(incl, 31), t1 = mlm_readlane(incl, 63);
@@ -1747,7 +1796,7 @@ __global__ __launch_bounds__(MLM_BLOCK) MLM_RANK_ATTR void k_rank(MLM_SLOT_ARGS,
         load_desc(pw + 2 * n_waves, rec_nn, rf_nn);
         const bool v_nn = desc_valid(pw + 2 * n_waves);
         const bool again = process_pair(rec_cur, rf_cur, v_cur, r_cur);
-        const unsigned long long again_lanes = __ballot(again);
+        const unsigned long long again_lanes = mlm_ballot(again);
         for (int h = 0; h < 2; ++h) // (uniform) the whole wave on a cell that did not fit half of it
             if ((again_lanes >> (32 * h)) & 1ull) {
                 mlm_u32x4 rec_f;
@@ -1851,7 +1900,7 @@ __global__ __launch_bounds__(MLM_BLOCK) void k_chain_lanes(MLM_SLOT_ARGS, unsign
         for (int r = 0; r < R; ++r) // (a cell's segment of `subs` is padded to whole 16-byte words; past it: the harmless address)
             kinds_in[r] = *(const MLM_GLOBAL mlm_u32x4 *)(mlm_gp(P.subs) + ((r == 0 || 16u * r < k_left) ? k_at + 16u * r : 0u));
         // ---- idle lanes draw cells
-        const unsigned long long need = __ballot(state == 0);
+        const unsigned long long need = mlm_ballot(state == 0);
         uint32_t d_at = 0u; // the descriptor this lane requests this round
         if (need && !exhausted) {
             if (loc_next >= loc_end) {
@@ -1876,7 +1925,9 @@ __global__ __launch_bounds__(MLM_BLOCK) void k_chain_lanes(MLM_SLOT_ARGS, unsign
             const mlm_u32x3 d3 = *(const MLM_GLOBAL mlm_u32x3 *)(mlm_gp(P.mt_rec) + d_at);
             desc_in = mlm_u32x4{d3.x, d3.y, d3.z, 0u};
         }
-        if (exhausted && !__any(state != 0)) break;
+        if (exhausted && !mlm_any(state != 0)) break;
+        // (HIP's int votes on purpose, here and below: with the builtin on the bool the compiler folds the wave-uniform branch into flush()'s
+        // own predicate and adds a select per round — 2 % more vector instructions for this kernel, profiles/r9a)
         if (__popcll(__ballot(pend)) >= 40) flush();
         // ---- sixteen steps of the running chains
         if (state == 3) {
@@ -2402,7 +2453,7 @@ __global__ __launch_bounds__(MLM_BLOCK) __attribute__((amdgpu_waves_per_eu(8))) 
             wxm = max(wxm, __shfl_xor(wxm, off, 64));
             z0 = min(z0, __shfl_xor(z0, off, 64));
         }
-        const unsigned long long bad = __ballot(!ok && lane >= f_begin && lane < n_frames);
+        const unsigned long long bad = mlm_ballot(!ok && lane >= f_begin && lane < n_frames);
         if (lane == 0) {
             s_wx0 = wx;
             s_wy0 = wy;
@@ -2686,7 +2737,7 @@ __global__ __launch_bounds__(MLM_BLOCK) void k_alloc_retry(const MlmDev P, const
             else failed = true;
         }
     }
-    if (__any(failed) && (threadIdx.x & 63) == 0) mlm_gp(P.ctr)->pool_short = 2u; // (2: still short after this pass)
+    if (mlm_any(failed) && (threadIdx.x & 63) == 0) mlm_gp(P.ctr)->pool_short = 2u; // (2: still short after this pass)
 }
 // (second launch of the pair: turns "not seen short by the pass above" into "complete")
 __global__ void k_alloc_retry_done(const MlmDev P) {

@@ -274,23 +274,23 @@ int launch_stage_a_sector(mlm_handle *h, int base, int n, bool on_main = false) 
         const int nt = (n == 1 && P.sec_tab >= 512u) ? 512 : h->sec_threads;
         if (P.explore && nt == 256)
             tlaunch(h, "k_sector", k_sector<true, 256>, dim3((unsigned int)P.nPhi, 1, n), dim3(256), P.sec_lds_bytes, st, h->d_slot_tab,
-                    h->d_frame_tab, base, mode == 0 ? F.width : 0, (int)nb, rm, rs, 1ull, big, dm, ds);
+                    h->d_frame_tab, base, mode == 0 ? F.width : 0, (int)nb, rm, rs, bkt_mod(1), big, dm, ds);
         else if (P.explore)
             tlaunch(h, "k_sector", k_sector<true, 512>, dim3((unsigned int)P.nPhi, 1, n), dim3(512), P.sec_lds_bytes, st, h->d_slot_tab,
-                    h->d_frame_tab, base, mode == 0 ? F.width : 0, (int)nb, rm, rs, 1ull, big, dm, ds);
+                    h->d_frame_tab, base, mode == 0 ? F.width : 0, (int)nb, rm, rs, bkt_mod(1), big, dm, ds);
         else if (nt == 256)
             tlaunch(h, "k_sector", k_sector<false, 256>, dim3((unsigned int)P.nPhi, 1, n), dim3(256), P.sec_lds_bytes, st, h->d_slot_tab,
-                    h->d_frame_tab, base, mode == 0 ? F.width : 0, (int)nb, rm, rs, (unsigned long long)h->hit_n_bkt, big, dm, ds);
+                    h->d_frame_tab, base, mode == 0 ? F.width : 0, (int)nb, rm, rs, bkt_mod(h->hit_n_bkt), big, dm, ds);
         else
             tlaunch(h, "k_sector", k_sector<false, 512>, dim3((unsigned int)P.nPhi, 1, n), dim3(512), P.sec_lds_bytes, st, h->d_slot_tab,
-                    h->d_frame_tab, base, mode == 0 ? F.width : 0, (int)nb, rm, rs, (unsigned long long)h->hit_n_bkt, big, dm, ds);
+                    h->d_frame_tab, base, mode == 0 ? F.width : 0, (int)nb, rm, rs, bkt_mod(h->hit_n_bkt), big, dm, ds);
         if (big) { // the columns whose cell table overflowed, with the large table (a few workgroups per frame walk the list)
             if (P.explore)
                 tlaunch(h, "k_sector_big", k_sector_big<true>, dim3(h->big_grid), dim3(MLM_SEC_THREADS), P.sec_big_lds_bytes, st, h->d_slot_tab, h->d_frame_tab, base, n,
-                        mode == 0 ? F.width : 0, (int)nb, rm, rs, 1ull, dm, ds);
+                        mode == 0 ? F.width : 0, (int)nb, rm, rs, bkt_mod(1), dm, ds);
             else
                 tlaunch(h, "k_sector_big", k_sector_big<false>, dim3(h->big_grid), dim3(MLM_SEC_THREADS), P.sec_big_lds_bytes, st, h->d_slot_tab, h->d_frame_tab, base, n,
-                        mode == 0 ? F.width : 0, (int)nb, rm, rs, (unsigned long long)h->hit_n_bkt, dm, ds);
+                        mode == 0 ? F.width : 0, (int)nb, rm, rs, bkt_mod(h->hit_n_bkt), dm, ds);
         }
         const bool fused_chain = n == 1 && nb <= kFusedChainStrips; // (a small frame on its own: k_rank<true> runs the chains of the cells it ranks)
         // (frontier mode, a synchronous call's lone frame: the bucket-first pass of its containers rides along, explore_spec_begin)

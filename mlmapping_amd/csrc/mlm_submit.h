@@ -201,7 +201,7 @@ int redo_overflow_columns(mlm_handle *h, MlmSlot &R) {
     div_magic((unsigned int)row_w, dm, ds);
     div_magic((unsigned int)P.nRho, rm, rs);
     tlaunch(h, "k_sector_big", k_sector_big<false>, dim3(h->big_grid), dim3(MLM_SEC_THREADS), P.sec_big_lds_bytes, st, h->d_slot_tab, h->d_frame_tab, si, 1, tile_w, 0, rm,
-            rs, (unsigned long long)h->hit_n_bkt, dm, ds);
+            rs, bkt_mod(h->hit_n_bkt), dm, ds);
     tlaunch(h, "k_rank", k_rank<false>, dim3(1024, 1, 1), dim3(MLM_BLOCK), 0, st, h->d_slot_tab, h->d_frame_tab, si, tile_w, row_w, dm, ds, MlmExOrder{});
     tlaunch(h, "k_chain_lanes", k_chain_lanes<4>, dim3(64, 1, 1), dim3(MLM_BLOCK), (size_t)32 * P.nRho * sizeof(float), st, h->d_slot_tab, h->d_frame_tab, si, 64u);
     tlaunch(h, "k_tile", k_tile, dim3((unsigned int)(P.n_tiles <= 4096 ? P.n_tiles : 1024), 1, 1), dim3(MLM_TILE_THREADS), h->tile_lds_bytes, st, h->d_slot_tab,
@@ -480,13 +480,13 @@ hipError_t enqueue_single_frame(mlm_handle *h, int base, unsigned int nb, int bi
     // (a single frame is alone on the GPU: the 512-thread workgroup finishes a column sooner; the table is the same)
     if (h->sec_threads == 256 && P.sec_tab < 512u)
         hipLaunchKernelGGL((k_sector<false, 256>), dim3((unsigned int)P.nPhi, 1, 1), dim3(256), P.sec_lds_bytes, st, h->d_slot_tab, h->d_frame_tab, base,
-                           S.mode == 0 ? S.F.width : 0, (int)nb, rm, rs, (unsigned long long)h->hit_n_bkt, big | (2 << 4), dm, ds); // (| 2 << 4: sixteen lanes per ray)
+                           S.mode == 0 ? S.F.width : 0, (int)nb, rm, rs, bkt_mod(h->hit_n_bkt), big | (2 << 4), dm, ds); // (| 2 << 4: sixteen lanes per ray)
     else
         hipLaunchKernelGGL((k_sector<false, 512>), dim3((unsigned int)P.nPhi, 1, 1), dim3(512), P.sec_lds_bytes, st, h->d_slot_tab, h->d_frame_tab, base,
-                           S.mode == 0 ? S.F.width : 0, (int)nb, rm, rs, (unsigned long long)h->hit_n_bkt, big | (2 << 4), dm, ds); // (| 2 << 4: sixteen lanes per ray)
+                           S.mode == 0 ? S.F.width : 0, (int)nb, rm, rs, bkt_mod(h->hit_n_bkt), big | (2 << 4), dm, ds); // (| 2 << 4: sixteen lanes per ray)
     if (big)
         hipLaunchKernelGGL(k_sector_big<false>, dim3(h->big_grid), dim3(MLM_SEC_THREADS), P.sec_big_lds_bytes, st, h->d_slot_tab, h->d_frame_tab, base, 1,
-                           S.mode == 0 ? S.F.width : 0, (int)nb, rm, rs, (unsigned long long)h->hit_n_bkt, dm, ds);
+                           S.mode == 0 ? S.F.width : 0, (int)nb, rm, rs, bkt_mod(h->hit_n_bkt), dm, ds);
     if (nb <= kFusedChainStrips) { // (a small frame on its own: the wave that ranks a cell runs its chain, no k_chain_lanes — k_rank<true>)
         hipLaunchKernelGGL(k_rank<true>, dim3(h->single_rank_grid, 1, 1), dim3(MLM_BLOCK), 0, st, h->d_slot_tab, h->d_frame_tab, base, S.mode == 0 ? S.F.width : 0, row_w, dm, ds, MlmExOrder{});
     } else {

@@ -150,6 +150,13 @@ struct MlmDev {
     const float *sigma3;       // [nRho] 3*sigma_in_dr(rho)  (float, map_awareness.cpp:149)
     const uint32_t *sec_const; // k_sector's constant LDS tables as it lays them out (mlm_sec_lds: odds .. sigma): a strength byte per entry of
     unsigned int sec_const_words; // the odds table, then sigma3 — one copy, one trip to memory
+    // Order-free hit values (k_sector): n applications of ONE odds-table entry a — p_1 = a, p_(n+1) = 1 - (1 - p_n)(1 - a), each operation
+    // rounded to float — and logit(p_n), for n = 1 .. hit_tab_n, laid out [entry of the odds table][n - 1].  Filled on the device by
+    // k_fill_hit_tables with the very loop body and mlm_logit the kernels run (mlm_create, after logit_exact is settled): same bits.
+    const float *hit_p;        // [21*nRho][hit_tab_n] p_n
+    const float *hit_inc;      // [21*nRho][hit_tab_n] mlm_logit(p_n)
+    unsigned int hit_tab_n;    // power of two (knob hit_tab_n, default 256, halved until both tables fit 16 MB); 0: no tables
+    float logit_one;           // mlm_logit(1.0f) from the same kernel: the increment of a cell with enough strong contributions
     const double *cos_phi;     // [nPhi] cos/sin of the cell-centre azimuth (map_awareness.cpp:59-61)
     const double *sin_phi;
     // ---- per-frame awareness scratch

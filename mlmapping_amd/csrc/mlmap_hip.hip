@@ -436,6 +436,28 @@ int mlm_create(const mlm_config *cfg, const mlm_limits *lim_in, int device, mlm_
     }
     P.cos_phi = d_c;
     P.sin_phi = d_s;
+    {
+        // order-free hit values (MlmDev::hit_p / hit_inc): filled on the device from the uploaded odds table with the kernels' own chain and
+        // logit, now that logit_exact is settled (neither changes during the handle's life).  Largest power of two up to the knob's
+        // (default 256) with which both tables fit 16 MB; S1 takes 2 x 1.4 MB.
+        unsigned int tn = 256;
+        if (knob("hit_tab_n", kv)) tn = (unsigned int)kv;
+        const size_t entries = h->odds_table.size();
+        while (tn && 2 * entries * tn * sizeof(float) > ((size_t)16 << 20)) tn >>= 1;
+        P.hit_tab_n = tn;
+        P.logit_one = 0.0f;
+        if (tn) {
+            float *d_hp, *d_hi, *d_one;
+            if ((rc = dev_alloc(h, &d_hp, entries * tn))) return rc;
+            if ((rc = dev_alloc(h, &d_hi, entries * tn))) return rc;
+            if ((rc = dev_alloc(h, &d_one, 1))) return rc;
+            hipLaunchKernelGGL(k_fill_hit_tables, dim3((unsigned int)((entries + 255) / 256)), dim3(256), 0, 0, P, d_hp, d_hi, d_one);
+            HIPCHK(h, hipGetLastError());
+            HIPCHK(h, hipMemcpy(&P.logit_one, d_one, sizeof(float), hipMemcpyDeviceToHost));
+            P.hit_p = d_hp;
+            P.hit_inc = d_hi;
+        }
+    }
 
     const size_t NC = (size_t)P.nCells;
     // the emulated container can never hold more than nCells keys: bucket counts stay below the first
