@@ -253,6 +253,29 @@ class mlmap {
                                summary),
               "mlm_export_route");
     }
+    // paths through a parent field of exportReach (kind MLM_PATH_REACH) or exportRoute (MLM_PATH_ROUTE), traced from each goal to its
+    // seed and shortened to way points (mlm_query_paths; lookahead 1 .. 4096, max_moves 1 .. 2^20; parent, goals and outputs host or
+    // device memory, NULL = skipped; cap rows of way3 per goal, 0 with way3 == NULL)
+    void queryPaths(const int32_t lo[3], const int32_t dims[3], const uint8_t *parent, int kind, const int32_t *goals3, int n, int lookahead,
+                    int max_moves, int cap, int8_t *status, int32_t *way3 = nullptr, double *length = nullptr, int64_t *table = nullptr) {
+        check(mlm_query_paths(h_, lo, dims, parent, kind, goals3, n, lookahead, max_moves, cap, status, way3, length, table), "mlm_query_paths");
+    }
+    // one goal: its way points, goal first, seed last; empty if there is no path (goal not reached or outside the box, path longer than
+    // max_moves, broken field).  length (optional): the polyline in metres.
+    std::vector<Vec3I> tracePath(const int32_t lo[3], const int32_t dims[3], const uint8_t *parent, int kind, const Vec3I &goal, int lookahead,
+                                 int max_moves, double *length = nullptr) {
+        const int32_t g[3] = {goal[0], goal[1], goal[2]};
+        int8_t st = 0;
+        int64_t row[MLM_PATH_ROW] = {};
+        check(mlm_query_paths(h_, lo, dims, parent, kind, g, 1, lookahead, max_moves, 0, &st, nullptr, nullptr, row), "mlm_query_paths");
+        std::vector<Vec3I> out;
+        if (st != 1) return out;
+        std::vector<int32_t> way((size_t)row[1] * 3);
+        check(mlm_query_paths(h_, lo, dims, parent, kind, g, 1, lookahead, max_moves, (int)row[1], nullptr, way.data(), length, nullptr),
+              "mlm_query_paths");
+        for (size_t t = 0; t < (size_t)row[1]; ++t) out.push_back(Vec3I{{way[3 * t], way[3 * t + 1], way[3 * t + 2]}});
+        return out;
+    }
 
     // connected components of a voxel set of a box with per-component statistics (mlm_export_clusters; flags MLM_CLUSTER_*;
     // connectivity 6 / 18 / 26; labels / table host or device memory, table [cap][MLM_CLUSTER_ROW], summary host memory, NULL = skipped)

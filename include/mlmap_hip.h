@@ -595,6 +595,54 @@ int mlm_export_route(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], 
                      int flags, int clearance, int connectivity, const int32_t move_cost[3],
                      const int32_t *penalty, int n_penalty, int max_cost,
                      int32_t *cost, uint8_t *parent, int64_t summary[4]);
+/* Paths through a parent field, traced and shortened to way points (no reference counterpart: the reference has neither a cost field
+ * nor a path query; the rule is defined here, in integers, with exactly one answer).  The call reads the field it is given and no map
+ * state.  Window (lo, dims), layout ([dims[2]][dims[1]][dims[0]], x fastest) and errors are those of mlm_export_window.
+ *   Field: `parent` holds one byte per voxel of the box: what mlm_export_reach (kind MLM_PATH_REACH, M = 6) or mlm_export_route (kind
+ *   MLM_PATH_ROUTE, M = 26) wrote for it.  Bytes 0 .. M - 1 are moves with the offsets of mlm_export_route's codes (the first six are
+ *   mlm_export_reach's), M is a seed.  open(v) iff v lies in the box and parent[v] <= M.  The answer is defined, and the call ends, for
+ *   any content of `parent`: nothing relies on the field being genuine.
+ *   Trace: goal i is the absolute voxel goals3[3i .. 3i+2].  Outside the box or not open: status 0, table row all zero.  Else u_0 =
+ *   goal, k = 0, and in this order: c = parent[u_k]; if c == M: status 1, K = k, stop; if k == max_moves: status -1 (too long), K = k,
+ *   stop; u' = u_k + offset(c); if u' is outside the box or not open: status -2 (broken field), K = k, stop; else u_{k+1} = u', k += 1.
+ *   Visibility: vis(a, b), for open voxels a, b with |b_x - a_x| <= lookahead on every axis, in integers: n_x = |b_x - a_x|, s_x =
+ *   sign(b_x - a_x); a walk starts at c = a with counters k_x = 0; while c != b: of the axes with k_x < n_x take the smallest crossing
+ *   parameter (2 k_x + 1) / (2 n_x) (compared by cross-multiplication) and the set T of all axes that attain it (1, 2 or 3 axes); for
+ *   every non-empty subset S of T the voxel c + sum over S of s_x e_x must be open, else vis is false; then c += sum over T of
+ *   s_x e_x and k_x += 1 for x in T.  This is mlm_query_rays' path between the two voxel centres plus every voxel the segment grazes at
+ *   an exact edge or corner tie; for a unit offset it is mlm_export_route's permitted-move rule, so a shortened path cuts no corner
+ *   the field's own moves may not cut; vis(a, b) == vis(b, a).  An open voxel is a reached traversable voxel, so every voxel under a
+ *   shortened leg keeps the field's hard clearance; the soft penalty is not re-optimised: the shortening is geometric.
+ *   Shortening (status 1; L = lookahead, 1 .. 4096): i_0 = 0, i_{t+1} = max{ j : i_t < j <= min(K, i_t + L), j == i_t + 1 or
+ *   vis(u_{i_t}, u_j) }, until i_t == K.  The maximum is over all j of the window, not over the first run of visible ones.  The way
+ *   points are u_{i_0} .. u_{i_{W-1}}, goal first, seed last; W = 1 for a goal that is a seed; L = 1 returns the raw path, W = K + 1.
+ *   Per goal:
+ *     status  int8               1, 0, -1 or -2 as above
+ *     way3    int32 [cap][3]     status 1: the first min(W, cap) way points as absolute voxel indices, rows beyond left as they were;
+ *                                nothing is written at another status.  cap >= 0; cap == 0 iff way3 == NULL.
+ *     length  double             status 1: the way-point polyline in metres: acc = 0.0, then for t = 0 .. W - 2 in order
+ *                                acc = acc + ((double)(float)subbox_d_xyz * sqrt((double)sq_t)), sq_t the integer squared voxel length
+ *                                of leg t; every operation one IEEE double operation, nothing fused, sqrt correctly rounded; all legs
+ *                                count, whatever cap.  -1.0 at another status.
+ *     table   int64 [MLM_PATH_ROW]  [0] K (at status -1 and -2 too: the moves taken); at status 1 also [1] W, [2] [3] [4] the face, edge
+ *                                and corner moves of the raw path, [5] the longest leg in moves (max of i_{t+1} - i_t; 0 for W = 1),
+ *                                [6] the sum over t of min(K, i_t + L) - i_{t+1}: the candidates beyond the chosen one, [7] 0;
+ *                                otherwise [1 .. 7] are 0.
+ * parent, goals3 and each output on its own may be host or device memory; any output may be NULL, at least one must not be.  The call
+ * takes the handle's lock, runs on the stream of mlm_set_stream and returns when the outputs are written; it does not read the map,
+ * so it does not wait for submitted frames.  With parent in host memory the whole call runs on the host (same rule, same answers; no
+ * launch, no copy of the field; goals and outputs in device memory are copied across); with parent in device memory it runs as a
+ * kernel, host goals and outputs staged in mlm_query_rays' buffer.  MLM_ERR_INVALID: the window errors, parent NULL, kind not 0 or 1,
+ * n < 0 or goals3 NULL with n > 0, lookahead outside [1, 4096], max_moves outside [1, 2^20], cap < 0 or at odds with way3, no output;
+ * n == 0 is MLM_OK.  MLM_ERR_CAPACITY: no device memory for the path scratch (12 bytes x (max_moves + 1) per goal, taken for chunks of
+ * goals of at most 256 MiB, kept by the handle and counted in mlm_frame_stats.device_bytes) or for the staging (85 + 12 cap bytes per
+ * goal, chunks of at most 64 MiB).  The handle stays usable after either error. */
+#define MLM_PATH_REACH 0 /* parent field of mlm_export_reach: move codes 0..5,  seed code 6  */
+#define MLM_PATH_ROUTE 1 /* parent field of mlm_export_route: move codes 0..25, seed code 26 */
+#define MLM_PATH_ROW 8
+int mlm_query_paths(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], const uint8_t *parent, int kind,
+                    const int32_t *goals3, int n, int lookahead, int max_moves, int cap,
+                    int8_t *status, int32_t *way3, double *length, int64_t *table);
 /* Connected components of a voxel set of a box, with per-component statistics (no reference counterpart: the reference has no
  * clustering, its visualiser publishes the frontier cloud raw; the classes behind the set are those of its point queries, set,
  * components and numbering are defined here, in integers).  Voxel indices, window, layout ([dims[2]][dims[1]][dims[0]], x

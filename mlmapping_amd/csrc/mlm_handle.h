@@ -146,6 +146,11 @@ constexpr unsigned int kBoxGrid = 8192;      // most workgroups of k_boxes (a wa
 constexpr long long kNearMirrorVoxels = 1ll << 18;
 constexpr int kNearChunk = 1 << 18;          // points per launch of k_nearest: bounds the staging of host inputs / outputs (65 bytes per point)
 constexpr unsigned int kNearGrid = 8192;     // most workgroups of k_nearest (a wave per point, grid-stride), as kBoxGrid
+// mlm_query_paths: goals per launch of k_paths (a wave and a scratch slot of 12 bytes x (max_moves + 1) per goal), the most path scratch
+// and the most staging of host goals / outputs (85 + 12 cap bytes per goal) of one launch
+constexpr int kPathChunk = 1 << 16;
+constexpr size_t kPathScratchBytes = (size_t)256 << 20;
+constexpr size_t kPathStageBytes = (size_t)64 << 20;
 
 // A frame on its own with at most this many strips of 256 points (sampled callbacks, point lists: 4 096 points) runs its cells' float chains
 // inside k_rank<true> instead of launching k_chain_lanes — a launch of its own costs a lone frame the kernel boundary (1.5 us) and the few
@@ -191,7 +196,11 @@ struct mlm_handle {
     // need (staged rays use d_ray_stage, a staged exclude / mark d_win_stage)
     void *d_views = nullptr;
     size_t views_bytes = 0;
-    // mlm_query_boxes stages the host inputs / outputs of one chunk of boxes in d_ray_stage too, mlm_query_nearest those of one chunk of points
+    // mlm_query_boxes stages the host inputs / outputs of one chunk of boxes in d_ray_stage too, mlm_query_nearest those of one chunk of
+    // points, mlm_query_paths those of one chunk of goals
+    // mlm_query_paths: the traced paths of one chunk of goals (three int32 arrays of max_moves + 1 entries per goal), kept and enlarged by need
+    void *d_path = nullptr;
+    size_t path_bytes = 0;
     unsigned int rays_grid = 1024; // most workgroups of k_rays (knob "rays_grid"): 2^20 rays are four per lane
     // mlm_render_depth stages host poses, one chunk of host per-pixel outputs and a host table in d_ray_stage too
     int render_tile = kRenderTileDefault; // (knob "render_tile")

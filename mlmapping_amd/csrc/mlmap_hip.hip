@@ -18,7 +18,9 @@
 #include <cstdio>
 #include <cstring>
 #include <deque>
+#include <memory>
 #include <mutex>
+#include <new>
 #include <string>
 #include <type_traits>
 #include <unordered_map>
@@ -39,6 +41,7 @@
 #include "mlm_kernels_views.h"
 #include "mlm_kernels_reach.h"
 #include "mlm_kernels_route.h"
+#include "mlm_kernels_path.h"
 #include "mlm_kernels_cluster.h"
 #include "mlm_host.h"
 #include "mlm_mapview.h"
@@ -2268,6 +2271,111 @@ int mlm_query_nearest(mlm_handle *h, const double *pos, int n, int max_dist, int
         for (int c = 1; c < 6; ++c)
             if (staged[c])
                 HIPCHK(h, hipMemcpyAsync((char *)ch[c] + (size_t)i0 * elem[c], at[c], (size_t)m * elem[c], hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MLM_OK;
+}
+
+int mlm_query_paths(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], const uint8_t *parent, int kind, const int32_t *goals3, int n,
+                    int lookahead, int max_moves, int cap, int8_t *status, int32_t *way3, double *length, int64_t *table) {
+    if (!h) return MLM_ERR_INVALID;
+    MLM_LOCK(h);
+    if (!lo || !dims || !parent || (kind != MLM_PATH_REACH && kind != MLM_PATH_ROUTE) || n < 0 || (n > 0 && !goals3) || lookahead < 1 ||
+        lookahead > MLM_PATH_MAX_LOOKAHEAD || max_moves < 1 || max_moves > MLM_PATH_MAX_MOVES || cap < 0 || (cap == 0) != (way3 == nullptr) ||
+        (!status && !way3 && !length && !table)) {
+        h->err = "mlm_query_paths: null window or parent, kind not 0 / 1, negative n, null goals, lookahead outside [1, 4096], max_moves outside "
+                 "[1, 2^20], cap negative or at odds with way3, or no output";
+        return MLM_ERR_INVALID;
+    }
+    long long nvox = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (dims[a] < 1 || (long long)lo[a] + dims[a] > 0x7FFFFFFFll) {
+            h->err = "mlm_query_paths: dims must be >= 1 and lo + dims must fit an int32";
+            return MLM_ERR_INVALID;
+        }
+        nvox *= dims[a];
+        if (nvox > 0x7FFFFFFFll) {
+            h->err = "mlm_query_paths: more than 2^31 - 1 voxels";
+            return MLM_ERR_INVALID;
+        }
+    }
+    if (n == 0) return MLM_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    const MlmPathField F{parent, {dims[0], dims[1], dims[2]}, mlm_path_seed_code(kind)};
+    const double d = (double)(float)h->P.d_sub;
+    // channels: the goals, then the four outputs; bytes per goal; way3 is read too (rows beyond W keep their content)
+    void *ch[5] = {(void *)goals3, status, way3, length, table};
+    const size_t elem[5] = {3 * sizeof(int32_t), 1, (size_t)cap * 3 * sizeof(int32_t), sizeof(double), MLM_PATH_ROW * sizeof(int64_t)};
+    bool on_dev[5];
+    for (int c = 0; c < 5; ++c) on_dev[c] = ch[c] && win_in_place(ch[c]);
+
+    if (!win_in_place(parent)) {
+        // the field is in host memory: the shared rule on the host, no launch and no copy of the field; goals and outputs in device
+        // memory are copied across
+        std::vector<std::vector<char>> tmp(5);
+        void *at[5];
+        for (int c = 0; c < 5; ++c) {
+            at[c] = ch[c];
+            if (!on_dev[c]) continue;
+            tmp[c].resize((size_t)n * elem[c]);
+            at[c] = tmp[c].data();
+            if (c == 0 || c == 2) HIPCHK(h, hipMemcpyAsync(at[c], ch[c], tmp[c].size(), hipMemcpyDeviceToHost, h->stream));
+        }
+        if (on_dev[0] || on_dev[2]) HIPCHK(h, hipStreamSynchronize(h->stream));
+        const size_t len = (size_t)max_moves + 1;
+        std::unique_ptr<int32_t[]> path(new (std::nothrow) int32_t[3 * len]); // (not touched beyond the longest path)
+        if (!path) {
+            h->err = "mlm_query_paths: no host memory for the path";
+            return MLM_ERR_CAPACITY;
+        }
+        MlmPathSerial X{path.get(), path.get() + len, path.get() + 2 * len};
+        for (int i = 0; i < n; ++i) {
+            const MlmPathOut o{at[1] ? (int8_t *)at[1] + i : nullptr, at[2] ? (int32_t *)at[2] + 3 * (size_t)i * (size_t)cap : nullptr,
+                               at[3] ? (double *)at[3] + i : nullptr, at[4] ? (int64_t *)at[4] + (size_t)i * MLM_PATH_ROW : nullptr};
+            mlm_path_goal(F, lo, (const int32_t *)at[0] + 3 * (size_t)i, lookahead, max_moves, cap, d, X, o);
+        }
+        bool copied = false;
+        for (int c = 1; c < 5; ++c)
+            if (on_dev[c]) {
+                HIPCHK(h, hipMemcpyAsync(ch[c], at[c], tmp[c].size(), hipMemcpyHostToDevice, h->stream));
+                copied = true;
+            }
+        if (copied) HIPCHK(h, hipStreamSynchronize(h->stream));
+        return MLM_OK;
+    }
+
+    // the field is in device memory: k_paths, a wave per goal.  Chunks of goals: the path scratch of a chunk (12 bytes x (max_moves + 1)
+    // per goal) takes at most kPathScratchBytes, its staged host channels at most kPathStageBytes, and it has at most kPathChunk goals
+    const size_t per_goal = 3 * sizeof(int32_t) * ((size_t)max_moves + 1);
+    size_t stage_per_goal = 0;
+    for (int c = 0; c < 5; ++c)
+        if (ch[c] && !on_dev[c]) stage_per_goal += elem[c];
+    size_t chunk = std::min<size_t>({(size_t)n, (size_t)kPathChunk, std::max<size_t>(1, kPathScratchBytes / per_goal)});
+    if (stage_per_goal) chunk = std::min(chunk, std::max<size_t>(1, kPathStageBytes / stage_per_goal));
+    size_t off[5], stage_bytes = 0;
+    for (int c = 0; c < 5; ++c) {
+        off[c] = stage_bytes;
+        if (ch[c] && !on_dev[c]) stage_bytes += (chunk * elem[c] + 255) & ~(size_t)255;
+    }
+    int rc;
+    if ((rc = win_reserve(h, h->d_path, h->path_bytes, chunk * per_goal, "mlm_query_paths"))) return rc;
+    if (stage_bytes && (rc = win_reserve(h, h->d_ray_stage, h->ray_stage_bytes, stage_bytes, "mlm_query_paths"))) return rc;
+    for (size_t i0 = 0; i0 < (size_t)n; i0 += chunk) {
+        const size_t m = std::min(chunk, (size_t)n - i0);
+        void *at[5];
+        for (int c = 0; c < 5; ++c)
+            at[c] = !ch[c] ? nullptr : on_dev[c] ? (void *)((char *)ch[c] + i0 * elem[c]) : (void *)((char *)h->d_ray_stage + off[c]);
+        for (int c : {0, 2}) // goals in; way3 in, for the rows the kernel leaves as they were
+            if (ch[c] && !on_dev[c])
+                HIPCHK(h, hipMemcpyAsync(at[c], (const char *)ch[c] + i0 * elem[c], m * elem[c], hipMemcpyHostToDevice, h->stream));
+        MlmPaths Q{F, {lo[0], lo[1], lo[2]}, (const int32_t *)at[0], (int)m, lookahead, max_moves, cap, d, (int32_t *)h->d_path,
+                   (int8_t *)at[1], (int32_t *)at[2], (double *)at[3], (int64_t *)at[4]};
+        // one wave per goal and scratch slot, four to a workgroup (m <= kPathChunk: at most 16 384 workgroups)
+        const dim3 grid((unsigned int)((m + MLM_BLOCK / 64 - 1) / (MLM_BLOCK / 64)));
+        hipLaunchKernelGGL(k_paths, grid, dim3(MLM_BLOCK), 0, h->stream, Q);
+        HIPCHK(h, hipGetLastError());
+        for (int c = 1; c < 5; ++c)
+            if (ch[c] && !on_dev[c]) HIPCHK(h, hipMemcpyAsync((char *)ch[c] + i0 * elem[c], at[c], m * elem[c], hipMemcpyDeviceToHost, h->stream));
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MLM_OK;

@@ -32,6 +32,7 @@ MLM_GRID_OCC, MLM_GRID_INFL, MLM_GRID_UNKNOWN, MLM_GRID_DIST_UNOBSERVED, MLM_GRI
 MLM_REACH_OCC, MLM_REACH_INFL, MLM_REACH_UNKNOWN, MLM_REACH_NONE, MLM_REACH_SEED = 1, 2, 4, -1, 6
 # mlm_export_route: the same predicates, cost of a voxel not reached, parent code of a seed (0..25 are the moves' codes)
 MLM_ROUTE_OCC, MLM_ROUTE_INFL, MLM_ROUTE_UNKNOWN, MLM_ROUTE_NONE, MLM_ROUTE_SEED = 1, 2, 4, -1, 26
+MLM_PATH_REACH, MLM_PATH_ROUTE, MLM_PATH_ROW = 0, 1, 8
 # mlm_export_clusters: the set (FRONTIER alone, or a union of the class bits), labels off the set / in a dropped component, int64 per row
 MLM_CLUSTER_OCC, MLM_CLUSTER_INFL, MLM_CLUSTER_UNKNOWN, MLM_CLUSTER_FRONTIER = 1, 2, 4, 16
 MLM_CLUSTER_NONE, MLM_CLUSTER_SMALL, MLM_CLUSTER_ROW = -1, -2, 16
@@ -54,7 +55,7 @@ ABI_SYMBOLS = [
     "mlm_query_odds", "mlm_query_odd_grad", "mlm_query_odds_at", "mlm_export_frontier_points", "mlm_import_blocks",
     "mlm_merge_pack", "mlm_merge_finish",
     "mlm_set_free_in_bound", "mlm_inflate_map", "mlm_block_count",
-    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_grid2d", "mlm_export_reach", "mlm_export_route", "mlm_export_clusters", "mlm_query_rays", "mlm_render_depth", "mlm_query_views", "mlm_query_boxes", "mlm_query_nearest", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
+    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_grid2d", "mlm_export_reach", "mlm_export_route", "mlm_export_clusters", "mlm_query_rays", "mlm_render_depth", "mlm_query_views", "mlm_query_boxes", "mlm_query_nearest", "mlm_query_paths", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
     "mlm_get_awareness_hits",
     "mlm_get_awareness_misses", "mlm_get_T_ls", "mlm_get_odds_table", "mlm_get_kernel_times",
     "mlm_enable_kernel_timing", "mlm_set_timed_kernel", "mlm_host_register", "mlm_host_unregister", "mlm_debug_set", "mlm_debug_reset",
@@ -158,6 +159,7 @@ def load_library(path: Optional[str] = None):
     L.mlm_query_views.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.mlm_query_boxes.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.mlm_query_nearest.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
+    L.mlm_query_paths.argtypes = [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp]
     L.mlm_export_global_map.argtypes = [vp, i32, vp, vp]
     L.mlm_export_block_flags.argtypes = [vp, i32, vp, vp]
     L.mlm_export_frontier.argtypes = [vp, i32, vp, vp]
@@ -895,6 +897,108 @@ class MLMap:
         ptr = [None if v is None else ctypes.c_void_p(v) for v in (status, voxel, delta, sq, dist)]
         self._chk(self._L.mlm_query_nearest(self._h, ctypes.c_void_p(pos), int(n), int(max_dist), self._ray_flags(occ, infl, unknown), *ptr),
                   "mlm_query_nearest")
+
+    PATH_OUTPUTS = ("status", "way", "length", "table")
+    PATH_KINDS = {"reach": MLM_PATH_REACH, "route": MLM_PATH_ROUTE, MLM_PATH_REACH: MLM_PATH_REACH, MLM_PATH_ROUTE: MLM_PATH_ROUTE}
+
+    @staticmethod
+    def _path_max_moves(dims_a, max_moves) -> int:
+        """None: eight times the box's edge sum, at most voxels - 1 (no genuine path is longer) and 2^20, at least 1"""
+        if max_moves is not None:
+            return int(max_moves)
+        d = [int(v) for v in dims_a]
+        return max(1, min(2 ** 20, d[0] * d[1] * d[2] - 1, 8 * sum(d)))
+
+    def query_paths(self, lo, dims, parent, goals, kind="route", lookahead: int = 64, max_moves: Optional[int] = None, cap: int = 64,
+                    outputs=None):
+        """Paths through a parent field, traced and shortened to way points (mlm_query_paths).  lo, dims: the voxel box of the field
+        (as export_window); parent: its uint8 bytes (dz, dy, dx) as export_route (kind "route") or export_reach (kind "reach") wrote
+        them — a numpy array (the call runs on the host) or a torch device tensor (it runs as a kernel); goals: n x 3 int32 absolute
+        voxel indices — a numpy array (numpy results) or a torch device tensor (torch device results).  lookahead: 1 .. 4096 moves,
+        how far ahead of a way point the next one is looked for (1: the raw path); max_moves: 1 .. 2^20, the longest path traced
+        (None: eight times the sum of the box's edges, at most the box's voxels - 1); cap: rows of "way" per goal.  outputs: the names
+        wanted (None: all four).  {"status": int8 (1 path, 0 goal not reached or outside the box, -1 longer than max_moves, -2
+        broken field), "way": int32 (n, cap, 3) the first min(W, cap) way points, goal first, seed last, zeros beyond, "length":
+        float64 the way-point polyline in metres (-1.0 without a path), "table": int64 (n, 8) [moves K, way points W, face, edge,
+        corner moves, longest leg in moves, candidates beyond the chosen ones, 0]}."""
+        names = self.PATH_OUTPUTS if outputs is None else tuple(outputs)
+        if not names or any(k not in self.PATH_OUTPUTS for k in names):
+            raise MlmError("query_paths: outputs must name at least one of " + ", ".join(self.PATH_OUTPUTS))
+        if kind not in self.PATH_KINDS:
+            raise MlmError("query_paths: kind must be 'reach' or 'route'")
+        lo_a, dims_a = self._window_args(lo, dims)
+        nvox = int(dims_a[0]) * int(dims_a[1]) * int(dims_a[2])
+        if isinstance(parent, np.ndarray) or not hasattr(parent, "data_ptr"):
+            par = np.ascontiguousarray(np.asarray(parent, dtype=np.uint8))
+            if par.size != nvox:
+                raise MlmError("query_paths: parent must hold one byte per voxel of the box")
+            par_p = _p(par)
+        else:
+            import torch
+
+            if parent.dtype != torch.uint8 or parent.numel() != nvox or not parent.is_contiguous():
+                raise MlmError("query_paths: a parent tensor must be contiguous uint8 with one byte per voxel of the box")
+            par_p = ctypes.c_void_p(parent.data_ptr())
+        cap = int(cap)
+        if cap < 0 or (cap == 0 and "way" in names):
+            raise MlmError("query_paths: cap must be >= 1 with the output 'way' (>= 0 without)")
+        if "way" not in names:
+            cap = 0
+        if isinstance(goals, np.ndarray) or not hasattr(goals, "data_ptr"):
+            g = np.ascontiguousarray(np.asarray(goals, dtype=np.int32).reshape(-1, 3))
+            n = g.shape[0]
+            shapes = {"status": ((n,), np.int8), "way": ((n, cap, 3), np.int32), "length": ((n,), np.float64),
+                      "table": ((n, MLM_PATH_ROW), np.int64)}
+            out = {k: np.zeros(*shapes[k]) for k in names}
+            ptr = [_p(g)] + [_p(out[k]) if k in out else None for k in self.PATH_OUTPUTS]
+        else:
+            import torch
+
+            if goals.dtype != torch.int32 or goals.numel() % 3 or not goals.is_contiguous():
+                raise MlmError("query_paths: a tensor of goals must be contiguous int32 with 3 values per goal")
+            n = goals.numel() // 3
+            shapes = {"status": ((n,), torch.int8), "way": ((n, cap, 3), torch.int32), "length": ((n,), torch.float64),
+                      "table": ((n, MLM_PATH_ROW), torch.int64)}
+            out = {k: torch.zeros(shapes[k][0], dtype=shapes[k][1], device=goals.device) for k in names}
+            ptr = [ctypes.c_void_p(goals.data_ptr())] + [ctypes.c_void_p(out[k].data_ptr()) if k in out else None for k in self.PATH_OUTPUTS]
+        self._chk(self._L.mlm_query_paths(self._h, _p(lo_a), _p(dims_a), par_p, self.PATH_KINDS[kind], ptr[0], n, int(lookahead),
+                                          self._path_max_moves(dims_a, max_moves), cap, *ptr[1:]), "mlm_query_paths")
+        return out
+
+    def query_paths_dev(self, lo, dims, parent: int, goals: int, n: int, kind="route", lookahead: int = 64, max_moves: Optional[int] = None,
+                        cap: int = 0, status: Optional[int] = None, way: Optional[int] = None, length: Optional[int] = None,
+                        table: Optional[int] = None):
+        """Same on pointers (ints; device or host memory, each on its own): parent dz*dy*dx uint8, goals n x 3 int32, outputs n int8 /
+        n x cap x 3 int32 / n float64 / n x 8 int64, None = skipped (cap 0 without way)."""
+        if kind not in self.PATH_KINDS:
+            raise MlmError("query_paths: kind must be 'reach' or 'route'")
+        lo_a, dims_a = self._window_args(lo, dims)
+        ptr = [None if v is None else ctypes.c_void_p(v) for v in (status, way, length, table)]
+        self._chk(self._L.mlm_query_paths(self._h, _p(lo_a), _p(dims_a), ctypes.c_void_p(parent), self.PATH_KINDS[kind], ctypes.c_void_p(goals),
+                                          int(n), int(lookahead), self._path_max_moves(dims_a, max_moves), int(cap), *ptr), "mlm_query_paths")
+
+    def route_paths(self, lo, dims, seeds, goals, occ=True, infl=False, unknown=False, clearance: int = 0, connectivity: int = 26,
+                    move_cost=(10, 14, 17), penalty=(), max_cost: Optional[int] = None, lookahead: int = 64,
+                    max_moves: Optional[int] = None, cap: int = 64, outputs=None):
+        """export_route into a device tensor, then query_paths on it: the way points from each goal to its cheapest seed; the field
+        never leaves the device.  seeds: k x 3 voxel indices (array or int32 device tensor); goals and results as query_paths (plus
+        "summary", export_route's four counters); the other arguments as export_route and query_paths."""
+        import torch
+
+        lo_a, dims_a = self._window_args(lo, dims)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        if hasattr(seeds, "data_ptr"):
+            if seeds.dtype != torch.int32 or seeds.numel() % 3 or not seeds.is_contiguous():
+                raise MlmError("route_paths: a tensor of seeds must be contiguous int32 with 3 values per seed")
+            s = seeds
+        else:
+            s = torch.from_numpy(np.ascontiguousarray(np.asarray(seeds, dtype=np.int32).reshape(-1, 3))).to(dev)
+        field = torch.empty((int(dims_a[2]), int(dims_a[1]), int(dims_a[0])), dtype=torch.uint8, device=s.device)
+        summary = self.export_route_dev(lo_a, dims_a, s.data_ptr(), s.numel() // 3, occ, infl, unknown, clearance, connectivity, move_cost,
+                                        penalty, max_cost, parent=field.data_ptr(), summary=True)
+        out = self.query_paths(lo_a, dims_a, field, goals, "route", lookahead, max_moves, cap, outputs)
+        out["summary"] = summary
+        return out
 
     @staticmethod
     def _ray_flags(occ, infl, unknown) -> int:
