@@ -375,6 +375,12 @@ class mlmap {
         voxel = Vec3I{{v[0], v[1], v[2]}};
         return st == 1;
     }
+    // exact batched segment casts for a ball of `radius` voxels (mlm_query_sweeps; flags MLM_SWEEP_*, radius 0 .. 16; inputs and
+    // outputs host or device memory, NULL = skipped)
+    void querySweeps(const double *p0, const double *p1, int n, int radius, int flags, int8_t *status, int32_t *voxel3 = nullptr, double *t = nullptr,
+                     int32_t *n_steps = nullptr, int32_t *n_unknown = nullptr, int32_t *hit3 = nullptr, int32_t *hit_sq = nullptr) {
+        check(mlm_query_sweeps(h_, p0, p1, n, radius, flags, status, voxel3, t, n_steps, n_unknown, hit3, hit_sq), "mlm_query_sweeps");
+    }
 
     // planners that query thousands of positions per cycle should use the batched entry points directly
     mlm_handle *handle() { return h_; }

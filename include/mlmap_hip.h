@@ -506,6 +506,46 @@ int mlm_query_boxes(mlm_handle *h, const int32_t *box6, int n, int flags, const 
 #define MLM_NEAR_NONE (-1) /* sq of a point with no obstacle in range */
 int mlm_query_nearest(mlm_handle *h, const double *pos, int n, int max_dist, int flags,
                       int8_t *status, int32_t *voxel3, int32_t *delta3, int64_t *sq, double *dist);
+/* Exact batched segment casts for a ball of robot radius: "is the piece from a to b free for a vehicle of radius r, and if not, where
+ * does it stop and which obstacle voxel is responsible?"  (No reference counterpart: the reference has no segment query; the classes
+ * are those of its point queries, the stop rule is defined here, in integers, with exactly one answer.)  Segment i runs from
+ * p0[3i .. 3i+2] to p1[3i .. 3i+2].  The lattice, the validity rule, the path u_0 .. u_N, the tie rule of the walk and the classes
+ * are mlm_query_rays'.
+ *   Stop predicate: O(o) is the union of what `flags` selects (MLM_SWEEP_OCC / _INFL / _UNKNOWN, as MLM_RAY_*; flags == 0: nothing
+ *   stops a ray).  r = radius, 0 .. MLM_SWEEP_MAX_RADIUS voxels.  BLOCKED_r(v) holds iff some voxel o of the whole map has O(o) and
+ *   |o - v|^2 <= r^2 (integer squared index distance) — mlm_export_reach's BLOCKED at clearance r, so an edge checked here and a field
+ *   of mlm_export_reach / mlm_export_route agree voxel for voxel about "free for radius r".  The sweep stops at the smallest path
+ *   index k with BLOCKED_r(u_k).
+ *   Per ray:                stopped at k                                        not stopped     invalid
+ *     status     int8       1                                                   0               -1
+ *     voxel3     int32 x 3  u_k (the ball's centre voxel)                       e               0,0,0
+ *     t          double     (double)m / (double)|D| of the step that entered    1.0             0.0
+ *                           u_k; 0.0 for k = 0
+ *     n_steps    int32      k                                                   N + 1           0
+ *     n_unknown  int32      centre-path voxels 0 .. k-1 whose occ is UNKNOWN    over the path   0
+ *     hit3       int32 x 3  the o with O(o), |o - u_k|^2 <= r^2 and the         e               0,0,0
+ *                           smallest (|o - u_k|^2, o_z, o_y, o_x)
+ *     hit_sq     int32      |hit3 - u_k|^2                                      MLM_SWEEP_NONE  MLM_SWEEP_NONE
+ *   (hit3's tie rule is mlm_query_nearest's.)  With radius 0 status, voxel3, t, n_steps and n_unknown are mlm_query_rays' bytes, and at
+ *   a stop hit3 == voxel3, hit_sq == 0.  For a stopped ray mlm_export_esdf's sqdist at max_dist r + 1 equals hit_sq at u_k and is
+ *   greater than r^2 at u_0 .. u_{k-1}.  Every word is a function of the map and the arguments alone.
+ * Any output may be NULL, at least one must not be; p0, p1 and each output on its own may be host or device memory.  The call observes
+ * the map as queries do (async mode: waits for everything submitted), runs on the stream of mlm_set_stream and returns when the
+ * outputs are written.  A batch in host memory of at most 64 rays (8 while the host mirror needs a refresh) whose valid rays' sum of
+ * (2r + 1)^3 + N * L(r) is at most 2^18 — L(r) the number of (p, q) with p^2 + q^2 <= r^2 — is answered from the host mirror without a
+ * launch (same answers); everything else, and every batch after mlm_set_host_mirror_limit(h, 0), runs as a kernel.  MLM_ERR_INVALID:
+ * n < 0, a NULL input with n > 0, an unknown flag bit, radius outside [0, 16], no output; n == 0 is MLM_OK.  MLM_ERR_CAPACITY: no
+ * device memory for the staging of host inputs / outputs (at most 93 bytes x 2^18 rays, each part rounded up to 256 bytes, in the
+ * buffer mlm_query_rays stages in, kept by the handle and counted in mlm_frame_stats.device_bytes; larger batches run in chunks).
+ * The handle stays usable after either error. */
+#define MLM_SWEEP_OCC 1 /* same bits and same meaning as MLM_RAY_OCC / _INFL / _UNKNOWN */
+#define MLM_SWEEP_INFL 2
+#define MLM_SWEEP_UNKNOWN 4
+#define MLM_SWEEP_MAX_RADIUS 16
+#define MLM_SWEEP_NONE (-1) /* hit_sq of a ray that was not stopped */
+int mlm_query_sweeps(mlm_handle *h, const double *p0, const double *p1, int n, int radius, int flags,
+                     int8_t *status, int32_t *voxel3, double *t, int32_t *n_steps, int32_t *n_unknown,
+                     int32_t *hit3, int32_t *hit_sq);
 /* Cost-to-go field through the free space of a box of voxels (no reference counterpart: the reference has no such field; the
  * classes behind it are those of its point queries, the field is defined here, in integers).  Voxel indices, window, layout
  * ([dims[2]][dims[1]][dims[0]], x fastest) and centres are those of mlm_export_window.

@@ -146,6 +146,12 @@ constexpr unsigned int kBoxGrid = 8192;      // most workgroups of k_boxes (a wa
 constexpr long long kNearMirrorVoxels = 1ll << 18;
 constexpr int kNearChunk = 1 << 18;          // points per launch of k_nearest: bounds the staging of host inputs / outputs (65 bytes per point)
 constexpr unsigned int kNearGrid = 8192;     // most workgroups of k_nearest (a wave per point, grid-stride), as kBoxGrid
+// mlm_query_sweeps: a batch in host memory is answered on the host when it has at most as many rays as mlm_query_rays allows (64 / 8 by
+// default) AND the voxels the sweep can read — the start ball (2r + 1)^3 plus L(r) per step, summed over the valid rays, known from the
+// arguments alone — are at most kSweepMirrorVoxels
+constexpr long long kSweepMirrorVoxels = 1ll << 18;
+constexpr int kSweepChunk = 1 << 18;         // rays per launch of k_sweeps: bounds the staging of host inputs / outputs (93 bytes per ray)
+constexpr unsigned int kSweepGrid = 8192;    // most workgroups of k_sweeps (a wave per ray, grid-stride), as kNearGrid
 // mlm_query_paths: goals per launch of k_paths (a wave and a scratch slot of 12 bytes x (max_moves + 1) per goal), the most path scratch
 // and the most staging of host goals / outputs (85 + 12 cap bytes per goal) of one launch
 constexpr int kPathChunk = 1 << 16;
@@ -197,7 +203,7 @@ struct mlm_handle {
     void *d_views = nullptr;
     size_t views_bytes = 0;
     // mlm_query_boxes stages the host inputs / outputs of one chunk of boxes in d_ray_stage too, mlm_query_nearest those of one chunk of
-    // points, mlm_query_paths those of one chunk of goals
+    // points, mlm_query_paths those of one chunk of goals, mlm_query_sweeps those of one chunk of rays
     // mlm_query_paths: the traced paths of one chunk of goals (three int32 arrays of max_moves + 1 entries per goal), kept and enlarged by need
     void *d_path = nullptr;
     size_t path_bytes = 0;

@@ -15,6 +15,7 @@
 #include "mlm_boxgrow.h"
 #include "mlm_nearest.h"
 #include "mlm_raywalk.h"
+#include "mlm_sweep.h"
 
 namespace mlm_host {
 
@@ -336,6 +337,75 @@ struct MapView {
             }
             if (sq) sq[i] = o.sq;
             if (dist) dist[i] = o.dist;
+        }
+    }
+    // mlm_query_sweeps on the mirrored planes: the walk of mlm_sweep.h over the same classes.  The cap's voxels are looked up one by
+    // one (the block of the previous one is kept); the start voxel's ball is NearScan's.
+    struct SweepVox {
+        const MapView &v;
+        const uint32_t *tab; // the column table of the call's radius
+        int cols;
+        RayClasses cls;
+        NearScan near;
+        int bg[3] = {0, 0, 0}, slot = -1; // the block of the last cap voxel
+        bool have = false;
+        SweepVox(const MapView &view, const uint32_t *t, int L) : v(view), tab(t), cols(L), cls{view}, near{view} {}
+        int centre(const int g[3], const int c[3], bool new_block) { return cls(g, c, new_block); }
+        unsigned long long start(const MlmRayState &S, int r, int flags) {
+            const int u[3] = {S.g[0] * v.n + S.c[0], S.g[1] * v.n + S.c[1], S.g[2] * v.n + S.c[2]};
+            return mlm_sweep_start(u, v.n, r, flags, near);
+        }
+        unsigned long long cap(const MlmRayState &S, int axis, int s, bool, int, int flags) {
+            unsigned long long best = MLM_SWEEP_NOKEY;
+            for (int j = 0; j < cols; ++j) {
+                int off[3], g[3], c[3];
+                const unsigned long long key = mlm_sweep_column_key(tab[j], axis, s, off);
+                for (int a = 0; a < 3; ++a) {
+                    g[a] = S.g[a];
+                    c[a] = S.c[a] + off[a];
+                    while (c[a] < 0) c[a] += v.n, --g[a];
+                    while (c[a] >= v.n) c[a] -= v.n, ++g[a];
+                }
+                if (!have || g[0] != bg[0] || g[1] != bg[1] || g[2] != bg[2]) {
+                    slot = v.find(g[0], g[1], g[2]);
+                    bg[0] = g[0], bg[1] = g[1], bg[2] = g[2];
+                    have = true;
+                }
+                int bits;
+                if (slot < 0) bits = 4;
+                else if (v.col[slot]) bits = RayClasses::occ_bits(v.occ[(size_t)slot * v.cells]);
+                else {
+                    const size_t at = (size_t)slot * v.cells + (size_t)((c[2] * v.n + c[1]) * v.n + c[0]);
+                    bits = RayClasses::occ_bits(v.occ[at]);
+                    if (flags & 2) bits |= v.infl[at] == 'o' ? 2 : 0; // (infl is read only when INFL is selected, as in k_sweeps)
+                }
+                if ((bits & flags) && key < best) best = key;
+            }
+            return best;
+        }
+    };
+    // tab: mlm_sweep_table(radius), L columns
+    void sweep_one(const double p0[3], const double p1[3], int radius, int flags, const uint32_t *tab, int L, MlmSweepResult &o) const {
+        SweepVox vox(*this, tab, L);
+        mlm_sweep_walk(p0, p1, d_sub, n, radius, flags, vox, o);
+    }
+    // a batch, any output may be null (mlm_query_sweeps' layout)
+    void sweep(const double *p0, const double *p1, int count, int radius, int flags, int8_t *status, int32_t *voxel3, double *t, int32_t *n_steps,
+               int32_t *n_unknown, int32_t *hit3, int32_t *hit_sq) const {
+        std::vector<uint32_t> tab(MLM_SWEEP_MAX_COLS);
+        const int L = mlm_sweep_table(radius, tab.data());
+        for (int i = 0; i < count; ++i) {
+            MlmSweepResult o;
+            sweep_one(p0 + 3 * (size_t)i, p1 + 3 * (size_t)i, radius, flags, tab.data(), L, o);
+            if (status) status[i] = (int8_t)o.ray.status;
+            for (int a = 0; a < 3; ++a) {
+                if (voxel3) voxel3[3 * (size_t)i + a] = o.ray.voxel[a];
+                if (hit3) hit3[3 * (size_t)i + a] = o.hit[a];
+            }
+            if (t) t[i] = o.ray.t;
+            if (n_steps) n_steps[i] = o.ray.n_steps;
+            if (n_unknown) n_unknown[i] = o.ray.n_unknown;
+            if (hit_sq) hit_sq[i] = o.hit_sq;
         }
     }
 };

@@ -293,6 +293,20 @@ bool mirror_nearest_wanted(const mlm_handle *h, int n, int max_dist) {
     const long long side = 2 * (long long)max_dist + 1;
     return n * side * side * side <= kNearMirrorVoxels;
 }
+// ... and a batch of rays of mlm_query_sweeps: few rays whose start balls and caps are small enough together (kSweepMirrorVoxels, mlm_handle.h)
+bool mirror_sweeps_wanted(const mlm_handle *h, const double *p0, const double *p1, int n, int radius) {
+    const MlmMirror &M = h->mir;
+    if (!M.enabled || (long long)n * 4 > (M.dirty ? M.max_dirty : M.max_clean)) return false;
+    const long long side = 2 * (long long)radius + 1, L = mlm_sweep_columns(radius);
+    long long vox = 0;
+    for (int i = 0; i < n; ++i) {
+        MlmRayState S;
+        if (!mlm_ray_setup(p0 + 3 * (size_t)i, p1 + 3 * (size_t)i, h->P.d_sub, h->P.n, S)) continue;
+        vox += side * side * side + ((long long)S.r[0] + S.r[1] + S.r[2]) * L;
+        if (vox > kSweepMirrorVoxels) return false;
+    }
+    return true;
+}
 // drain + refresh if the map changed since the mirror was filled; the caller holds the lock
 int mirror_sync(mlm_handle *h) {
     if (h->mir.eager_pending) {

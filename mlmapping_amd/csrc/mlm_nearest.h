@@ -115,13 +115,10 @@ MLM_RW_HD void mlm_near_none(const MlmNearPoint &p, bool valid, MlmNearResult &o
     o.dist = -1.0;
 }
 
-// The whole contract for one point.  n = subbox_n, d = subbox_d_xyz.
-template <class Vox> MLM_RW_HD void mlm_near_search(const double pos[3], double d, int n, int C, int flags, Vox &vox, MlmNearResult &o) {
-    MlmNearPoint p;
-    if (!mlm_near_point(pos, d, C, p)) {
-        mlm_near_none(p, false, o);
-        return;
-    }
+// The ring search for a point already on the lattice: the smallest key, or MLM_NEAR_NOKEY.  n = subbox_n.  (Also the full ball at the
+// start voxel of mlm_query_sweeps: mlm_sweep.h.)
+template <class Vox> MLM_RW_HD unsigned long long mlm_near_best(const MlmNearPoint &p, int n, int flags, Vox &vox) {
+    const int C = p.C;
     int gv[3], g0[3], g1[3], K = 0;
     MLM_RW_UNROLL
     for (int a = 0; a < 3; ++a) {
@@ -174,6 +171,17 @@ template <class Vox> MLM_RW_HD void mlm_near_search(const double pos[3], double 
                 }
             }
     }
+    return best;
+}
+
+// The whole contract for one point.  n = subbox_n, d = subbox_d_xyz.
+template <class Vox> MLM_RW_HD void mlm_near_search(const double pos[3], double d, int n, int C, int flags, Vox &vox, MlmNearResult &o) {
+    MlmNearPoint p;
+    if (!mlm_near_point(pos, d, C, p)) {
+        mlm_near_none(p, false, o);
+        return;
+    }
+    const unsigned long long best = mlm_near_best(p, n, flags, vox);
     if (best == MLM_NEAR_NOKEY) {
         mlm_near_none(p, true, o);
         return;

@@ -38,6 +38,7 @@
 #include "mlm_kernels_render.h"
 #include "mlm_kernels_boxes.h"
 #include "mlm_kernels_nearest.h"
+#include "mlm_kernels_sweeps.h"
 #include "mlm_kernels_views.h"
 #include "mlm_kernels_reach.h"
 #include "mlm_kernels_route.h"
@@ -2269,6 +2270,74 @@ int mlm_query_nearest(mlm_handle *h, const double *pos, int n, int max_dist, int
         hipLaunchKernelGGL(k_nearest, grid, dim3(MLM_BLOCK), 0, h->stream, h->P, Q);
         HIPCHK(h, hipGetLastError());
         for (int c = 1; c < 6; ++c)
+            if (staged[c])
+                HIPCHK(h, hipMemcpyAsync((char *)ch[c] + (size_t)i0 * elem[c], at[c], (size_t)m * elem[c], hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MLM_OK;
+}
+
+int mlm_query_sweeps(mlm_handle *h, const double *p0, const double *p1, int n, int radius, int flags, int8_t *status, int32_t *voxel3, double *t,
+                     int32_t *n_steps, int32_t *n_unknown, int32_t *hit3, int32_t *hit_sq) {
+    if (!h) return MLM_ERR_INVALID;
+    MLM_LOCK(h);
+    if (n < 0 || (n > 0 && (!p0 || !p1)) || (flags & ~7) || radius < 0 || radius > MLM_SWEEP_MAX_RADIUS ||
+        (!status && !voxel3 && !t && !n_steps && !n_unknown && !hit3 && !hit_sq)) {
+        h->err = "mlm_query_sweeps: negative n, a null input, an unknown flag bit, radius outside [0, 16] or no output";
+        return MLM_ERR_INVALID;
+    }
+    if (n == 0) return MLM_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    // channels: the two inputs, then the seven outputs; bytes per ray; in device memory (used in place) or staged
+    void *ch[9] = {(void *)p0, (void *)p1, status, voxel3, t, n_steps, n_unknown, hit3, hit_sq};
+    const size_t elem[9] = {3 * sizeof(double), 3 * sizeof(double), 1, 3 * sizeof(int32_t), sizeof(double), sizeof(int32_t), sizeof(int32_t),
+                            3 * sizeof(int32_t), sizeof(int32_t)};
+    bool staged[9];
+    bool all_host = true;
+    for (int c = 0; c < 9; ++c) {
+        staged[c] = ch[c] && !win_in_place(ch[c]);
+        all_host = all_host && (staged[c] || !ch[c]);
+    }
+    // a planner's edge-by-edge calls: answered on the host (mlm_mirror.h), like mlm_query_rays' small batches
+    if (all_host && mirror_sweeps_wanted(h, p0, p1, n, radius)) {
+        const int rc = mirror_sync(h);
+        if (rc == MLM_OK) {
+            h->mir.view.sweep(p0, p1, n, radius, flags, status, voxel3, t, n_steps, n_unknown, hit3, hit_sq);
+            h->mir.n_host_queries += n;
+            return MLM_OK;
+        }
+        if (!h->mir.alloc_failed && rc != kMirrorUnavailable) return rc; // (an error of the frames in flight, reported by the drain)
+    }
+    int rc = drain(h);
+    if (rc) return rc;
+    // chunks: staged channels of a chunk share one kept buffer (at most 93 bytes per ray)
+    const int chunk = std::min(n, kSweepChunk);
+    size_t off[9], stage_bytes = 0;
+    for (int c = 0; c < 9; ++c) {
+        off[c] = stage_bytes;
+        if (staged[c]) stage_bytes += ((size_t)chunk * elem[c] + 255) & ~(size_t)255;
+    }
+    if (stage_bytes && (rc = win_reserve(h, h->d_ray_stage, h->ray_stage_bytes, stage_bytes, "mlm_query_sweeps"))) return rc;
+    // the slots of the block box around the ball stay in LDS while the box has at most kSweepNB blocks per axis (mlm_kernels_sweeps.h)
+    const bool cached = radius > 0 && (2 * radius - 1) / h->P.n + 2 <= kSweepNB;
+    for (int i0 = 0; i0 < n; i0 += chunk) {
+        const int m = std::min(chunk, n - i0);
+        void *at[9];
+        for (int c = 0; c < 9; ++c)
+            at[c] = !ch[c] ? nullptr : staged[c] ? (void *)((char *)h->d_ray_stage + off[c]) : (void *)((char *)ch[c] + (size_t)i0 * elem[c]);
+        for (int c = 0; c < 2; ++c)
+            if (staged[c])
+                HIPCHK(h, hipMemcpyAsync(at[c], (const char *)ch[c] + (size_t)i0 * elem[c], (size_t)m * elem[c], hipMemcpyHostToDevice, h->stream));
+        MlmSweeps R{(const double *)at[0], (const double *)at[1], m, radius, flags, mlm_sweep_columns(radius), (int8_t *)at[2], (int32_t *)at[3],
+                    (double *)at[4], (int32_t *)at[5], (int32_t *)at[6], (int32_t *)at[7], (int32_t *)at[8]};
+        if (radius == 0) { // one lane per ray, as k_rays
+            hipLaunchKernelGGL(k_sweeps0, dim3(std::min<unsigned int>(grid_for((size_t)m), h->rays_grid)), dim3(MLM_BLOCK), 0, h->stream, h->P, R);
+        } else { // one wave per ray, four to a workgroup; at most kSweepGrid workgroups (grid-stride)
+            const dim3 grid(std::min<unsigned int>(((unsigned int)m + MLM_BLOCK / 64 - 1) / (MLM_BLOCK / 64), kSweepGrid));
+            hipLaunchKernelGGL(cached ? k_sweeps<true> : k_sweeps<false>, grid, dim3(MLM_BLOCK), 0, h->stream, h->P, R);
+        }
+        HIPCHK(h, hipGetLastError());
+        for (int c = 2; c < 9; ++c)
             if (staged[c])
                 HIPCHK(h, hipMemcpyAsync((char *)ch[c] + (size_t)i0 * elem[c], at[c], (size_t)m * elem[c], hipMemcpyDeviceToHost, h->stream));
     }

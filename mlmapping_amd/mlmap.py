@@ -55,7 +55,7 @@ ABI_SYMBOLS = [
     "mlm_query_odds", "mlm_query_odd_grad", "mlm_query_odds_at", "mlm_export_frontier_points", "mlm_import_blocks",
     "mlm_merge_pack", "mlm_merge_finish",
     "mlm_set_free_in_bound", "mlm_inflate_map", "mlm_block_count",
-    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_grid2d", "mlm_export_reach", "mlm_export_route", "mlm_export_clusters", "mlm_query_rays", "mlm_render_depth", "mlm_query_views", "mlm_query_boxes", "mlm_query_nearest", "mlm_query_paths", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
+    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_grid2d", "mlm_export_reach", "mlm_export_route", "mlm_export_clusters", "mlm_query_rays", "mlm_render_depth", "mlm_query_views", "mlm_query_boxes", "mlm_query_nearest", "mlm_query_sweeps", "mlm_query_paths", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
     "mlm_get_awareness_hits",
     "mlm_get_awareness_misses", "mlm_get_T_ls", "mlm_get_odds_table", "mlm_get_kernel_times",
     "mlm_enable_kernel_timing", "mlm_set_timed_kernel", "mlm_host_register", "mlm_host_unregister", "mlm_debug_set", "mlm_debug_reset",
@@ -159,6 +159,7 @@ def load_library(path: Optional[str] = None):
     L.mlm_query_views.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.mlm_query_boxes.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.mlm_query_nearest.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
+    L.mlm_query_sweeps.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.mlm_query_paths.argtypes = [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp]
     L.mlm_export_global_map.argtypes = [vp, i32, vp, vp]
     L.mlm_export_block_flags.argtypes = [vp, i32, vp, vp]
@@ -897,6 +898,47 @@ class MLMap:
         ptr = [None if v is None else ctypes.c_void_p(v) for v in (status, voxel, delta, sq, dist)]
         self._chk(self._L.mlm_query_nearest(self._h, ctypes.c_void_p(pos), int(n), int(max_dist), self._ray_flags(occ, infl, unknown), *ptr),
                   "mlm_query_nearest")
+
+    SWEEP_OUTPUTS = ("status", "voxel", "t", "n_steps", "n_unknown", "hit", "hit_sq")
+
+    def query_sweeps(self, p0, p1, radius, occ=True, infl=False, unknown=False, outputs=None):
+        """Segment casts for a ball of `radius` voxels (mlm_query_sweeps): segment i runs from p0[i] to p1[i] (n x 3 float64 world
+        positions — numpy arrays give numpy results, torch device tensors torch device results) and stops at the first path voxel
+        within `radius` (0 .. 16, integer squared index distance) of a voxel that is occ (getOccupancy == OCCUPIED), infl
+        (getInflateOccupancy == OCCUPIED) or unknown (getOccupancy == UNKNOWN), whichever are selected — export_reach's BLOCKED at
+        that clearance.  outputs: the names wanted (None: all seven).  {"status", "voxel", "t", "n_steps", "n_unknown": as
+        cast_rays', the voxel being the ball's centre; "hit": int32 (n, 3) the obstacle voxel responsible (smallest distance, then z,
+        y, x; the end voxel without a stop), "hit_sq": int32 its squared distance from "voxel" (-1 without a stop)}."""
+        names = self.SWEEP_OUTPUTS if outputs is None else tuple(outputs)
+        if not names or any(k not in self.SWEEP_OUTPUTS for k in names):
+            raise MlmError("query_sweeps: outputs must name at least one of " + ", ".join(self.SWEEP_OUTPUTS))
+        flags = self._ray_flags(occ, infl, unknown)
+        if isinstance(p0, np.ndarray) or not hasattr(p0, "data_ptr"):
+            a, b = _f64(p0).reshape(-1, 3), _f64(p1).reshape(-1, 3)
+            if a.shape != b.shape:
+                raise MlmError("query_sweeps: p0 and p1 differ in shape")
+            n = a.shape[0]
+            shapes = {"status": ((n,), np.int8), "voxel": ((n, 3), np.int32), "t": ((n,), np.float64), "n_steps": ((n,), np.int32),
+                      "n_unknown": ((n,), np.int32), "hit": ((n, 3), np.int32), "hit_sq": ((n,), np.int32)}
+            out = {k: np.empty(*shapes[k]) for k in names}
+            ptr = [_p(a), _p(b)] + [_p(out[k]) if k in out else None for k in self.SWEEP_OUTPUTS]
+        else:
+            import torch
+
+            for x in (p0, p1):
+                if not hasattr(x, "data_ptr") or x.dtype != torch.float64 or x.numel() % 3 or not x.is_contiguous():
+                    raise MlmError("query_sweeps: tensors of end points must be contiguous float64 with 3 values per point")
+            if p0.numel() != p1.numel() or p0.device != p1.device:
+                raise MlmError("query_sweeps: p0 and p1 differ in size or device")
+            n = p0.numel() // 3
+            dev = p0.device
+            shapes = {"status": ((n,), torch.int8), "voxel": ((n, 3), torch.int32), "t": ((n,), torch.float64), "n_steps": ((n,), torch.int32),
+                      "n_unknown": ((n,), torch.int32), "hit": ((n, 3), torch.int32), "hit_sq": ((n,), torch.int32)}
+            out = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev) for k in names}
+            ptr = [ctypes.c_void_p(p0.data_ptr()), ctypes.c_void_p(p1.data_ptr())] + \
+                  [ctypes.c_void_p(out[k].data_ptr()) if k in out else None for k in self.SWEEP_OUTPUTS]
+        self._chk(self._L.mlm_query_sweeps(self._h, ptr[0], ptr[1], n, int(radius), flags, *ptr[2:]), "mlm_query_sweeps")
+        return out
 
     PATH_OUTPUTS = ("status", "way", "length", "table")
     PATH_KINDS = {"reach": MLM_PATH_REACH, "route": MLM_PATH_ROUTE, MLM_PATH_REACH: MLM_PATH_REACH, MLM_PATH_ROUTE: MLM_PATH_ROUTE}
