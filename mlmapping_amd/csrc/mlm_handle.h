@@ -180,35 +180,34 @@ struct mlm_handle {
     double *d_qpos = nullptr; // query positions
     void *d_qout = nullptr;
     size_t q_cap = 0;
-    // mlm_export_window: odds of the haloed tile (gradients) and the staging of host destinations, kept and enlarged by need
+    // The read-outs' kept buffers (enlarged by need, never shrunk; mlm_readout.h).  Host arrays are staged by one rule, ReadoutChannels:
+    // the exports (window .. clusters, and a host exclude / mark of mlm_query_views) in d_win_stage, the batched queries (rays, render,
+    // boxes, nearest, sweeps, paths, and the rays of views) in d_ray_stage.  The comments below name what else each read-out keeps.
+    // mlm_export_window: odds of the haloed tile (gradients)
     void *d_win_scratch = nullptr, *d_win_stage = nullptr;
     size_t win_scratch_bytes = 0, win_stage_bytes = 0;
-    // mlm_export_esdf: obstacle mask and the two fields of the grown tile (staging shares d_win_stage), kept and enlarged by need
+    // mlm_export_esdf: obstacle mask and the two fields of the grown tile
     void *d_esdf_scratch = nullptr;
     size_t esdf_scratch_bytes = 0;
-    // mlm_export_reach: field, mask, dirty arrays, control block and seeds of the whole box (mlm_reach_plan), kept and enlarged by
-    // need (the ESDF passes of clearance > 0 use d_esdf_scratch, staged outputs d_win_stage); pinned copy of the control block
+    // mlm_export_reach: field, mask, dirty arrays, control block and seeds of the whole box (mlm_reach_plan; the ESDF passes of
+    // clearance > 0 use d_esdf_scratch); pinned copy of the control block
     void *d_reach = nullptr;
     size_t reach_bytes = 0;
     unsigned int *h_reach_ctrl = nullptr;
     // mlm_export_clusters: field, size / number words, mask, grown occ classes, chunk counts, staged rows and counters of the whole
-    // box (mlm_cluster_plan), kept and enlarged by need (staged labels use d_win_stage, the counters' pinned copy h_reach_ctrl)
+    // box (mlm_cluster_plan; the counters' pinned copy is h_reach_ctrl)
     void *d_cluster = nullptr;
     size_t cluster_bytes = 0;
-    // mlm_query_rays: staging of the host inputs / outputs of one chunk of rays, kept and enlarged by need
+    // the batched queries' staging: the host inputs / outputs of one chunk
     void *d_ray_stage = nullptr;
     size_t ray_stage_bytes = 0;
-    // mlm_query_views: per-view boxes, job lists, staged rows and the global path's bitsets of one chunk of views, kept and enlarged by
-    // need (staged rays use d_ray_stage, a staged exclude / mark d_win_stage)
+    // mlm_query_views: per-view boxes, job lists, staged rows and the global path's bitsets of one chunk of views
     void *d_views = nullptr;
     size_t views_bytes = 0;
-    // mlm_query_boxes stages the host inputs / outputs of one chunk of boxes in d_ray_stage too, mlm_query_nearest those of one chunk of
-    // points, mlm_query_paths those of one chunk of goals, mlm_query_sweeps those of one chunk of rays
-    // mlm_query_paths: the traced paths of one chunk of goals (three int32 arrays of max_moves + 1 entries per goal), kept and enlarged by need
+    // mlm_query_paths: the traced paths of one chunk of goals (three int32 arrays of max_moves + 1 entries per goal)
     void *d_path = nullptr;
     size_t path_bytes = 0;
     unsigned int rays_grid = 1024; // most workgroups of k_rays (knob "rays_grid"): 2^20 rays are four per lane
-    // mlm_render_depth stages host poses, one chunk of host per-pixel outputs and a host table in d_ray_stage too
     int render_tile = kRenderTileDefault; // (knob "render_tile")
     // sort buffers (rehash frames only)
     unsigned long long *sk_in = nullptr, *sk_out = nullptr;

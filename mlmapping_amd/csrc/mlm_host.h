@@ -159,6 +159,43 @@ inline MlmEsdfPlan mlm_esdf_plan(const long long D[3], int C, bool grad, long lo
     return p;
 }
 
+// The voxel box [lo, lo + dims) of a read-out: D and nvox are its dims and voxel count in 64 bits.  0: ok; 1: a dim < 1 or lo + dims
+// beyond an int32; 2: more than 2^31 - 1 voxels.  Axis by axis, so a box that is wrong in both ways reports the earlier axis' fault.
+inline int mlm_box_check(const int32_t lo[3], const int32_t dims[3], long long D[3], long long &nvox) {
+    nvox = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (dims[a] < 1 || (long long)lo[a] + dims[a] > 0x7FFFFFFFll) return 1;
+        D[a] = dims[a];
+        nvox *= D[a];
+        if (nvox > 0x7FFFFFFFll) return 2;
+    }
+    return 0;
+}
+
+// The bricks (blocks of n voxels per axis) that cover [lo, lo + d) on one axis, d >= 1: the first brick's index (the floor of
+// lo / n) and their count.  64-bit: the box a read-out grows around a window at the int32 edge (a halo, a truncation distance, a
+// one-voxel rim) reaches past that edge.
+inline void mlm_brick_cover(int n, long long lo, long long d, long long &b0, int &nb) {
+    auto floor_div = [n](long long v) { return v >= 0 ? v / n : -((-v + n - 1) / n); };
+    b0 = floor_div(lo);
+    nb = (int)(floor_div(lo + d - 1) - b0 + 1);
+}
+
+// the parts of a kept device buffer start on multiples of 256 bytes
+inline size_t mlm_align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+// Where the channels of a read-out (inputs and outputs, `count[c]` elements of `elem[c]` bytes each) lie in one staging buffer: a
+// channel that is present and staged (its memory is not the device's) takes its bytes rounded up to a multiple of 256 at off[c],
+// in channel order; the others take nothing.  Returns the buffer's bytes.
+inline size_t mlm_stage_layout(int n, const bool *present, const bool *staged, const size_t *elem, const size_t *count, size_t *off) {
+    size_t total = 0;
+    for (int c = 0; c < n; ++c) {
+        off[c] = total;
+        if (present[c] && staged[c]) total += mlm_align256(count[c] * elem[c]);
+    }
+    return total;
+}
+
 // Tiles of mlm_export_grid2d (mlm_kernels_grid.h) for a plane of D[0] x D[1] cells, truncation C (cells), distances asked for or
 // not: mlm_esdf_plan's rule in two dimensions.  A tile is whole rows of the plane, else a piece of one row, so that its outputs
 // are one contiguous range of the plane's [D1][D0] layout.  The grown tile (the tile plus H = C - 1 cells per side with distances,

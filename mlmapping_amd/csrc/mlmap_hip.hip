@@ -9,7 +9,8 @@
 // are included in this order: mlm_handle.h (the handle, knobs, launch helpers) -> mlm_stage_a.h (Stage A launches, exact
 // ordering, statistics) -> mlm_explore_host.h (frontier mode) -> mlm_submit.h (submission, drain / replay, single-frame graph)
 // -> mlm_resources.h (device memory: pool growth, frame slots, queries' launcher) -> mlm_mirror.h (host mirror of the map for small
-// query batches); this file holds the extern "C" entry points.
+// query batches) -> mlm_readout.h (what the read-outs share: box check, staging of host arrays, ESDF tiles, settle loop); this file
+// holds the extern "C" entry points.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -53,6 +54,7 @@
 #include "mlm_submit.h"
 #include "mlm_resources.h"
 #include "mlm_mirror.h"
+#include "mlm_readout.h"
 
 extern "C" {
 
@@ -1095,40 +1097,7 @@ int mlm_export_blocks(mlm_handle *h, int cap, int32_t *keys, float *log_odds, ui
 }
 
 namespace {
-// mlm_export_window's tiles (mlm_kernels_window.h): the haloed tile's odds take at most kWinBoxVoxels floats (128 MB), a tile staged
-// for host destinations at most kWinStageVoxels voxels (<= 30 bytes each)
-constexpr long long kWinBoxVoxels = 1ll << 25;
-constexpr long long kWinStageVoxels = 1ll << 22;
-constexpr unsigned int kWinFillGrid = 2048, kWinGradGrid = 8192;
-
-// device memory this device's kernels write in place; anything else (pageable, pinned or managed host memory) is staged
-bool win_in_place(const void *p) {
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError(); // (pageable host memory is unknown to the runtime)
-        return false;
-    }
-    return a.type == hipMemoryTypeDevice;
-}
-
-// a kept buffer of at least `bytes`; a failed allocation leaves the handle as it was, minus the old buffer
-int win_reserve(mlm_handle *h, void *&p, size_t &cap, size_t bytes, const char *what = "mlm_export_window") {
-    if (bytes <= cap) return MLM_OK;
-    dev_free(h, p, cap);
-    p = nullptr;
-    cap = 0;
-    void *v = nullptr;
-    if (hipMalloc(&v, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        h->err = std::string(what) + ": no device memory for " + std::to_string(bytes >> 20) + " MB of scratch";
-        return MLM_ERR_CAPACITY;
-    }
-    h->alloc_bytes += bytes;
-    h->allocs.push_back(v);
-    p = v;
-    cap = bytes;
-    return MLM_OK;
-}
+constexpr unsigned int kWinFillGrid = 2048, kWinGradGrid = 8192; // most workgroups of mlm_export_window's kernels
 } // namespace
 
 int mlm_export_window(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], int max_iter, float *odds, int8_t *occ, int8_t *infl,
@@ -1139,64 +1108,22 @@ int mlm_export_window(mlm_handle *h, const int32_t lo[3], const int32_t dims[3],
         h->err = "mlm_export_window: null window, negative max_iter or no output";
         return MLM_ERR_INVALID;
     }
-    long long D[3], nvox = 1;
-    for (int a = 0; a < 3; ++a) {
-        if (dims[a] < 1 || (long long)lo[a] + dims[a] > 0x7FFFFFFFll) {
-            h->err = "mlm_export_window: dims must be >= 1 and lo + dims must fit an int32";
-            return MLM_ERR_INVALID;
-        }
-        D[a] = dims[a];
-        nvox *= D[a];
-        if (nvox > 0x7FFFFFFFll) {
-            h->err = "mlm_export_window: more than 2^31 - 1 voxels";
-            return MLM_ERR_INVALID;
-        }
-    }
-    HIPCHK(h, hipSetDevice(h->device));
-    int rc = drain(h);
+    long long D[3], nvox;
+    int rc = box_check(h, "mlm_export_window", lo, dims, D, nvox);
     if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    if ((rc = drain(h))) return rc;
 
-    // channels: destination, element size, written in place or staged
-    void *dst[4] = {odds, occ, infl, grad3};
-    const size_t elem[4] = {sizeof(float), 1, 1, 3 * sizeof(double)};
-    bool staged[4];
-    bool any_staged = false;
-    for (int c = 0; c < 4; ++c) {
-        staged[c] = dst[c] && !win_in_place(dst[c]);
-        any_staged |= staged[c];
-    }
-    // tile dims: whole planes if one fits, else rows of one plane, else pieces of one row — every tile's output is a contiguous range
-    // of the window's layout
+    ReadoutChannels<4> ch(h->d_win_stage, h->win_stage_bytes, {{odds, sizeof(float)}, {occ, 1}, {infl, 1}, {grad3, 3 * sizeof(double)}});
+    // tiles as mlm_export_esdf's (C - 1 = H, the halo of the gradients): the haloed tile's odds take at most kEsdfBoxVoxels floats
+    // (128 MB), a tile staged for host destinations at most kEsdfStageVoxels voxels (<= 30 bytes each); H <= MLM_WIN_HALO: a tile fits
     const long long H = grad3 ? std::min(max_iter, MLM_WIN_HALO) : 0;
-    const long long box_cap = grad3 ? kWinBoxVoxels : (1ll << 62), out_cap = any_staged ? kWinStageVoxels : (1ll << 62);
-    auto fits = [&](long long tx, long long ty, long long tz) { return (tx + 2 * H) * (ty + 2 * H) * (tz + 2 * H) <= box_cap && tx * ty * tz <= out_cap; };
-    long long T[3];
-    if (fits(D[0], D[1], 1)) {
-        T[0] = D[0];
-        T[1] = D[1];
-        T[2] = std::min({D[2], box_cap / ((D[0] + 2 * H) * (D[1] + 2 * H)) - 2 * H, out_cap / (D[0] * D[1])});
-    } else if (fits(D[0], 1, 1)) {
-        T[0] = D[0];
-        T[1] = std::min({D[1], box_cap / ((D[0] + 2 * H) * (1 + 2 * H)) - 2 * H, out_cap / D[0]});
-        T[2] = 1;
-    } else {
-        T[0] = std::min({D[0], box_cap / ((1 + 2 * H) * (1 + 2 * H)) - 2 * H, out_cap});
-        T[1] = T[2] = 1;
-    }
-    const long long tile_vox = T[0] * T[1] * T[2];
-    size_t stage_off[4] = {0, 0, 0, 0}, stage_bytes = 0;
-    for (int c = 0; c < 4; ++c)
-        if (staged[c]) {
-            stage_off[c] = stage_bytes;
-            stage_bytes += ((size_t)tile_vox * elem[c] + 255) & ~(size_t)255;
-        }
-    if (grad3 && (rc = win_reserve(h, h->d_win_scratch, h->win_scratch_bytes,
-                                   (size_t)((T[0] + 2 * H) * (T[1] + 2 * H) * (T[2] + 2 * H)) * sizeof(float))))
+    const MlmEsdfPlan plan = mlm_esdf_plan(D, (int)H + 1, false, grad3 ? kEsdfBoxVoxels : 1ll << 62, ch.any_staged ? kEsdfStageVoxels : 1ll << 62);
+    const long long *T = plan.T;
+    if (grad3 && (rc = readout_reserve(h, h->d_win_scratch, h->win_scratch_bytes, (size_t)plan.grown * sizeof(float), "mlm_export_window")))
         return rc;
-    if (stage_bytes && (rc = win_reserve(h, h->d_win_stage, h->win_stage_bytes, stage_bytes))) return rc;
+    if ((rc = ch.reserve(h, "mlm_export_window", (size_t)(T[0] * T[1] * T[2])))) return rc;
 
-    const int n = h->P.n;
-    auto floor_div = [n](long long v) { return v >= 0 ? v / n : -((-v + n - 1) / n); };
     for (long long z0 = 0; z0 < D[2]; z0 += T[2])
         for (long long y0 = 0; y0 < D[1]; y0 += T[1])
             for (long long x0 = 0; x0 < D[0]; x0 += T[0]) {
@@ -1209,20 +1136,14 @@ int mlm_export_window(mlm_handle *h, const int32_t lo[3], const int32_t dims[3],
                     W.td[a] = (int)std::min(T[a], D[a] - org[a]);
                     W.hlo[a] = W.tlo[a] - H;
                     W.hd[a] = W.td[a] + (int)(2 * H);
-                    W.b0[a] = floor_div(W.hlo[a]);
-                    W.nb[a] = (int)(floor_div(W.hlo[a] + W.hd[a] - 1) - W.b0[a] + 1);
                 }
+                brick_cover(h, 3, W.hlo, W.hd, W.b0, W.nb);
                 // (every channel pointer is where the tile's first voxel goes: out_base is the tile's index in the window)
                 W.out_base = (z0 * D[1] + y0) * D[0] + x0;
-                void *ch[4];
-                for (int c = 0; c < 4; ++c)
-                    ch[c] = !dst[c] ? nullptr
-                                    : staged[c] ? (void *)((char *)h->d_win_stage + stage_off[c])
-                                                : (void *)((char *)dst[c] + (size_t)W.out_base * elem[c]);
-                W.odds = (float *)ch[0];
-                W.occ = (int8_t *)ch[1];
-                W.infl = (int8_t *)ch[2];
-                W.grad = (double *)ch[3];
+                W.odds = (float *)ch.at(0, (size_t)W.out_base);
+                W.occ = (int8_t *)ch.at(1, (size_t)W.out_base);
+                W.infl = (int8_t *)ch.at(2, (size_t)W.out_base);
+                W.grad = (double *)ch.at(3, (size_t)W.out_base);
                 W.scratch = grad3 ? (float *)h->d_win_scratch : nullptr;
                 W.halo = (int)H;
                 W.max_iter = max_iter;
@@ -1234,55 +1155,11 @@ int mlm_export_window(mlm_handle *h, const int32_t lo[3], const int32_t dims[3],
                     hipLaunchKernelGGL(k_window_grad, dim3(std::min<unsigned int>(grid_for((size_t)nt), kWinGradGrid)), dim3(MLM_BLOCK), 0,
                                        h->stream, h->P, W);
                 HIPCHK(h, hipGetLastError());
-                for (int c = 0; c < 4; ++c)
-                    if (staged[c])
-                        HIPCHK(h, hipMemcpyAsync((char *)dst[c] + (size_t)W.out_base * elem[c], ch[c], (size_t)nt * elem[c], hipMemcpyDefault,
-                                                 h->stream));
+                if ((rc = ch.copy_out(h, 0, 4, (size_t)W.out_base, (size_t)nt))) return rc;
             }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MLM_OK;
 }
-
-extern "C++" {
-namespace {
-constexpr unsigned int kEsdfMaskGrid = 2048, kEsdfPassGrid = 4096;
-constexpr unsigned int kGridColGrid = 1u << 16; // most workgroups of k_grid_columns (a brick stack each, grid-stride)
-constexpr unsigned int kReachGrid = 1u << 16; // most workgroups of the mlm_export_reach kernels (grid-stride loops over voxels / tiles)
-
-// the mask and the three passes of one tile of mlm_export_esdf (mlm_kernels_esdf.h) into fa [ez][ey][ex]; T: u16 (unsigned) or
-// u16x2 (signed)
-template <bool SIGNED>
-void esdf_passes(mlm_handle *h, const MlmEsdf &E, int C, uint8_t *mask, void *fa, void *fb, int ex, int ey, int ez) {
-    using T = typename std::conditional<SIGNED, mlm_u16x2, uint16_t>::type;
-    const long long n_bricks = (long long)E.nb[0] * E.nb[1] * E.nb[2];
-    hipLaunchKernelGGL(k_esdf_mask, dim3((unsigned int)std::min<long long>(n_bricks, kEsdfMaskGrid)), dim3(MLM_BLOCK), 0, h->stream, h->P, E);
-    // x: mask [gd2 * gd1][gd0] -> fa [gd2 * gd1][ex]
-    const long long rows = (long long)E.gd[2] * E.gd[1], xtasks = rows * ((ex + 63) / 64);
-    hipLaunchKernelGGL(k_esdf_x<SIGNED>, dim3((unsigned int)std::min<long long>((xtasks + 3) / 4, kEsdfPassGrid)), dim3(MLM_BLOCK), 0,
-                       h->stream, mask, fa, rows, E.gd[0], ex, C);
-    // y: fa [gd2][gd1][ex] -> fb [gd2][ey][ex];  z: fb [gd2][ey * ex] -> fa [ez][ey * ex]
-    const int TLmax = SIGNED ? MLM_ESDF_LINE_TL / 2 : MLM_ESDF_LINE_TL;
-    auto line = [&](const void *in, void *out, long long X, int Lout, int outer) {
-        const int lc = (Lout + TLmax - 1) / TLmax, TL = (Lout + lc - 1) / lc; // (rows spread evenly over the line chunks)
-        const long long tiles = (long long)outer * lc * ((X + 63) / 64);
-        const size_t lds = (size_t)(TL + 2 * C - 2) * 64 * sizeof(T);
-        hipLaunchKernelGGL(k_esdf_line<T>, dim3((unsigned int)std::min<long long>(tiles, kEsdfPassGrid)), dim3(MLM_BLOCK), lds, h->stream,
-                           (const T *)in, (T *)out, X, Lout, outer, C, TL);
-    };
-    line(fa, fb, ex, ey, E.gd[2]);
-    line(fb, fa, (long long)ey * ex, ez, 1);
-}
-
-// the passes and the outputs of one tile of mlm_export_esdf
-template <bool SIGNED>
-void esdf_tile(mlm_handle *h, const MlmEsdf &E, int C, uint8_t *mask, void *fa, void *fb, const MlmEsdfOut &Q) {
-    esdf_passes<SIGNED>(h, E, C, mask, fa, fb, Q.fd[0], Q.fd[1], Q.fd[2]);
-    const long long nt = (long long)Q.td[0] * Q.td[1] * Q.td[2];
-    hipLaunchKernelGGL(k_esdf_out<SIGNED>, dim3(std::min<unsigned int>(grid_for((size_t)nt), kEsdfPassGrid)), dim3(MLM_BLOCK), 0, h->stream,
-                       (const void *)fa, Q);
-}
-} // namespace
-} // extern "C++"
 
 int mlm_export_esdf(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], int max_dist, int flags, int32_t *sqdist, float *dist,
                     float *grad3) {
@@ -1292,58 +1169,30 @@ int mlm_export_esdf(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], i
         h->err = "mlm_export_esdf: null window, max_dist outside [1, 64], no obstacle bit or an unknown bit in flags, or no output";
         return MLM_ERR_INVALID;
     }
-    long long D[3], nvox = 1;
-    for (int a = 0; a < 3; ++a) {
-        if (dims[a] < 1 || (long long)lo[a] + dims[a] > 0x7FFFFFFFll) {
-            h->err = "mlm_export_esdf: dims must be >= 1 and lo + dims must fit an int32";
-            return MLM_ERR_INVALID;
-        }
-        D[a] = dims[a];
-        nvox *= D[a];
-        if (nvox > 0x7FFFFFFFll) {
-            h->err = "mlm_export_esdf: more than 2^31 - 1 voxels";
-            return MLM_ERR_INVALID;
-        }
-    }
-    HIPCHK(h, hipSetDevice(h->device));
-    int rc = drain(h);
+    long long D[3], nvox;
+    int rc = box_check(h, "mlm_export_esdf", lo, dims, D, nvox);
     if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    if ((rc = drain(h))) return rc;
 
-    void *dst[3] = {sqdist, dist, grad3};
-    const size_t elem[3] = {sizeof(int32_t), sizeof(float), 3 * sizeof(float)};
-    bool staged[3];
-    bool any_staged = false;
-    for (int c = 0; c < 3; ++c) {
-        staged[c] = dst[c] && !win_in_place(dst[c]);
-        any_staged |= staged[c];
-    }
+    ReadoutChannels<3> ch(h->d_win_stage, h->win_stage_bytes, {{sqdist, sizeof(int32_t)}, {dist, sizeof(float)}, {grad3, 3 * sizeof(float)}});
     const bool sgn = (flags & MLM_ESDF_SIGNED) != 0;
     const int C = max_dist, G = grad3 ? 1 : 0;
     long long box_cap = kEsdfBoxVoxels, kv;
     if (knob("esdf_tile_vox", kv)) box_cap = kv;
-    const MlmEsdfPlan plan = mlm_esdf_plan(D, C, G != 0, box_cap, any_staged ? kEsdfStageVoxels : (1ll << 62));
+    const MlmEsdfPlan plan = mlm_esdf_plan(D, C, G != 0, box_cap, ch.any_staged ? kEsdfStageVoxels : (1ll << 62));
     if (plan.T[0] < 1) { // (not with the caps mlm_debug_set admits)
         h->err = "mlm_export_esdf: no tile fits the voxel cap";
         return MLM_ERR_INVALID;
     }
-    const long long tile_vox = plan.T[0] * plan.T[1] * plan.T[2];
-    size_t stage_off[3] = {0, 0, 0}, stage_bytes = 0;
-    for (int c = 0; c < 3; ++c)
-        if (staged[c]) {
-            stage_off[c] = stage_bytes;
-            stage_bytes += ((size_t)tile_vox * elem[c] + 255) & ~(size_t)255;
-        }
     // scratch: the mask, then two fields of the grown tile (the x pass and the z pass write the first, the y pass the second)
-    const size_t fe = sgn ? 4 : 2, mask_bytes = ((size_t)plan.grown + 255) & ~(size_t)255,
-                 field_bytes = ((size_t)plan.grown * fe + 255) & ~(size_t)255;
-    if ((rc = win_reserve(h, h->d_esdf_scratch, h->esdf_scratch_bytes, mask_bytes + 2 * field_bytes, "mlm_export_esdf"))) return rc;
-    if (stage_bytes && (rc = win_reserve(h, h->d_win_stage, h->win_stage_bytes, stage_bytes, "mlm_export_esdf"))) return rc;
+    const size_t fe = sgn ? 4 : 2, mask_bytes = mlm_align256((size_t)plan.grown), field_bytes = mlm_align256((size_t)plan.grown * fe);
+    if ((rc = readout_reserve(h, h->d_esdf_scratch, h->esdf_scratch_bytes, mask_bytes + 2 * field_bytes, "mlm_export_esdf"))) return rc;
+    if ((rc = ch.reserve(h, "mlm_export_esdf", (size_t)(plan.T[0] * plan.T[1] * plan.T[2])))) return rc;
     uint8_t *mask = (uint8_t *)h->d_esdf_scratch;
     void *fa = (char *)h->d_esdf_scratch + mask_bytes, *fb = (char *)h->d_esdf_scratch + mask_bytes + field_bytes;
 
-    const int n = h->P.n;
     const long long H = plan.H;
-    auto floor_div = [n](long long v) { return v >= 0 ? v / n : -((-v + n - 1) / n); };
     for (long long z0 = 0; z0 < D[2]; z0 += plan.T[2])
         for (long long y0 = 0; y0 < D[1]; y0 += plan.T[1])
             for (long long x0 = 0; x0 < D[0]; x0 += plan.T[0]) {
@@ -1354,11 +1203,10 @@ int mlm_export_esdf(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], i
                     Q.t0[a] = org[a];
                     Q.td[a] = (int)std::min(plan.T[a], D[a] - org[a]);
                     Q.fd[a] = Q.td[a] + 2 * G;
-                    E.glo[a] = lo[a] + org[a] - H; // (64-bit: the grown box of a window at the int32 edge reaches past it)
+                    E.glo[a] = lo[a] + org[a] - H;
                     E.gd[a] = Q.td[a] + (int)(2 * H);
-                    E.b0[a] = floor_div(E.glo[a]);
-                    E.nb[a] = (int)(floor_div(E.glo[a] + E.gd[a] - 1) - E.b0[a] + 1);
                 }
+                brick_cover(h, 3, E.glo, E.gd, E.b0, E.nb);
                 E.flags = flags & 7;
                 E.mask = mask;
                 Q.wd0 = D[0];
@@ -1367,24 +1215,15 @@ int mlm_export_esdf(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], i
                 Q.out_base = (z0 * D[1] + y0) * D[0] + x0;
                 Q.d = (float)h->cfg.subbox_d_xyz;
                 Q.inv = (float)(0.5 / h->cfg.subbox_d_xyz);
-                void *ch[3];
-                for (int c = 0; c < 3; ++c)
-                    ch[c] = !dst[c] ? nullptr
-                                    : staged[c] ? (void *)((char *)h->d_win_stage + stage_off[c])
-                                                : (void *)((char *)dst[c] + (size_t)Q.out_base * elem[c]);
-                Q.sqdist = (int32_t *)ch[0];
-                Q.dist = (float *)ch[1];
-                Q.grad = (float *)ch[2];
+                Q.sqdist = (int32_t *)ch.at(0, (size_t)Q.out_base);
+                Q.dist = (float *)ch.at(1, (size_t)Q.out_base);
+                Q.grad = (float *)ch.at(2, (size_t)Q.out_base);
                 if (sgn)
                     esdf_tile<true>(h, E, C, mask, fa, fb, Q);
                 else
                     esdf_tile<false>(h, E, C, mask, fa, fb, Q);
                 HIPCHK(h, hipGetLastError());
-                const long long nt = (long long)Q.td[0] * Q.td[1] * Q.td[2];
-                for (int c = 0; c < 3; ++c)
-                    if (staged[c])
-                        HIPCHK(h, hipMemcpyAsync((char *)dst[c] + (size_t)Q.out_base * elem[c], ch[c], (size_t)nt * elem[c], hipMemcpyDefault,
-                                                 h->stream));
+                if ((rc = ch.copy_out(h, 0, 3, (size_t)Q.out_base, (size_t)Q.td[0] * Q.td[1] * Q.td[2]))) return rc;
             }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MLM_OK;
@@ -1399,57 +1238,32 @@ int mlm_export_grid2d(mlm_handle *h, const int32_t lo[3], const int32_t dims[3],
         h->err = "mlm_export_grid2d: null window, no class bit or an unknown bit in flags, or no output";
         return MLM_ERR_INVALID;
     }
-    long long D[3], nvox = 1;
-    for (int a = 0; a < 3; ++a) {
-        if (dims[a] < 1 || (long long)lo[a] + dims[a] > 0x7FFFFFFFll) {
-            h->err = "mlm_export_grid2d: dims must be >= 1 and lo + dims must fit an int32";
-            return MLM_ERR_INVALID;
-        }
-        D[a] = dims[a];
-        nvox *= D[a];
-        if (nvox > 0x7FFFFFFFll) {
-            h->err = "mlm_export_grid2d: more than 2^31 - 1 voxels";
-            return MLM_ERR_INVALID;
-        }
-    }
+    long long D[3], nvox;
+    int rc = box_check(h, "mlm_export_grid2d", lo, dims, D, nvox);
+    if (rc) return rc;
     if (lo[2] == INT32_MIN || min_free < 0 || min_free > dims[2] || (cols && (z_ref < lo[2] || z_ref >= lo[2] + dims[2])) ||
         (want_dist && (max_dist < 1 || max_dist > 64))) {
         h->err = "mlm_export_grid2d: lo[2] == INT32_MIN, min_free outside [0, dims[2]], z_ref outside the slab or max_dist outside [1, 64]";
         return MLM_ERR_INVALID;
     }
     HIPCHK(h, hipSetDevice(h->device));
-    int rc = drain(h);
-    if (rc) return rc;
+    if ((rc = drain(h))) return rc;
 
-    // channels: destination, bytes per cell, written in place or staged
-    void *dst[4] = {grid, cols, sqdist, dist};
-    const size_t elem[4] = {1, MLM_GRID_COL * sizeof(int32_t), sizeof(int32_t), sizeof(float)};
-    bool staged[4];
-    bool any_staged = false;
-    for (int c = 0; c < 4; ++c) {
-        staged[c] = dst[c] && !win_in_place(dst[c]);
-        any_staged |= staged[c];
-    }
+    ReadoutChannels<4> ch(h->d_win_stage, h->win_stage_bytes,
+                          {{grid, 1}, {cols, MLM_GRID_COL * sizeof(int32_t)}, {sqdist, sizeof(int32_t)}, {dist, sizeof(float)}});
     const int C = want_dist ? max_dist : 1;
-    long long out_cap = any_staged ? kGridStageCells : (1ll << 62), kv;
+    long long out_cap = ch.any_staged ? kGridStageCells : (1ll << 62), kv;
     if (knob("grid_tile", kv)) out_cap = std::min(out_cap, kv);
     const MlmGridPlan plan = mlm_grid_plan(D, C, want_dist, kGridBoxCells, out_cap);
     if (plan.T[0] < 1) { // (not with the caps mlm_debug_set admits)
         h->err = "mlm_export_grid2d: no tile fits the cell cap";
         return MLM_ERR_INVALID;
     }
-    const long long tile_cells = plan.T[0] * plan.T[1];
-    size_t stage_off[4] = {0, 0, 0, 0}, stage_bytes = 0;
-    for (int c = 0; c < 4; ++c)
-        if (staged[c]) {
-            stage_off[c] = stage_bytes;
-            stage_bytes += ((size_t)tile_cells * elem[c] + 255) & ~(size_t)255;
-        }
     // scratch: the summary counters, then (with distances) the mask and two u16 fields of the grown tile
-    const size_t ctrl_bytes = 256, mask_bytes = want_dist ? ((size_t)plan.grown + 255) & ~(size_t)255 : 0,
-                 field_bytes = want_dist ? ((size_t)plan.grown * 2 + 255) & ~(size_t)255 : 0;
-    if ((rc = win_reserve(h, h->d_esdf_scratch, h->esdf_scratch_bytes, ctrl_bytes + mask_bytes + 2 * field_bytes, "mlm_export_grid2d"))) return rc;
-    if (stage_bytes && (rc = win_reserve(h, h->d_win_stage, h->win_stage_bytes, stage_bytes, "mlm_export_grid2d"))) return rc;
+    const size_t ctrl_bytes = 256, mask_bytes = want_dist ? mlm_align256((size_t)plan.grown) : 0,
+                 field_bytes = want_dist ? mlm_align256((size_t)plan.grown * 2) : 0;
+    if ((rc = readout_reserve(h, h->d_esdf_scratch, h->esdf_scratch_bytes, ctrl_bytes + mask_bytes + 2 * field_bytes, "mlm_export_grid2d"))) return rc;
+    if ((rc = ch.reserve(h, "mlm_export_grid2d", (size_t)(plan.T[0] * plan.T[1])))) return rc;
     if (summary && !h->h_reach_ctrl) HIPCHK(h, hipHostMalloc((void **)&h->h_reach_ctrl, (size_t)kReachCtrlBytes, hipHostMallocDefault));
     unsigned long long *sums = summary ? (unsigned long long *)h->d_esdf_scratch : nullptr;
     uint8_t *mask = want_dist ? (uint8_t *)h->d_esdf_scratch + ctrl_bytes : nullptr;
@@ -1458,7 +1272,6 @@ int mlm_export_grid2d(mlm_handle *h, const int32_t lo[3], const int32_t dims[3],
 
     const int n = h->P.n;
     const long long H = plan.H;
-    auto floor_div = [n](long long v) { return v >= 0 ? v / n : -((-v + n - 1) / n); };
     // a workgroup has one lane per column of a brick stack: whole waves, as many as a full brick's n^2 columns need
     const unsigned int block = (unsigned int)std::min<long long>(MLM_BLOCK, (((long long)n * n + 63) / 64) * 64);
     for (long long y0 = 0; y0 < D[1]; y0 += plan.T[1])
@@ -1468,26 +1281,19 @@ int mlm_export_grid2d(mlm_handle *h, const int32_t lo[3], const int32_t dims[3],
             for (int a = 0; a < 2; ++a) {
                 G.tlo[a] = lo[a] + org[a];
                 G.td[a] = (int)std::min(plan.T[a], D[a] - org[a]);
-                G.glo[a] = G.tlo[a] - H; // (64-bit: the grown tile of a window at the int32 edge reaches past it)
+                G.glo[a] = G.tlo[a] - H;
                 G.gd[a] = G.td[a] + (int)(2 * H);
-                G.b0[a] = floor_div(G.glo[a]);
-                G.nb[a] = (int)(floor_div(G.glo[a] + G.gd[a] - 1) - G.b0[a] + 1);
             }
+            brick_cover(h, 2, G.glo, G.gd, G.b0, G.nb);
             G.zlo = lo[2];
             G.zhi = lo[2] + dims[2];
-            G.b0[2] = floor_div(G.zlo);
-            G.nb[2] = (int)(floor_div((long long)G.zhi - 1) - G.b0[2] + 1);
+            mlm_brick_cover(n, G.zlo, dims[2], G.b0[2], G.nb[2]);
             G.flags = flags;
             G.min_free = min_free;
             G.z_ref = z_ref;
             const long long out_base = y0 * D[0] + x0; // (every channel pointer is where the tile's first cell goes)
-            void *ch[4];
-            for (int c = 0; c < 4; ++c)
-                ch[c] = !dst[c] ? nullptr
-                                : staged[c] ? (void *)((char *)h->d_win_stage + stage_off[c])
-                                            : (void *)((char *)dst[c] + (size_t)out_base * elem[c]);
-            G.grid = (int8_t *)ch[0];
-            G.cols = (int32_t *)ch[1];
+            G.grid = (int8_t *)ch.at(0, (size_t)out_base);
+            G.cols = (int32_t *)ch.at(1, (size_t)out_base);
             G.mask = mask;
             G.sums = sums;
             const long long stacks = (long long)G.nb[0] * G.nb[1];
@@ -1508,12 +1314,11 @@ int mlm_export_grid2d(mlm_handle *h, const int32_t lo[3], const int32_t dims[3],
                                    (size_t)(TL + 2 * C - 2) * 64 * sizeof(uint16_t), h->stream, (const uint16_t *)fa, fb, (long long)G.td[0], G.td[1],
                                    1, C, TL);
                 hipLaunchKernelGGL(k_grid_dist_out, dim3(std::min<unsigned int>(grid_for((size_t)nt), kEsdfPassGrid)), dim3(MLM_BLOCK), 0, h->stream,
-                                   (const uint16_t *)fb, nt, (float)h->cfg.subbox_d_xyz, (int32_t *)ch[2], (float *)ch[3]);
+                                   (const uint16_t *)fb, nt, (float)h->cfg.subbox_d_xyz, (int32_t *)ch.at(2, (size_t)out_base),
+                                   (float *)ch.at(3, (size_t)out_base));
             }
             HIPCHK(h, hipGetLastError());
-            for (int c = 0; c < 4; ++c)
-                if (staged[c])
-                    HIPCHK(h, hipMemcpyAsync((char *)dst[c] + (size_t)out_base * elem[c], ch[c], (size_t)nt * elem[c], hipMemcpyDefault, h->stream));
+            if ((rc = ch.copy_out(h, 0, 4, (size_t)out_base, (size_t)nt))) return rc;
         }
     unsigned long long *h_cnt = (unsigned long long *)h->h_reach_ctrl;
     if (summary) HIPCHK(h, hipMemcpyAsync(h_cnt, sums, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
@@ -1532,22 +1337,11 @@ int mlm_export_reach(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], 
         h->err = "mlm_export_reach: null window or seeds, n_seeds < 1, an unknown flag bit, clearance outside [0, 63], max_steps < 1 or no output";
         return MLM_ERR_INVALID;
     }
-    long long D[3], nvox = 1;
-    for (int a = 0; a < 3; ++a) {
-        if (dims[a] < 1 || (long long)lo[a] + dims[a] > 0x7FFFFFFFll) {
-            h->err = "mlm_export_reach: dims must be >= 1 and lo + dims must fit an int32";
-            return MLM_ERR_INVALID;
-        }
-        D[a] = dims[a];
-        nvox *= D[a];
-        if (nvox > 0x7FFFFFFFll) {
-            h->err = "mlm_export_reach: more than 2^31 - 1 voxels";
-            return MLM_ERR_INVALID;
-        }
-    }
-    HIPCHK(h, hipSetDevice(h->device));
-    int rc = drain(h);
+    long long D[3], nvox;
+    int rc = box_check(h, "mlm_export_reach", lo, dims, D, nvox);
     if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    if ((rc = drain(h))) return rc;
 
     long long tile = kReachTileDefault, group = kReachGroupDefault, kv;
     if (knob("reach_tile", kv)) tile = kv;
@@ -1557,24 +1351,11 @@ int mlm_export_reach(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], 
         h->err = "mlm_export_reach: no such tile";
         return MLM_ERR_INVALID;
     }
-    // outputs: written in place, or staged through d_win_stage in ranges of the box
-    void *dst[2] = {steps, parent};
-    const size_t elem[2] = {sizeof(int32_t), 1};
-    bool staged[2];
-    bool any_staged = false;
-    for (int c = 0; c < 2; ++c) {
-        staged[c] = dst[c] && !win_in_place(dst[c]);
-        any_staged |= staged[c];
-    }
-    const long long chunk = any_staged ? std::min(nvox, kEsdfStageVoxels) : nvox;
-    size_t stage_off[2] = {0, 0}, stage_bytes = 0;
-    for (int c = 0; c < 2; ++c)
-        if (staged[c]) {
-            stage_off[c] = stage_bytes;
-            stage_bytes += ((size_t)chunk * elem[c] + 255) & ~(size_t)255;
-        }
-    if ((rc = win_reserve(h, h->d_reach, h->reach_bytes, (size_t)plan.scratch_bytes, "mlm_export_reach"))) return rc;
-    if (stage_bytes && (rc = win_reserve(h, h->d_win_stage, h->win_stage_bytes, stage_bytes, "mlm_export_reach"))) return rc;
+    // outputs: written in place, or staged in ranges of the box
+    ReadoutChannels<2> ch(h->d_win_stage, h->win_stage_bytes, {{steps, sizeof(int32_t)}, {parent, 1}});
+    const long long chunk = ch.any_staged ? std::min(nvox, kEsdfStageVoxels) : nvox;
+    if ((rc = readout_reserve(h, h->d_reach, h->reach_bytes, (size_t)plan.scratch_bytes, "mlm_export_reach"))) return rc;
+    if ((rc = ch.reserve(h, "mlm_export_reach", (size_t)chunk))) return rc;
     if (!h->h_reach_ctrl) HIPCHK(h, hipHostMalloc((void **)&h->h_reach_ctrl, (size_t)kReachCtrlBytes, hipHostMallocDefault));
     char *base = (char *)h->d_reach;
     uint8_t *mask = (uint8_t *)(base + plan.off_mask), *dirty[2] = {(uint8_t *)(base + plan.off_dirty), (uint8_t *)(base + plan.off_dirty + plan.dirty_bytes)};
@@ -1592,55 +1373,15 @@ int mlm_export_reach(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], 
     R.field = (uint32_t *)base;
 
     // the blocked mask of the box
-    const int n = h->P.n;
-    auto floor_div = [n](long long v) { return v >= 0 ? v / n : -((-v + n - 1) / n); };
     if (clearance == 0) {
-        MlmEsdf E{};
-        for (int a = 0; a < 3; ++a) {
-            E.glo[a] = lo[a];
-            E.gd[a] = dims[a];
-            E.b0[a] = floor_div(E.glo[a]);
-            E.nb[a] = (int)(floor_div(E.glo[a] + E.gd[a] - 1) - E.b0[a] + 1);
-        }
-        E.flags = flags;
-        E.mask = mask;
-        const long long n_bricks = (long long)E.nb[0] * E.nb[1] * E.nb[2];
-        hipLaunchKernelGGL(k_esdf_mask, dim3((unsigned int)std::min<long long>(n_bricks, kEsdfMaskGrid)), dim3(MLM_BLOCK), 0, h->stream, h->P, E);
+        mask_box(h, lo, dims, flags, mask);
     } else {
-        // D_out <= clearance^2 of mlm_export_esdf at max_dist = clearance + 1, tile by tile (each a contiguous range of the box)
-        const int C = clearance + 1;
-        long long box_cap = kEsdfBoxVoxels;
-        if (knob("esdf_tile_vox", kv)) box_cap = kv;
-        const MlmEsdfPlan ep = mlm_esdf_plan(D, C, false, box_cap, 1ll << 62);
-        if (ep.T[0] < 1) { // (not with the caps mlm_debug_set admits)
-            h->err = "mlm_export_reach: no ESDF tile fits the voxel cap";
-            return MLM_ERR_INVALID;
-        }
-        const size_t mask_bytes = ((size_t)ep.grown + 255) & ~(size_t)255, field_bytes = ((size_t)ep.grown * 2 + 255) & ~(size_t)255;
-        if ((rc = win_reserve(h, h->d_esdf_scratch, h->esdf_scratch_bytes, mask_bytes + 2 * field_bytes, "mlm_export_reach"))) return rc;
-        uint8_t *emask = (uint8_t *)h->d_esdf_scratch;
-        void *fa = (char *)h->d_esdf_scratch + mask_bytes, *fb = (char *)h->d_esdf_scratch + mask_bytes + field_bytes;
-        for (long long z0 = 0; z0 < D[2]; z0 += ep.T[2])
-            for (long long y0 = 0; y0 < D[1]; y0 += ep.T[1])
-                for (long long x0 = 0; x0 < D[0]; x0 += ep.T[0]) {
-                    MlmEsdf E{};
-                    const long long org[3] = {x0, y0, z0};
-                    int td[3];
-                    for (int a = 0; a < 3; ++a) {
-                        td[a] = (int)std::min(ep.T[a], D[a] - org[a]);
-                        E.glo[a] = lo[a] + org[a] - ep.H;
-                        E.gd[a] = td[a] + (int)(2 * ep.H);
-                        E.b0[a] = floor_div(E.glo[a]);
-                        E.nb[a] = (int)(floor_div(E.glo[a] + E.gd[a] - 1) - E.b0[a] + 1);
-                    }
-                    E.flags = flags;
-                    E.mask = emask;
-                    esdf_passes<false>(h, E, C, emask, fa, fb, td[0], td[1], td[2]);
-                    const long long nt = (long long)td[0] * td[1] * td[2];
-                    hipLaunchKernelGGL(k_reach_blocked, dim3(std::min<unsigned int>(grid_for((size_t)nt), kEsdfPassGrid)), dim3(MLM_BLOCK), 0, h->stream,
-                                       (const uint16_t *)fa, mask + (z0 * D[1] + y0) * D[0] + x0, nt, (unsigned)(clearance * clearance));
-                    HIPCHK(h, hipGetLastError());
-                }
+        // D_out <= clearance^2 of mlm_export_esdf at max_dist = clearance + 1
+        rc = esdf_tiles(h, "mlm_export_reach", lo, D, clearance + 1, flags, [&](const uint16_t *fa, long long j0, long long nt) {
+            hipLaunchKernelGGL(k_reach_blocked, dim3(std::min<unsigned int>(grid_for((size_t)nt), kEsdfPassGrid)), dim3(MLM_BLOCK), 0, h->stream, fa,
+                               mask + j0, nt, (unsigned)(clearance * clearance));
+        });
+        if (rc) return rc;
     }
     // field, seeds, dirty arrays, control block
     HIPCHK(h, hipMemsetAsync(base + plan.off_dirty, 0, (size_t)(2 * plan.dirty_bytes + kReachCtrlBytes), h->stream));
@@ -1650,48 +1391,22 @@ int mlm_export_reach(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], 
     hipLaunchKernelGGL(k_reach_seed, dim3(std::min<unsigned int>(grid_for((size_t)n_seeds), 1024u)), dim3(MLM_BLOCK), 0, h->stream, R,
                        (const int32_t *)seeds, n_seeds, (long long)lo[0], (long long)lo[1], (long long)lo[2], dirty[0]);
     HIPCHK(h, hipGetLastError());
-    // sweeps in groups: the dirty arrays swap roles from sweep to sweep; after each group the host reads the group's "marked"
-    // words and stops at the first sweep that marked nothing (the sweeps enqueued behind it found no dirty tile)
+    // sweeps in groups (settle): the dirty arrays swap roles from sweep to sweep
     const size_t lds = (size_t)(plan.T[0] + 2) * (plan.T[1] + 2) * (plan.T[2] + 2) * sizeof(uint32_t);
     const dim3 sgrid((unsigned int)std::min<long long>(plan.tiles, kReachGrid));
-    long long sweeps = 0, needed = -1;
-    while (needed < 0) {
-        if (sweeps >= plan.cap) { // (mlm_reach.h: cannot happen; an endless loop otherwise)
-            h->err = "mlm_export_reach: the field did not settle within " + std::to_string(sweeps) + " sweeps";
-            return MLM_ERR_HIP;
-        }
-        if (sweeps) HIPCHK(h, hipMemsetAsync(marked, 0, (size_t)group * sizeof(unsigned int), h->stream));
-        for (long long g = 0; g < group; ++g, ++sweeps)
-            hipLaunchKernelGGL(k_reach_sweep, sgrid, dim3(MLM_BLOCK), lds, h->stream, R, dirty[sweeps & 1], dirty[(sweeps & 1) ^ 1], marked + g);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(h->h_reach_ctrl, marked, (size_t)group * sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        for (long long g = 0; g < group && needed < 0; ++g)
-            if (h->h_reach_ctrl[g] == 0) needed = sweeps - group + g + 1;
-    }
+    const long long needed = settle(h, "mlm_export_reach", plan.cap, group, marked, [&](long long s, unsigned int *word) {
+        hipLaunchKernelGGL(k_reach_sweep, sgrid, dim3(MLM_BLOCK), lds, h->stream, R, dirty[s & 1], dirty[(s & 1) ^ 1], word);
+    });
+    if (needed < 0) return (int)needed;
     // outputs and counters
     for (long long j0 = 0; j0 < nvox; j0 += chunk) {
         const long long j1 = std::min(nvox, j0 + chunk);
-        void *ch[2];
-        for (int c = 0; c < 2; ++c)
-            ch[c] = !dst[c] ? nullptr : staged[c] ? (void *)((char *)h->d_win_stage + stage_off[c]) : (void *)((char *)dst[c] + (size_t)j0 * elem[c]);
         hipLaunchKernelGGL(k_reach_out, dim3(std::min<unsigned int>(grid_for((size_t)(j1 - j0)), kReachGrid)), dim3(MLM_BLOCK), 0, h->stream, R, j0, j1,
-                           (int32_t *)ch[0], (uint8_t *)ch[1], cnt);
+                           (int32_t *)ch.at(0, (size_t)j0), (uint8_t *)ch.at(1, (size_t)j0), cnt);
         HIPCHK(h, hipGetLastError());
-        for (int c = 0; c < 2; ++c)
-            if (staged[c])
-                HIPCHK(h, hipMemcpyAsync((char *)dst[c] + (size_t)j0 * elem[c], ch[c], (size_t)(j1 - j0) * elem[c], hipMemcpyDefault, h->stream));
+        if ((rc = ch.copy_out(h, 0, 2, (size_t)j0, (size_t)(j1 - j0)))) return rc;
     }
-    unsigned long long *h_cnt = (unsigned long long *)h->h_reach_ctrl;
-    if (summary) HIPCHK(h, hipMemcpyAsync(h_cnt, cnt, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (summary) {
-        summary[0] = (int64_t)h_cnt[0];
-        summary[1] = (int64_t)h_cnt[1];
-        summary[2] = (int64_t)h_cnt[2] - 1;
-        summary[3] = (int64_t)needed;
-    }
-    return MLM_OK;
+    return settle_finish(h, cnt, needed, summary);
 }
 
 int mlm_export_route(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], const int32_t *seeds3, int n_seeds, int flags, int clearance,
@@ -1710,22 +1425,11 @@ int mlm_export_route(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], 
                  "entry outside [0, 65535], max_cost < 1 or no output";
         return MLM_ERR_INVALID;
     }
-    long long D[3], nvox = 1;
-    for (int a = 0; a < 3; ++a) {
-        if (dims[a] < 1 || (long long)lo[a] + dims[a] > 0x7FFFFFFFll) {
-            h->err = "mlm_export_route: dims must be >= 1 and lo + dims must fit an int32";
-            return MLM_ERR_INVALID;
-        }
-        D[a] = dims[a];
-        nvox *= D[a];
-        if (nvox > 0x7FFFFFFFll) {
-            h->err = "mlm_export_route: more than 2^31 - 1 voxels";
-            return MLM_ERR_INVALID;
-        }
-    }
-    HIPCHK(h, hipSetDevice(h->device));
-    int rc = drain(h);
+    long long D[3], nvox;
+    int rc = box_check(h, "mlm_export_route", lo, dims, D, nvox);
     if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    if ((rc = drain(h))) return rc;
 
     long long tile = kRouteTileDefault, group = kRouteGroupDefault, kv;
     if (knob("route_tile", kv)) tile = kv;
@@ -1735,24 +1439,11 @@ int mlm_export_route(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], 
         h->err = "mlm_export_route: no such tile";
         return MLM_ERR_INVALID;
     }
-    // outputs: written in place, or staged through d_win_stage in ranges of the box
-    void *dst[2] = {cost, parent};
-    const size_t elem[2] = {sizeof(int32_t), 1};
-    bool staged[2];
-    bool any_staged = false;
-    for (int c = 0; c < 2; ++c) {
-        staged[c] = dst[c] && !win_in_place(dst[c]);
-        any_staged |= staged[c];
-    }
-    const long long chunk = any_staged ? std::min(nvox, kEsdfStageVoxels) : nvox;
-    size_t stage_off[2] = {0, 0}, stage_bytes = 0;
-    for (int c = 0; c < 2; ++c)
-        if (staged[c]) {
-            stage_off[c] = stage_bytes;
-            stage_bytes += ((size_t)chunk * elem[c] + 255) & ~(size_t)255;
-        }
-    if ((rc = win_reserve(h, h->d_reach, h->reach_bytes, (size_t)plan.scratch_bytes, "mlm_export_route"))) return rc;
-    if (stage_bytes && (rc = win_reserve(h, h->d_win_stage, h->win_stage_bytes, stage_bytes, "mlm_export_route"))) return rc;
+    // outputs: written in place, or staged in ranges of the box
+    ReadoutChannels<2> ch(h->d_win_stage, h->win_stage_bytes, {{cost, sizeof(int32_t)}, {parent, 1}});
+    const long long chunk = ch.any_staged ? std::min(nvox, kEsdfStageVoxels) : nvox;
+    if ((rc = readout_reserve(h, h->d_reach, h->reach_bytes, (size_t)plan.scratch_bytes, "mlm_export_route"))) return rc;
+    if ((rc = ch.reserve(h, "mlm_export_route", (size_t)chunk))) return rc;
     if (!h->h_reach_ctrl) HIPCHK(h, hipHostMalloc((void **)&h->h_reach_ctrl, (size_t)kReachCtrlBytes, hipHostMallocDefault));
     char *base = (char *)h->d_reach;
     uint8_t *cls = (uint8_t *)(base + plan.off_class), *dirty[2] = {(uint8_t *)(base + plan.off_dirty), (uint8_t *)(base + plan.off_dirty + plan.dirty_bytes)};
@@ -1775,55 +1466,15 @@ int mlm_export_route(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], 
     R.pen = pen;
 
     // the class bytes of the box
-    const int n = h->P.n;
-    auto floor_div = [n](long long v) { return v >= 0 ? v / n : -((-v + n - 1) / n); };
     if (clearance == 0 && n_penalty == 0) {
-        MlmEsdf E{};
-        for (int a = 0; a < 3; ++a) {
-            E.glo[a] = lo[a];
-            E.gd[a] = dims[a];
-            E.b0[a] = floor_div(E.glo[a]);
-            E.nb[a] = (int)(floor_div(E.glo[a] + E.gd[a] - 1) - E.b0[a] + 1);
-        }
-        E.flags = flags;
-        E.mask = cls;
-        const long long n_bricks = (long long)E.nb[0] * E.nb[1] * E.nb[2];
-        hipLaunchKernelGGL(k_esdf_mask, dim3((unsigned int)std::min<long long>(n_bricks, kEsdfMaskGrid)), dim3(MLM_BLOCK), 0, h->stream, h->P, E);
+        mask_box(h, lo, dims, flags, cls);
     } else {
-        // the rings of D_out of mlm_export_esdf at max_dist = clearance + n_penalty + 1, tile by tile (each a contiguous range of the box)
-        const int C = clearance + n_penalty + 1;
-        long long box_cap = kEsdfBoxVoxels;
-        if (knob("esdf_tile_vox", kv)) box_cap = kv;
-        const MlmEsdfPlan ep = mlm_esdf_plan(D, C, false, box_cap, 1ll << 62);
-        if (ep.T[0] < 1) { // (not with the caps mlm_debug_set admits)
-            h->err = "mlm_export_route: no ESDF tile fits the voxel cap";
-            return MLM_ERR_INVALID;
-        }
-        const size_t mask_bytes = ((size_t)ep.grown + 255) & ~(size_t)255, field_bytes = ((size_t)ep.grown * 2 + 255) & ~(size_t)255;
-        if ((rc = win_reserve(h, h->d_esdf_scratch, h->esdf_scratch_bytes, mask_bytes + 2 * field_bytes, "mlm_export_route"))) return rc;
-        uint8_t *emask = (uint8_t *)h->d_esdf_scratch;
-        void *fa = (char *)h->d_esdf_scratch + mask_bytes, *fb = (char *)h->d_esdf_scratch + mask_bytes + field_bytes;
-        for (long long z0 = 0; z0 < D[2]; z0 += ep.T[2])
-            for (long long y0 = 0; y0 < D[1]; y0 += ep.T[1])
-                for (long long x0 = 0; x0 < D[0]; x0 += ep.T[0]) {
-                    MlmEsdf E{};
-                    const long long org[3] = {x0, y0, z0};
-                    int td[3];
-                    for (int a = 0; a < 3; ++a) {
-                        td[a] = (int)std::min(ep.T[a], D[a] - org[a]);
-                        E.glo[a] = lo[a] + org[a] - ep.H;
-                        E.gd[a] = td[a] + (int)(2 * ep.H);
-                        E.b0[a] = floor_div(E.glo[a]);
-                        E.nb[a] = (int)(floor_div(E.glo[a] + E.gd[a] - 1) - E.b0[a] + 1);
-                    }
-                    E.flags = flags;
-                    E.mask = emask;
-                    esdf_passes<false>(h, E, C, emask, fa, fb, td[0], td[1], td[2]);
-                    const long long nt = (long long)td[0] * td[1] * td[2];
-                    hipLaunchKernelGGL(k_route_class, dim3(std::min<unsigned int>(grid_for((size_t)nt), kEsdfPassGrid)), dim3(MLM_BLOCK), 0, h->stream,
-                                       (const uint16_t *)fa, cls + (z0 * D[1] + y0) * D[0] + x0, nt, clearance, n_penalty);
-                    HIPCHK(h, hipGetLastError());
-                }
+        // the rings of D_out of mlm_export_esdf at max_dist = clearance + n_penalty + 1
+        rc = esdf_tiles(h, "mlm_export_route", lo, D, clearance + n_penalty + 1, flags, [&](const uint16_t *fa, long long j0, long long nt) {
+            hipLaunchKernelGGL(k_route_class, dim3(std::min<unsigned int>(grid_for((size_t)nt), kEsdfPassGrid)), dim3(MLM_BLOCK), 0, h->stream, fa,
+                               cls + j0, nt, clearance, n_penalty);
+        });
+        if (rc) return rc;
     }
     // field, seeds, dirty arrays, control block with the penalty table (staged in the pinned block behind what the host reads back)
     uint32_t *h_pen = (uint32_t *)((char *)h->h_reach_ctrl + kRoutePenOffset);
@@ -1841,44 +1492,19 @@ int mlm_export_route(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], 
     const size_t lds = (size_t)plan.lds_bytes;
     if (lds > 65536) HIPCHK(h, hipFuncSetAttribute((const void *)sweep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const dim3 sgrid((unsigned int)std::min<long long>(plan.tiles, kReachGrid));
-    long long sweeps = 0, needed = -1;
-    while (needed < 0) {
-        if (sweeps >= plan.cap) { // (mlm_route.h: cannot happen; an endless loop otherwise)
-            h->err = "mlm_export_route: the field did not settle within " + std::to_string(sweeps) + " sweeps";
-            return MLM_ERR_HIP;
-        }
-        if (sweeps) HIPCHK(h, hipMemsetAsync(marked, 0, (size_t)group * sizeof(unsigned int), h->stream));
-        for (long long g = 0; g < group; ++g, ++sweeps)
-            hipLaunchKernelGGL(sweep, sgrid, dim3(MLM_BLOCK), lds, h->stream, R, dirty[sweeps & 1], dirty[(sweeps & 1) ^ 1], marked + g);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(h->h_reach_ctrl, marked, (size_t)group * sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        for (long long g = 0; g < group && needed < 0; ++g)
-            if (h->h_reach_ctrl[g] == 0) needed = sweeps - group + g + 1;
-    }
+    const long long needed = settle(h, "mlm_export_route", plan.cap, group, marked, [&](long long s, unsigned int *word) {
+        hipLaunchKernelGGL(sweep, sgrid, dim3(MLM_BLOCK), lds, h->stream, R, dirty[s & 1], dirty[(s & 1) ^ 1], word);
+    });
+    if (needed < 0) return (int)needed;
     // outputs and counters
     for (long long j0 = 0; j0 < nvox; j0 += chunk) {
         const long long j1 = std::min(nvox, j0 + chunk);
-        void *ch[2];
-        for (int c = 0; c < 2; ++c)
-            ch[c] = !dst[c] ? nullptr : staged[c] ? (void *)((char *)h->d_win_stage + stage_off[c]) : (void *)((char *)dst[c] + (size_t)j0 * elem[c]);
         hipLaunchKernelGGL(k_route_out, dim3(std::min<unsigned int>(grid_for((size_t)(j1 - j0)), kReachGrid)), dim3(MLM_BLOCK), 0, h->stream, R, j0, j1,
-                           (int32_t *)ch[0], (uint8_t *)ch[1], cnt);
+                           (int32_t *)ch.at(0, (size_t)j0), (uint8_t *)ch.at(1, (size_t)j0), cnt);
         HIPCHK(h, hipGetLastError());
-        for (int c = 0; c < 2; ++c)
-            if (staged[c])
-                HIPCHK(h, hipMemcpyAsync((char *)dst[c] + (size_t)j0 * elem[c], ch[c], (size_t)(j1 - j0) * elem[c], hipMemcpyDefault, h->stream));
+        if ((rc = ch.copy_out(h, 0, 2, (size_t)j0, (size_t)(j1 - j0)))) return rc;
     }
-    unsigned long long *h_cnt = (unsigned long long *)h->h_reach_ctrl;
-    if (summary) HIPCHK(h, hipMemcpyAsync(h_cnt, cnt, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (summary) {
-        summary[0] = (int64_t)h_cnt[0];
-        summary[1] = (int64_t)h_cnt[1];
-        summary[2] = (int64_t)h_cnt[2] - 1;
-        summary[3] = (int64_t)needed;
-    }
-    return MLM_OK;
+    return settle_finish(h, cnt, needed, summary);
 }
 
 int mlm_export_clusters(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], int flags, int connectivity, int min_size, int32_t *labels,
@@ -1893,26 +1519,15 @@ int mlm_export_clusters(mlm_handle *h, const int32_t lo[3], const int32_t dims[3
                  "min_size < 1, cap < 0, cap == 0 with a table or cap > 0 without one, or no output";
         return MLM_ERR_INVALID;
     }
-    long long D[3], nvox = 1;
-    for (int a = 0; a < 3; ++a) {
-        if (dims[a] < 1 || (long long)lo[a] + dims[a] > 0x7FFFFFFFll) {
-            h->err = "mlm_export_clusters: dims must be >= 1 and lo + dims must fit an int32";
-            return MLM_ERR_INVALID;
-        }
-        D[a] = dims[a];
-        nvox *= D[a];
-        if (nvox > 0x7FFFFFFFll) {
-            h->err = "mlm_export_clusters: more than 2^31 - 1 voxels";
-            return MLM_ERR_INVALID;
-        }
-    }
-    HIPCHK(h, hipSetDevice(h->device));
-    int rc = drain(h);
+    long long D[3], nvox;
+    int rc = box_check(h, "mlm_export_clusters", lo, dims, D, nvox);
     if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    if ((rc = drain(h))) return rc;
 
     long long tile = kClusterTileDefault, kv;
     if (knob("cluster_tile", kv)) tile = kv;
-    const bool table_staged = table && !win_in_place(table), labels_staged = labels && !win_in_place(labels);
+    const bool table_staged = table && !readout_in_place(table), labels_staged = labels && !readout_in_place(labels);
     const MlmClusterPlan plan = mlm_cluster_plan(D, tile, frontier, table_staged ? std::min<long long>(cap, nvox) : 0); // (K <= voxels)
     if (!plan.ok) { // (not with the tiles mlm_debug_set admits)
         h->err = "mlm_export_clusters: no such tile";
@@ -1920,8 +1535,8 @@ int mlm_export_clusters(mlm_handle *h, const int32_t lo[3], const int32_t dims[3
     }
     // labels: written in place, or staged through d_win_stage in ranges of the box; rows: in place, or in the scratch
     const long long chunk = labels_staged ? std::min(nvox, kEsdfStageVoxels) : nvox;
-    if ((rc = win_reserve(h, h->d_cluster, h->cluster_bytes, (size_t)plan.scratch_bytes, "mlm_export_clusters"))) return rc;
-    if (labels_staged && (rc = win_reserve(h, h->d_win_stage, h->win_stage_bytes, (size_t)chunk * sizeof(int32_t), "mlm_export_clusters")))
+    if ((rc = readout_reserve(h, h->d_cluster, h->cluster_bytes, (size_t)plan.scratch_bytes, "mlm_export_clusters"))) return rc;
+    if (labels_staged && (rc = readout_reserve(h, h->d_win_stage, h->win_stage_bytes, (size_t)chunk * sizeof(int32_t), "mlm_export_clusters")))
         return rc;
     if (!h->h_reach_ctrl) HIPCHK(h, hipHostMalloc((void **)&h->h_reach_ctrl, (size_t)kReachCtrlBytes, hipHostMallocDefault));
     char *base = (char *)h->d_cluster;
@@ -1944,33 +1559,20 @@ int mlm_export_clusters(mlm_handle *h, const int32_t lo[3], const int32_t dims[3
     R.num = (uint32_t *)(base + plan.off_num);
 
     // the mask of the box
-    const int n = h->P.n;
-    auto floor_div = [n](long long v) { return v >= 0 ? v / n : -((-v + n - 1) / n); };
     const dim3 vgrid(std::min<unsigned int>(grid_for((size_t)nvox), kReachGrid));
     if (frontier) {
         MlmClusterOcc E{};
         for (int a = 0; a < 3; ++a) {
-            E.glo[a] = (long long)lo[a] - 1; // (64-bit: the grown box of a window at the int32 edge reaches past it)
+            E.glo[a] = (long long)lo[a] - 1;
             E.gd[a] = D[a] + 2;
-            E.b0[a] = floor_div(E.glo[a]);
-            E.nb[a] = (int)(floor_div(E.glo[a] + E.gd[a] - 1) - E.b0[a] + 1);
         }
+        brick_cover(h, 3, E.glo, E.gd, E.b0, E.nb);
         E.out = (uint8_t *)(base + plan.off_grown);
         const long long n_bricks = (long long)E.nb[0] * E.nb[1] * E.nb[2];
         hipLaunchKernelGGL(k_cluster_occ, dim3((unsigned int)std::min<long long>(n_bricks, kEsdfMaskGrid)), dim3(MLM_BLOCK), 0, h->stream, h->P, E);
         hipLaunchKernelGGL(k_cluster_frontier, vgrid, dim3(MLM_BLOCK), 0, h->stream, (const uint8_t *)E.out, mask, D[0], D[1], nvox);
     } else {
-        MlmEsdf E{};
-        for (int a = 0; a < 3; ++a) {
-            E.glo[a] = lo[a];
-            E.gd[a] = dims[a];
-            E.b0[a] = floor_div(E.glo[a]);
-            E.nb[a] = (int)(floor_div(E.glo[a] + E.gd[a] - 1) - E.b0[a] + 1);
-        }
-        E.flags = flags;
-        E.mask = mask;
-        const long long n_bricks = (long long)E.nb[0] * E.nb[1] * E.nb[2];
-        hipLaunchKernelGGL(k_esdf_mask, dim3((unsigned int)std::min<long long>(n_bricks, kEsdfMaskGrid)), dim3(MLM_BLOCK), 0, h->stream, h->P, E);
+        mask_box(h, lo, dims, flags, mask);
     }
     HIPCHK(h, hipGetLastError());
     // local, merge, flatten and sizes, numbering
@@ -2021,50 +1623,27 @@ int mlm_query_rays(mlm_handle *h, const double *p0, const double *p1, int n, int
     if (n == 0) return MLM_OK;
     HIPCHK(h, hipSetDevice(h->device));
     // channels: the two inputs, then the five outputs; bytes per ray; in device memory (used in place) or staged
-    void *ch[7] = {(void *)p0, (void *)p1, status, voxel3, t, n_steps, n_unknown};
-    const size_t elem[7] = {3 * sizeof(double), 3 * sizeof(double), 1, 3 * sizeof(int32_t), sizeof(double), sizeof(int32_t), sizeof(int32_t)};
-    bool staged[7];
-    bool all_host = true;
-    for (int c = 0; c < 7; ++c) {
-        staged[c] = ch[c] && !win_in_place(ch[c]);
-        all_host = all_host && (staged[c] || !ch[c]);
-    }
+    ReadoutChannels<7> ch(h->d_ray_stage, h->ray_stage_bytes,
+                          {{p0, 3 * sizeof(double)}, {p1, 3 * sizeof(double)}, {status, 1}, {voxel3, 3 * sizeof(int32_t)}, {t, sizeof(double)},
+                           {n_steps, sizeof(int32_t)}, {n_unknown, sizeof(int32_t)}},
+                          true);
     // a planner's edge-by-edge calls: answered on the host (mlm_mirror.h), like run_query's small batches
-    if (all_host && mirror_rays_wanted(h, p0, p1, n)) {
-        const int rc = mirror_sync(h);
-        if (rc == MLM_OK) {
-            h->mir.view.rays(p0, p1, n, flags, status, voxel3, t, n_steps, n_unknown);
-            h->mir.n_host_queries += n;
-            return MLM_OK;
-        }
-        if (!h->mir.alloc_failed && rc != kMirrorUnavailable) return rc; // (an error of the frames in flight, reported by the drain)
-        // (no pinned host memory for the mirror, or more than its limit allows: this and all later batches run as kernels)
-    }
-    int rc = drain(h);
-    if (rc) return rc;
+    int rc = mirror_try(h, ch.all_host && mirror_rays_wanted(h, p0, p1, n), n, [&] { h->mir.view.rays(p0, p1, n, flags, status, voxel3, t, n_steps, n_unknown); });
+    if (rc) return rc > 0 ? MLM_OK : rc;
+    if ((rc = drain(h))) return rc;
     // chunks: staged channels of a chunk share one kept buffer (at most 77 bytes per ray)
     const int chunk = std::min(n, kRayChunk);
-    size_t off[7], stage_bytes = 0;
-    for (int c = 0; c < 7; ++c) {
-        off[c] = stage_bytes;
-        if (staged[c]) stage_bytes += ((size_t)chunk * elem[c] + 255) & ~(size_t)255;
-    }
-    if (stage_bytes && (rc = win_reserve(h, h->d_ray_stage, h->ray_stage_bytes, stage_bytes, "mlm_query_rays"))) return rc;
+    if ((rc = ch.reserve(h, "mlm_query_rays", (size_t)chunk))) return rc;
     for (int i0 = 0; i0 < n; i0 += chunk) {
         const int m = std::min(chunk, n - i0);
         void *at[7];
-        for (int c = 0; c < 7; ++c)
-            at[c] = !ch[c] ? nullptr : staged[c] ? (void *)((char *)h->d_ray_stage + off[c]) : (void *)((char *)ch[c] + (size_t)i0 * elem[c]);
-        for (int c = 0; c < 2; ++c)
-            if (staged[c])
-                HIPCHK(h, hipMemcpyAsync(at[c], (const char *)ch[c] + (size_t)i0 * elem[c], (size_t)m * elem[c], hipMemcpyHostToDevice, h->stream));
+        for (int c = 0; c < 7; ++c) at[c] = ch.at(c, (size_t)i0);
+        if ((rc = ch.copy_in(h, 0, 2, (size_t)i0, (size_t)m))) return rc;
         MlmRays R{(const double *)at[0], (const double *)at[1], m, flags, (int8_t *)at[2], (int32_t *)at[3], (double *)at[4], (int32_t *)at[5], (int32_t *)at[6]};
         const dim3 grid(std::min<unsigned int>(grid_for((size_t)m), h->rays_grid));
         hipLaunchKernelGGL(k_rays, grid, dim3(MLM_BLOCK), 0, h->stream, h->P, R);
         HIPCHK(h, hipGetLastError());
-        for (int c = 2; c < 7; ++c)
-            if (staged[c])
-                HIPCHK(h, hipMemcpyAsync((char *)ch[c] + (size_t)i0 * elem[c], at[c], (size_t)m * elem[c], hipMemcpyDeviceToHost, h->stream));
+        if ((rc = ch.copy_out(h, 2, 7, (size_t)i0, (size_t)m))) return rc;
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MLM_OK;
@@ -2098,39 +1677,33 @@ int mlm_render_depth(mlm_handle *h, const double *T_ws, int n_poses, int width, 
     auto first_pixel = [&](long long q) { return ((q / tiles_y) * height + (q % tiles_y) * TH) * width; };
     // channels: the poses, the four per-pixel outputs, the table; in device memory (used in place) or staged — poses and table for the
     // whole call, the per-pixel outputs chunk by chunk (at most 19 bytes per pixel)
-    void *ch[6] = {(void *)T_ws, depth, status, voxel3, n_unknown, table};
-    const size_t elem[6] = {12 * sizeof(double), sizeof(uint16_t), 1, 3 * sizeof(int32_t), sizeof(int32_t), MLM_RENDER_ROW * sizeof(int64_t)};
-    bool staged[6];
-    size_t off[6], stage_bytes = 0;
-    for (int c = 0; c < 6; ++c) {
-        staged[c] = ch[c] && !win_in_place(ch[c]);
-        off[c] = stage_bytes;
-        if (staged[c]) stage_bytes += ((size_t)(c == 0 || c == 5 ? n_poses : chunk_pixels) * elem[c] + 255) & ~(size_t)255;
-    }
-    if (stage_bytes && (rc = win_reserve(h, h->d_ray_stage, h->ray_stage_bytes, stage_bytes, "mlm_render_depth"))) return rc;
-    auto dev = [&](int c) { return !ch[c] ? nullptr : staged[c] ? (void *)((char *)h->d_ray_stage + off[c]) : ch[c]; };
-    if (staged[0]) HIPCHK(h, hipMemcpyAsync(dev(0), T_ws, (size_t)n_poses * elem[0], hipMemcpyHostToDevice, h->stream));
-    if (table) HIPCHK(h, hipMemsetAsync(dev(5), 0, (size_t)n_poses * elem[5], h->stream));
+    ReadoutChannels<6> ch(h->d_ray_stage, h->ray_stage_bytes,
+                          {{T_ws, 12 * sizeof(double)}, {depth, sizeof(uint16_t)}, {status, 1}, {voxel3, 3 * sizeof(int32_t)},
+                           {n_unknown, sizeof(int32_t)}, {table, MLM_RENDER_ROW * sizeof(int64_t)}},
+                          true);
+    const size_t np = (size_t)n_poses, cp = (size_t)chunk_pixels;
+    if ((rc = ch.reserve(h, "mlm_render_depth", {np, cp, cp, cp, cp, np}))) return rc;
+    if ((rc = ch.copy_in(h, 0, 1, 0, np))) return rc;
+    if (table) HIPCHK(h, hipMemsetAsync(ch.at(5, 0), 0, np * ch.elem[5], h->stream));
     MlmRender R{};
-    R.T = (const double *)dev(0);
+    R.T = (const double *)ch.at(0, 0);
     for (int k = 0; k < 4; ++k) R.K[k] = k4[k];
     R.Z = (double)max_depth_mm / 1000.0;
     R.width = width, R.height = height, R.max_mm = max_depth_mm, R.flags = flags;
     R.tiles_x = tiles_x, R.tiles_y = tiles_y;
-    R.table = (unsigned long long *)dev(5);
+    R.table = (unsigned long long *)ch.at(5, 0);
     for (long long q0 = 0; q0 < q_total; q0 += q_chunk) {
         const long long q1 = std::min(q_total, q0 + q_chunk), i0 = first_pixel(q0), m = first_pixel(q1) - i0;
         void *at[5];
-        for (int c = 1; c < 5; ++c) at[c] = !ch[c] ? nullptr : staged[c] ? dev(c) : (void *)((char *)ch[c] + (size_t)i0 * elem[c]);
+        for (int c = 1; c < 5; ++c) at[c] = ch.at(c, (size_t)i0);
         R.q0 = (int)q0, R.n_tiles = (int)((q1 - q0) * tiles_x), R.pix0 = i0;
         R.depth = (uint16_t *)at[1], R.status = (int8_t *)at[2], R.voxel3 = (int32_t *)at[3], R.n_unknown = (int32_t *)at[4];
         // one wave per tile, four to a workgroup
-        hipLaunchKernelGGL(kern, dim3(((unsigned int)R.n_tiles + MLM_BLOCK / 64 - 1) / (MLM_BLOCK / 64)), dim3(MLM_BLOCK), 0, h->stream, h->P, R);
+        hipLaunchKernelGGL(kern, dim3(wave_grid((size_t)R.n_tiles)), dim3(MLM_BLOCK), 0, h->stream, h->P, R);
         HIPCHK(h, hipGetLastError());
-        for (int c = 1; c < 5; ++c)
-            if (staged[c]) HIPCHK(h, hipMemcpyAsync((char *)ch[c] + (size_t)i0 * elem[c], at[c], (size_t)m * elem[c], hipMemcpyDeviceToHost, h->stream));
+        if ((rc = ch.copy_out(h, 1, 5, (size_t)i0, (size_t)m))) return rc;
     }
-    if (staged[5]) HIPCHK(h, hipMemcpyAsync(table, dev(5), (size_t)n_poses * elem[5], hipMemcpyDeviceToHost, h->stream));
+    if ((rc = ch.copy_out(h, 5, 6, 0, np))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MLM_OK;
 }
@@ -2153,17 +1726,9 @@ int mlm_query_boxes(mlm_handle *h, const int32_t *box6, int n, int flags, const 
     }
     if (lo) {
         L.on = 1;
-        long long nvox = 1;
+        long long D[3], nvox;
+        if (int rc = box_check(h, "mlm_query_boxes", lo, dims, D, nvox)) return rc;
         for (int a = 0; a < 3; ++a) {
-            if (dims[a] < 1 || (long long)lo[a] + dims[a] > 0x7FFFFFFFll) {
-                h->err = "mlm_query_boxes: dims must be >= 1 and lo + dims must fit an int32";
-                return MLM_ERR_INVALID;
-            }
-            nvox *= dims[a];
-            if (nvox > 0x7FFFFFFFll) {
-                h->err = "mlm_query_boxes: more than 2^31 - 1 voxels";
-                return MLM_ERR_INVALID;
-            }
             L.wlo[a] = lo[a];
             L.whi[a] = lo[a] + (dims[a] - 1);
         }
@@ -2171,48 +1736,26 @@ int mlm_query_boxes(mlm_handle *h, const int32_t *box6, int n, int flags, const 
     if (n == 0) return MLM_OK;
     HIPCHK(h, hipSetDevice(h->device));
     // channels: the input, then the four outputs; bytes per box; in device memory (used in place) or staged
-    void *ch[5] = {(void *)box6, status, out6, closed, table};
-    const size_t elem[5] = {6 * sizeof(int32_t), 1, 6 * sizeof(int32_t), 1, MLM_BOX_ROW * sizeof(int64_t)};
-    bool staged[5];
-    bool all_host = true;
-    for (int c = 0; c < 5; ++c) {
-        staged[c] = ch[c] && !win_in_place(ch[c]);
-        all_host = all_host && (staged[c] || !ch[c]);
-    }
+    ReadoutChannels<5> ch(h->d_ray_stage, h->ray_stage_bytes,
+                          {{box6, 6 * sizeof(int32_t)}, {status, 1}, {out6, 6 * sizeof(int32_t)}, {closed, 1}, {table, MLM_BOX_ROW * sizeof(int64_t)}}, true);
     // a planner's waypoint-by-waypoint calls: answered on the host (mlm_mirror.h), like mlm_query_rays' small batches
-    if (all_host && mirror_boxes_wanted(h, box6, n, L)) {
-        const int rc = mirror_sync(h);
-        if (rc == MLM_OK) {
-            h->mir.view.boxes(box6, n, flags, L, status, out6, closed, table);
-            h->mir.n_host_queries += n;
-            return MLM_OK;
-        }
-        if (!h->mir.alloc_failed && rc != kMirrorUnavailable) return rc; // (an error of the frames in flight, reported by the drain)
-    }
-    int rc = drain(h);
-    if (rc) return rc;
+    int rc = mirror_try(h, ch.all_host && mirror_boxes_wanted(h, box6, n, L), n, [&] { h->mir.view.boxes(box6, n, flags, L, status, out6, closed, table); });
+    if (rc) return rc > 0 ? MLM_OK : rc;
+    if ((rc = drain(h))) return rc;
     // chunks: staged channels of a chunk share one kept buffer (at most 82 bytes per box)
     const int chunk = std::min(n, kBoxChunk);
-    size_t off[5], stage_bytes = 0;
-    for (int c = 0; c < 5; ++c) {
-        off[c] = stage_bytes;
-        if (staged[c]) stage_bytes += ((size_t)chunk * elem[c] + 255) & ~(size_t)255;
-    }
-    if (stage_bytes && (rc = win_reserve(h, h->d_ray_stage, h->ray_stage_bytes, stage_bytes, "mlm_query_boxes"))) return rc;
+    if ((rc = ch.reserve(h, "mlm_query_boxes", (size_t)chunk))) return rc;
     for (int i0 = 0; i0 < n; i0 += chunk) {
         const int m = std::min(chunk, n - i0);
         void *at[5];
-        for (int c = 0; c < 5; ++c)
-            at[c] = !ch[c] ? nullptr : staged[c] ? (void *)((char *)h->d_ray_stage + off[c]) : (void *)((char *)ch[c] + (size_t)i0 * elem[c]);
-        if (staged[0]) HIPCHK(h, hipMemcpyAsync(at[0], (const char *)ch[0] + (size_t)i0 * elem[0], (size_t)m * elem[0], hipMemcpyHostToDevice, h->stream));
+        for (int c = 0; c < 5; ++c) at[c] = ch.at(c, (size_t)i0);
+        if ((rc = ch.copy_in(h, 0, 1, (size_t)i0, (size_t)m))) return rc;
         MlmBoxes B{(const int32_t *)at[0], m, flags, L, (int8_t *)at[1], (int32_t *)at[2], (uint8_t *)at[3], (int64_t *)at[4]};
         // one wave per box, four to a workgroup; at most kBoxGrid workgroups (grid-stride)
-        const dim3 grid(std::min<unsigned int>(((unsigned int)m + MLM_BLOCK / 64 - 1) / (MLM_BLOCK / 64), kBoxGrid));
+        const dim3 grid(wave_grid((size_t)m, kBoxGrid));
         hipLaunchKernelGGL(k_boxes, grid, dim3(MLM_BLOCK), 0, h->stream, h->P, B);
         HIPCHK(h, hipGetLastError());
-        for (int c = 1; c < 5; ++c)
-            if (staged[c])
-                HIPCHK(h, hipMemcpyAsync((char *)ch[c] + (size_t)i0 * elem[c], at[c], (size_t)m * elem[c], hipMemcpyDeviceToHost, h->stream));
+        if ((rc = ch.copy_out(h, 1, 5, (size_t)i0, (size_t)m))) return rc;
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MLM_OK;
@@ -2230,48 +1773,28 @@ int mlm_query_nearest(mlm_handle *h, const double *pos, int n, int max_dist, int
     if (n == 0) return MLM_OK;
     HIPCHK(h, hipSetDevice(h->device));
     // channels: the input, then the five outputs; bytes per point; in device memory (used in place) or staged
-    void *ch[6] = {(void *)pos, status, voxel3, delta3, sq, dist};
-    const size_t elem[6] = {3 * sizeof(double), 1, 3 * sizeof(int32_t), 3 * sizeof(int32_t), sizeof(int64_t), sizeof(double)};
-    bool staged[6];
-    bool all_host = true;
-    for (int c = 0; c < 6; ++c) {
-        staged[c] = ch[c] && !win_in_place(ch[c]);
-        all_host = all_host && (staged[c] || !ch[c]);
-    }
+    ReadoutChannels<6> ch(h->d_ray_stage, h->ray_stage_bytes,
+                          {{pos, 3 * sizeof(double)}, {status, 1}, {voxel3, 3 * sizeof(int32_t)}, {delta3, 3 * sizeof(int32_t)}, {sq, sizeof(int64_t)},
+                           {dist, sizeof(double)}},
+                          true);
     // an optimiser's few control points: answered on the host (mlm_mirror.h), like mlm_query_boxes' small batches
-    if (all_host && mirror_nearest_wanted(h, n, max_dist)) {
-        const int rc = mirror_sync(h);
-        if (rc == MLM_OK) {
-            h->mir.view.nearest(pos, n, max_dist, flags, status, voxel3, delta3, sq, dist);
-            h->mir.n_host_queries += n;
-            return MLM_OK;
-        }
-        if (!h->mir.alloc_failed && rc != kMirrorUnavailable) return rc; // (an error of the frames in flight, reported by the drain)
-    }
-    int rc = drain(h);
-    if (rc) return rc;
+    int rc = mirror_try(h, ch.all_host && mirror_nearest_wanted(h, n, max_dist), n, [&] { h->mir.view.nearest(pos, n, max_dist, flags, status, voxel3, delta3, sq, dist); });
+    if (rc) return rc > 0 ? MLM_OK : rc;
+    if ((rc = drain(h))) return rc;
     // chunks: staged channels of a chunk share one kept buffer (at most 65 bytes per point)
     const int chunk = std::min(n, kNearChunk);
-    size_t off[6], stage_bytes = 0;
-    for (int c = 0; c < 6; ++c) {
-        off[c] = stage_bytes;
-        if (staged[c]) stage_bytes += ((size_t)chunk * elem[c] + 255) & ~(size_t)255;
-    }
-    if (stage_bytes && (rc = win_reserve(h, h->d_ray_stage, h->ray_stage_bytes, stage_bytes, "mlm_query_nearest"))) return rc;
+    if ((rc = ch.reserve(h, "mlm_query_nearest", (size_t)chunk))) return rc;
     for (int i0 = 0; i0 < n; i0 += chunk) {
         const int m = std::min(chunk, n - i0);
         void *at[6];
-        for (int c = 0; c < 6; ++c)
-            at[c] = !ch[c] ? nullptr : staged[c] ? (void *)((char *)h->d_ray_stage + off[c]) : (void *)((char *)ch[c] + (size_t)i0 * elem[c]);
-        if (staged[0]) HIPCHK(h, hipMemcpyAsync(at[0], (const char *)ch[0] + (size_t)i0 * elem[0], (size_t)m * elem[0], hipMemcpyHostToDevice, h->stream));
+        for (int c = 0; c < 6; ++c) at[c] = ch.at(c, (size_t)i0);
+        if ((rc = ch.copy_in(h, 0, 1, (size_t)i0, (size_t)m))) return rc;
         MlmNearest Q{(const double *)at[0], m, max_dist, flags, (int8_t *)at[1], (int32_t *)at[2], (int32_t *)at[3], (int64_t *)at[4], (double *)at[5]};
         // one wave per point, four to a workgroup; at most kNearGrid workgroups (grid-stride)
-        const dim3 grid(std::min<unsigned int>(((unsigned int)m + MLM_BLOCK / 64 - 1) / (MLM_BLOCK / 64), kNearGrid));
+        const dim3 grid(wave_grid((size_t)m, kNearGrid));
         hipLaunchKernelGGL(k_nearest, grid, dim3(MLM_BLOCK), 0, h->stream, h->P, Q);
         HIPCHK(h, hipGetLastError());
-        for (int c = 1; c < 6; ++c)
-            if (staged[c])
-                HIPCHK(h, hipMemcpyAsync((char *)ch[c] + (size_t)i0 * elem[c], at[c], (size_t)m * elem[c], hipMemcpyDeviceToHost, h->stream));
+        if ((rc = ch.copy_out(h, 1, 6, (size_t)i0, (size_t)m))) return rc;
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MLM_OK;
@@ -2289,57 +1812,34 @@ int mlm_query_sweeps(mlm_handle *h, const double *p0, const double *p1, int n, i
     if (n == 0) return MLM_OK;
     HIPCHK(h, hipSetDevice(h->device));
     // channels: the two inputs, then the seven outputs; bytes per ray; in device memory (used in place) or staged
-    void *ch[9] = {(void *)p0, (void *)p1, status, voxel3, t, n_steps, n_unknown, hit3, hit_sq};
-    const size_t elem[9] = {3 * sizeof(double), 3 * sizeof(double), 1, 3 * sizeof(int32_t), sizeof(double), sizeof(int32_t), sizeof(int32_t),
-                            3 * sizeof(int32_t), sizeof(int32_t)};
-    bool staged[9];
-    bool all_host = true;
-    for (int c = 0; c < 9; ++c) {
-        staged[c] = ch[c] && !win_in_place(ch[c]);
-        all_host = all_host && (staged[c] || !ch[c]);
-    }
+    ReadoutChannels<9> ch(h->d_ray_stage, h->ray_stage_bytes,
+                          {{p0, 3 * sizeof(double)}, {p1, 3 * sizeof(double)}, {status, 1}, {voxel3, 3 * sizeof(int32_t)}, {t, sizeof(double)},
+                           {n_steps, sizeof(int32_t)}, {n_unknown, sizeof(int32_t)}, {hit3, 3 * sizeof(int32_t)}, {hit_sq, sizeof(int32_t)}},
+                          true);
     // a planner's edge-by-edge calls: answered on the host (mlm_mirror.h), like mlm_query_rays' small batches
-    if (all_host && mirror_sweeps_wanted(h, p0, p1, n, radius)) {
-        const int rc = mirror_sync(h);
-        if (rc == MLM_OK) {
-            h->mir.view.sweep(p0, p1, n, radius, flags, status, voxel3, t, n_steps, n_unknown, hit3, hit_sq);
-            h->mir.n_host_queries += n;
-            return MLM_OK;
-        }
-        if (!h->mir.alloc_failed && rc != kMirrorUnavailable) return rc; // (an error of the frames in flight, reported by the drain)
-    }
-    int rc = drain(h);
-    if (rc) return rc;
+    int rc = mirror_try(h, ch.all_host && mirror_sweeps_wanted(h, p0, p1, n, radius), n, [&] { h->mir.view.sweep(p0, p1, n, radius, flags, status, voxel3, t, n_steps, n_unknown, hit3, hit_sq); });
+    if (rc) return rc > 0 ? MLM_OK : rc;
+    if ((rc = drain(h))) return rc;
     // chunks: staged channels of a chunk share one kept buffer (at most 93 bytes per ray)
     const int chunk = std::min(n, kSweepChunk);
-    size_t off[9], stage_bytes = 0;
-    for (int c = 0; c < 9; ++c) {
-        off[c] = stage_bytes;
-        if (staged[c]) stage_bytes += ((size_t)chunk * elem[c] + 255) & ~(size_t)255;
-    }
-    if (stage_bytes && (rc = win_reserve(h, h->d_ray_stage, h->ray_stage_bytes, stage_bytes, "mlm_query_sweeps"))) return rc;
+    if ((rc = ch.reserve(h, "mlm_query_sweeps", (size_t)chunk))) return rc;
     // the slots of the block box around the ball stay in LDS while the box has at most kSweepNB blocks per axis (mlm_kernels_sweeps.h)
     const bool cached = radius > 0 && (2 * radius - 1) / h->P.n + 2 <= kSweepNB;
     for (int i0 = 0; i0 < n; i0 += chunk) {
         const int m = std::min(chunk, n - i0);
         void *at[9];
-        for (int c = 0; c < 9; ++c)
-            at[c] = !ch[c] ? nullptr : staged[c] ? (void *)((char *)h->d_ray_stage + off[c]) : (void *)((char *)ch[c] + (size_t)i0 * elem[c]);
-        for (int c = 0; c < 2; ++c)
-            if (staged[c])
-                HIPCHK(h, hipMemcpyAsync(at[c], (const char *)ch[c] + (size_t)i0 * elem[c], (size_t)m * elem[c], hipMemcpyHostToDevice, h->stream));
+        for (int c = 0; c < 9; ++c) at[c] = ch.at(c, (size_t)i0);
+        if ((rc = ch.copy_in(h, 0, 2, (size_t)i0, (size_t)m))) return rc;
         MlmSweeps R{(const double *)at[0], (const double *)at[1], m, radius, flags, mlm_sweep_columns(radius), (int8_t *)at[2], (int32_t *)at[3],
                     (double *)at[4], (int32_t *)at[5], (int32_t *)at[6], (int32_t *)at[7], (int32_t *)at[8]};
         if (radius == 0) { // one lane per ray, as k_rays
             hipLaunchKernelGGL(k_sweeps0, dim3(std::min<unsigned int>(grid_for((size_t)m), h->rays_grid)), dim3(MLM_BLOCK), 0, h->stream, h->P, R);
         } else { // one wave per ray, four to a workgroup; at most kSweepGrid workgroups (grid-stride)
-            const dim3 grid(std::min<unsigned int>(((unsigned int)m + MLM_BLOCK / 64 - 1) / (MLM_BLOCK / 64), kSweepGrid));
+            const dim3 grid(wave_grid((size_t)m, kSweepGrid));
             hipLaunchKernelGGL(cached ? k_sweeps<true> : k_sweeps<false>, grid, dim3(MLM_BLOCK), 0, h->stream, h->P, R);
         }
         HIPCHK(h, hipGetLastError());
-        for (int c = 2; c < 9; ++c)
-            if (staged[c])
-                HIPCHK(h, hipMemcpyAsync((char *)ch[c] + (size_t)i0 * elem[c], at[c], (size_t)m * elem[c], hipMemcpyDeviceToHost, h->stream));
+        if ((rc = ch.copy_out(h, 2, 9, (size_t)i0, (size_t)m))) return rc;
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MLM_OK;
@@ -2356,29 +1856,24 @@ int mlm_query_paths(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], c
                  "[1, 2^20], cap negative or at odds with way3, or no output";
         return MLM_ERR_INVALID;
     }
-    long long nvox = 1;
-    for (int a = 0; a < 3; ++a) {
-        if (dims[a] < 1 || (long long)lo[a] + dims[a] > 0x7FFFFFFFll) {
-            h->err = "mlm_query_paths: dims must be >= 1 and lo + dims must fit an int32";
-            return MLM_ERR_INVALID;
-        }
-        nvox *= dims[a];
-        if (nvox > 0x7FFFFFFFll) {
-            h->err = "mlm_query_paths: more than 2^31 - 1 voxels";
-            return MLM_ERR_INVALID;
-        }
-    }
+    long long D[3], nvox;
+    int rc = box_check(h, "mlm_query_paths", lo, dims, D, nvox);
+    if (rc) return rc;
     if (n == 0) return MLM_OK;
     HIPCHK(h, hipSetDevice(h->device));
     const MlmPathField F{parent, {dims[0], dims[1], dims[2]}, mlm_path_seed_code(kind)};
     const double d = (double)(float)h->P.d_sub;
     // channels: the goals, then the four outputs; bytes per goal; way3 is read too (rows beyond W keep their content)
-    void *ch[5] = {(void *)goals3, status, way3, length, table};
-    const size_t elem[5] = {3 * sizeof(int32_t), 1, (size_t)cap * 3 * sizeof(int32_t), sizeof(double), MLM_PATH_ROW * sizeof(int64_t)};
-    bool on_dev[5];
-    for (int c = 0; c < 5; ++c) on_dev[c] = ch[c] && win_in_place(ch[c]);
+    ReadoutChannels<5> chs(h->d_ray_stage, h->ray_stage_bytes,
+                           {{goals3, 3 * sizeof(int32_t)}, {status, 1}, {way3, (size_t)cap * 3 * sizeof(int32_t)}, {length, sizeof(double)},
+                            {table, MLM_PATH_ROW * sizeof(int64_t)}},
+                           true);
 
-    if (!win_in_place(parent)) {
+    if (!readout_in_place(parent)) {
+        void *const *ch = chs.ptr;
+        const size_t *elem = chs.elem;
+        bool on_dev[5];
+        for (int c = 0; c < 5; ++c) on_dev[c] = ch[c] && !chs.staged[c];
         // the field is in host memory: the shared rule on the host, no launch and no copy of the field; goals and outputs in device
         // memory are copied across
         std::vector<std::vector<char>> tmp(5);
@@ -2418,33 +1913,24 @@ int mlm_query_paths(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], c
     const size_t per_goal = 3 * sizeof(int32_t) * ((size_t)max_moves + 1);
     size_t stage_per_goal = 0;
     for (int c = 0; c < 5; ++c)
-        if (ch[c] && !on_dev[c]) stage_per_goal += elem[c];
+        if (chs.staged[c]) stage_per_goal += chs.elem[c];
     size_t chunk = std::min<size_t>({(size_t)n, (size_t)kPathChunk, std::max<size_t>(1, kPathScratchBytes / per_goal)});
     if (stage_per_goal) chunk = std::min(chunk, std::max<size_t>(1, kPathStageBytes / stage_per_goal));
-    size_t off[5], stage_bytes = 0;
-    for (int c = 0; c < 5; ++c) {
-        off[c] = stage_bytes;
-        if (ch[c] && !on_dev[c]) stage_bytes += (chunk * elem[c] + 255) & ~(size_t)255;
-    }
-    int rc;
-    if ((rc = win_reserve(h, h->d_path, h->path_bytes, chunk * per_goal, "mlm_query_paths"))) return rc;
-    if (stage_bytes && (rc = win_reserve(h, h->d_ray_stage, h->ray_stage_bytes, stage_bytes, "mlm_query_paths"))) return rc;
+    if ((rc = readout_reserve(h, h->d_path, h->path_bytes, chunk * per_goal, "mlm_query_paths"))) return rc;
+    if ((rc = chs.reserve(h, "mlm_query_paths", chunk))) return rc;
     for (size_t i0 = 0; i0 < (size_t)n; i0 += chunk) {
         const size_t m = std::min(chunk, (size_t)n - i0);
         void *at[5];
-        for (int c = 0; c < 5; ++c)
-            at[c] = !ch[c] ? nullptr : on_dev[c] ? (void *)((char *)ch[c] + i0 * elem[c]) : (void *)((char *)h->d_ray_stage + off[c]);
+        for (int c = 0; c < 5; ++c) at[c] = chs.at(c, i0);
         for (int c : {0, 2}) // goals in; way3 in, for the rows the kernel leaves as they were
-            if (ch[c] && !on_dev[c])
-                HIPCHK(h, hipMemcpyAsync(at[c], (const char *)ch[c] + i0 * elem[c], m * elem[c], hipMemcpyHostToDevice, h->stream));
+            if ((rc = chs.copy_in(h, c, c + 1, i0, m))) return rc;
         MlmPaths Q{F, {lo[0], lo[1], lo[2]}, (const int32_t *)at[0], (int)m, lookahead, max_moves, cap, d, (int32_t *)h->d_path,
                    (int8_t *)at[1], (int32_t *)at[2], (double *)at[3], (int64_t *)at[4]};
         // one wave per goal and scratch slot, four to a workgroup (m <= kPathChunk: at most 16 384 workgroups)
-        const dim3 grid((unsigned int)((m + MLM_BLOCK / 64 - 1) / (MLM_BLOCK / 64)));
+        const dim3 grid(wave_grid(m));
         hipLaunchKernelGGL(k_paths, grid, dim3(MLM_BLOCK), 0, h->stream, Q);
         HIPCHK(h, hipGetLastError());
-        for (int c = 1; c < 5; ++c)
-            if (ch[c] && !on_dev[c]) HIPCHK(h, hipMemcpyAsync((char *)ch[c] + i0 * elem[c], at[c], m * elem[c], hipMemcpyDeviceToHost, h->stream));
+        if ((rc = chs.copy_out(h, 1, 5, i0, m))) return rc;
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MLM_OK;
@@ -2453,7 +1939,6 @@ int mlm_query_paths(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], c
 namespace {
 constexpr int kViewChunkViews = 1 << 16;    // views per pass: bounds the job lists and the staged rows (64 bytes per view)
 constexpr unsigned int kViewGrid = 1 << 16; // most workgroups of a launch (grid-stride over the jobs)
-inline size_t view_align(size_t b) { return (b + 255) & ~(size_t)255; }
 } // namespace
 
 int mlm_query_views(mlm_handle *h, const double *p0, const double *p1, const int32_t *view_begin, int n_views, int flags, const int32_t lo[3],
@@ -2468,22 +1953,14 @@ int mlm_query_views(mlm_handle *h, const double *p0, const double *p1, const int
         return MLM_ERR_INVALID;
     }
     MlmViewWindow B{};
-    long long nvox = 0;
+    long long D[3], nvox = 0;
+    int rc;
     if (boxed) {
         B.on = 1;
-        nvox = 1;
+        if ((rc = box_check(h, "mlm_query_views", lo, dims, D, nvox))) return rc;
         for (int a = 0; a < 3; ++a) {
-            if (dims[a] < 1 || (long long)lo[a] + dims[a] > 0x7FFFFFFFll) {
-                h->err = "mlm_query_views: dims must be >= 1 and lo + dims must fit an int32";
-                return MLM_ERR_INVALID;
-            }
             B.lo[a] = lo[a];
             B.d[a] = dims[a];
-            nvox *= dims[a];
-            if (nvox > 0x7FFFFFFFll) {
-                h->err = "mlm_query_views: more than 2^31 - 1 voxels";
-                return MLM_ERR_INVALID;
-            }
         }
     }
     if (n_views == 0) return MLM_OK;
@@ -2491,7 +1968,7 @@ int mlm_query_views(mlm_handle *h, const double *p0, const double *p1, const int
     // view_begin: validated on the host (copied back when it is device memory, behind the caller's work on the stream)
     std::vector<int32_t> vb_copy;
     const int32_t *vb = view_begin;
-    if (win_in_place(view_begin)) {
+    if (readout_in_place(view_begin)) {
         vb_copy.resize((size_t)n_views + 1);
         HIPCHK(h, hipMemcpyAsync(vb_copy.data(), view_begin, vb_copy.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2503,17 +1980,16 @@ int mlm_query_views(mlm_handle *h, const double *p0, const double *p1, const int
         h->err = "mlm_query_views: view_begin must start at >= 0 and must not decrease; rays need p0 and p1";
         return MLM_ERR_INVALID;
     }
-    int rc = drain(h);
-    if (rc) return rc;
+    if ((rc = drain(h))) return rc;
 
     long long lds_bits = kViewLdsBits, kv;
     if (knob("view_lds_bits", kv)) lds_bits = kv;
-    const bool p_staged[2] = {p0 && !win_in_place(p0), p1 && !win_in_place(p1)};
-    const bool ex_staged = exclude && !win_in_place(exclude), mark_staged = mark && !win_in_place(mark), table_staged = table && !win_in_place(table);
+    const bool p_staged[2] = {p0 && !readout_in_place(p0), p1 && !readout_in_place(p1)};
+    const bool ex_staged = exclude && !readout_in_place(exclude), mark_staged = mark && !readout_in_place(mark), table_staged = table && !readout_in_place(table);
     // a host exclude / mark: the whole box once (mark with its contents: bytes no view touches stay as they were)
-    const size_t box_bytes = view_align((size_t)nvox);
+    const size_t box_bytes = mlm_align256((size_t)nvox);
     if ((ex_staged || mark_staged) &&
-        (rc = win_reserve(h, h->d_win_stage, h->win_stage_bytes, box_bytes * ((ex_staged ? 1 : 0) + (mark_staged ? 1 : 0)), "mlm_query_views")))
+        (rc = readout_reserve(h, h->d_win_stage, h->win_stage_bytes, box_bytes * ((ex_staged ? 1 : 0) + (mark_staged ? 1 : 0)), "mlm_query_views")))
         return rc;
     const uint8_t *d_exclude = exclude;
     uint8_t *d_mark = mark;
@@ -2538,9 +2014,9 @@ int mlm_query_views(mlm_handle *h, const double *p0, const double *p1, const int
         begin.resize((size_t)nv + 1);
         for (int k = 0; k <= nv; ++k) begin[(size_t)k] = (long long)vb[k0 + k] - r0;
         const double *ray[2] = {p0, p1};
-        const size_t ray_bytes = view_align((size_t)nr * 3 * sizeof(double));
+        const size_t ray_bytes = mlm_align256((size_t)nr * 3 * sizeof(double));
         if (nr && (p_staged[0] || p_staged[1]) &&
-            (rc = win_reserve(h, h->d_ray_stage, h->ray_stage_bytes, ray_bytes * ((p_staged[0] ? 1 : 0) + (p_staged[1] ? 1 : 0)), "mlm_query_views")))
+            (rc = readout_reserve(h, h->d_ray_stage, h->ray_stage_bytes, ray_bytes * ((p_staged[0] ? 1 : 0) + (p_staged[1] ? 1 : 0)), "mlm_query_views")))
             return rc;
         for (int c = 0; c < 2; ++c) {
             if (!nr) continue;
@@ -2557,8 +2033,8 @@ int mlm_query_views(mlm_handle *h, const double *p0, const double *p1, const int
         for (int k = 0; k < nv; ++k)
             for (long long i = begin[(size_t)k]; i < begin[(size_t)k + 1]; i += kViewBoxRays)
                 jobs.push_back(MlmViewJob{k, (int)i, (int)std::min(i + kViewBoxRays, begin[(size_t)k + 1]), 0, 1, 0, 0});
-        const size_t raw_bytes = view_align((size_t)nv * sizeof(MlmViewBox));
-        if ((rc = win_reserve(h, h->d_views, h->views_bytes, raw_bytes + view_align(jobs.size() * sizeof(MlmViewJob)), "mlm_query_views"))) return rc;
+        const size_t raw_bytes = mlm_align256((size_t)nv * sizeof(MlmViewBox));
+        if ((rc = readout_reserve(h, h->d_views, h->views_bytes, raw_bytes + mlm_align256(jobs.size() * sizeof(MlmViewJob)), "mlm_query_views"))) return rc;
         MlmViewBox *d_raw = (MlmViewBox *)h->d_views;
         MlmViewJob *d_jobs = (MlmViewJob *)((char *)h->d_views + raw_bytes);
         hipLaunchKernelGGL(k_views_box_init, dim3((unsigned int)((nv + 255) / 256)), dim3(256), 0, h->stream, d_raw, nv);
@@ -2581,9 +2057,9 @@ int mlm_query_views(mlm_handle *h, const double *p0, const double *p1, const int
         }
         first[kViewGlobal] = jobs.size();
         jobs.insert(jobs.end(), plan.global.begin(), plan.global.end());
-        const size_t jobs_bytes = view_align(jobs.size() * sizeof(MlmViewJob)), ref_bytes = view_align(plan.refused.size() * sizeof(int)),
-                     rows_bytes = table_staged ? view_align((size_t)nv * kViewRow * sizeof(int64_t)) : 0;
-        if ((rc = win_reserve(h, h->d_views, h->views_bytes, raw_bytes + jobs_bytes + ref_bytes + rows_bytes + (size_t)plan.scratch_words * 4, "mlm_query_views")))
+        const size_t jobs_bytes = mlm_align256(jobs.size() * sizeof(MlmViewJob)), ref_bytes = mlm_align256(plan.refused.size() * sizeof(int)),
+                     rows_bytes = table_staged ? mlm_align256((size_t)nv * kViewRow * sizeof(int64_t)) : 0;
+        if ((rc = readout_reserve(h, h->d_views, h->views_bytes, raw_bytes + jobs_bytes + ref_bytes + rows_bytes + (size_t)plan.scratch_words * 4, "mlm_query_views")))
             return rc;
         char *base = (char *)h->d_views;
         d_raw = (MlmViewBox *)base;
