@@ -42,6 +42,8 @@
 // for), the 8 global copies of the miss mask and their scan, and the scattered insertion-time stores (0.9 M per VGA frame).
 #pragma once
 #include "mlm_kernels.h"
+#include "mlm_sector_refs.h"
+#include "mlm_sector_ray.h"
 
 // Wave votes on a bool.  HIP's __ballot / __any / __all take an int: the predicate is materialised as 0 / 1 in a register and compared
 // with zero again (v_cndmask + v_cmp per vote); the builtin takes the compare's lane mask as it stands.
@@ -66,7 +68,8 @@ struct MlmSecCell {
     uint32_t key;   // low 16 bits: z * nRho + rho (nZ * nRho < 65 536), MLM_NIL = empty; high 16 bits, set once the column's lists are
                     // built (cells that need their order): where the cell's references start, in units of MLM_SEC_REF_ALIGN references
                     // from the column's first
-    uint32_t tmin;  // first-touch time (min over contributions)
+    uint32_t tmin;  // first-touch time (min over contributions); a cell that needs its order: once the hit list has taken the time, the cell's
+                    // origin for the reference pass (mlm_sec_origin, mlm_sector_refs.h)
     uint32_t kg;    // kinds (bits 0..20) | (record, kind) references of the cell << 21: counted up while the contributions are booked,
                     // counted down while the references are written (the count hands every writer its own stretch of the cell's segment)
     uint32_t cnt;   // contributions
@@ -112,20 +115,7 @@ __device__ __forceinline__ uint32_t mlm_mask_rows(unsigned long long m) {
     return (uint32_t)__popcll(m & 0x0101010101010101ull);
 }
 
-// A reference of a multi-kind cell = one non-empty row of the 8x8 lane mask of one contribution group, 4 bytes:
-//   bits 0-7 the row's byte of the mask, 8-12 the kind, 13-31 where the row's first lane lies relative to the cell's FIRST pixel
-//   (its earliest contribution, MlmSecCell::tmin: no contribution lies in a row above it):
-//     dense images   (rows below the first pixel's) << 8 | 128 + (tile column - the first pixel's tile column)   11 + 8 bits
-//     lists          (64-item rows below the first item's) << 3 | mask row      16 + 3 bits (2^22 items)
-#define MLM_REF_DY_DENSE 2047u
-#define MLM_REF_DY_LIST 65535u
-// (xrel: the row's tile column relative to the tile column of the cell's first pixel, + MLM_REF_XREL0: an image may be any width, a cell's
-// contributions lie within 1 016 pixels of its first one's column — else the frame gives the sector path up)
-#define MLM_REF_XREL0 128u
-__device__ __forceinline__ uint32_t mlm_ref_pack(uint32_t bits, uint32_t kind, bool dense, uint32_t dy0, uint32_t row, uint32_t xrel) {
-    const uint32_t pos = dense ? ((dy0 + row) << 8) | xrel : (dy0 << 3) | row;
-    return bits | (kind << 8) | (pos << 13);
-}
+// (a reference of a multi-kind cell, mlm_ref_pack; a cell's origin and a record's row flags as the reference pass keeps them: mlm_sector_refs.h)
 // A hit record's tile origin (MlmSecRec, second word).  Dense images: (row >> 3) << 13 | column >> 3 of the wave's 8x8 pixel tile
 // (both multiples of eight: images up to 65 528 pixels wide); lists: the wave's run of 64 items << 11.
 #define MLM_REC_XT_BITS 13
@@ -760,7 +750,7 @@ __device__ __forceinline__ void mlm_sector_column(const MlmDev &P, const MlmFram
     // keeps the record it handled first: a column with at most NT records (the usual case) is not read twice.
     uint32_t keep_cell = MLM_NIL, keep_yx = 0, keep_total = 0xFFFFFFFFu;
     unsigned long long keep_mask = 0;
-    // ... and the record it handled second as it came (its targets are looked up again): a column with at most 2 NT records — nearly
+    // ... and the record it handled second as it came: a column with at most 2 NT records — nearly
     // every column of a camera frame — is not read from memory twice (the second read, with its descriptors staged again, was a
     // fifth of the kernel's wave-cycles: tools/sector_phase.py)
     uint32_t keep2_cell = MLM_NIL, keep2_yx = 0;
@@ -768,16 +758,18 @@ __device__ __forceinline__ void mlm_sector_column(const MlmDev &P, const MlmFram
     // ... and the table entries of its targets, so that the second pass neither recomputes them nor probes the table:
     // (entry | kind << 12) in 16 bits each, four in keep_lo, the fifth in keep_hi's low half, the count in its high half
     // (MLM_SEC_KEEP_MORE: more than five targets or a kind above 15 — the record is recomputed)
-    unsigned long long keep_lo = 0;
-    uint32_t keep_hi = 0;
-    // the non-empty rows of a group's lane mask, once per record (three bits each): the same for every target cell
-    auto rows_of = [&](unsigned long long mask, uint32_t &rows3, uint32_t &n_rows) {
-        rows3 = 0, n_rows = 0;
-#pragma unroll
-        for (uint32_t row = 0; row < 8u; ++row)
-            if ((uint32_t)(mask >> (8u * row)) & 0xFFu) rows3 |= row << (3u * n_rows++);
-    };
-    auto emit_refs = [&](int e, uint32_t sub, uint32_t yx, unsigned long long mask, uint32_t rows3, uint32_t n_rows) {
+    // (both kept records' in a 256-thread workgroup, whose columns usually have a second record per thread: its targets went through an
+    // FP64 slope and the table's probe loop again before.  Not with 512 threads: a second record is rare there — a column of more than
+    // 512 — and the three registers would not fit that form's 80 without scratch)
+    constexpr bool KEEP2 = NT <= 256;
+    unsigned long long keep_lo = 0, keep2_lo = 0;
+    uint32_t keep_hi = 0, keep2_hi = 0;
+    // A cell's origin — the row and tile column of its first pixel, what its references are relative to — is worked out once per
+    // cell (the hit list's loop below puts it in place of MlmSecCell::tmin), not once per (record, cell) pair; a record's non-empty
+    // mask rows are kept as flags and taken with a find-first-bit (mlm_sector_refs.h).
+    const bool dense = tile_w > 0;
+    const uint32_t osh = mlm_sec_origin_shift(tile_w), ref_rsh = mlm_ref_row_shift(dense);
+    auto emit_refs = [&](int e, uint32_t sub, uint32_t yx, unsigned long long mask, uint32_t flags, uint32_t n_rows) {
         if (!mlm_sec_needs_order(s_tab[e])) return;
         // one 4-byte reference per non-empty ROW of the group's lane mask (mlm_ref_pack): row byte, kind, and the row's
         // position relative to the cell's first pixel — what k_rank needs, with no empty rows in its rounds (a group
@@ -786,47 +778,49 @@ __device__ __forceinline__ void mlm_sector_column(const MlmDev &P, const MlmFram
         // stretch of the cell's segment; the order of the references inside a segment does not matter)
         const uint32_t left = atomicSub(&s_tab[e].kg, n_rows << MLM_SEC_KIND_BITS) >> MLM_SEC_KIND_BITS;
         const uint32_t at = s_base[2] + (s_tab[e].key >> 16) * MLM_SEC_REF_ALIGN + (left - n_rows);
-        const uint32_t pix0 = s_tab[e].tmin / MLM_TIME_SLOTS;
-        const uint32_t y0c = tile_w > 0 ? (uint32_t)(((unsigned long long)pix0 * row_m) >> row_s) : pix0 >> 6;
-        const uint32_t dy0 = (tile_w > 0 ? (yx >> MLM_REC_XT_BITS) << 3 : yx >> 11) - y0c; // (>= 0: the cell's first pixel is its contributions' smallest)
+        const uint32_t origin = s_tab[e].tmin; // (mlm_sec_origin: no longer the first-touch time)
+        const uint32_t dy0 = (dense ? (yx >> MLM_REC_XT_BITS) << 3 : yx >> 11) - mlm_sec_origin_row(origin, dense, osh); // (>= 0: the cell's first pixel is its contributions' smallest)
         // (dense images: the tile's column relative to the first pixel's tile column)
-        const uint32_t xrel = tile_w > 0 ? (yx & MLM_REC_XT_MASK) - ((pix0 - y0c * (uint32_t)tile_w) >> 3) + MLM_REF_XREL0 : 0u;
-        if (dy0 + 7u > (tile_w > 0 ? MLM_REF_DY_DENSE : MLM_REF_DY_LIST) || xrel > 255u) {
+        const uint32_t xrel = dense ? (yx & MLM_REC_XT_MASK) - mlm_sec_origin_xt(origin, osh) + MLM_REF_XREL0 : 0u;
+        if (dy0 + 7u > (dense ? MLM_REF_DY_DENSE : MLM_REF_DY_LIST) || xrel > 255u) {
             s_fail = 1; // (a cell whose pixels lie more than 2 047 rows below or 1 016 columns beside its first one: not expressible — the frame falls back)
         } else if (at + n_rows <= P.refs_cap) {
             MLM_GLOBAL uint32_t *dst = mlm_gp(P.refs) + at;
-            for (uint32_t k = 0; k < n_rows; ++k) {
-                const uint32_t row = (rows3 >> (3u * k)) & 7u;
-                dst[k] = mlm_ref_pack((uint32_t)(mask >> (8u * row)) & 0xFFu, sub, tile_w > 0, dy0, row, xrel);
+            const uint32_t base = mlm_ref_pack(0u, sub, dense, dy0, 0u, xrel);
+            for (uint32_t k = 0; flags; ++k, flags &= flags - 1u) {
+                uint32_t row, bits;
+                mlm_sec_row_take(flags, mask, row, bits);
+                dst[k] = mlm_ref_repack(base, ref_rsh, row, bits);
             }
         }
     };
     auto refs_of = [&](uint32_t cell, uint32_t yx, unsigned long long mask) {
         const int z = (int)(cell >> 16), rho = (int)(cell & 0xFFFFu);
-        uint32_t rows3, n_rows;
-        rows_of(mask, rows3, n_rows);
+        const uint32_t flags = mlm_sec_row_flags(mask), n_rows = (uint32_t)__popc(flags);
         mlm_sec_targets(P, rho, phi, z, s_sigma[rho], [&](uint32_t key, int sub, int) {
             const int e = mlm_sec_entry<false>(s_tab, tab_mask, key);
-            if (e >= 0) emit_refs(e, (uint32_t)sub, yx, mask, rows3, n_rows);
+            if (e >= 0) emit_refs(e, (uint32_t)sub, yx, mask, flags, n_rows);
         });
     };
-    auto refs_of_kept = [&]() {
-        const uint32_t nt = keep_hi >> 16;
+    auto refs_of_kept = [&](uint32_t k_cell, uint32_t k_yx, unsigned long long k_mask, unsigned long long k_lo, uint32_t k_hi) {
+        const uint32_t nt = k_hi >> 16;
         if (nt == MLM_SEC_KEEP_MORE) {
-            refs_of(keep_cell, keep_yx, keep_mask);
+            refs_of(k_cell, k_yx, k_mask);
             return;
         }
-        uint32_t rows3, n_rows;
-        rows_of(keep_mask, rows3, n_rows);
+        const uint32_t flags = mlm_sec_row_flags(k_mask), n_rows = (uint32_t)__popc(flags);
         for (uint32_t k = 0; k < nt; ++k) {
-            const uint32_t t = k < 4u ? (uint32_t)(keep_lo >> (16u * k)) & 0xFFFFu : keep_hi & 0xFFFFu;
-            emit_refs((int)(t & 0xFFFu), t >> 12, keep_yx, keep_mask, rows3, n_rows);
+            const uint32_t t = k < 4u ? (uint32_t)(k_lo >> (16u * k)) & 0xFFFFu : k_hi & 0xFFFFu;
+            emit_refs((int)(t & 0xFFFu), t >> 12, k_yx, k_mask, flags, n_rows);
         }
     };
     auto for_records = [&](int pass) {
         if (pass == 1 && nch <= CH && keep_total <= 2u * NT) {
-            if (keep_cell != MLM_NIL) refs_of_kept();
-            if (keep2_cell != MLM_NIL) refs_of(keep2_cell, keep2_yx, keep2_mask);
+            if (keep_cell != MLM_NIL) refs_of_kept(keep_cell, keep_yx, keep_mask, keep_lo, keep_hi);
+            if (keep2_cell != MLM_NIL) {
+                if constexpr (KEEP2) refs_of_kept(keep2_cell, keep2_yx, keep2_mask, keep2_lo, keep2_hi);
+                else refs_of(keep2_cell, keep2_yx, keep2_mask);
+            }
             return;
         }
         for (uint32_t c0 = 0; c0 < nch; c0 += CH) {
@@ -881,7 +875,8 @@ __device__ __forceinline__ void mlm_sector_column(const MlmDev &P, const MlmFram
                         keep_yx = a.y;
                         keep_mask = mask;
                     }
-                    if (c0 == 0 && r == threadIdx.x + (uint32_t)NT) {
+                    const bool kept2 = c0 == 0 && r == threadIdx.x + (uint32_t)NT;
+                    if (kept2) {
                         keep2_cell = cell;
                         keep2_yx = a.y;
                         keep2_mask = mask;
@@ -898,10 +893,15 @@ __device__ __forceinline__ void mlm_sector_column(const MlmDev &P, const MlmFram
                             s_tab_full = 1;
                             return;
                         }
-                        if (kept) {
+                        if (kept || (KEEP2 && kept2)) { // (each into its own registers: no copy of the three lives across the loop)
                             const uint32_t t = (uint32_t)e | (uint32_t)sub << 12;
-                            if (nt < 4u) keep_lo |= (unsigned long long)t << (16u * nt);
-                            else keep_hi |= t & 0xFFFFu;
+                            if (kept) {
+                                if (nt < 4u) keep_lo |= (unsigned long long)t << (16u * nt);
+                                else keep_hi |= t & 0xFFFFu;
+                            } else if constexpr (KEEP2) {
+                                if (nt < 4u) keep2_lo |= (unsigned long long)t << (16u * nt);
+                                else keep2_hi |= t & 0xFFFFu;
+                            }
                             if (nt >= 5u || sub > 15) nt = MLM_SEC_KEEP_MORE - 1u;
                             ++nt;
                         }
@@ -920,6 +920,7 @@ __device__ __forceinline__ void mlm_sector_column(const MlmDev &P, const MlmFram
                         if (EX && sub == 0) atomicMin(&s_p0[e], i_first);
                     });
                     if (kept) keep_hi |= nt << 16;
+                    if (KEEP2 && kept2) keep2_hi |= nt << 16;
                 }
             }
             if (pass == 0 && c0 == 0) keep_total = total;
@@ -1065,66 +1066,28 @@ __device__ __forceinline__ void mlm_sector_column(const MlmDev &P, const MlmFram
             key_rz(s_tab[s_rays[it >> ray_sh]].key & MLM_SEC_KEY_MASK, rho, z);
             if (EX) t0 = s_ray_p0[it >> ray_sh] * 256u;
         }
-        const int seg = (rho + (int)ray_lanes - 2) >> ray_sh; // steps k = 1 .. rho-1 in `ray_lanes` segments of `seg`
-        const int k_lo = 1 + (int)(it & (ray_lanes - 1u)) * seg, k_hi = min(rho, k_lo + seg); // [k_lo, k_hi)
-        const int dz = z - P.zc, two_rho = 2 * rho;
-        // per step: N -= 2 dz = sq * 2 rho + fr with 0 <= fr < 2 rho
-        int sq = 0, fr = 0, q = 0, rem = 0;
-        if (k_lo < k_hi) {
-            auto floor_div = [&](int a, int &quo, int &r) { // a = quo * two_rho + r, 0 <= r < two_rho (|a| < 2^24)
-                quo = (int)floorf((float)a / (float)two_rho);
-                r = a - quo * two_rho;
-                if (r < 0) {
-                    r += two_rho;
-                    --quo;
-                } else if (r >= two_rho) {
-                    r -= two_rho;
-                    ++quo;
-                }
-            };
-            floor_div(2 * dz, sq, fr);
-            floor_div(rho * (2 * z + 1) - (k_lo - 1) * 2 * dz, q, rem); // N at k_lo - 1
-        }
-        int cur_w = -1;
-        uint32_t cur_bits = 0;
-        unsigned long long ties = 0;
-        for (int k = k_lo; k < k_hi; ++k) {
-            const int r = rho - k;
-            rem -= fr;
-            q -= sq;
-            if (rem < 0) {
-                rem += two_rho;
-                --q;
-            }
-            if (rem == 0) { // exact tie: the reference's FP64 sequence decides (below)
-                ties |= 1ull << ((k - k_lo) & 63);
-                if (k - k_lo < 64) continue;
-            }
-            int zr = q;
-            if (rem == 0) zr = mlm_cvt_int(round(z - (k * (dz / (rho * 1.0))))); // (segments longer than 64 steps: nRho > 256)
-            if (EX) {
-                if (0 <= zr && zr < P.nZ) atomicMin(&s_miss[zr * P.nRho + r], t0 + (uint32_t)(k - 1));
-                continue;
-            }
-            const int w = (0 <= zr && zr < P.nZ) ? zr * P.RW + (r >> 5) : -1;
-            if (w != cur_w) {
-                if (cur_w >= 0) atomicOr(&s_miss[cur_w], cur_bits);
-                cur_w = w;
-                cur_bits = 0;
-            }
-            cur_bits |= 1u << (r & 31);
-        }
-        if (!EX && cur_w >= 0) atomicOr(&s_miss[cur_w], cur_bits);
-        if (mlm_any(ties != 0)) {
-            const double slope = (rho > 0) ? dz / (rho * 1.0) : 0.0;
-            while (ties) {
-                const int k = k_lo + __ffsll((long long)ties) - 1;
-                ties &= ties - 1;
-                const int r = rho - k;
-                const int zr = mlm_cvt_int(round(z - (k * slope)));
-                if (0 <= zr && zr < P.nZ) {
-                    if (EX) atomicMin(&s_miss[zr * P.nRho + r], t0 + (uint32_t)(k - 1));
-                    else atomicOr(&s_miss[zr * P.RW + (r >> 5)], 1u << (r & 31));
+        // (the lane's share of the ray's steps and its walk: mlm_sector_ray.h; a share longer than the walk's 64 steps — rho above 256 with
+        // four lanes — goes in pieces, each with its own ties)
+        int s_lo, s_hi; // [s_lo, s_hi)
+        mlm_sray_share(rho, it & (ray_lanes - 1u), ray_sh, s_lo, s_hi);
+        const int dz = z - P.zc;
+        for (int k_lo = s_lo; k_lo < s_hi; k_lo += MLM_SRAY_MAX_STEPS) {
+            const int k_hi = min(s_hi, k_lo + MLM_SRAY_MAX_STEPS);
+            unsigned long long ties = mlm_sray_walk<EX>(rho, z, P.zc, P.nZ, k_lo, k_hi, [&](int row, int a, uint32_t b) {
+                if (EX) atomicMin(&s_miss[row * P.nRho + a], t0 + b - 1u); // (cell, step)
+                else atomicOr(&s_miss[row * P.RW + a], b);                 // (word, bits)
+            });
+            if (mlm_any(ties != 0)) {
+                const double slope = (rho > 0) ? dz / (rho * 1.0) : 0.0;
+                while (ties) {
+                    const int k = k_lo + __ffsll((long long)ties) - 1;
+                    ties &= ties - 1;
+                    const int r = rho - k;
+                    const int zr = mlm_cvt_int(round(z - (k * slope)));
+                    if (0 <= zr && zr < P.nZ) {
+                        if (EX) atomicMin(&s_miss[zr * P.nRho + r], t0 + (uint32_t)(k - 1));
+                        else atomicOr(&s_miss[zr * P.RW + (r >> 5)], 1u << (r & 31));
+                    }
                 }
             }
         }
@@ -1142,7 +1105,9 @@ __device__ __forceinline__ void mlm_sector_column(const MlmDev &P, const MlmFram
         mlm_gp(P.hl_cell)[pos] = (uint32_t)(z * P.nRhoPhi + phi * P.nRho + rho);
         mlm_gp(P.hl_t)[pos] = c.tmin;
         mlm_gp(P.hl_vt)[pos] = c.tmin; // (the replay kernels re-rank it: k_assign_rank)
-        if (!mlm_sec_needs_order(c)) {
+        // (the time has left for the hit list, and for the cell's descriptor above: the reference pass finds the cell's origin in its place)
+        if (mlm_sec_needs_order(c)) s_tab[s_occ[i]].tmin = mlm_sec_origin(c.tmin, tile_w, osh, row_m, row_s);
+        else {
             // one kind: cnt applications of one value (update_odds_hashmap, map_awareness.h:147-154), 1.0f is absorbing;
             // several kinds with enough strong contributions: 1.0f in any order; two contributions: their product (mlm_sec_needs_order).
             // n applications of one value and their logit are constants of the handle: from MlmDev::hit_p / hit_inc (one load instead
@@ -1198,7 +1163,10 @@ __device__ __forceinline__ void mlm_sector_column(const MlmDev &P, const MlmFram
     }
     MLM_PHASE(4);
     // ---- references of the multi-kind cells (their fill cursors were set above)
-    if (n_multi) for_records(1);
+    if (n_multi) { // (uniform)
+        __syncthreads(); // (the cells' origins are in place)
+        for_records(1);
+    }
     MLM_PHASE(5);
     if (EX) {
         // frontier mode: the unique miss list with insertion times and world voxels (what k_ex_collect_misses leaves);
@@ -1236,10 +1204,11 @@ __device__ __forceinline__ void mlm_sector_column(const MlmDev &P, const MlmFram
         //      table's space is idle by now), one coalesced copy into the column's own stretch of the frame's miss list; then the
         //      descriptors of its tile runs (below).
         // (a byte of a mask word per thread: the bits of a word are a serial chain of LDS atomics)
+        // (the word's row z = w / RW as the high word of (2 w) * rw_m, MlmDev::rw_m: exact, no division sequence per lane)
         for (uint32_t it = threadIdx.x; it < 4u * NMISS; it += NT) {
             const uint32_t w = it >> 2, part = (it & 3u) * 8u;
             uint32_t bits = (s_miss[w] >> part) & 0xFFu;
-            const uint32_t z = w / (uint32_t)P.RW, rho0 = (w - z * (uint32_t)P.RW) * 32u + part;
+            const uint32_t z = __umulhi(w << 1, P.rw_m), rho0 = (w - z * (uint32_t)P.RW) * 32u + part;
             while (bits) {
                 atomicAdd(&s_rho_miss[rho0 + (uint32_t)__ffs((int)bits) - 1u], 1u);
                 bits &= bits - 1;
@@ -1273,7 +1242,7 @@ __device__ __forceinline__ void mlm_sector_column(const MlmDev &P, const MlmFram
             for (uint32_t it = threadIdx.x; it < 4u * NMISS; it += NT) {
                 const uint32_t w = it >> 2, part = (it & 3u) * 8u;
                 uint32_t bits = (s_miss[w] >> part) & 0xFFu;
-                const uint32_t z = w / (uint32_t)P.RW, rho0 = (w - z * (uint32_t)P.RW) * 32u + part;
+                const uint32_t z = __umulhi(w << 1, P.rw_m), rho0 = (w - z * (uint32_t)P.RW) * 32u + part;
                 const uint32_t zz = (uint32_t)s_vz[z].x;
                 while (bits) {
                     const uint32_t rho = rho0 + (uint32_t)__ffs((int)bits) - 1u;

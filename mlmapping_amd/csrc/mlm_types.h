@@ -132,6 +132,7 @@ struct MlmDev {
     int nRho, nPhi, nZ, zc;    // zc = map_center_z_idx
     int nRhoPhi, nCells;
     int RW;                    // 32-bit words per (phi,z) row of the miss bit mask = ceil(nRho/32)
+    uint32_t rw_m;             // k_sector: w / RW is the high word of (2 w) * rw_m (mlm_host.h: strip_magic; w < nZ * RW < 2^16, RW <= 2^11)
     int nMissWords;
     int visibility;
     int logit_exact;           // 1: the host's log10f equals mlm_glibc_log10f (mlm_host.h) -> hit increments with the reference's float bits

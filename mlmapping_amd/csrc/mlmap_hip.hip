@@ -221,6 +221,7 @@ int mlm_create(const mlm_config *cfg, const mlm_limits *lim_in, int device, mlm_
     }
     P.nCells = (int)ncells;
     P.RW = (P.nRho + 31) / 32;
+    P.rw_m = mlm_host::strip_magic((unsigned int)P.RW); // (0 beyond 2^11 words: such a cylinder never takes the sector path, use_sectors below)
     P.nMissWords = P.nZ * P.nPhi * P.RW;
     P.visibility = cfg->use_raycasting != 0;
     // local constants, map_local.cpp:56-62,126-130 (float casts as mlmap.cpp:77-81)
