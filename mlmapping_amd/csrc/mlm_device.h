@@ -153,8 +153,10 @@ __device__ __forceinline__ double mlm_sqrt_approx(double a) {
     return fma(g, fma(-h, g, 0.5), g);
 }
 // (vx, vy, vz): the point in the sensor frame; v_l1 >= |vx| + |vy| + |vz|
-__device__ __forceinline__ bool mlm_bin_point_fast(const MlmDev &P, const MlmFrame &F, double vx, double vy, double vz, double v_l1, int &rho_idx,
-                                                   int &phi_idx, int &z_idx, bool &can_do_cast, bool &sure) {
+// (P, F: MlmDev / MlmFrame, or the copy of their fields that the caller staged in registers — MlmBinStage, mlm_kernels_sector.h)
+template <class PD, class FD>
+__device__ __forceinline__ bool mlm_bin_point_fast(const PD &P, const FD &F, double vx, double vy, double vz, double v_l1, int &rho_idx, int &phi_idx,
+                                                   int &z_idx, bool &can_do_cast, bool &sure) {
     // p_l = T_ls p_s as a matrix product with fused multiply-adds: nothing here has to round like the reference
     const double x = fma(F.m_ls[0], vx, fma(F.m_ls[1], vy, fma(F.m_ls[2], vz, F.t_ls[0])));
     const double y = fma(F.m_ls[3], vx, fma(F.m_ls[4], vy, fma(F.m_ls[5], vz, F.t_ls[1])));
@@ -178,13 +180,16 @@ __device__ __forceinline__ bool mlm_bin_point_fast(const MlmDev &P, const MlmFra
     // 1 / cell-size factors, plus the quotients' own roundings
     const double M = (4.0 * E * (1.0 + mlm_rcp_approx(rho)) + 2e-11 * (1.0 + rho)) * P.inv_d_max + 2e-12 * (((1.0 + qr) + qp) + fabs(qz));
     // (NaN and infinities fail the comparisons: a point on the axis, x = y = 0, goes to the exact sequence)
-    sure = fabs(qr - rint(qr)) > M && fabs(qp - rint(qp)) > M && fabs(qz - rint(qz)) > M && qr < 1e9 && fabs(qz) < 1e9 && rho > 1e-9 &&
-           ax > 4.0 * E; // (x = +0 exactly is a value of its own in the reference: 3 pi / 2 for y > 0)
+    // (both chains without short-circuit evaluation: every operand is in a register and free of side effects, so they are straight-line
+    // compares joined by scalar ANDs — no branch on the lanes' mask, no load inside one)
+    sure = (int)(fabs(qr - rint(qr)) > M) & (int)(fabs(qp - rint(qp)) > M) & (int)(fabs(qz - rint(qz)) > M) & (int)(qr < 1e9) & (int)(fabs(qz) < 1e9) &
+           (int)(rho > 1e-9) & (int)(ax > 4.0 * E); // (x = +0 exactly is a value of its own in the reference: 3 pi / 2 for y > 0)
     rho_idx = (int)qr;
     phi_idx = (int)qp;
     z_idx = (int)floor(qz);
-    can_do_cast = (rho_idx >= 0 && phi_idx >= 0 && phi_idx < P.nPhi);
-    return can_do_cast && z_idx >= 0 && rho_idx < P.nRho && z_idx < P.nZ;
+    const int n_rho = P.nRho, n_phi = P.nPhi, n_z = P.nZ;
+    can_do_cast = (int)(rho_idx >= 0) & (int)(phi_idx >= 0) & (int)(phi_idx < n_phi);
+    return (int)can_do_cast & (int)(z_idx >= 0) & (int)(rho_idx < n_rho) & (int)(z_idx < n_z);
 }
 
 // VectorHasher (map_awareness.h:31-41): 32-bit wrap-around int arithmetic, arithmetic >>, result sign-extended

@@ -146,7 +146,7 @@ struct MlmStripItem {
     int px, py;      // dense images: the pixel's column and row
     uint32_t by, bx; // dense images: the strip's row and column in the image (the same for the whole workgroup)
 };
-template <int MODE> __device__ __forceinline__ MlmStripItem mlm_strip_item(const MlmFrame &F, unsigned int strip) {
+template <int MODE, class FD> __device__ __forceinline__ MlmStripItem mlm_strip_item(const FD &F, unsigned int strip) { // (FD: MlmFrame or MlmBinStage)
     MlmStripItem t;
     if (MODE == 0) {
         // strip / tiles_x without a division: the high word of (2 strip) * tx_m (mlm_host.h: strip_magic; strip < 2^20, tiles_x <= 2^11)
@@ -167,14 +167,146 @@ template <int MODE> __device__ __forceinline__ MlmStripItem mlm_strip_item(const
     return t;
 }
 
+// k_bin_sectors' parameters, fetched UP FRONT.  P and F are references into the slot tables in device memory, and the compiler may
+// not keep a field loaded across the barriers, atomics and stores of the kernel: left alone, every field is fetched with a scalar load at
+// its point of use and waited for at once (s_waitcnt lgkmcnt(0): a round trip to the scalar cache in the middle of the wave's stream,
+// which drains the wave's LDS operations as well).  No kernel writes MlmDev, and MlmFrame is written only by launches in front of this
+// one (k_frame_prologue), so everything the strip's hot path needs is read through the constant address space (as mlm_uniform_word) in
+// ONE group of wide loads at the kernel's start — the group is waited for together with the image pointer and width that the pixel's
+// address needs anyway — and held in registers: nothing behind the first barrier issues a scalar load, except the wave in 10^5 that takes the
+// reference's own sequence and the paths that give the frame up (they keep their own loads).  The tables stay the single source of
+// truth: values are never passed by kernel argument (a launch serves a batch of frames, the host changes capacities between launches).
+#define MLM_CONST __attribute__((address_space(4)))
+// N consecutive words of a parameter block, fetched HERE: a volatile load is neither sunk to its use, nor repeated, nor merged or split
+// (through the constant address space it is still one s_load of that width)
+template <int N> struct MlmWords {
+    typedef uint32_t type __attribute__((ext_vector_type(N), aligned(4)));
+};
+template <> struct MlmWords<1> {
+    typedef uint32_t type;
+};
+template <int N, class T> __device__ __forceinline__ typename MlmWords<N>::type mlm_param_words(const T *first) {
+    return *(const volatile MLM_CONST typename MlmWords<N>::type *)(unsigned long long)first;
+}
+__device__ __forceinline__ double mlm_f64_of(uint32_t lo, uint32_t hi) { return __hiloint2double((int)hi, (int)lo); }
+template <class T> __device__ __forceinline__ MLM_GLOBAL T *mlm_gp_of(uint32_t lo, uint32_t hi) {
+    return (MLM_GLOBAL T *)((unsigned long long)hi << 32 | lo);
+}
+struct MlmBinStage {
+    const uint16_t *img;                                                               // MlmFrame: where the strip's input is ...
+    const int32_t *pix, *raw;
+    const double *pts;
+    int width, height, row_stride, n;
+    uint32_t tx_m;
+    double m_ls[9], t_ls[3], m_gain, t_l1;                                             // ... and the pose block of mlm_bin_point_fast
+    float cx, cy;                                                                      // MlmDev
+    double inv_factor, inv_fx, inv_fy, z_border_min, inv_dRho, inv_dPhi, inv_dZ, inv_d_max; // MlmDev
+    int nRho, nPhi, nZ, nRhoPhi, visibility;
+    unsigned int chunk_cap;
+    MLM_GLOBAL mlm_u32x4 *bnodes;
+    MLM_GLOBAL unsigned int *blk_stats, *col_cnt;
+    MLM_GLOBAL uint32_t *col_chunks;
+    MLM_GLOBAL MlmCounters *ctr;
+};
+#define MLM_ADJACENT(S, a, b, bytes) static_assert(offsetof(S, b) == offsetof(S, a) + (bytes), "fields fetched as one block")
+template <bool F_CONST> __device__ __forceinline__ MlmBinStage mlm_bin_stage(const MlmDev &P, const MlmFrame &F) {
+    MlmBinStage B;
+    if (F_CONST) { // (k_bin_sectors_hostf keeps the frame's parameters in LDS and reads the pose block there, where it is used)
+        MLM_ADJACENT(MlmFrame, m_ls, m_gain, 72);
+        MLM_ADJACENT(MlmFrame, m_gain, t_l1, 8);
+        MLM_ADJACENT(MlmFrame, img, pix, 8);
+        MLM_ADJACENT(MlmFrame, pix, raw, 8);
+        MLM_ADJACENT(MlmFrame, raw, pts, 8);
+        MLM_ADJACENT(MlmFrame, width, height, 4);
+        MLM_ADJACENT(MlmFrame, height, row_stride, 4);
+        MLM_ADJACENT(MlmFrame, row_stride, n, 4);
+        const auto in = mlm_param_words<8>(&F.img); // img, pix, raw, pts
+        const auto wh = mlm_param_words<4>(&F.width);
+        B.tx_m = mlm_param_words<1>(&F.tx_m);
+        B.img = (const uint16_t *)((unsigned long long)in[1] << 32 | in[0]);
+        B.pix = (const int32_t *)((unsigned long long)in[3] << 32 | in[2]);
+        B.raw = (const int32_t *)((unsigned long long)in[5] << 32 | in[4]);
+        B.pts = (const double *)((unsigned long long)in[7] << 32 | in[6]);
+        B.width = (int)wh[0];
+        B.height = (int)wh[1];
+        B.row_stride = (int)wh[2];
+        B.n = (int)wh[3];
+        const auto t0 = mlm_param_words<4>(&F.t_ls[0]);
+        const auto t1 = mlm_param_words<2>(&F.t_ls[2]);
+        const auto m0 = mlm_param_words<16>(&F.m_ls[0]);
+        const auto m1 = mlm_param_words<4>(&F.m_ls[8]);
+        const auto m2 = mlm_param_words<2>(&F.t_l1);
+        B.t_ls[0] = mlm_f64_of(t0[0], t0[1]);
+        B.t_ls[1] = mlm_f64_of(t0[2], t0[3]);
+        B.t_ls[2] = mlm_f64_of(t1[0], t1[1]);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) B.m_ls[k] = mlm_f64_of(m0[2 * k], m0[2 * k + 1]);
+        B.m_ls[8] = mlm_f64_of(m1[0], m1[1]);
+        B.m_gain = mlm_f64_of(m1[2], m1[3]);
+        B.t_l1 = mlm_f64_of(m2[0], m2[1]);
+    }
+    MLM_ADJACENT(MlmDev, z_border_min, nRho, 8);
+    MLM_ADJACENT(MlmDev, nRho, nPhi, 4);
+    MLM_ADJACENT(MlmDev, nPhi, nZ, 4);
+    MLM_ADJACENT(MlmDev, nZ, nRhoPhi, 8);
+    MLM_ADJACENT(MlmDev, inv_dRho, inv_dPhi, 8);
+    MLM_ADJACENT(MlmDev, inv_dPhi, inv_dZ, 8);
+    MLM_ADJACENT(MlmDev, inv_factor, inv_fx, 8);
+    MLM_ADJACENT(MlmDev, inv_fx, inv_fy, 8);
+    MLM_ADJACENT(MlmDev, inv_fy, inv_d_max, 8);
+    MLM_ADJACENT(MlmDev, col_cnt, col_chunks, 8);
+    MLM_ADJACENT(MlmDev, col_chunks, chunk_cap, 8);
+    MLM_ADJACENT(MlmDev, cx, cy, 4);
+    const auto cxy = mlm_param_words<2>(&P.cx);
+    B.cx = __uint_as_float(cxy[0]);
+    B.cy = __uint_as_float(cxy[1]);
+    const auto g = mlm_param_words<8>(&P.z_border_min); // z_border_min, nRho, nPhi, nZ, zc, nRhoPhi, nCells
+    const auto vis = mlm_param_words<1>(&P.visibility);
+    const auto d0 = mlm_param_words<4>(&P.inv_dRho);
+    const auto d1 = mlm_param_words<2>(&P.inv_dZ);
+    const auto c = mlm_param_words<8>(&P.inv_factor); // inv_factor, inv_fx, inv_fy, inv_d_max
+    const auto bn = mlm_param_words<2>(&P.bnodes);
+    const auto bs = mlm_param_words<2>(&P.blk_stats);
+    const auto cc = mlm_param_words<4>(&P.col_cnt); // col_cnt, col_chunks
+    const auto cap = mlm_param_words<1>(&P.chunk_cap);
+    const auto ct = mlm_param_words<2>(&P.ctr);
+    B.z_border_min = mlm_f64_of(g[0], g[1]);
+    B.nRho = (int)g[2];
+    B.nPhi = (int)g[3];
+    B.nZ = (int)g[4];
+    B.nRhoPhi = (int)g[6];
+    B.visibility = (int)vis;
+    B.inv_dRho = mlm_f64_of(d0[0], d0[1]);
+    B.inv_dPhi = mlm_f64_of(d0[2], d0[3]);
+    B.inv_dZ = mlm_f64_of(d1[0], d1[1]);
+    B.inv_factor = mlm_f64_of(c[0], c[1]);
+    B.inv_fx = mlm_f64_of(c[2], c[3]);
+    B.inv_fy = mlm_f64_of(c[4], c[5]);
+    B.inv_d_max = mlm_f64_of(c[6], c[7]);
+    B.bnodes = mlm_gp_of<mlm_u32x4>(bn[0], bn[1]);
+    B.blk_stats = mlm_gp_of<unsigned int>(bs[0], bs[1]);
+    B.col_cnt = mlm_gp_of<unsigned int>(cc[0], cc[1]);
+    B.col_chunks = mlm_gp_of<uint32_t>(cc[2], cc[3]);
+    B.chunk_cap = cap;
+    B.ctr = mlm_gp_of<MlmCounters>(ct[0], ct[1]);
+    return B;
+}
+
+template <bool F_CONST> __device__ __forceinline__ const auto &mlm_bin_frame(const MlmBinStage &B, const MlmFrame &F) {
+    if constexpr (F_CONST) return B;
+    else return F;
+}
+
 // S strips per workgroup, worked on TOGETHER (every phase runs for all S before the next starts).  The launches use S = 1: two
 // and four strips in flight measured 1-4 % slower in the pipeline (profiles/r4b_*) — the kernel is bound by vector-instruction issue,
 // not by the waits of a strip's chain.  A record never touches LDS: the lane that leads a group of pixels keeps it in registers until
 // its place in the strip's slice is known (a lane leads at most one record) — what is staged per strip is the column table (phi,
 // count, offset: 768 bytes for a dense strip).
-template <int MODE, int S>
+template <int MODE, int S, bool F_CONST = true> // (F_CONST: F is in device memory and no kernel-mate writes it — see mlm_bin_stage)
 __device__ __forceinline__ void mlm_bin_sectors_body(const MlmDev &P, const MlmFrame &F, unsigned int n_strips, bool pre = false, int pre_pix = 0,
                                                      int pre_raw = 0) { // (pre: this thread's list entry has been fetched already, k_bin_sectors_hostf)
+    const MlmBinStage B = mlm_bin_stage<F_CONST>(P, F);
+    const auto &FS = mlm_bin_frame<F_CONST>(B, F); // the frame's parameters: staged, or (k_bin_sectors_hostf) in LDS
     constexpr uint32_t COLS = MODE == 0 ? 64u : (uint32_t)MLM_SEC_COLS; // entries of a strip's column table
     static_assert(MODE == 0 || S == 1, "list modes: one strip per workgroup (one column entry per thread)");
     __shared__ uint32_t s_col_phi[S][COLS], s_col_cnt[S][COLS], s_col_off[S][COLS];
@@ -195,7 +327,7 @@ __device__ __forceinline__ void mlm_bin_sectors_body(const MlmDev &P, const MlmF
     uint32_t tile_yx[S]; // dense images: the strip's row << MLM_REC_XT_BITS | 8-pixel column of its first wave (a record's tile origin)
 #pragma unroll
     for (int j = 0; j < S; ++j) {
-        MlmStripItem T = mlm_strip_item<MODE>(F, strip0 + (unsigned int)j);
+        MlmStripItem T = mlm_strip_item<MODE>(FS, strip0 + (unsigned int)j);
         tile_yx[j] = (T.by << MLM_REC_XT_BITS) | (T.bx * 4u);
         if (strip0 + (unsigned int)j >= n_strips) T.valid = false;
         item[j] = T.i;
@@ -204,18 +336,18 @@ __device__ __forceinline__ void mlm_bin_sectors_body(const MlmDev &P, const MlmF
         raw[j] = 0;
         if (have[j]) {
             if (MODE == 2) {
-                xs[j] = mlm_gp(F.pts)[3 * (size_t)T.i + 0];
-                ys[j] = mlm_gp(F.pts)[3 * (size_t)T.i + 1];
-                zs[j] = mlm_gp(F.pts)[3 * (size_t)T.i + 2];
+                xs[j] = mlm_gp(FS.pts)[3 * (size_t)T.i + 0];
+                ys[j] = mlm_gp(FS.pts)[3 * (size_t)T.i + 1];
+                zs[j] = mlm_gp(FS.pts)[3 * (size_t)T.i + 2];
             } else {
                 // (dense images: column and row come from the strip's place in the image; a list's pixel index has to be divided)
-                const int pix = (MODE == 1) ? (pre ? pre_pix : mlm_gp(F.pix)[T.i]) : T.i;
-                const int v = MODE == 0 ? T.py : pix / F.width;
-                const int u = MODE == 0 ? T.px : pix - v * F.width;
-                raw[j] = (MODE == 1 && pre) ? (uint16_t)pre_raw : (MODE == 1 && F.raw) ? (uint16_t)mlm_gp(F.raw)[T.i] : mlm_gp(F.img)[(size_t)v * F.row_stride + u];
+                const int pix = (MODE == 1) ? (pre ? pre_pix : mlm_gp(FS.pix)[T.i]) : T.i;
+                const int v = MODE == 0 ? T.py : pix / FS.width;
+                const int u = MODE == 0 ? T.px : pix - v * FS.width;
+                raw[j] = (MODE == 1 && pre) ? (uint16_t)pre_raw : (MODE == 1 && FS.raw) ? (uint16_t)mlm_gp(FS.raw)[T.i] : mlm_gp(FS.img)[(size_t)v * FS.row_stride + u];
                 // mlmap.cpp:329,344-346: (size_t u - float cx_) is a float subtraction, the rest is double (the depth factor below)
-                xs[j] = (double)((float)u - P.cx);
-                ys[j] = (double)((float)v - P.cy);
+                xs[j] = (double)((float)u - B.cx);
+                ys[j] = (double)((float)v - B.cy);
             }
         }
     }
@@ -229,7 +361,7 @@ __device__ __forceinline__ void mlm_bin_sectors_body(const MlmDev &P, const MlmF
             if (raw[j] == 0) { // mlmap.cpp:338-341
                 have[j] = false;
             } else {
-                const double depth = raw[j] * P.inv_factor;
+                const double depth = raw[j] * B.inv_factor;
                 xs[j] = xs[j] * depth; // (the division by the focal length follows below: x = (u - cx) * depth / fx, mlmap.cpp:344-346)
                 ys[j] = ys[j] * depth;
                 zs[j] = depth;
@@ -243,14 +375,15 @@ __device__ __forceinline__ void mlm_bin_sectors_body(const MlmDev &P, const MlmF
         // the bins by the cheap evaluation with certified margins (mlm_bin_point_fast) ...
 #ifndef MLM_BIN_EXACT // (experiment builds: make alt ALT_FLAGS=-DMLM_BIN_EXACT evaluates the reference's sequence for every wave)
         if (have[j]) {
-            const double vx = MODE == 2 ? xs[j] : xs[j] * P.inv_fx, vy = MODE == 2 ? ys[j] : ys[j] * P.inv_fy;
-            inside = mlm_bin_point_fast(P, F, vx, vy, zs[j], (fabs(vx) + fabs(vy)) + fabs(zs[j]), rho, phi, zi, can_do_cast, sure);
+            const double vx = MODE == 2 ? xs[j] : xs[j] * B.inv_fx, vy = MODE == 2 ? ys[j] : ys[j] * B.inv_fy;
+            const double v_l1 = (fabs(vx) + fabs(vy)) + fabs(zs[j]);
+            inside = mlm_bin_point_fast(B, FS, vx, vy, zs[j], v_l1, rho, phi, zi, can_do_cast, sure);
         }
 #else
         sure = !have[j];
 #endif
         if (!mlm_all(sure)) { // ... and, for a wave with a lane too close to a cell boundary to be sure, by the reference's own sequence
-            if (lane == 0) g_atomic_add(&mlm_gp(P.ctr)->bin_exact, 1u); // (statistic: mlm_frame_stats.n_bin_exact_waves)
+            if (lane == 0) g_atomic_add(&B.ctr->bin_exact, 1u); // (statistic: mlm_frame_stats.n_bin_exact_waves)
             if (have[j]) {
                 // p_l = T_ls * p_s (map_awareness.cpp:222; se3.cpp:91-95)
                 double x, y, z;
@@ -261,7 +394,7 @@ __device__ __forceinline__ void mlm_bin_sectors_body(const MlmDev &P, const MlmF
                 inside = mlm_bin_point(P, x, y, z, rho, phi, zi, can_do_cast);
             }
         }
-        if (inside) c0 = zi * P.nRhoPhi + phi * P.nRho + rho;
+        if (inside) c0 = zi * B.nRhoPhi + phi * B.nRho + rho;
         const uint32_t i00 = (uint32_t)mlm_readlane(item[j], 0); // work item of lane 0 of this wave (see MlmNode)
         // lanes of one centre cell -> one record, held by their lowest lane (= earliest insertion time).  The lanes of a group take the
         // group's mask inside the branch on the very compare the vote was made from — there the active lanes ARE the group, so the mask is
@@ -278,7 +411,7 @@ __device__ __forceinline__ void mlm_bin_sectors_body(const MlmDev &P, const MlmF
             }
         }
         // points outside the map that can still cast (map_awareness.cpp:241,249-265): identical starts merged per wave
-        const bool outer = have[j] && !inside && can_do_cast && P.visibility;
+        const bool outer = have[j] && !inside && can_do_cast && B.visibility;
         {
             unsigned long long todo = mlm_ballot(outer);
             while (todo) {
@@ -317,7 +450,7 @@ __device__ __forceinline__ void mlm_bin_sectors_body(const MlmDev &P, const MlmF
             else s_over = 1; // (dense tiles only: more than 64 columns in one 32x8 pixel strip)
         }
         const unsigned int n_pts = (unsigned int)__popcll(mlm_ballot(have[j]));
-        const unsigned int n_oor = (unsigned int)__popcll(mlm_ballot(have[j] && !(can_do_cast && P.visibility)));
+        const unsigned int n_oor = (unsigned int)__popcll(mlm_ballot(have[j] && !(can_do_cast && B.visibility)));
         if (lane == 0) s_cnt[j][wid] = n_pts | (n_oor << 10);
     }
     __syncthreads();
@@ -346,7 +479,7 @@ __device__ __forceinline__ void mlm_bin_sectors_body(const MlmDev &P, const MlmF
 #pragma unroll
     for (int j = 0; j < S; ++j) {
         if (rec_place[j] != MLM_NIL) {
-            *((MLM_GLOBAL mlm_u32x4 *)mlm_gp(P.bnodes) + ((size_t)(strip0 + (unsigned int)j) * 256u + s_col_off[j][rec_place[j] & 0xFFFFu] + (rec_place[j] >> 16))) =
+            *(B.bnodes + ((size_t)(strip0 + (unsigned int)j) * 256u + s_col_off[j][rec_place[j] & 0xFFFFu] + (rec_place[j] >> 16))) =
                 mlm_u32x4{rec_cell[j], rec_pos[j], (uint32_t)rec_mask[j], (uint32_t)(rec_mask[j] >> 32)};
         }
     }
@@ -359,7 +492,7 @@ __device__ __forceinline__ void mlm_bin_sectors_body(const MlmDev &P, const MlmF
                 pts += s_cnt[j][w] & 1023u;
                 oor += s_cnt[j][w] >> 10;
             }
-            *(MLM_GLOBAL mlm_u32x4 *)(mlm_gp(P.blk_stats) + 4 * (size_t)(strip0 + (unsigned int)j)) = mlm_u32x4{pts, oor, run_tot, 0u};
+            *(MLM_GLOBAL mlm_u32x4 *)(B.blk_stats + 4 * (size_t)(strip0 + (unsigned int)j)) = mlm_u32x4{pts, oor, run_tot, 0u};
         }
         if (threadIdx.x == 0 && s_over) mlm_sector_fail(P, F);
     }
@@ -367,9 +500,9 @@ __device__ __forceinline__ void mlm_bin_sectors_body(const MlmDev &P, const MlmF
     if (run_cnt) { // one chunk descriptor per run, its place in the column's list from a returning atomic
         const int j = MODE == 0 ? wid : 0;
         const uint32_t ph = s_col_phi[j][MODE == 0 ? lane : (int)threadIdx.x];
-        const unsigned int k = g_atomic_add(&mlm_gp(P.col_cnt)[ph], 1u);
-        if (k < P.chunk_cap)
-            *(MLM_GLOBAL mlm_u32x2 *)(mlm_gp(P.col_chunks) + 2 * ((size_t)ph * P.chunk_cap + k)) = mlm_u32x2{(strip0 + (unsigned int)j) * 256u + run_off, run_cnt};
+        const unsigned int k = g_atomic_add(&B.col_cnt[ph], 1u);
+        if (k < B.chunk_cap)
+            *(MLM_GLOBAL mlm_u32x2 *)(B.col_chunks + 2 * ((size_t)ph * B.chunk_cap + k)) = mlm_u32x2{(strip0 + (unsigned int)j) * 256u + run_off, run_cnt};
         else
             mlm_sector_fail(P, F);
     }
@@ -406,7 +539,7 @@ __global__ __launch_bounds__(256) void k_bin_sectors_hostf(const MlmDev *__restr
     }
     __syncthreads();
     pre = pre && s_F.pix == list_pix && s_F.raw == list_raw;
-    mlm_bin_sectors_body<MODE, 1>(P, s_F, n_strips, pre, pre_pix, pre_raw);
+    mlm_bin_sectors_body<MODE, 1, false>(P, s_F, n_strips, pre, pre_pix, pre_raw);
 }
 
 // MlmDev::hit_p / hit_inc / logit_one (mlm_types.h): one thread per entry of the odds table runs the hit-list loop's own chain and
