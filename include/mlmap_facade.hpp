@@ -381,6 +381,13 @@ class mlmap {
                      int32_t *n_steps = nullptr, int32_t *n_unknown = nullptr, int32_t *hit3 = nullptr, int32_t *hit_sq = nullptr) {
         check(mlm_query_sweeps(h_, p0, p1, n, radius, flags, status, voxel3, t, n_steps, n_unknown, hit3, hit_sq), "mlm_query_sweeps");
     }
+    // scan-to-map scores of candidate poses (mlm_score_poses): pts_s n_pts x 3 sensor-frame points, T_ws n_poses x 12 poses as
+    // mlm_render_depth takes them, table n_poses x MLM_SCORE_ROW int64 (valid, occ, free, unknown, infl, in box, cost, zero); flags
+    // MLM_SCORE_CLASSES and / or a field (lo, dims, sqdist as mlm_export_esdf wrote it; sq_cap 1 .. 2^20); every array host or device memory
+    void scorePoses(const double *pts_s, int n_pts, const double *T_ws, int n_poses, int flags, int64_t *table, const int32_t *lo = nullptr,
+                    const int32_t *dims = nullptr, const int32_t *sqdist = nullptr, int sq_cap = 64) {
+        check(mlm_score_poses(h_, pts_s, n_pts, T_ws, n_poses, flags, lo, dims, sqdist, sq_cap, table), "mlm_score_poses");
+    }
 
     // planners that query thousands of positions per cycle should use the batched entry points directly
     mlm_handle *handle() { return h_; }

@@ -546,6 +546,52 @@ int mlm_query_nearest(mlm_handle *h, const double *pos, int n, int max_dist, int
 int mlm_query_sweeps(mlm_handle *h, const double *p0, const double *p1, int n, int radius, int flags,
                      int8_t *status, int32_t *voxel3, double *t, int32_t *n_steps, int32_t *n_unknown,
                      int32_t *hit3, int32_t *hit_sq);
+/* Exact scan-to-map scores of candidate poses: for every pose, what the map says at the voxels a cloud of sensor-frame points falls
+ * into under that pose — class counts and the summed cost of a distance field — the inner loop of a correlative scan matcher or a
+ * particle filter.  One lookup per (pose, point), summed per pose; no ray is walked.  (No reference counterpart: the reference takes
+ * T_wb from an external odometry and only compensates its latency, mlmap.cpp:485-498; the classes are those of its point queries,
+ * the lattice is mlm_query_rays', the field is mlm_export_esdf's sqdist — the likelihood-field model's log-likelihood up to a scale.)
+ *   Points and poses: pts_s is [n_pts][3] positions in the sensor frame (what project_depth makes of a depth image, or any cloud);
+ *   T_ws is [n_poses][12] as in mlm_render_depth: R (3 x 3, sensor to world, row major), then the optical centre o.
+ *   World position of point j under pose k: w_a = ((R[a][0] * s0 + R[a][1] * s1) + R[a][2] * s2) + o[a], every operation one IEEE
+ *   double operation in that order, nothing fused.
+ *   Lattice and voxel: per axis Q = floor((w / d) * 1024.0) (d = subbox_d_xyz): mlm_query_rays' lattice.  The pair (k, j) is INVALID
+ *   if a Q is not finite or |Q| >= 2^40, and then contributes to no word; otherwise v = Q >> 10 (floor) is the voxel whose
+ *   mlm_export_window entry is read, as in mlm_query_nearest.  A NaN or an infinity anywhere in pts_s or T_ws is no error.
+ *   Classes (read only with MLM_SCORE_CLASSES): occ and infl are what mlm_export_window's channels return at v — absent blocks,
+ *   released frontier-mode blocks (element 0 answers, inflated class UNKNOWN) and voxels beyond the key range (UNKNOWN) included.
+ *   Field: lo, dims and sqdist are all NULL or all given.  The window follows mlm_export_window's rules and errors; sqdist holds one
+ *   int32 per voxel, laid out [dims[2]][dims[1]][dims[0]]: what mlm_export_esdf wrote for that box, unsigned or signed.  sq_cap lies
+ *   in 1 .. 2^20.  The answer is defined for any content of sqdist: the cost of a valid pair is min(max(sqdist[v], 0), sq_cap) if v
+ *   lies in the box, sq_cap otherwise.
+ *   Row k of table (int64 [n_poses][MLM_SCORE_ROW]; all eight words are always written):
+ *     [0] valid pairs
+ *     [1] pairs with occ == OCCUPIED                       (CLASSES, else 0)
+ *     [2] pairs with occ == FREE                           (CLASSES, else 0)
+ *     [3] pairs with occ == UNKNOWN                        (CLASSES, else 0)
+ *     [4] pairs with infl == OCCUPIED                      (CLASSES, else 0)
+ *     [5] valid pairs whose voxel lies in the box          (field, else 0)
+ *     [6] sum of the costs over the valid pairs            (field, else 0)
+ *     [7] valid pairs in the box with sqdist[v] <= 0       (field, else 0)
+ *   [1] + [2] + [3] == [0].  Every word is a count or a sum of integers, below 2^43, with one value whatever the schedule.  For a
+ *   matcher: [6] small and [1] large mean the frame lies on the map's surfaces; [2] counts returns from inside known free space
+ *   (something new, or a wrong pose); [3] counts returns the map cannot judge.
+ * pts_s, T_ws, sqdist and table may each be host or device memory.  The call runs on the stream of mlm_set_stream and returns when
+ * table is written.  With MLM_SCORE_CLASSES it observes the map as queries do (async mode: waits for everything submitted); without,
+ * it reads no map state and does not wait, as mlm_query_paths.  When every array is host memory, n_poses * n_pts <= 2^16 and n_poses
+ * is at most what mlm_query_nearest allows points (64; 8 while the host mirror needs a refresh), the batch is answered on the host
+ * without a launch (same answers): from the host mirror with CLASSES, by the same host code with no mirror without.  Everything
+ * else, and every batch after mlm_set_host_mirror_limit(h, 0), runs as a kernel.  MLM_ERR_INVALID: n_pts or n_poses outside
+ * 0 .. 2^22, a NULL input with a count > 0, table NULL, an unknown flag bit, neither CLASSES nor a field, lo / dims / sqdist only
+ * partly given, a window error, sq_cap outside 1 .. 2^20 with a field; n_poses == 0 is MLM_OK, n_pts == 0 writes zero rows.
+ * MLM_ERR_CAPACITY: no device memory for the staging of host pts_s (24 bytes x n_pts), T_ws (96 bytes) and table (64 bytes per pose,
+ * at most 2^18 poses at a time; each part rounded up to 256 bytes, in the buffer mlm_query_rays stages in), or for the kept device
+ * copy of a host sqdist (4 bytes per voxel, a buffer of its own); both are kept by the handle and counted in
+ * mlm_frame_stats.device_bytes.  The handle stays usable after either error. */
+#define MLM_SCORE_CLASSES 1
+#define MLM_SCORE_ROW 8
+int mlm_score_poses(mlm_handle *h, const double *pts_s, int n_pts, const double *T_ws, int n_poses, int flags,
+                    const int32_t lo[3], const int32_t dims[3], const int32_t *sqdist, int sq_cap, int64_t *table);
 /* Cost-to-go field through the free space of a box of voxels (no reference counterpart: the reference has no such field; the
  * classes behind it are those of its point queries, the field is defined here, in integers).  Voxel indices, window, layout
  * ([dims[2]][dims[1]][dims[0]], x fastest) and centres are those of mlm_export_window.

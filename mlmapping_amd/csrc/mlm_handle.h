@@ -26,7 +26,7 @@ struct KernelTime {
 // switches MLM_DEBUG_CREATE / MLM_DEBUG_ALLOC / MLM_DEBUG_DRAIN, which print).
 const char *const kKnobNames[] = {"agg_lds", "big_arm", "big_grid", "bin_block", "chain_grid", "cluster_tile", "collect_grid", "cu_reserve", "cu_split",
                                   "esdf_tile_vox", "ex_spec", "expand_block", "graph", "grid_tile", "hit_tab_n", "logit_exact", "mirror", "mirror_max", "mirror_mb", "need_slots", "node_lds", "pool_grow",
-                                  "rank_grid", "rays_grid", "reach_group", "reach_tile", "render_tile", "route_group", "route_tile", "sc_block", "sc_grid", "sec_backoff", "sec_fail_every", "sec_tab", "sec_tab_big", "sec_threads",
+                                  "rank_grid", "rays_grid", "reach_group", "reach_tile", "render_tile", "route_group", "route_tile", "sc_block", "sc_grid", "score_chunk", "sec_backoff", "sec_fail_every", "sec_tab", "sec_tab_big", "sec_threads",
                                   "sectors", "single_apply_grid", "single_chain_grid", "single_rank_grid", "slot_sets", "sort_block", "sort_grid", "tile_grid", "tile_sh", "view_lds_bits"};
 struct KnobStore {
     std::mutex mu;
@@ -58,6 +58,7 @@ bool knob_value_ok(const char *name, long long v) {
     if (is("reach_group")) return v >= 1 && v <= kReachGroupMax; // (sweeps between two looks at the "marked" words)
     if (is("hit_tab_n")) return v >= 0 && v <= 65536 && (v & (v - 1)) == 0; // (entries per chain of MlmDev::hit_p / hit_inc: a power of two, 0 = no tables)
     if (is("render_tile")) return v >= 0 && v <= 2; // (k_render has three instantiations: 64 x 1, 16 x 4, 8 x 8)
+    if (is("score_chunk")) return v >= 0 && v <= (1ll << 22) && v % MLM_SCORE_TILE == 0; // (points per chunk of k_score: whole LDS tiles; 0: automatic)
     return true;
 }
 bool knob(const char *name, long long &out) {
@@ -157,6 +158,12 @@ constexpr unsigned int kSweepGrid = 8192;    // most workgroups of k_sweeps (a w
 constexpr int kPathChunk = 1 << 16;
 constexpr size_t kPathScratchBytes = (size_t)256 << 20;
 constexpr size_t kPathStageBytes = (size_t)64 << 20;
+// mlm_score_poses: poses per launch of k_score (bounds the staging of host poses and rows: 160 bytes per pose), the most pairs and —
+// mlm_query_nearest's rule — poses of a batch in host memory that the host code answers, and the workgroups the automatic chunk aims
+// at (four per CU of a 256-CU chip: a lane per pose leaves a grid of few poses and many points empty otherwise)
+constexpr int kScorePoseChunk = 1 << 18;
+constexpr long long kScoreHostPairs = 1ll << 16;
+constexpr long long kScoreGridTarget = 1024;
 
 // A frame on its own with at most this many strips of 256 points (sampled callbacks, point lists: 4 096 points) runs its cells' float chains
 // inside k_rank<true> instead of launching k_chain_lanes — a launch of its own costs a lone frame the kernel boundary (1.5 us) and the few
@@ -182,7 +189,7 @@ struct mlm_handle {
     size_t q_cap = 0;
     // The read-outs' kept buffers (enlarged by need, never shrunk; mlm_readout.h).  Host arrays are staged by one rule, ReadoutChannels:
     // the exports (window .. clusters, and a host exclude / mark of mlm_query_views) in d_win_stage, the batched queries (rays, render,
-    // boxes, nearest, sweeps, paths, and the rays of views) in d_ray_stage.  The comments below name what else each read-out keeps.
+    // boxes, nearest, sweeps, paths, score, and the rays of views) in d_ray_stage.  The comments below name what else each read-out keeps.
     // mlm_export_window: odds of the haloed tile (gradients)
     void *d_win_scratch = nullptr, *d_win_stage = nullptr;
     size_t win_scratch_bytes = 0, win_stage_bytes = 0;
@@ -207,6 +214,10 @@ struct mlm_handle {
     // mlm_query_paths: the traced paths of one chunk of goals (three int32 arrays of max_moves + 1 entries per goal)
     void *d_path = nullptr;
     size_t path_bytes = 0;
+    // mlm_score_poses: the device copy of a distance field handed over in host memory (4 bytes per voxel)
+    void *d_score_field = nullptr;
+    size_t score_field_bytes = 0;
+    int score_chunk = 0; // points per chunk of k_score (knob "score_chunk"; 0: automatic)
     unsigned int rays_grid = 1024; // most workgroups of k_rays (knob "rays_grid"): 2^20 rays are four per lane
     int render_tile = kRenderTileDefault; // (knob "render_tile")
     // sort buffers (rehash frames only)

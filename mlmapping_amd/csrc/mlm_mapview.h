@@ -15,6 +15,7 @@
 #include "mlm_boxgrow.h"
 #include "mlm_nearest.h"
 #include "mlm_raywalk.h"
+#include "mlm_score.h"
 #include "mlm_sweep.h"
 
 namespace mlm_host {
@@ -407,6 +408,24 @@ struct MapView {
             if (n_unknown) n_unknown[i] = o.ray.n_unknown;
             if (hit_sq) hit_sq[i] = o.hit_sq;
         }
+    }
+    // mlm_score_poses on the mirrored planes: the rule of mlm_score.h, pose by pose and point by point, over the same classes (one
+    // table probe per run of points inside one block).  Without classes nothing of the planes is read: a view that has only d_sub and
+    // n answers a field-only call.  F.sqdist null: no field.  All eight words of every row are written.
+    template <bool CLASSES, bool FIELD> void score_rows(const double *pts_s, int n_pts, const double *T_ws, int n_poses, const MlmScoreField &F, int64_t *table) const {
+        for (int k = 0; k < n_poses; ++k) {
+            unsigned long long acc[MLM_SCORE_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
+            RayClasses cls{*this};
+            MlmScoreBlock B{};
+            for (int j = 0; j < n_pts; ++j)
+                mlm_score_pair<CLASSES, FIELD>(T_ws + 12 * (size_t)k, pts_s + 3 * (size_t)j, d_sub, n, F, cls, B, acc);
+            for (int w = 0; w < MLM_SCORE_WORDS; ++w) table[MLM_SCORE_WORDS * (size_t)k + w] = (int64_t)acc[w];
+        }
+    }
+    void score(const double *pts_s, int n_pts, const double *T_ws, int n_poses, bool classes, const MlmScoreField &F, int64_t *table) const {
+        if (classes && F.sqdist) score_rows<true, true>(pts_s, n_pts, T_ws, n_poses, F, table);
+        else if (classes) score_rows<true, false>(pts_s, n_pts, T_ws, n_poses, F, table);
+        else score_rows<false, true>(pts_s, n_pts, T_ws, n_poses, F, table);
     }
 };
 

@@ -307,6 +307,12 @@ bool mirror_sweeps_wanted(const mlm_handle *h, const double *p0, const double *p
     }
     return true;
 }
+// ... and a batch of mlm_score_poses: few poses (mlm_query_nearest's bound on its points) with few pairs together (kScoreHostPairs, mlm_handle.h)
+bool mirror_score_wanted(const mlm_handle *h, int n_poses, int n_pts) {
+    const MlmMirror &M = h->mir;
+    if (!M.enabled || (long long)n_poses * 4 > (M.dirty ? M.max_dirty : M.max_clean)) return false;
+    return (long long)n_poses * n_pts <= kScoreHostPairs;
+}
 // drain + refresh if the map changed since the mirror was filled; the caller holds the lock
 int mirror_sync(mlm_handle *h) {
     if (h->mir.eager_pending) {

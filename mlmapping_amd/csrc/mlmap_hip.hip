@@ -44,6 +44,7 @@
 #include "mlm_kernels_reach.h"
 #include "mlm_kernels_route.h"
 #include "mlm_kernels_path.h"
+#include "mlm_kernels_score.h"
 #include "mlm_kernels_cluster.h"
 #include "mlm_host.h"
 #include "mlm_mapview.h"
@@ -505,6 +506,7 @@ int mlm_create(const mlm_config *cfg, const mlm_limits *lim_in, int device, mlm_
         if (knob("mirror_mb", kv)) h->mir.max_bytes = (size_t)std::max(0, (int)kv) << 20;
         if (knob("rays_grid", kv)) h->rays_grid = (unsigned int)kv;
         if (knob("render_tile", kv)) h->render_tile = (int)kv;
+        if (knob("score_chunk", kv)) h->score_chunk = (int)kv;
         if (knob("mirror_max", kv)) h->mir.max_clean = std::max(0, (int)kv), h->mir.max_dirty = std::min(h->mir.max_dirty, h->mir.max_clean);
         mirror_apply_limit(h);
     }
@@ -1932,6 +1934,82 @@ int mlm_query_paths(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], c
         hipLaunchKernelGGL(k_paths, grid, dim3(MLM_BLOCK), 0, h->stream, Q);
         HIPCHK(h, hipGetLastError());
         if ((rc = chs.copy_out(h, 1, 5, i0, m))) return rc;
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MLM_OK;
+}
+
+int mlm_score_poses(mlm_handle *h, const double *pts_s, int n_pts, const double *T_ws, int n_poses, int flags, const int32_t lo[3],
+                    const int32_t dims[3], const int32_t *sqdist, int sq_cap, int64_t *table) {
+    if (!h) return MLM_ERR_INVALID;
+    MLM_LOCK(h);
+    const bool classes = (flags & MLM_SCORE_CLASSES) != 0, field = lo || dims || sqdist;
+    if (n_pts < 0 || n_pts > MLM_SCORE_MAX_COUNT || n_poses < 0 || n_poses > MLM_SCORE_MAX_COUNT || (n_pts > 0 && !pts_s) || (n_poses > 0 && !T_ws) ||
+        !table || (flags & ~MLM_SCORE_CLASSES) || (!classes && !field) || (field && (!lo || !dims || !sqdist)) ||
+        (field && (sq_cap < 1 || sq_cap > MLM_SCORE_MAX_CAP))) {
+        h->err = "mlm_score_poses: n_pts or n_poses outside [0, 2^22], a null input, a null table, an unknown flag bit, neither classes nor a field, "
+                 "lo / dims / sqdist only partly given, or sq_cap outside [1, 2^20]";
+        return MLM_ERR_INVALID;
+    }
+    long long D[3], nvox = 0;
+    int rc;
+    if (field && (rc = box_check(h, "mlm_score_poses", lo, dims, D, nvox))) return rc;
+    if (n_poses == 0) return MLM_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    MlmScoreField F{};
+    if (field) {
+        F.sqdist = sqdist;
+        for (int a = 0; a < 3; ++a) F.lo[a] = lo[a], F.dims[a] = dims[a];
+        F.cap = sq_cap;
+    }
+    // channels: the points, the poses, the rows; in device memory (used in place) or staged — the points for the whole call, poses and
+    // rows chunk by chunk
+    ReadoutChannels<3> ch(h->d_ray_stage, h->ray_stage_bytes,
+                          {{pts_s, 3 * sizeof(double)}, {T_ws, 12 * sizeof(double)}, {table, MLM_SCORE_ROW * sizeof(int64_t)}}, true);
+    const bool field_staged = field && !readout_in_place(sqdist);
+    // a matcher's few hypotheses: answered on the host like mlm_query_nearest's small batches — from the host mirror (mlm_mirror.h) with
+    // classes, with no mirror and no look at the map without
+    if (ch.all_host && (!field || field_staged) && mirror_score_wanted(h, n_poses, n_pts)) {
+        if (classes) {
+            rc = mirror_try(h, true, n_poses, [&] { h->mir.view.score(pts_s, n_pts, T_ws, n_poses, true, F, table); });
+            if (rc) return rc > 0 ? MLM_OK : rc;
+        } else {
+            mlm_host::MapView v;
+            v.d_sub = h->P.d_sub;
+            v.n = h->P.n;
+            v.score(pts_s, n_pts, T_ws, n_poses, false, F, table);
+            return MLM_OK;
+        }
+    }
+    // with classes the call observes the map as queries do; a field-only call reads nothing of it and waits for nothing
+    if (classes && (rc = drain(h))) return rc;
+    if (field_staged) { // the field crosses the link once, into a buffer of its own
+        const size_t bytes = (size_t)nvox * sizeof(int32_t);
+        if ((rc = readout_reserve(h, h->d_score_field, h->score_field_bytes, bytes, "mlm_score_poses"))) return rc;
+        HIPCHK(h, hipMemcpyAsync(h->d_score_field, sqdist, bytes, hipMemcpyHostToDevice, h->stream));
+        F.sqdist = (const int32_t *)h->d_score_field;
+    }
+    const int pose_chunk = std::min(n_poses, kScorePoseChunk);
+    if ((rc = ch.reserve(h, "mlm_score_poses", {(size_t)n_pts, (size_t)pose_chunk, (size_t)pose_chunk}))) return rc;
+    if ((rc = ch.copy_in(h, 0, 1, 0, (size_t)n_pts))) return rc;
+    void (*const kern)(const MlmDev, const MlmScore) = classes ? (field ? k_score<true, true> : k_score<true, false>) : k_score<false, true>;
+    const int tiles = std::max(1, (n_pts + MLM_SCORE_TILE - 1) / MLM_SCORE_TILE);
+    for (int i0 = 0; i0 < n_poses; i0 += pose_chunk) {
+        const int m = std::min(pose_chunk, n_poses - i0);
+        const int groups = (m + MLM_BLOCK - 1) / MLM_BLOCK;
+        // points per chunk: the knob's, else as many chunks as bring the grid to kScoreGridTarget workgroups, whole tiles each
+        int chunk = h->score_chunk;
+        if (chunk <= 0) {
+            const int want = (int)std::min<long long>(tiles, (kScoreGridTarget + groups - 1) / groups);
+            chunk = (tiles + want - 1) / want * MLM_SCORE_TILE;
+        }
+        const int chunks = std::max(1, (n_pts + chunk - 1) / chunk);
+        if ((rc = ch.copy_in(h, 1, 2, (size_t)i0, (size_t)m))) return rc;
+        MlmScore Q{(const double *)ch.at(0, 0), (const double *)ch.at(1, (size_t)i0), n_pts, m, chunk, chunks > 1, F, (unsigned long long *)ch.at(2, (size_t)i0)};
+        if (chunks > 1) HIPCHK(h, hipMemsetAsync(Q.table, 0, (size_t)m * MLM_SCORE_ROW * sizeof(int64_t), h->stream));
+        hipLaunchKernelGGL(kern, dim3((unsigned int)chunks, (unsigned int)groups), dim3(MLM_BLOCK), 0, h->stream, h->P, Q);
+        HIPCHK(h, hipGetLastError());
+        if ((rc = ch.copy_out(h, 2, 3, (size_t)i0, (size_t)m))) return rc;
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MLM_OK;

@@ -33,6 +33,7 @@ MLM_REACH_OCC, MLM_REACH_INFL, MLM_REACH_UNKNOWN, MLM_REACH_NONE, MLM_REACH_SEED
 # mlm_export_route: the same predicates, cost of a voxel not reached, parent code of a seed (0..25 are the moves' codes)
 MLM_ROUTE_OCC, MLM_ROUTE_INFL, MLM_ROUTE_UNKNOWN, MLM_ROUTE_NONE, MLM_ROUTE_SEED = 1, 2, 4, -1, 26
 MLM_PATH_REACH, MLM_PATH_ROUTE, MLM_PATH_ROW = 0, 1, 8
+MLM_SCORE_CLASSES, MLM_SCORE_ROW = 1, 8
 # mlm_export_clusters: the set (FRONTIER alone, or a union of the class bits), labels off the set / in a dropped component, int64 per row
 MLM_CLUSTER_OCC, MLM_CLUSTER_INFL, MLM_CLUSTER_UNKNOWN, MLM_CLUSTER_FRONTIER = 1, 2, 4, 16
 MLM_CLUSTER_NONE, MLM_CLUSTER_SMALL, MLM_CLUSTER_ROW = -1, -2, 16
@@ -55,7 +56,7 @@ ABI_SYMBOLS = [
     "mlm_query_odds", "mlm_query_odd_grad", "mlm_query_odds_at", "mlm_export_frontier_points", "mlm_import_blocks",
     "mlm_merge_pack", "mlm_merge_finish",
     "mlm_set_free_in_bound", "mlm_inflate_map", "mlm_block_count",
-    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_grid2d", "mlm_export_reach", "mlm_export_route", "mlm_export_clusters", "mlm_query_rays", "mlm_render_depth", "mlm_query_views", "mlm_query_boxes", "mlm_query_nearest", "mlm_query_sweeps", "mlm_query_paths", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
+    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_grid2d", "mlm_export_reach", "mlm_export_route", "mlm_export_clusters", "mlm_query_rays", "mlm_render_depth", "mlm_query_views", "mlm_query_boxes", "mlm_query_nearest", "mlm_query_sweeps", "mlm_query_paths", "mlm_score_poses", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
     "mlm_get_awareness_hits",
     "mlm_get_awareness_misses", "mlm_get_T_ls", "mlm_get_odds_table", "mlm_get_kernel_times",
     "mlm_enable_kernel_timing", "mlm_set_timed_kernel", "mlm_host_register", "mlm_host_unregister", "mlm_debug_set", "mlm_debug_reset",
@@ -161,6 +162,7 @@ def load_library(path: Optional[str] = None):
     L.mlm_query_nearest.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
     L.mlm_query_sweeps.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.mlm_query_paths.argtypes = [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp]
+    L.mlm_score_poses.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp, vp, i32, vp]
     L.mlm_export_global_map.argtypes = [vp, i32, vp, vp]
     L.mlm_export_block_flags.argtypes = [vp, i32, vp, vp]
     L.mlm_export_frontier.argtypes = [vp, i32, vp, vp]
@@ -1042,6 +1044,91 @@ class MLMap:
         out["summary"] = summary
         return out
 
+    SCORE_COLUMNS = ("valid", "occ", "free", "unknown", "infl", "in_box", "cost", "zero")
+
+    def score_poses(self, pts_s, T_ws, classes=True, box=None, sqdist=None, sq_cap: int = 64):
+        """Scan-to-map scores of candidate poses (mlm_score_poses).  pts_s: m x 3 float64 points in the sensor frame (backproject's,
+        or any cloud), T_ws: n x 12 float64 poses as render_depth takes them (pose_grid's, compose_T_ws') — numpy arrays (numpy
+        results) or torch device tensors (torch device results).  classes: count the classes of the voxels the points fall into.
+        box = (lo, dims) and sqdist: a distance field over that voxel box, dz x dy x dx int32 as export_esdf's "sqdist" (a numpy
+        array or a device tensor, whatever the rest is); the cost of a point is its sqdist clamped to 0 .. sq_cap, sq_cap outside
+        the box.  Returns {"table": int64 (n, 8)} and its columns by name: "valid" pairs, those whose voxel is "occ", "free",
+        "unknown" and "infl" (inflated-occupied), those "in_box", the summed "cost", and those in the box at sqdist <= 0 ("zero")."""
+        if (box is None) != (sqdist is None):
+            raise MlmError("score_poses: box and sqdist go together")
+        on_dev = hasattr(pts_s, "data_ptr") and not isinstance(pts_s, np.ndarray)
+        keep = []
+        if on_dev:
+            import torch
+
+            for t, k, what in ((pts_s, 3, "points"), (T_ws, 12, "poses")):
+                if not hasattr(t, "data_ptr") or t.dtype != torch.float64 or t.numel() % k or not t.is_contiguous():
+                    raise MlmError(f"score_poses: a tensor of {what} must be contiguous float64 with {k} values per row")
+            m, n = pts_s.numel() // 3, T_ws.numel() // 12
+            table = torch.empty((n, MLM_SCORE_ROW), dtype=torch.int64, device=pts_s.device)
+            ptr = [pts_s.data_ptr(), T_ws.data_ptr(), table.data_ptr()]
+        else:
+            p, T = _f64(pts_s).reshape(-1, 3), _f64(T_ws).reshape(-1, 12)
+            keep += [p, T]
+            m, n = p.shape[0], T.shape[0]
+            table = np.empty((n, MLM_SCORE_ROW), dtype=np.int64)
+            ptr = [p.ctypes.data, T.ctypes.data, table.ctypes.data]
+        lo_a = dims_a = sq_p = None
+        if box is not None:
+            lo_a, dims_a = self._window_args(*box)
+            nvox = int(dims_a[0]) * int(dims_a[1]) * int(dims_a[2])
+            if hasattr(sqdist, "data_ptr") and not isinstance(sqdist, np.ndarray):
+                import torch
+
+                if sqdist.dtype != torch.int32 or sqdist.numel() != nvox or not sqdist.is_contiguous():
+                    raise MlmError("score_poses: a tensor of sqdist must be contiguous int32 with one value per voxel of the box")
+                sq_p = sqdist.data_ptr()
+            else:
+                f = np.ascontiguousarray(sqdist, dtype=np.int32)
+                if f.size != nvox:
+                    raise MlmError("score_poses: sqdist must hold one value per voxel of the box")
+                keep.append(f)
+                sq_p = f.ctypes.data
+        self.score_poses_dev(ptr[0], m, ptr[1], n, ptr[2], classes, lo_a, dims_a, sq_p, sq_cap)
+        out = {"table": table}
+        for i, name in enumerate(self.SCORE_COLUMNS):
+            out[name] = table[:, i]
+        return out
+
+    def score_poses_dev(self, pts_s: int, n_pts: int, T_ws: int, n_poses: int, table: int, classes=True, lo=None, dims=None,
+                        sqdist: Optional[int] = None, sq_cap: int = 64):
+        """Same on pointers (ints; device or host memory, each on its own): n_pts x 3 float64 points, n_poses x 12 float64 poses,
+        n_poses x 8 int64 table; lo, dims and sqdist (dz*dy*dx int32) together or not at all."""
+        lo_p = dims_p = None
+        if lo is not None or dims is not None:
+            lo_a, dims_a = self._window_args(lo, dims)
+            lo_p, dims_p = _p(lo_a), _p(dims_a)
+        vp = lambda v: None if v is None else ctypes.c_void_p(v)
+        self._chk(self._L.mlm_score_poses(self._h, vp(pts_s), int(n_pts), vp(T_ws), int(n_poses), MLM_SCORE_CLASSES if classes else 0,
+                                          lo_p, dims_p, vp(sqdist), int(sq_cap), vp(table)), "mlm_score_poses")
+
+    def match_pose(self, pts_s, T_ws, lo, dims, max_dist: int = 8, occ=True, infl=False, unknown=False, classes=False):
+        """export_esdf {sqdist} into a device tensor, then score_poses on it with sq_cap = max_dist^2: the likelihood-field cost of
+        every candidate pose; the field never leaves the device.  pts_s, T_ws and the results as score_poses (numpy arrays are
+        copied to the device and the table comes back as numpy); lo, dims, max_dist, occ, infl, unknown as export_esdf.  Adds
+        "best": the index of the smallest cost, ties to the largest "occ", then to the lowest index."""
+        import torch
+
+        lo_a, dims_a = self._window_args(lo, dims)
+        host = not (hasattr(pts_s, "data_ptr") and not isinstance(pts_s, np.ndarray))
+        dev = torch.device("cuda", torch.cuda.current_device())
+        if host:
+            pts_s = torch.from_numpy(_f64(pts_s).reshape(-1, 3)).to(dev)
+            T_ws = torch.from_numpy(_f64(T_ws).reshape(-1, 12)).to(dev)
+        field = torch.empty((int(dims_a[2]), int(dims_a[1]), int(dims_a[0])), dtype=torch.int32, device=pts_s.device)
+        self.export_esdf_dev(lo_a, dims_a, max_dist, occ, infl, unknown, False, sqdist=field.data_ptr())
+        out = self.score_poses(pts_s, T_ws, classes, (lo_a, dims_a), field, int(max_dist) ** 2)
+        t = out["table"].cpu().numpy()
+        if host:
+            out = {"table": t, **{name: t[:, i] for i, name in enumerate(self.SCORE_COLUMNS)}}
+        out["best"] = best_score_row(t)
+        return out
+
     @staticmethod
     def _ray_flags(occ, infl, unknown) -> int:
         return (MLM_RAY_OCC if occ else 0) | (MLM_RAY_INFL if infl else 0) | (MLM_RAY_UNKNOWN if unknown else 0)
@@ -1174,3 +1261,49 @@ def compose_T_ws(q_wb, t_wb, T_bs) -> np.ndarray:
     out[:, :9] = (R @ B[:3, :3]).reshape(-1, 9)
     out[:, 9:] = t + R @ B[:3, 3]
     return out
+
+
+def best_score_row(table) -> int:
+    """The row of a score_poses table a matcher takes: the smallest cost [6], ties to the largest occ count [1], then to the lowest
+    index; -1 for an empty table."""
+    t = np.asarray(table, dtype=np.int64).reshape(-1, MLM_SCORE_ROW)
+    if not len(t):
+        return -1
+    return int(np.lexsort((np.arange(len(t)), -t[:, 1], t[:, 6]))[0])
+
+
+def backproject(depth_u16, K, step: int = 1) -> np.ndarray:
+    """The sensor-frame points update_map makes of a depth image (project_depth's arithmetic, mlmap.cpp:338-346): every `step`-th
+    pixel of every `step`-th row, v outer and u fastest, raw 0 skipped; depth = raw * (1 / 1000.0), x = (float(u) - float(cx)) * depth
+    / float(fx) — the subtraction in float32, the rest in float64 — y likewise, z = depth.  K = (fx, fy, cx, cy).  (m, 3) float64."""
+    img = np.asarray(depth_u16)
+    if img.ndim != 2 or img.dtype != np.uint16 or int(step) < 1:
+        raise MlmError("backproject: a 2-D uint16 image and step >= 1")
+    fx, fy, cx, cy = (np.float32(k) for k in np.asarray(K, dtype=np.float64).reshape(4))
+    v, u = np.meshgrid(np.arange(0, img.shape[0], int(step)), np.arange(0, img.shape[1], int(step)), indexing="ij")
+    raw = img[v, u]
+    keepm = raw != 0
+    u, v, raw = u[keepm], v[keepm], raw[keepm]
+    depth = raw.astype(np.float64) * (1.0 / 1000.0)
+    x = (u.astype(np.float32) - cx).astype(np.float64) * depth / np.float64(fx)
+    y = (v.astype(np.float32) - cy).astype(np.float64) * depth / np.float64(fy)
+    return np.ascontiguousarray(np.stack([x, y, depth], axis=1))
+
+
+def pose_grid(T_ws, d: float, half_xyz=(3, 3, 1), yaw_deg=(-2, -1, 0, 1, 2)) -> np.ndarray:
+    """A correlative search grid around one pose T_ws (12 float64: R row major, then o): for every yaw (outermost; degrees about the
+    world z axis through the optical centre, R' = Rz(yaw) R in float64) the translations o + (ix, iy, iz) * d with |ix| <= half_xyz[0]
+    and so on, z outer, x fastest — neighbouring rows differ by one voxel in x, which is what score_poses gathers fastest.
+    (len(yaw_deg) * (2 hz + 1) * (2 hy + 1) * (2 hx + 1), 12) float64."""
+    T = _f64(T_ws).reshape(12)
+    R, o = T[:9].reshape(3, 3), T[9:]
+    hx, hy, hz = (int(h) for h in half_xyz)
+    iz, iy, ix = np.meshgrid(np.arange(-hz, hz + 1), np.arange(-hy, hy + 1), np.arange(-hx, hx + 1), indexing="ij")
+    off = np.stack([ix.ravel(), iy.ravel(), iz.ravel()], axis=1).astype(np.float64) * float(d)
+    out = np.empty((len(yaw_deg), len(off), 12), dtype=np.float64)
+    for k, deg in enumerate(yaw_deg):
+        a = np.deg2rad(np.float64(deg))
+        Rz = np.array([[np.cos(a), -np.sin(a), 0.0], [np.sin(a), np.cos(a), 0.0], [0.0, 0.0, 1.0]])
+        out[k, :, :9] = (Rz @ R).reshape(9)
+        out[k, :, 9:] = o + off
+    return out.reshape(-1, 12)
