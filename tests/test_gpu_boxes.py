@@ -312,3 +312,48 @@ def test_arguments_and_single_outputs(mods, knobs):
         assert call(g=None, l=None, d=None) == 0  # max_grow NULL, no window: a pure count
         assert outs[1].tolist() == boxes.tolist() and outs[3][0].tolist() == [4, 0, 0, 0]
         gpu.close()
+
+
+# ---- other block sizes ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [3, 16])
+def test_growth_across_absent_and_released_blocks(mods, n):
+    """subbox_n 3 and 16 on a frontier-mode handle: a box whose lo is negative and no multiple of subbox_n grows through an absent
+    block on its -x side and through a released one (element 0 FREE, then UNKNOWN) on its +x side, up to single OCCUPIED voxels and
+    the limits; with UNKNOWN selected both stop it"""
+    import torch
+
+    from tests.test_gpu_nearest import dump, load
+
+    MLMap, _ = mods
+    cfg = S1.with_(use_exploration_frontiers=True, subbox_n=n)
+    absent, released = (-3, -1, -1), (0, -1, -1)
+    free = [(gx, gy, gz) for gx in range(-4, 3) for gy in range(-4, 3) for gz in range(-4, 3) if (gx, gy, gz) not in (absent, released)]
+    b0 = [-n - 1, -2, -1, -n, -1, 0]  # (x in blocks -2 and -1, y in block -1, z across 0)
+    obstacles = [(n + 1, -1, 0), (-n - 1, -n - 3, -1)]  # closes +x beyond the released block, and -y
+    mg = 2 * n + 2
+    maps = []
+    for fill in (b"f", b"u"):
+        b = dump(obstacles, free, released={released: fill}, n=n)
+        classes = rw.block_classes(b, n)
+        cases = [(OCC, mg), (OCC | UNKNOWN, mg), (OCC | INFL, [mg, 1, 0, 2, n, n + 1]), (0, None)]
+        exp = [br.grow_all([b0], f, classes, g) for f, g in cases]
+        e = one(exp[0])
+        assert e[0] == 1 and e[2] & (1 << 1) and e[2] & (1 << 2), e                     # +x and -y closed by the obstacles
+        assert e[1][0] <= -3 * n and e[1][3] == n, e                                    # through the absent block, through the released one
+        inside = lambda g: int(np.prod([max(0, min(e[1][3 + a], g[a] * n + n - 1) - max(e[1][a], g[a] * n) + 1) for a in range(3)]))
+        assert inside(absent) > 0 and inside(released) > 0, e
+        assert e[3][1] == inside(absent) + (inside(released) if fill == b"u" else 0), e  # a released block of UNKNOWN counts as UNKNOWN
+        e = one(exp[1])
+        assert e[0] == 1 and e[1][0] == -2 * n and e[2] & 1 and (e[1][3] == -1) == (fill == b"u"), e  # UNKNOWN: stopped at the absent block's face
+        maps.append((fill, b, cases, exp))
+    for fill, b, cases, exp in maps:
+        for staged in (False, True):
+            gpu = load(MLMap, b, cfg)
+            if staged:
+                gpu.set_host_mirror_limit(0)
+            for (f, g), x in zip(cases, exp):
+                what = f"n={n} released={fill} flags={f} max_grow={g} staged={staged}"
+                br.assert_equal(gpu.query_boxes(np.array([b0], dtype=np.int32), max_grow=g, **kw(f)), x, what)
+                br.assert_equal(to_numpy(gpu.query_boxes(torch.tensor([b0], dtype=torch.int32).cuda(), max_grow=g, **kw(f))), x, "device tensors " + what)
+            assert not staged or gpu.frame_stats()["n_host_queries"] == 0
+            gpu.close()

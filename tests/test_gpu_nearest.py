@@ -393,3 +393,45 @@ def test_arguments_and_single_outputs(mods, knobs):
             assert np.array_equal(outs[k], full[k]), k
         assert call(c=64, f=OCC | INFL | UNKNOWN) == 0 and outs[0].tolist() == [1, 1, -1]
         gpu.close()
+
+
+# ---- blocks with fewer cells than a wave has lanes ------------------------------------------------------------------------------
+def small_block_maps(n, C):
+    """two maps around the point voxel (1, 1, 1): A with OCCUPIED voxels C away along y and inflated ones C away along x (ties within
+    a plane and across them), B with OCCUPIED voxels C away along z, one just outside the ball and, far from these, one in the first
+    cell of the block diagonally behind the upper corner of block (far(n, C) / n, far(n, C) / n, 0)"""
+    W = -(-(min(C, 10) + 2) // n)
+    free = [(gx, gy, gz) for gx in range(-W, W + 1) for gy in range(-W, W + 1) for gz in range(-W, W + 1)]
+    a = dump([(1, 1 + C, 1), (1, 1 - C, 1)], free, inflated=[(1 + C, 1, 1), (1 - C, 1, 1)], n=n)
+    S = far(n, C)
+    b = dump([(1, 1, 1 + C), (1, 1, 1 - C), (1 + C, 2, 1), (S + n, S + n, 0)], free + [(S // n, S // n, 0)], n=n)
+    return a, b
+
+
+def far(n, C):
+    """a multiple of subbox_n more than 6 C voxels away"""
+    return n * (-(-(6 * C + 8) // n))
+
+
+@pytest.mark.parametrize("C", [1, "n", "n + 1", 17])
+@pytest.mark.parametrize("n", [2, 3, 7, 16])
+def test_nearest_small_blocks(mods, n, C):
+    """subbox_n 2, 3 (a whole block has 8 and 27 cells), 7 and 16 at max_dist 1, n, n + 1 and 17, voxel size 0.15: the winner lies
+    C / n block rings out, at a distance of exactly C voxels; two voxels at that distance in different blocks tie and z, then y, then x
+    decides; the parts of the blocks at the cube's faces have fewer than 64 cells; a point far from everything finds nothing"""
+    MLMap, _ = mods
+    C = {"n": n, "n + 1": n + 1}.get(C, C)
+    d = 0.15
+    cfg = S1.with_(subbox_n=n, subbox_d_xyz=d)
+    a, b = small_block_maps(n, C)
+    S = far(n, C)
+    pts = np.concatenate([centre([(1, 1, 1)], d), at([(1024, 1024 + 512, 1024 + 512), (1024, 1024, 1024)], d),  # a centre, a face, a corner
+                          centre([(1, 4 * C + 4, 1)], d), at([(1024 * (S + n - 1) + 1000, 1024 * (S + n - 1) + 1000, 512)], d)])
+    ea = three_ways(lambda: load(MLMap, a, cfg), [(pts, OCC, C), (pts, INFL, C), (pts, OCC | INFL, C)], rw.block_classes(a, n), d)
+    win = (1, (1, 1 - C, 1), (0, -1024 * C, 0), C * C << 20)
+    assert one(ea[0])[:4] == win and one(ea[2])[:4] == win             # y decides between (1, 1 - C, 1) and (1, 1 + C, 1), and before x
+    assert one(ea[1])[:4] == (1, (1 - C, 1, 1), (-1024 * C, 0, 0), C * C << 20)  # x decides
+    assert [one(e, 3)[0] for e in ea] == [0, 0, 0]                     # nothing in range
+    eb = three_ways(lambda: load(MLMap, b, cfg), [(pts, OCC, C), (pts, OCC | UNKNOWN, C)], rw.block_classes(b, n), d)
+    assert one(eb[0])[:4] == (1, (1, 1, 1 - C), (0, 0, -1024 * C), C * C << 20)  # z decides; (1 + C, 2, 1) is outside the ball
+    assert one(eb[0], 4)[:3] == (1, (S + n, S + n, 0), (536, 536, 0))    # the first cell of its block, a part of one to four cells at C 1

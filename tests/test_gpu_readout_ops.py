@@ -30,7 +30,6 @@ SEEDS = [2, 7, 12]  # subbox_n 3, 7, 16 and subbox_d_xyz 0.15, 0.05, 0.15 (geome
 STEPS = 60
 OCC, INFL, UNKNOWN, SIGNED = 1, 2, 4, 8  # (the same bits in mlm_export_esdf, mlm_export_reach, mlm_export_clusters, mlm_query_rays)
 FRONTIER = 16
-KINDS = ("window", "esdf", "rays", "reach", "clusters")
 GEOM_N, GEOM_D = (2, 3, 4, 5, 7, 8, 10, 16), (0.05, 0.1, 0.15, 0.2, 0.25)
 MAX_BLOCKS = 8  # the pool the handle starts with: every sequence outgrows it
 EDGE = 22  # longest box edge, voxels
@@ -73,6 +72,8 @@ def grow(lo, dims, g):
 
 
 class Sequence:
+    KINDS = ("window", "esdf", "rays", "reach", "clusters")  # (a subclass adds kinds, their methods and their weights in OPS)
+
     def __init__(self, cfg, seed, gpu, cpu):
         self.cfg, self.seed, self.gpu, self.cpu = cfg, seed, gpu, cpu
         self.n, self.d = cfg.subbox_n, cfg.subbox_d_xyz
@@ -84,13 +85,13 @@ class Sequence:
         self.is_async, self.fresh, self.imports, self.stream_ops = False, False, 0, 0
         self.cap0 = MAX_BLOCKS if gpu is None else max(MAX_BLOCKS, gpu.frame_stats()["block_capacity"])
         self.dump = None  # the oracle's block dump and the class function of the map as it is
-        self.boxes = []
+        self.noted = []  # every box of the sequence
         self.streams, self.on_stream = None, 0
-        self.calls = {k: 0 for k in KINDS}
-        self.unsynced = {k: 0 for k in KINDS}   # read-outs whose immediately preceding operation was a map change in async mode
-        self.in_async = {k: 0 for k in KINDS}
-        self.after_growth = {k: 0 for k in KINDS}
-        self.rich = {k: 0 for k in KINDS}       # calls with a non-trivial answer
+        self.calls = {k: 0 for k in self.KINDS}
+        self.unsynced = {k: 0 for k in self.KINDS}   # read-outs whose immediately preceding operation was a map change in async mode
+        self.in_async = {k: 0 for k in self.KINDS}
+        self.after_growth = {k: 0 for k in self.KINDS}
+        self.rich = {k: 0 for k in self.KINDS}       # calls with a non-trivial answer
         self.grew_in_flight = 0                 # pool growth between the start of an async batch and the end of the read-out behind it
         self.host_rays = self.pinned = self.straddle = self.thin = self.absent = self.skipped = 0
 
@@ -162,7 +163,7 @@ class Sequence:
         return lo, dims
 
     def note(self, lo, dims):
-        self.boxes.append((lo, dims))
+        self.noted.append((lo, dims))
         self.straddle += any(lo[a] < 0 < lo[a] + dims[a] for a in range(3))
         self.thin += 1 in dims
         g = np.unique(np.floor_divide(grid(lo, dims), self.n), axis=0)
@@ -479,8 +480,10 @@ class Sequence:
 
     def readout(self, kind, lo, dims, small_rays=False):
         self.log.append(kind)
-        {"window": self.window, "esdf": self.esdf, "reach": self.reach, "clusters": self.clusters,
-         "rays": lambda lo, dims: self.rays(lo, dims, small_rays)}[kind](lo, dims)
+        if kind == "rays":
+            self.rays(lo, dims, small_rays)
+        else:
+            getattr(self, kind)(lo, dims)
 
     # ---- the sequence ---------------------------------------------------------------------------------------------------------
     OPS = {"dense": 0.11, "sampled": 0.05, "growbatch": 0.06, "setfree": 0.05, "inflate": 0.06, "import": 0.04, "mode": 0.05, "stream": 0.03,
@@ -490,13 +493,13 @@ class Sequence:
         names, p = list(self.OPS), np.array(list(self.OPS.values()))
         # the first frames of the map arrive as an asynchronous batch, a read-out right behind it: the pool of MAX_BLOCKS blocks grows
         # while the batch is in flight, and the read-out must see the planes where they have moved
-        self.behind_a_batch(KINDS[self.seed % len(KINDS)])
+        self.behind_a_batch(self.KINDS[self.seed % len(self.KINDS)])
         for op in ("mode", "dense", "dense", "import"):
             self.log.append(op)
             getattr(self, "op_" + op)()
         for self.step in range(steps):
             op = str(self.rng.choice(names, p=p / p.sum()))
-            if op in KINDS or op == "rays_small":
+            if op in self.KINDS or op == "rays_small":
                 self.readout("rays" if op == "rays_small" else op, *self.box(), small_rays=op == "rays_small")
             else:
                 self.log.append(op)
@@ -504,22 +507,26 @@ class Sequence:
             if self.step == steps // 2:
                 self.pin_classes(*self.box())
         self.step = steps
-        for kind in KINDS:  # every kind once directly behind an asynchronous batch
+        for kind in self.KINDS:  # every kind once directly behind an asynchronous batch
             self.behind_a_batch(kind)
+        self.before_the_tail()
         # the tail: the largest box of the sequence through every read-out, the smallest ones, the largest again
-        big = max(self.boxes, key=lambda b: b[1][0] * b[1][1] * b[1][2])
+        big = max(self.noted, key=lambda b: b[1][0] * b[1][1] * b[1][2])
         tiny = [(list(big[0]), [1, 1, 1]), ([big[0][0] + 1, big[0][1], big[0][2] + 2], [1, big[1][1], 1])]
         for i, (lo, dims) in enumerate([big] + tiny + [big]):
             if i == 3:
                 self.log.append("stream")
                 self.op_stream()
             self.note(lo, dims)
-            for kind in KINDS:
+            for kind in self.KINDS:
                 self.readout(kind, lo, dims, small_rays=dims[0] == 1)
         self.pin_classes(*big)
 
+    def before_the_tail(self):
+        """(a subclass's own fixed steps)"""
+
     def check_not_vacuous(self):
-        for k in KINDS:
+        for k in self.KINDS:
             assert self.calls[k] >= 4 and self.unsynced[k] >= 1 and self.in_async[k] >= 1 and self.after_growth[k] >= 1 and self.rich[k] >= 1, \
                 self.ctx(f"{k}: calls {self.calls[k]}, unsynced {self.unsynced[k]}, async {self.in_async[k]}, after growth {self.after_growth[k]}, "
                          f"non-trivial {self.rich[k]}")

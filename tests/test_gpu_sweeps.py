@@ -427,3 +427,153 @@ def test_arguments_and_single_outputs(mods, knobs):
         assert call(a=a8, c=c8, n=8, r=16, o=o8) == 0 and gpu.frame_stats()["n_host_queries"] == before and o8[0].tolist() == [1] * 8
         assert call(a=a8, c=c8, n=5, r=16, o=o8) == 0 and gpu.frame_stats()["n_host_queries"] == before + 5 * mirror
         gpu.close()
+
+
+# ---- the slot cache's bound in small-block geometries ---------------------------------------------------------------------------
+BOUNDARY = [(2, 4), (2, 5), (3, 6), (3, 7), (4, 8), (4, 9), (7, 14), (7, 15), (16, 16), (16, 1)]  # (subbox_n, radius): 2 n is the largest cached radius
+DB = 0.15
+
+
+def boundary_rays(n):
+    """(start voxel, end voxel) of an axis-parallel and a diagonal ray, each in positive space, in negative space and across voxel 0;
+    every one crosses a block boundary"""
+    L, m = n + 2, n // 2 + 2
+    h = (m + 1) // 2
+    return [((1, 1, 1), (1 + L, 1, 1)), ((-2, -2, -2), (-2, -2 - L, -2)), ((0, 1, -L // 2 - 1), (0, 1, L - L // 2)),
+            ((1, 1, 1), (1 + m, 1 + m, 1 + m)), ((-2, -2, -2), (-2 - m, -2 - m, -2 - m)), ((-h, h, -h), (-h + m, h - m, -h + m))]
+
+
+def boundary_map(n):
+    """the FREE blocks of a cube wide enough for every ray and the largest ball of this subbox_n, less one absent block (dead ahead of
+    the first ray) and with one released block (dead ahead of the second): (free blocks, absent key, released key)"""
+    R = max(r for k, r in BOUNDARY if k == n)
+    B = -(-(R + n + 6) // n)
+    absent, released = ((n + 3) // n, 0, 0), (-1, (-n - 4) // n, -1)
+    free = [g for g in blocks(-B, B) if g != absent and g != released]
+    return free, absent, released
+
+
+def place(path, r, n, kind, forbidden):
+    """an obstacle voxel for a ray with the path voxels `path` and the path index at which it stops the ray (None: the ray passes), or
+    None where the geometry has no such voxel.  exact: at squared distance r^2 of the stop voxel; outside: r^2 + 1 from the nearest
+    path voxel; layer: in the block layer that enters the box around the ball at the stop's own step; corner: two blocks away from
+    the stop voxel's block on as many axes as the ball allows (the corner of a box of five blocks per axis); sixth_lo / sixth_hi: in
+    the first / last block layer of a box that is six blocks wide on some axis (a torus of five would hold both in one cell)"""
+    P = np.array(path, dtype=np.int64)
+    off, sq = sr.ball(r)
+    blk = lambda v: np.floor_divide(v, n)
+    ok = lambda c: ~np.array([(blk(c) == np.array(g)).all(axis=-1) for g in forbidden]).any(axis=0)
+    clear_before = lambda c, k: ((c[:, None, :] - P[None, :k, :]) ** 2).sum(axis=2).min(axis=1) > r * r  # no path voxel before k within r
+
+    if kind == "outside":
+        a = np.arange(-r - 1, r + 2)
+        cube = np.stack(np.meshgrid(a, a, a, indexing="ij"), axis=-1).reshape(-1, 3) + P[len(P) // 2]
+        dist = ((cube[:, None, :] - P[None, :, :]) ** 2).sum(axis=2).min(axis=1)
+        cand = cube[(dist == r * r + 1) & ok(cube)]
+        return (tuple(int(x) for x in cand[0]), None) if len(cand) else None
+    best = None
+    for k in range(len(P) - 1, 0, -1):
+        step = P[k] - P[k - 1]
+        a = int(np.flatnonzero(step)[0])
+        s = int(step[a])
+        c = P[k] + off
+        if kind == "exact":
+            c = c[sq == r * r]
+        if kind == "exact" and k > 2 * len(P) // 3:
+            continue
+        c = c[ok(c)]
+        if kind != "layer" and len(c):
+            c = c[clear_before(c, k)]
+        if kind.startswith("sixth"):
+            lo_g, hi_g = blk(P[k] - r), blk(P[k] + r)
+            for b in np.flatnonzero(hi_g - lo_g == 5):
+                cb = c[blk(c)[:, b] == (lo_g if kind == "sixth_lo" else hi_g)[b]] if len(c) else c
+                if len(cb):
+                    return tuple(int(x) for x in cb[0]), k
+        elif kind == "exact":
+            if len(c):
+                return tuple(int(x) for x in c[0]), k
+        elif kind == "layer":
+            lead = (P[k][a] + s * r) // n
+            if lead != (P[k - 1][a] + s * r) // n:  # (no earlier path voxel reaches this layer)
+                c = c[blk(c)[:, a] == lead]
+                if len(c):
+                    return tuple(int(x) for x in c[-1]), k
+        elif kind == "corner" and len(c):
+            wide = (blk(P[k] + r) - blk(P[k] - r) == 4) | ((2 * r - 1) // n + 2 > 5)  # (five blocks wide where the box is cached at all)
+            score = ((np.abs(blk(c) - blk(P[k])) == 2) & wide).sum(axis=1)
+            i = int(np.argmax(score))
+            if score[i] >= 1 and (best is None or score[i] > best[2]):
+                best = (tuple(int(x) for x in c[i]), k, int(score[i]))
+    return best[:2] if best else None
+
+
+def boundary_scenes(n, r):
+    """[(what, block dump, ray index, flags, the path index of the stop or None, the obstacle or None)]"""
+    free, absent, released = boundary_map(n)
+    rays = boundary_rays(n)
+    scenes = []
+    for i, (a, b) in enumerate(rays):
+        path = [v for v, _ in rw.path(*rw.valid(centre(a, DB)[0], centre(b, DB)[0], DB))[0]]
+        for j, kind in enumerate(("layer", "corner", "exact", "outside", "sixth_lo", "sixth_hi")):
+            got = place(path, r, n, kind, {absent, released})
+            if got is None:
+                continue
+            o, k = got
+            inflated = (i + j) % 2 == 1  # (every other obstacle is an inflated voxel, met with OCC | INFL)
+            d = dump([] if inflated else [o], free, inflated=[o] if inflated else (), released={released: b"f"}, n=n)
+            # (the scene in full: the ray's voxels, the one obstacle among FREE blocks, where it stops the ray)
+            stop = "passes" if k is None else f"stops at path index {k}, voxel {tuple(int(x) for x in path[k])}"
+            scenes.append((f"ray {i} {kind} {o}: {'inflated' if inflated else 'OCCUPIED'} voxel {o}, ray from voxel {a} to {b} {stop}, absent block {absent}, "
+                           f"released block {released}", d, i, OCC | INFL if inflated else OCC, k, o))
+    plain = dump([], free, released={released: b"f"}, n=n)
+    scenes += [(f"ray {i} absent block {absent}: ray from voxel {a} to {b}, no obstacle", plain, i, UNKNOWN, None, None) for i, (a, b) in enumerate(rays)]
+    solid = dump([], free, released={released: b"o"}, n=n)
+    scenes += [(f"ray {i} released block {released}, OCCUPIED: ray from voxel {a} to {b}, no other obstacle", solid, i, OCC, None, None) for i, (a, b) in enumerate(rays)]
+    return scenes, rays, absent, released
+
+
+@pytest.mark.parametrize("n,r", BOUNDARY)
+def test_sweep_cache_boundary_geometries(mods, n, r):
+    """subbox_n 2, 3, 4 and 7 at the largest radius whose block box stays in the slot cache (2 n: the box is exactly five blocks wide,
+    an entering layer takes the torus cells of the leaving one) and at the next one (probed per lane), 16 at radius 16 and 1.  One
+    obstacle per scene — in the block layer that enters at the step of the stop, in the corner block of the box, on the sphere, just
+    outside it, and at radius 2 n + 1 in the first and in the last layer of a box six blocks wide — for six rays; then no obstacle at
+    all: the absent block under UNKNOWN, and the released block once it is OCCUPIED.  Every scene is imported into the same two
+    handles in turn: mirror and device tensors on one, the staged kernel on the other.  A failure names its scene in full (ray,
+    obstacle, stop, subbox_n, radius): dump([obstacle], boundary_map(n)[0], n=n) and one query_sweeps reproduce it."""
+    import torch
+
+    MLMap, _ = mods
+    cfg = SX.with_(subbox_n=n, subbox_d_xyz=DB)
+    scenes, rays, absent, released = boundary_scenes(n, r)
+    p0, p1 = centre([a for a, _ in rays], DB), centre([b for _, b in rays], DB)
+    exp, kinds = [], set()
+    for what, b, i, f, k, o in scenes:
+        e = sr.sweep_all(p0[i:i + 1], p1[i:i + 1], DB, r, rw.block_classes(b, n), (f,))[0][f]
+        exp.append(e)
+        if o is not None and k is not None:
+            assert one(e)[0] == 1 and one(e)[2] == k and one(e)[3] == o, (what, one(e))
+            kinds.add(what.split()[2])
+        elif o is not None:
+            assert one(e)[0] == 0, (what, one(e))
+            kinds.add("outside")
+    assert {"layer", "exact", "outside"} <= kinds and ("corner" in kinds) == (2 * n <= r + 1), kinds  # (a block two away lies in the ball from r = 2 n - 1 on)
+    assert ({"sixth_lo", "sixth_hi"} <= kinds) == (r == 2 * n + 1) and (r == 2 * n + 1 or not {"sixth_lo", "sixth_hi"} & kinds), kinds
+    in_block = lambda e, g: one(e)[0] == 1 and tuple(np.floor_divide(one(e)[3], n).tolist()) == g
+    assert in_block(exp[-12], absent) and in_block(exp[-5], released), (one(exp[-12]), one(exp[-5]))  # (the first ray, the second ray)
+    zeros = np.zeros(scenes[0][1]["occ"].shape, np.float32)
+    for staged in (False, True):
+        gpu = load(MLMap, scenes[0][1], cfg)
+        if staged:
+            gpu.set_host_mirror_limit(0)
+        for (what, b, i, f, k, o), e in zip(scenes, exp):
+            gpu.import_blocks(b["keys"], zeros, b["occ"], b["infl"], b["collapsed"])
+            a, c = np.ascontiguousarray(p0[i:i + 1]), np.ascontiguousarray(p1[i:i + 1])
+            if staged:
+                sr.assert_equal(gpu.query_sweeps(a, c, r, **kw(f)), e, f"staged kernel n={n} r={r} {what}")
+            else:
+                sr.assert_equal(through_mirror(gpu, a, c, r, f, DB), e, f"mirror n={n} r={r} {what}")
+                sr.assert_equal(to_numpy(gpu.query_sweeps(torch.from_numpy(a).cuda(), torch.from_numpy(c).cuda(), r, **kw(f))), e, f"device tensors n={n} r={r} {what}")
+        assert staged == (gpu.frame_stats()["n_host_queries"] == 0)
+        gpu.close()
