@@ -10,12 +10,6 @@ extern "C" int mlm_sort_pairs_u64_u32(void *temp, size_t temp_bytes, const unsig
 
 namespace {
 
-#ifndef MLM_SETS
-#define MLM_SETS 3
-#endif
-// MLM_SETS slot sets: batches in flight (one being filled, one in Stage A, one draining).  Measured on config 2 with the sector
-// path: round 2 44.7k frames/s with 2, 48.4k with 3, 45.3k with 4; round 3 74.0k / 80.9k / 78.7k
-
 struct KernelTime {
     const char *name;
     hipEvent_t a, b;
@@ -96,17 +90,12 @@ struct MlmSlot {
 
 // Host-resident mirror of the map for small query batches (mlm_mirror.h): pinned host planes that mirror the block pool slot by
 // slot, a host table block key -> slot, and the record of what changed on the device since the last refresh.
-struct MlmMirror {
-    bool enabled = true;           // knob "mirror" = 0: every query runs as a kernel
+struct MlmMirror : MlmMirrorLimits { // (the knobs' limits: mlm_plan.h)
     bool alloc_failed = false;     // the pinned planes could not be allocated: disabled for good, queries run as kernels
-    int max_clean = 256;           // largest batch answered on the host while the mirror is up to date (knob "mirror_max") ...
-    int max_dirty = 32;            // ... and while it needs a refresh first (a large batch is then cheaper as one kernel)
     // mlm_query_rays: a ray costs a walk, not one lookup, so a batch of rays is answered on the host when it has at most a quarter
     // as many rays as the limits above allow positions (64 / 8 by default; "mirror_max" scales both) AND its paths together have at
     // most kRayMirrorSteps voxels (known from the end points before anything is walked); everything else is one kernel
     size_t cap = 0;                // blocks the planes hold
-    size_t max_bytes = (size_t)1 << 30; // most pinned host memory the planes may take (mlm_set_host_mirror_limit; knob "mirror_mb"): a map
-                                   // that needs more is queried by kernels only (over_limit) — nothing is pinned behind the caller's back without bound
     bool over_limit = false;
     float *lo = nullptr;           // [cap * cells] pinned, device-visible
     uint8_t *occ = nullptr, *infl = nullptr; // [cap * cells]
@@ -138,7 +127,6 @@ constexpr int kRayChunk = 1 << 20;           // rays per launch of k_rays: bound
 // window: the most voxels the growth can read, known before anything is read — sum to at most kBoxMirrorVoxels
 constexpr long long kBoxMirrorVoxels = 16384;
 constexpr int kRenderChunk = 1 << 20;        // most pixels per launch of k_render: bounds the staging of host outputs (19 bytes per pixel)
-constexpr int kRenderTileDefault = 2;        // k_render's tile: 0 64 x 1, 1 16 x 4, 2 8 x 8 (profiles/render_rate.json)
 constexpr int kBoxChunk = 1 << 18;           // boxes per launch of k_boxes: bounds the staging of host inputs / outputs (82 bytes per box)
 constexpr unsigned int kBoxGrid = 8192;      // most workgroups of k_boxes (a wave per box, grid-stride): 32 768 waves, four times what the chip holds
 // mlm_query_nearest: a batch in host memory is answered on the host when it has at most as many points as mlm_query_boxes allows
@@ -171,7 +159,8 @@ constexpr long long kScoreGridTarget = 1024;
 // k_chain_lanes' cell-per-lane replay (measured: 128 -> 201 us for a dense VGA frame with the chains in k_rank)
 constexpr unsigned int kFusedChainStrips = 16;
 static inline double mlm_now_us() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-struct mlm_handle {
+struct mlm_handle : MlmHandlePlan { // (MlmHandlePlan, mlm_plan.h: the members mlm_create's plan decides)
+    using SlotCaps = MlmSlotCaps;
     int device = 0;
     hipStream_t stream = nullptr; // main stream: Stage B/C (ordered across frames), queries
     bool own_stream = true;
@@ -180,9 +169,6 @@ struct mlm_handle {
     MlmDev P{};                   // template: constants + shared pointers
     std::vector<MlmSlot> slots;
     int last_slot = 0;
-    Q4 q_bs{};
-    D3 t_bs{};
-    std::vector<float> odds_table;
     std::vector<void *> allocs;
     double *d_qpos = nullptr; // query positions
     void *d_qout = nullptr;
@@ -217,9 +203,6 @@ struct mlm_handle {
     // mlm_score_poses: the device copy of a distance field handed over in host memory (4 bytes per voxel)
     void *d_score_field = nullptr;
     size_t score_field_bytes = 0;
-    int score_chunk = 0; // points per chunk of k_score (knob "score_chunk"; 0: automatic)
-    unsigned int rays_grid = 1024; // most workgroups of k_rays (knob "rays_grid"): 2^20 rays are four per lane
-    int render_tile = kRenderTileDefault; // (knob "render_tile")
     // sort buffers (rehash frames only)
     unsigned long long *sk_in = nullptr, *sk_out = nullptr;
     uint32_t *sv_in = nullptr, *sv_out = nullptr;
@@ -230,7 +213,6 @@ struct mlm_handle {
     // clear() (map_awareness.cpp:178) keeps both, so they persist across frames.
     size_t hit_n_bkt = 1;
     std::__detail::_Prime_rehash_policy hit_pol;
-    size_t max_buckets = 0;
     // the same for awareness_map->miss_idx_set (only tracked in frontier mode, where its iteration order matters)
     size_t miss_n_bkt = 1;
     std::__detail::_Prime_rehash_policy miss_pol;
@@ -244,11 +226,6 @@ struct mlm_handle {
     std::vector<MlmSlot *> pending;
     int next_seq = 0;
     int cur_set = 0;
-    unsigned int expand_block = 256;         // threads per k_expand_nodes block (128 and 64 measured slower)
-    unsigned int sort_block = 256;           // threads per k_sort_contribs<1024> block
-    unsigned int sort_grid = 256;            // blocks per frame of k_sort_contribs<1024> in a batch
-    unsigned int rank_grid = 128;            // blocks per frame of k_rank in a batch (config 2 with two cells per wave: 87.5k frames/s, 64: 87.7k, 256: 86.4k,
-                                             // 512: 84.7k; MLM_RANK_GRID)
     // Sector-path handles: the three large buffers only the cell-table Stage A uses — the block slices of contribution nodes sized
     // for its LDS overflow, the (block, cell) pairs and the node lists — exist ONCE per handle instead of once per slot; a
     // cell-table Stage A (a frame's fall-back, or a batch submitted while the sector path backs off) then runs one frame at a
@@ -258,19 +235,10 @@ struct mlm_handle {
     size_t map_bytes = 0;                    // ... of it the map, its tables and the buffers shared by all frame slots
     bool debug_alloc = getenv("MLM_DEBUG_ALLOC") != nullptr;
     size_t alloc_bytes = 0;                  // device memory the handle holds (MLM_DEBUG_CREATE prints it)
-    unsigned int chain_grid = 0;             // blocks per frame of k_chain_lanes (0: from the last confirmed frame's ranked cells; MLM_CHAIN_GRID)
-    unsigned int collect_grid = 16;          // blocks per sub-list of k_collect_hits (grid-stride loop)
-    unsigned int sc_block = 64;              // threads per block of the per-frame apply kernels: single-wave blocks are placed as soon as any wave
-                                             // slot frees between Stage A's workgroups (config 2: 66.5k frames/s, 128: 64.1k, 256: 57.2k)
-    bool sc_grid_fixed = false;              // MLM_SC_GRID given: do not adapt
-    unsigned int sc_grid = 80;               // blocks per list of k_apply_voxelize (grid-stride loops; 40..120 measured equal, 160 3 % slower)
     std::string timed_kernel = "k_bin_points"; // the kernel bracketed in timing mode 3 ...
     unsigned int timed_every = 1, timed_count = 0; // ... on every timed_every-th launch
-    int n_sets = MLM_SETS;     // slot sets in use (2 when three do not fit the device memory)
     int set_pending[MLM_SETS] = {};
     bool async_mode = false;
-    int cu_split = 0;
-    int cu_reserve = 0;
     uint16_t *d_img_set[MLM_SETS] = {};      // per slot set: device buffer of a whole batch of host frames that arrive back to back
     size_t img_set_cap[MLM_SETS] = {};       // (mlm_integrate_depth_batch: one upload per batch)
     float *d_f32 = nullptr;                  // staging of a 32FC1 frame (mlm_integrate_callback)
@@ -287,7 +255,6 @@ struct mlm_handle {
     hipEvent_t batch_done[MLM_SETS] = {};
     hipEvent_t inputs_ready = nullptr;       // caller-supplied stream only: orders Stage A after the caller's work on it
     MlmGlobal *h_gb[MLM_SETS] = {}; // pinned snapshots of P.g taken at the end of each batch
-    bool use_sectors = true;   // Stage A by azimuth sector (mlm_kernels_sector.h); MLM_SECTORS=0: the cell-table path
     struct ExBatch {
         int set, n;
         bool bc_enqueued;
@@ -297,32 +264,18 @@ struct mlm_handle {
     MlmSlot *ex_tail = nullptr; // frontier mode: the frame whose miss phase + release scan ride with the next frame's ordering launches
     int ex_tag = 0;            // frontier mode: per-frame tag of the bucket-first tables (k_ex_order_min)
     unsigned int ex_frame_no = 0; // frontier mode: frames submitted (MlmFrame::pad2)
-    int sector_backoff_len = 16; // (MLM_SEC_BACKOFF)
     int sector_backoff = 0;    // batches that go straight to the cell-table path after a sector overflow (the scene does not fit the sectors' LDS tables: do not pay for both paths)
     long long n_sector_fallbacks = 0; // frames redone by the cell-table path because a sector's LDS tables overflowed
     std::recursive_mutex mu;   // serialises the entry points of this handle (see MLM_LOCK)
     long long n_spec_miss = 0; // frames replayed because the speculative "no rehash" plan did not hold
-    bool pool_grow = true;     // the block pool grows on demand (MLM_POOL_GROW=0: fixed at mlm_limits.max_blocks, MLM_ERR_CAPACITY when full)
-    size_t frame_block_bound = 0; // most blocks one frame can create
-    unsigned int tile_lds_bytes = 0; // dynamic LDS of k_tile
     int ov_heavy = 0;                // confirmed batches in a row whose last frame had many overflowed columns
     bool want_widen = false;         // ... the cell table is doubled before the next submission (widen_sec_tab)
-    int sec_threads = 512;           // threads of a column's workgroup (k_sector<.., 256 | 512>; MLM_SEC_THREADS)
     double clk[8] = {}, clk_t = 0;   // host clocks of the single-frame path (mlm_debug_clocks): microseconds per section, summed over the calls
     MlmExOrder ex_om{};              // frontier mode: what the next lone frame's k_rank needs to run the bucket-first pass (explore_spec_begin; on = 0: nothing)
     bool ex_om_launched = false;     // ... and whether the frame's Stage A took it along (else explore_stage_bc_spec launches k_ex_order_min)
     unsigned int wait_ticket = 0;    // nonzero: the single-frame graph in flight ends by writing this into h_g->pad (pinned)
-    unsigned int single_rank_grid = 256;   // workgroups of a lone frame's k_rank<true> (ranking + chains; knob "single_rank_grid")
-    unsigned int single_chain_grid = 64;  // workgroups of a lone frame's k_chain_lanes: 256 waves x 64 cells cover a dense VGA frame's ranked cells in one turn
-    unsigned int single_apply_grid = 256; // workgroups of k_apply_single: a VGA frame's ~33 k voxel records, one per thread (more: in turns)
-    unsigned int tile_grid = 0;      // workgroups of k_tile per frame of a batch: they walk the frame's touched tiles (MLM_TILE_GRID)
-    unsigned int apply_lds_bytes = 0; // dynamic LDS of k_apply_tiles (mlm_apply_lds): 5 bytes per voxel of a tile, its layer and block tables
-    unsigned int big_grid = 256;     // workgroups of k_sector_big per batch: one per CU (MLM_BIG_GRID)
-    int ex_spec = 1;                 // frontier mode: a synchronous frame's map-dependent part is enqueued before its counts are known (explore_stage_bc_spec);
-                                     // knob "ex_spec": 0 never, 2 with thresholds of zero (every frame misses: the test of the way back)
     int big_armed = 0;               // batches (single frames) for which the pass with the large cell table stays scheduled
     int big_armed_from = 0;          // first frame (sequence number; frontier mode: frame number) submitted after it was scheduled
-    int big_arm_len = 64;            // (MLM_BIG_ARM: 0 never schedules it)
     // Single frames in synchronous mode — the reference's own call pattern, one frame per depth callback (mlmap.cpp:463-507) — are
     // submitted as ONE replay of a HIP graph on the main stream (parameter upload, counter reset, six kernels, counter
     // read-back) instead of a dozen launches and copies spread over two streams: the call's cost is launch latency, not work.
@@ -336,9 +289,6 @@ struct mlm_handle {
         hipGraphExec_t exec;
     };
     std::vector<SingleGraph> graphs;
-    bool use_graph = true;       // (MLM_GRAPH=0: always the general submission)
-    bool no_spread = false;      // the noise model never spreads a hit beyond its own cell (3 sigma < 1 cell everywhere, e.g. the reference's default
-                                 // depth_noise_coe 1e-6): k_chain_lanes has nothing to do and is not launched
     hipStream_t last_upload = nullptr; // the stream the current call's inputs were uploaded on (run_slots orders Stage A behind it)
     hipEvent_t upload_ev = nullptr;
     hipEvent_t host_read_ev = nullptr; // asynchronous mode: recorded behind the copies that read a caller's host buffer (borrowed_mark / borrowed_wait)
@@ -356,14 +306,6 @@ struct mlm_handle {
     MlmNode *fb_bnodes = nullptr, *fb_nodes = nullptr; // sector-path handles: the cell-table path's shared buffers
     MlmPair *fb_pairs = nullptr;
     MlmMirror mir;               // host mirror for small query batches (mlm_mirror.h)
-    // Frame slots sized by NEED (sector-path handles, not frontier mode): the per-frame lists whose worst case is
-    // "every awareness cell is a multi-kind hit" start at what a camera frame of max_points pixels needs and are doubled at a
-    // drained point when a frame's Stage A runs out of room (grow_slots, like grow_pool for the block pool).  The cell-table path,
-    // which a frame falls back to one at a time, gets ONE full-size set of those lists per handle, allocated at its first use.
-    bool need_sized = false;
-    struct SlotCaps {
-        size_t hl = 0, mt = 0, vh = 0, rec = 0, refs = 0, sub = 0, sbkt = 0;
-    } caps_worst, caps_now;
     long long n_slot_grows = 0;
     std::vector<std::pair<void *, size_t>> regrow_trash; // lists replaced by resize_slots, freed once the copies into the new ones are through
     struct CtFull { // the cell-table path's full-size lists (ensure_ct_full)

@@ -16,6 +16,8 @@
 #include <utility>
 #include <vector>
 
+#include "mlm_types.h"
+
 #ifdef __HIPCC__
 #define MLM_HD __host__ __device__
 #else
@@ -119,6 +121,81 @@ MLM_HD inline MlmApplyLds mlm_apply_lds(uint32_t edge, uint32_t nz, uint32_t n) 
     L.ztab = (5u * nv + 3u) & ~3u;
     L.blk = L.ztab + 4u * nz;
     L.total = (L.blk + 4u * cx * cx * cz + 15u) & ~15u;
+    return L;
+}
+
+// ---- LDS layouts and limits of the sector path's kernels (mlm_kernels_sector.h): pure layout arithmetic, shared by the kernels, by the
+// plan mlm_create runs with (mlm_plan.h) and by the CPU tests
+#define MLM_SEC_THREADS 512 // threads of a column's workgroup (k_sector also exists with 256: MlmDev::sec_tab <= 1024)
+#define MLM_SEC_CHUNKS 256  // chunk descriptors staged per pass of k_sector (a column of a VGA frame has ~50)
+// one hit cell of the column while k_sector works on it (16 bytes: a 2 048-entry table is 32 KB of LDS)
+struct MlmSecCell {
+    uint32_t key;   // low 16 bits: z * nRho + rho (nZ * nRho < 65 536), MLM_NIL = empty; high 16 bits, set once the column's lists are
+                    // built (cells that need their order): where the cell's references start, in units of MLM_SEC_REF_ALIGN references
+                    // from the column's first
+    uint32_t tmin;  // first-touch time (min over contributions); a cell that needs its order: once the hit list has taken the time, the cell's
+                    // origin for the reference pass (mlm_sec_origin, mlm_sector_refs.h)
+    uint32_t kg;    // kinds (bits 0..20) | (record, kind) references of the cell << 21: counted up while the contributions are booked,
+                    // counted down while the references are written (the count hands every writer its own stretch of the cell's segment)
+    uint32_t cnt;   // contributions
+};
+#define MLM_SEC_REF_ALIGN 4u // a cell's references start at a multiple of this many (16 bytes) from the column's first
+#ifndef MLM_SEC_CNT_BITS
+#define MLM_SEC_CNT_BITS 21 // MlmSecCell::cnt: contributions in the low bits (mlm_limits.max_points < 2^21 on this path: a full-HD depth image),
+                            // the sum of their strengths above them (mod 2^11: a wrap only makes a cell look weaker than it is)
+#endif
+MLM_HD inline __attribute__((always_inline)) uint32_t mlm_sec_strength(float a) { return a >= 0.875f ? 3u : (a >= 0.75f ? 2u : (a >= 0.5f ? 1u : 0u)); }
+// LDS plan of k_sector (dynamic): the host computes the same offsets
+struct MlmSecLds {
+    uint32_t tab, miss, odds, sigma, rays, occ, multi, chunk, ray_p0, vox, aux, total;
+};
+// n_miss: words of the column's miss table (bit mask: nZ * RW; frontier mode keeps insertion times: nZ * nRho)
+MLM_HD inline MlmSecLds mlm_sec_lds(uint32_t TAB, uint32_t n_miss, uint32_t n_rho, uint32_t n_z, bool explore) {
+    MlmSecLds L;
+    uint32_t o = 0;
+    L.tab = o;      o += TAB * (uint32_t)sizeof(MlmSecCell);
+    {
+        // staged chunk descriptors of the record passes; later the list of occupied table entries (L.occ)
+        uint32_t b = 2u * MLM_SEC_CHUNKS * 4u;
+        if (b < TAB * 2u) b = TAB * 2u;
+        L.chunk = o;
+        o += (b + 15u) & ~15u;
+    }
+    L.odds = o;     o += ((2u * MLM_DIFF_RANGE + 1u) * n_rho + 3u) & ~3u; // a byte per entry of the odds table: its strength
+    L.sigma = o;    o += ((n_rho + 3u) & ~3u) * 4u;
+    L.miss = o;     o += ((n_miss + 3u) & ~3u) * 4u;
+    L.rays = o;     o += TAB * 2u;                       // table entries that start a ray
+    L.occ = L.chunk;                                     // occupied table entries (= the column's unique hits): in the chunk
+                                                         // staging, idle between the first record pass and the second
+    L.multi = o;    if (explore) o += TAB * 4u;          // frontier mode: per table entry, the first point whose hit centre is the cell
+    L.ray_p0 = o;   if (explore) o += TAB * 4u;          // frontier mode: first point of every ray start
+    o = (o + 15u) & ~15u;
+    L.vox = o;      o += (n_rho + n_z) * 16u;            // world voxel per axis: x, y by rho; z by z (see k_sector)
+    L.aux = o;      o += n_rho * 24u;                    // per tile run along rho: tile, first rho, hits (count, offset); per rho: miss cells
+                                                         // (count -> fill cursor, offset)
+    L.total = (o + 15u) & ~15u;
+    return L;
+}
+#ifndef MLM_TILE_DESC
+#define MLM_TILE_DESC 128
+#endif
+// ^ descriptors staged per pass (a tile of a VGA frame has ~15; 128 instead of 256: 3 KB of LDS, a fifth workgroup per CU)
+#define MLM_TILE_WORDS 64    // most words of a tile's column mask: MlmDev::tile_words = ceil(nPhi / 32) (sector path: nPhi <= 2048)
+#define MLM_TILE_COMBOS 2048 // most blocks a tile may overlap: limit of MlmDev::tile_combos (their pool slots are kept in LDS)
+struct MlmTileLds {
+    uint32_t cnt, place, desc, slot, ztab, total;
+};
+MLM_HD inline MlmTileLds mlm_tile_lds(uint32_t n_vox, uint32_t lv_nz, uint32_t combos) {
+    MlmTileLds L;
+    uint32_t o = 0;
+    L.cnt = o;      o += n_vox * 4u;                 // per voxel: misses | hits << 16 (the hit half doubles as the fill cursor later)
+    L.place = o;    o += n_vox * 4u;                 // per touched voxel: record index in the tile | (offset of its hits, 0xFFFF: one hit) << 16
+    o = (o + 15u) & ~15u;
+    L.desc = o;     o += MLM_TILE_DESC * 16u + MLM_TILE_DESC * 8u; // staged descriptors + exclusive prefixes (miss cells, hits)
+    L.slot = o;     o += combos * 4u + combos;           // pool slot per overlapped block + "the frame touches it" flags (combos: multiple of 4)
+    o = (o + 3u) & ~3u;
+    L.ztab = o;     o += ((lv_nz + 1u) & ~1u) * 4u;  // per grid z: block index << 8 ... (gz, cz) packed
+    L.total = (o + 15u) & ~15u;
     return L;
 }
 

@@ -182,16 +182,6 @@ __device__ __forceinline__ bool mlm_spread_active(const MlmDev &P, int rho, int 
 }
 
 
-// MlmDev::node_lds contribution nodes are buffered per k_bin_points block; MlmDev::agg_lds (a power of two) entries of
-// a block-local table merge the block's groups per awareness cell
-struct MlmCellAgg {
-    uint32_t cell;      // MLM_NIL = empty
-    uint32_t tmin;      // earliest insertion time of the block's contributions to the cell
-    uint32_t kmask;     // kinds
-    uint32_t cnt;       // contributions
-    uint32_t idx;       // dense index of the entry inside the block = its slot in the block's slice of MlmDev::pairs
-    uint32_t start_min; // explore mode: first point whose hit centre is the cell
-};
 
 // MODE 0: dense depth image, 1: indexed depth pixels, 2: explicit sensor-frame points
 // Stage A kernels are launched once per BATCH: blockIdx.z selects the frame slot (its MlmDev and MlmFrame live in
@@ -212,7 +202,6 @@ __device__ __forceinline__ void mlm_store_node(MLM_GLOBAL MlmNode *dst, const Ml
     *(MLM_GLOBAL unsigned long long *)(d + 4) = nd.mask;
 }
 
-#define MLM_RAY_LDS 128 // rays buffered per k_bin_points block (overflow: walked on the spot)
 #ifdef MLM_PHASE_PROF // diagnostic build only (tools/phase_prof.py): shader-clock cycles per phase of k_bin_points
 #define MLM_PHASE_BLOCKS 32768
 __device__ unsigned long long g_mlm_phase[MLM_PHASE_BLOCKS * 16]; // per block: no contended atomics in the measurement

@@ -1,5 +1,5 @@
 // mlm_resources.h — device memory of a handle: staging buffers, the block table + pool and its growth, the column table's widening,
-// one frame slot's scratch; the query launcher.  Part of mlmap_hip.hip.
+// one frame slot's scratch, the device stages of mlm_create; the query launcher.  Part of mlmap_hip.hip.
 #pragma once
 namespace {
 
@@ -202,12 +202,21 @@ int upload_slot_tab(mlm_handle *h) {
 // one of them is redone by the pass that has a CU to itself): double the table.  The table only exists in LDS, so this is a
 // change of parameters — at a point where nothing is in flight.  The smaller table is the default because its footprint is
 // worth 5 % of throughput on scenes that fit it.
+// the dynamic-LDS limit of k_sector's instantiations of this handle's mode (both thread counts: a frame on its own takes the
+// 512-thread one where the table allows)
+int set_sector_lds(mlm_handle *h, unsigned int bytes) {
+    const void *k256 = h->P.explore ? (const void *)k_sector<true, 256> : (const void *)k_sector<false, 256>;
+    const void *k512 = h->P.explore ? (const void *)k_sector<true, 512> : (const void *)k_sector<false, 512>;
+    HIPCHK(h, hipFuncSetAttribute(k256, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    HIPCHK(h, hipFuncSetAttribute(k512, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return MLM_OK;
+}
 int widen_sec_tab(mlm_handle *h) {
     MlmDev &P = h->P;
-    const unsigned int tab = P.sec_tab * 2u, n_miss = (unsigned int)(P.nZ * (P.explore ? P.nRho : P.RW));
-    const unsigned int lds = mlm_sec_lds(tab, n_miss, (unsigned int)P.nRho, (unsigned int)P.nZ, P.explore).total;
+    const unsigned int tab = P.sec_tab * 2u;
     const int nt = h->sec_threads == 256 && tab <= 1024u ? 256 : 512;
-    if (!h->use_sectors || tab > 2048u || tab > 4u * (unsigned int)nt || lds > 159u * 1024u || (P.sec_tab_big && tab >= P.sec_tab_big)) return MLM_OK;
+    if (!h->use_sectors || tab > 2048u || !mlm_sec_tab_fits(P, tab, nt, 159u * 1024u) || (P.sec_tab_big && tab >= P.sec_tab_big)) return MLM_OK;
+    const unsigned int lds = mlm_col_lds(P, tab);
     {
         const int rc = drain(h);
         if (rc) return rc;
@@ -220,12 +229,9 @@ int widen_sec_tab(mlm_handle *h) {
         S.P.sec_tab = tab;
         S.P.sec_lds_bytes = lds;
     }
-    if (P.explore) {
-        HIPCHK(h, hipFuncSetAttribute((const void *)k_sector<true, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIPCHK(h, hipFuncSetAttribute((const void *)k_sector<true, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    } else {
-        HIPCHK(h, hipFuncSetAttribute((const void *)k_sector<false, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIPCHK(h, hipFuncSetAttribute((const void *)k_sector<false, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    {
+        const int rc = set_sector_lds(h, lds);
+        if (rc) return rc;
     }
     for (auto &g : h->graphs) hipGraphExecDestroy(g.exec); // (the single-frame graphs hold the old launch geometry)
     h->graphs.clear();
@@ -317,7 +323,8 @@ int ensure_free_blocks(mlm_handle *h, size_t need) {
     return ensure_free_blocks_idle(h, need);
 }
 
-int alloc_slot(mlm_handle *h, MlmSlot &S, size_t index, const std::vector<float> &sigma3) {
+// (the capacities: MlmSlotPlan and the handle's caps_now, mlm_plan.h)
+int alloc_slot(mlm_handle *h, MlmSlot &S, size_t index, const MlmSlotPlan &cap) {
     S.P = h->P;
     MlmDev &P = S.P;
     int rc;
@@ -343,67 +350,39 @@ int alloc_slot(mlm_handle *h, MlmSlot &S, size_t index, const std::vector<float>
     if ((rc = dev_alloc(h, &P.mt_list, caps.mt))) return rc;
     if ((rc = dev_alloc(h, &P.mt_rec, caps.mt))) return rc;
     MLM_CT_ALLOC(mt_big, NC);
-    P.touch_cap = (unsigned int)NC;
+    P.touch_cap = cap.touch_cap;
     MLM_CT_ALLOC(touched, (size_t)MLM_RAY_LISTS * P.touch_cap);
-    size_t max_contrib = 0; // most contributions one frame can make
-    // (256 work items per bin block; image edges and short lists add blocks: twice the quotient + 256)
-    P.nb_cap = (unsigned int)((size_t)h->lim.max_points / 128 + 256);
+    P.nb_cap = cap.nb_cap;
     if ((rc = dev_alloc(h, &P.blk_stats, 4 * (size_t)P.nb_cap))) return rc;
     // (sector path: k_bin_sectors writes at most 256 records per block; the cell-table path's buffers are shared, mlm_create)
     if ((rc = dev_alloc(h, &P.bnodes, (size_t)P.nb_cap * (h->use_sectors ? 256u : P.node_lds)))) return rc;
     if (!h->use_sectors && (rc = dev_alloc(h, &P.pairs, (size_t)P.nb_cap * P.agg_lds))) return rc;
-    {
-        // most contributions one point can make: centre + (+d,-d) while d < 3*sigma(rho) (map_awareness.cpp:149)
-        int dmax = 0;
-        for (int r = 0; r < P.nRho; ++r) {
-            int d = 1;
-            while ((float)d < sigma3[r] && r + d < P.nRho && d <= MLM_DIFF_RANGE) ++d;
-            dmax = std::max(dmax, d - 1);
-        }
-        const size_t cap = (size_t)h->lim.max_points * (size_t)(1 + 2 * dmax);
-        max_contrib = cap;
-        if (cap > 0xFFFFFFF0ull) {
-            h->err = "contribution buffer too large";
-            return MLM_ERR_UNSUPPORTED;
-        }
-        // segments are padded to 16 entries; a multi-kind cell has >= 2 contributions
-        const size_t cap_pad = cap + 15 * std::min<size_t>(NC, cap / 2) + 64;
-        if (cap_pad > 0xFFFFFFF0ull) {
-            h->err = "contribution buffer too large";
-            return MLM_ERR_UNSUPPORTED;
-        }
-        P.contrib_cap = (unsigned int)caps.sub; // (<= cap_pad, the worst case: mlm_create)
-        if ((rc = dev_alloc(h, &P.contrib, caps.sub))) return rc;
-        if ((rc = dev_alloc(h, &P.subs, caps.sub))) return rc;
-        P.node_cap = (unsigned int)(cap / MLM_RAY_LISTS + 4096);
-        if (!h->use_sectors && (rc = dev_alloc(h, &P.nodes, (size_t)MLM_RAY_LISTS * P.node_cap))) return rc;
-    }
+    P.contrib_cap = (unsigned int)caps.sub;
+    if ((rc = dev_alloc(h, &P.contrib, caps.sub))) return rc;
+    if ((rc = dev_alloc(h, &P.subs, caps.sub))) return rc;
+    P.node_cap = cap.node_cap;
+    if (!h->use_sectors && (rc = dev_alloc(h, &P.nodes, (size_t)MLM_RAY_LISTS * P.node_cap))) return rc;
     if ((rc = dev_alloc(h, &P.ov_list, (size_t)P.nPhi))) return rc;
-    P.chunk_cap = P.nb_cap; // a column can at most get one run from every bin block
+    P.chunk_cap = cap.chunk_cap;
     if ((rc = dev_alloc(h, &P.col_cnt, (size_t)P.nPhi))) return rc;
     if ((rc = dev_alloc(h, &P.col_chunks, h->use_sectors ? 2 * (size_t)P.nPhi * P.chunk_cap : 2))) return rc;
     if (h->use_sectors && !P.explore) { // (frontier mode's own Stage B+C takes over after k_sector: no tiles)
-        P.mc_list_cap = (unsigned int)NC; // unique miss cells of a frame
+        P.mc_list_cap = cap.mc_list_cap;
         if ((rc = dev_alloc(h, &P.mc_list, (size_t)P.mc_list_cap + 8))) return rc;
         if ((rc = dev_alloc(h, &P.hl_vt16, caps.hl + 8))) return rc;
         if ((rc = dev_alloc(h, &P.tile_cols, (size_t)P.n_tiles * P.tile_words))) return rc;
         HIPCHK(h, hipMemset(P.tile_cols, 0, (size_t)P.n_tiles * P.tile_words * sizeof(uint32_t)));
         if ((rc = dev_alloc(h, &P.tile_desc, 4 * (size_t)P.n_tiles * (size_t)P.nPhi))) return rc;
-        // a frame touches at most one voxel per awareness cell, and no more voxels than its grid has
         P.rec_cap = (unsigned int)caps.rec;
         if ((rc = dev_alloc(h, &P.vr_rec, (size_t)P.rec_cap))) return rc;
         if ((rc = dev_alloc(h, &P.vr_hit, caps.vh))) return rc;
         if ((rc = dev_alloc(h, &P.tile_dir, 4 * (size_t)P.n_tiles))) return rc;
         HIPCHK(h, hipMemset(P.tile_dir, 0xFF, 4 * (size_t)P.n_tiles * sizeof(uint32_t))); // (no frame carries that sequence number)
-        // bucket-first table of this slot: room for the emulated container of a frame with up to 2 * max_points unique
-        // hit cells (more: the handle continues on the cell-table path)
+        // (more unique hit cells than its bucket-first table has room for: the handle continues on the cell-table path)
         P.sbkt_cap = (unsigned int)caps.sbkt;
         if ((rc = dev_alloc(h, &P.sbkt, (size_t)P.sbkt_cap))) return rc;
         HIPCHK(h, hipMemset(P.sbkt, 0xFF, (size_t)P.sbkt_cap * sizeof(unsigned long long)));
     }
-    // (a reference — one row of a group's lane mask — stands for at least one contribution; a cell's references start at a multiple
-    // of MLM_SEC_REF_ALIGN, and a cell that needs references has at least two contributions)
-    (void)max_contrib;
     P.refs_cap = (unsigned int)caps.refs;
     if ((rc = dev_alloc(h, &P.refs, h->use_sectors ? (size_t)P.refs_cap : 4))) return rc;
     if ((rc = dev_alloc(h, &P.mt_ref, h->use_sectors ? 2 * caps.mt : 2))) return rc;
@@ -423,7 +402,7 @@ int alloc_slot(mlm_handle *h, MlmSlot &S, size_t index, const std::vector<float>
     MLM_CT_ALLOC(hl_bkey, NC);
     MLM_CT_ALLOC(hl_cid, NC);
     MLM_CT_ALLOC(hl_slot, NC);
-    P.mc_cap = (unsigned int)((size_t)P.nMissWords * 32 / MLM_RAY_LISTS + 4096);
+    P.mc_cap = cap.mc_cap;
     MLM_CT_ALLOC(mc_bkey, (size_t)MLM_RAY_LISTS * P.mc_cap);
     MLM_CT_ALLOC(mc_cid, (size_t)MLM_RAY_LISTS * P.mc_cap);
     MLM_CT_ALLOC(mc_slot, (size_t)MLM_RAY_LISTS * P.mc_cap);
@@ -444,7 +423,7 @@ int alloc_slot(mlm_handle *h, MlmSlot &S, size_t index, const std::vector<float>
         HIPCHK(h, hipMemset(P.start_t, 0xFF, NC * sizeof(uint32_t)));
         HIPCHK(h, hipMemset(P.miss_t, 0xFF, NC * sizeof(uint32_t)));
     }
-    P.mvox_cap = (unsigned int)((size_t)P.nMissWords * 32 / MLM_RAY_LISTS + 512);
+    P.mvox_cap = cap.mvox_cap;
     MLM_CT_ALLOC(miss_vox, (size_t)MLM_RAY_LISTS * P.mvox_cap);
 #undef MLM_CT_ALLOC
     if (own) {
@@ -457,36 +436,185 @@ int alloc_slot(mlm_handle *h, MlmSlot &S, size_t index, const std::vector<float>
     return MLM_OK;
 }
 
-// The worst-case and the initial capacities of a frame slot's lists (mlm_create, before the slots are allocated).
-// Worst case: every awareness cell a multi-kind hit.  By need: what camera frames of max_points pixels produce, with room —
-// config 2 (307 k pixels): 20 k hits, 8 k ranked cells, 260 k references, 730 k ordered kinds, 33 k voxel records per frame;
-// config 3 (922 k pixels): 137 k hits, all ranked, 4.1 M references, 7.7 M kinds, 350 k records.
-void slot_capacities(mlm_handle *h, const std::vector<float> &sigma3) {
-    const MlmDev &P = h->P;
-    const size_t NC = (size_t)P.nCells, Pn = (size_t)std::max(1, h->lim.max_points);
-    int dmax = 0;
-    for (int r = 0; r < P.nRho; ++r) {
-        int d = 1;
-        while ((float)d < sigma3[r] && r + d < P.nRho && d <= MLM_DIFF_RANGE) ++d;
-        dmax = std::max(dmax, d - 1);
+// ---- The device stages of mlm_create, in the order it runs them.  The plan (mlm_plan.h) has decided every size and geometry and is
+// in the handle already; the stages only create streams and events, allocate, initialise and upload.
+
+// CUs [first, end) of a device with n_cu of them, as hipExtStreamCreateWithCUMask takes them
+std::vector<uint32_t> cu_mask(int n_cu, int first, int end) {
+    std::vector<uint32_t> mask((size_t)(n_cu + 31) / 32, 0u);
+    for (int c = first; c < end; ++c) mask[(size_t)c / 32] |= 1u << (c % 32);
+    return mask;
+}
+int open_device(mlm_handle *h, int *n_cu) {
+    int ndev = 0;
+    HIPCHK(h, hipGetDeviceCount(&ndev));
+    if (ndev <= 0 || h->device < 0 || h->device >= ndev) {
+        h->err = "no such HIP device";
+        return MLM_ERR_HIP;
     }
-    const size_t max_contrib = Pn * (size_t)(1 + 2 * dmax);
-    auto &w = h->caps_worst;
-    w.hl = w.mt = w.vh = NC;
-    w.rec = std::min<size_t>(NC, (size_t)P.lv_nx * P.lv_ny * P.lv_nz);
-    w.refs = std::min<size_t>(0xFFFFFFF0ull, max_contrib + (MLM_SEC_REF_ALIGN - 1) * std::min<size_t>(NC, max_contrib / 2) + 64);
-    w.sub = std::min<size_t>(0xFFFFFFF0ull, max_contrib + 15 * std::min<size_t>(NC, max_contrib / 2) + 64); // (checked against 2^32 by alloc_slot's caller)
-    w.sbkt = std::min<size_t>(h->max_buckets, std::__detail::_Prime_rehash_policy()._M_next_bkt(4 * Pn + 2));
-    h->caps_now = w;
-    if (!h->need_sized) return;
-    auto &c = h->caps_now;
-    c.hl = std::min(w.hl, std::max<size_t>(32768, Pn / 4));
-    c.mt = c.hl;
-    c.vh = c.hl;
-    c.rec = std::min(w.rec, 2 * c.hl);
-    c.refs = std::min(w.refs, std::max<size_t>(262144, 6 * Pn));
-    c.sub = std::min(w.sub, std::max<size_t>(1u << 20, 10 * Pn));
-    c.sbkt = std::min(w.sbkt, std::__detail::_Prime_rehash_policy()._M_next_bkt(2 * c.hl + 2));
+    HIPCHK(h, hipSetDevice(h->device));
+    hipDeviceProp_t prop;
+    HIPCHK(h, hipGetDeviceProperties(&prop, h->device));
+    *n_cu = prop.multiProcessorCount;
+    return MLM_OK;
+}
+// the main stream (knob "cu_split" = k: on the first k CUs, which Stage A then leaves alone), the batches' events and pinned blocks
+int create_main_stream(mlm_handle *h, int n_cu) {
+    if (h->cu_split > 0) {
+        const std::vector<uint32_t> mask = cu_mask(n_cu, 0, h->cu_split);
+        HIPCHK(h, hipExtStreamCreateWithCUMask(&h->stream, (uint32_t)mask.size(), mask.data()));
+    } else {
+        int lo = 0, hi = 0; // numerically lower = higher priority
+        HIPCHK(h, hipDeviceGetStreamPriorityRange(&lo, &hi));
+        HIPCHK(h, hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, hi));
+    }
+    for (int k = 0; k < MLM_SETS; ++k) {
+        HIPCHK(h, hipEventCreateWithFlags(&h->batch_done[k], hipEventDisableTiming));
+        HIPCHK(h, hipHostMalloc((void **)&h->h_gb[k], sizeof(MlmGlobal), hipHostMallocDefault));
+        std::memset(h->h_gb[k], 0, sizeof(MlmGlobal));
+    }
+    return MLM_OK;
+}
+// the kernels whose dynamic LDS is above the default limit of 48 KB
+int set_kernel_lds(mlm_handle *h) {
+    const MlmDev &P = h->P;
+    auto set = [](const void *kernel, unsigned int bytes) { return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); };
+    if (P.bin_lds_bytes > 48 * 1024) {
+        HIPCHK(h, set((const void *)k_bin_points<0>, P.bin_lds_bytes));
+        HIPCHK(h, set((const void *)k_bin_points<1>, P.bin_lds_bytes));
+        HIPCHK(h, set((const void *)k_bin_points<2>, P.bin_lds_bytes));
+    }
+    if (!h->use_sectors) return MLM_OK;
+    const int rc = set_sector_lds(h, P.sec_lds_bytes);
+    if (rc) return rc;
+    if (!P.explore) HIPCHK(h, set((const void *)k_tile, h->tile_lds_bytes));
+    if (!P.explore) HIPCHK(h, set((const void *)k_apply_tiles, h->apply_lds_bytes));
+    if (P.sec_tab_big) HIPCHK(h, set(P.explore ? (const void *)k_sector_big<true> : (const void *)k_sector_big<false>, P.sec_big_lds_bytes));
+    return MLM_OK;
+}
+template <class T> int dev_upload(mlm_handle *h, const T **p, const std::vector<T> &v) {
+    T *d = nullptr;
+    const int rc = dev_alloc(h, &d, v.size());
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    *p = d;
+    return MLM_OK;
+}
+// the plan's host tables, and the order-free hit values (MlmDev::hit_p / hit_inc): filled on the device from the uploaded odds table with
+// the kernels' own chain and logit, now that logit_exact is settled (neither changes during the handle's life)
+int upload_tables(mlm_handle *h, const MlmPlan &plan) {
+    MlmDev &P = h->P;
+    int rc;
+    if ((rc = dev_upload(h, &P.odds_table, h->odds_table))) return rc;
+    if ((rc = dev_upload(h, &P.sigma3, plan.sigma3))) return rc;
+    if ((rc = dev_upload(h, &P.cos_phi, plan.cos_phi))) return rc;
+    if ((rc = dev_upload(h, &P.sin_phi, plan.sin_phi))) return rc;
+    if ((rc = dev_upload(h, &P.sec_const, plan.sec_const))) return rc;
+    P.logit_one = 0.0f;
+    if (!P.hit_tab_n) return MLM_OK;
+    const size_t entries = h->odds_table.size();
+    float *d_hp, *d_hi, *d_one;
+    if ((rc = dev_alloc(h, &d_hp, entries * P.hit_tab_n))) return rc;
+    if ((rc = dev_alloc(h, &d_hi, entries * P.hit_tab_n))) return rc;
+    if ((rc = dev_alloc(h, &d_one, 1))) return rc;
+    hipLaunchKernelGGL(k_fill_hit_tables, dim3((unsigned int)((entries + 255) / 256)), dim3(256), 0, 0, P, d_hp, d_hi, d_one);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpy(&P.logit_one, d_one, sizeof(float), hipMemcpyDeviceToHost));
+    P.hit_p = d_hp;
+    P.hit_inc = d_hi;
+    return MLM_OK;
+}
+// what all frame slots share: the emulated container's bucket tables, the block table + pool (grows on demand: grow_pool), the sort buffers
+int alloc_map(mlm_handle *h) {
+    MlmDev &P = h->P;
+    const size_t NC = (size_t)P.nCells;
+    int rc;
+    if ((rc = dev_alloc(h, &P.bkt_first, h->max_buckets))) return rc;
+    P.bkt_stride = h->max_buckets;
+    if ((rc = dev_alloc(h, &P.bkt64, 2 * h->max_buckets))) return rc;
+    HIPCHK(h, hipMemset(P.bkt64, 0xFF, 2 * h->max_buckets * sizeof(unsigned long long)));
+    if ((rc = dev_alloc(h, &P.g, 1))) return rc;
+    if ((rc = alloc_pool(h, P, h->lim.max_blocks))) return rc;
+    if (P.explore && (rc = dev_alloc(h, &P.bktm_first, h->max_buckets))) return rc;
+    MlmGlobal g0{};
+    g0.fail_frame = 0x7FFFFFFF;
+    HIPCHK(h, hipMemcpy(P.g, &g0, sizeof(MlmGlobal), hipMemcpyHostToDevice));
+    HIPCHK(h, hipHostMalloc((void **)&h->h_g, sizeof(MlmGlobal), hipHostMallocDefault));
+    std::memset(h->h_g, 0, sizeof(MlmGlobal));
+    h->sort_tmp_bytes = mlm_sort_temp_bytes(NC);
+    if ((rc = dev_alloc(h, &h->sk_in, NC))) return rc;
+    if ((rc = dev_alloc(h, &h->sk_out, NC))) return rc;
+    if ((rc = dev_alloc(h, &h->sv_in, NC))) return rc;
+    if ((rc = dev_alloc(h, &h->sv_out, NC))) return rc;
+    return dev_alloc(h, (char **)&h->sort_tmp, h->sort_tmp_bytes);
+}
+// the slots' tables (counters, parameter blocks, frames) and Stage A's streams and events, one per slot set (knobs "cu_split" /
+// "cu_reserve": Stage A stays off the first CUs)
+int create_stage_a(mlm_handle *h, int n_cu) {
+    const size_t NS = (size_t)h->lim.max_batch * h->n_sets; // one set being filled while the others are in flight
+    int rc;
+    h->slots.resize(NS);
+    if ((rc = dev_alloc(h, &h->d_ctr_all, NS))) return rc;
+    if ((rc = dev_alloc(h, &h->d_slot_tab, NS))) return rc;
+    if ((rc = dev_alloc(h, &h->d_frame_tab, NS))) return rc;
+    HIPCHK(h, hipMemset(h->d_ctr_all, 0, NS * sizeof(MlmCounters)));
+    HIPCHK(h, hipHostMalloc((void **)&h->h_ctr_all, NS * sizeof(MlmCounters), hipHostMallocDefault));
+    HIPCHK(h, hipHostMalloc((void **)&h->h_frame_tab, NS * sizeof(MlmFrame), hipHostMallocDefault));
+    std::memset(h->h_ctr_all, 0, NS * sizeof(MlmCounters));
+    std::memset(h->h_frame_tab, 0, NS * sizeof(MlmFrame));
+    const std::vector<uint32_t> mask = cu_mask(n_cu, std::max(h->cu_split, h->cu_reserve), n_cu);
+    for (int k = 0; k < MLM_SETS; ++k) {
+        if (h->cu_split > 0 || h->cu_reserve > 0) HIPCHK(h, hipExtStreamCreateWithCUMask(&h->stream_as[k], (uint32_t)mask.size(), mask.data()));
+        else HIPCHK(h, hipStreamCreateWithFlags(&h->stream_as[k], hipStreamNonBlocking));
+    }
+    for (int k = 0; k < MLM_SETS; ++k) {
+        HIPCHK(h, hipEventCreateWithFlags(&h->ex_counts[k], hipEventDisableTiming));
+        HIPCHK(h, hipEventCreateWithFlags(&h->ex_bc_done[k], hipEventDisableTiming));
+        HIPCHK(h, hipEventCreateWithFlags(&h->stage_a_done[k], hipEventDisableTiming));
+        HIPCHK(h, hipEventCreateWithFlags(&h->set_free[k], hipEventDisableTiming));
+    }
+    return MLM_OK;
+}
+// The frame slots are most of the footprint (S1 ~1 GB, S3 ~3.8 GB each): three sets of max_batch if they fit the device
+// memory, else two sets (a few percent less throughput on config 2), else the error says what would be needed.
+int alloc_slots(mlm_handle *h, const MlmSlotPlan &cap) {
+    const size_t mark = h->allocs.size(), two_sets = 2 * (size_t)h->lim.max_batch;
+    size_t got = 0;
+    int rc = MLM_OK;
+    for (; got < h->slots.size(); ++got)
+        if ((rc = alloc_slot(h, h->slots[got], got, cap))) break;
+    if (rc && got >= two_sets && h->n_sets > 2) {
+        (void)hipGetLastError();
+        // (keep the first two sets; give the partial third one back)
+        size_t keep = mark;
+        for (size_t i = 0; i < two_sets; ++i) keep = h->slots[i].alloc_end;
+        for (size_t a = keep; a < h->allocs.size(); ++a)
+            if (h->allocs[a]) hipFree(h->allocs[a]);
+        h->allocs.resize(keep);
+        for (size_t i = two_sets; i < h->slots.size(); ++i)
+            if (h->slots[i].d_img) {
+                hipFree(h->slots[i].d_img);
+                h->slots[i].d_img = nullptr;
+            }
+        h->n_sets = 2;
+        h->slots.resize(two_sets);
+        h->err.clear();
+        rc = MLM_OK;
+    }
+    if (rc) h->err += " (frame slots: lower mlm_limits.max_batch or max_points)";
+    return rc;
+}
+// sector-path handles: the cell-table path's buffers that the slots share (alloc_slot)
+int alloc_ct_shared(mlm_handle *h) {
+    if (!h->use_sectors) return MLM_OK;
+    const MlmDev &P0 = h->slots[0].P;
+    int rc;
+    if ((rc = dev_alloc(h, &h->fb_bnodes, (size_t)P0.nb_cap * P0.node_lds))) return rc;
+    if ((rc = dev_alloc(h, &h->fb_pairs, (size_t)P0.nb_cap * P0.agg_lds))) return rc;
+    if ((rc = dev_alloc(h, &h->fb_nodes, (size_t)MLM_RAY_LISTS * P0.node_cap))) return rc;
+    if ((rc = dev_alloc(h, &h->d_slot_tab_fb, h->slots.size()))) return rc;
+    HIPCHK(h, hipEventCreateWithFlags(&h->fb_done, hipEventDisableTiming));
+    return MLM_OK;
 }
 
 // One list of one slot re-allocated with room for `n_new` elements; `keep`: the slot holds a frame whose Stage A output is still

@@ -6,7 +6,7 @@
 #include <stdint.h>
 
 #ifndef MLM_TIME_SLOTS
-#define MLM_TIME_SLOTS 21 // (mlm_types.h, whose device types a CPU build cannot take)
+#define MLM_TIME_SLOTS 21 // (as mlm_types.h has it: the CPU drivers include this header on its own)
 #endif
 
 #ifdef __HIPCC__

@@ -1,6 +1,10 @@
 // mlm_types.h — device-visible parameter blocks of the map-update path (gfx950).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
+#ifndef __HIPCC__
+struct uint4; // (a CPU build — mlm_plan.h and its test driver — only ever holds pointers to it)
+#endif
 
 #define MLM_EMPTY_T 0xFFFFFFFFu      // hit_t: cell not hit this frame
 #define MLM_HT_EMPTY 0xFFFFFFFFFFFFFFFFull
@@ -124,6 +128,18 @@ struct MlmVoxHit {
     float inc;
     uint32_t pos;            // index in hl_*
 };
+
+// MlmDev::node_lds contribution nodes are buffered per k_bin_points block; MlmDev::agg_lds (a power of two) entries of
+// a block-local table merge the block's groups per awareness cell
+struct MlmCellAgg {
+    uint32_t cell;      // MLM_NIL = empty
+    uint32_t tmin;      // earliest insertion time of the block's contributions to the cell
+    uint32_t kmask;     // kinds
+    uint32_t cnt;       // contributions
+    uint32_t idx;       // dense index of the entry inside the block = its slot in the block's slice of MlmDev::pairs
+    uint32_t start_min; // explore mode: first point whose hit centre is the cell
+};
+#define MLM_RAY_LDS 128 // rays buffered per k_bin_points block (overflow: walked on the spot)
 
 #define MLM_LV_SLOTS 8
 struct MlmDev {

@@ -6,9 +6,9 @@
 // CPU fallback: every entry point fails with MLM_ERR_HIP when the device is unavailable.
 //
 // ONE device translation unit (the kernels live in headers and are launched from here); the host driver is cut into parts that
-// are included in this order: mlm_handle.h (the handle, knobs, launch helpers) -> mlm_stage_a.h (Stage A launches, exact
+// are included in this order: mlm_plan.h (host only: what mlm_create decides without the device) -> mlm_handle.h (the handle, knobs, launch helpers) -> mlm_stage_a.h (Stage A launches, exact
 // ordering, statistics) -> mlm_explore_host.h (frontier mode) -> mlm_submit.h (submission, drain / replay, single-frame graph)
-// -> mlm_resources.h (device memory: pool growth, frame slots, queries' launcher) -> mlm_mirror.h (host mirror of the map for small
+// -> mlm_resources.h (device memory: mlm_create's stages, pool growth, frame slots, queries' launcher) -> mlm_mirror.h (host mirror of the map for small
 // query batches) -> mlm_readout.h (what the read-outs share: box check, staging of host arrays, ESDF tiles, settle loop); this file
 // holds the extern "C" entry points.
 #include <hip/hip_runtime.h>
@@ -47,6 +47,7 @@
 #include "mlm_kernels_score.h"
 #include "mlm_kernels_cluster.h"
 #include "mlm_host.h"
+#include "mlm_plan.h"
 #include "mlm_mapview.h"
 
 #include "mlm_handle.h"
@@ -129,474 +130,43 @@ int mlm_host_unregister(mlm_handle *h, const void *ptr) {
 
 const char *mlm_last_error(mlm_handle *h) { return h ? h->err.c_str() : "null handle"; }
 
+// The plan (mlm_plan.h) decides everything that needs no device — and makes every refusal that needs none —, the stages of
+// mlm_resources.h then build the handle's device state with it, in this order.
 int mlm_create(const mlm_config *cfg, const mlm_limits *lim_in, int device, mlm_handle **out) {
     if (!cfg || !out) return MLM_ERR_INVALID;
     *out = nullptr;
-    if (cfg->am_n_rho <= 1 || cfg->am_d_rho <= 0 || cfg->am_d_phi_deg <= 0 || cfg->am_d_z <= 0 || cfg->subbox_n <= 0 ||
-        cfg->subbox_d_xyz <= 0 || cfg->am_n_z_below < 0 || cfg->am_n_z_over < 0)
-        return MLM_ERR_INVALID;
+    if (!mlm_plan_args_ok(*cfg)) return MLM_ERR_INVALID;
     mlm_handle *h = new mlm_handle();
     *out = h; // returned even on failure so that mlm_last_error can be read; caller must mlm_destroy it
-    long long kv = 0; // (value of a test / experiment knob, see mlm_debug_set)
     h->device = device;
     h->cfg = *cfg;
-    if (lim_in) h->lim = *lim_in;
-    if (h->lim.max_blocks <= 0) h->lim.max_blocks = 65536;
-    if (h->lim.max_points <= 0) h->lim.max_points = 1280 * 720;
-    if (h->lim.max_batch <= 0) h->lim.max_batch = 8;
-    if (h->lim.max_batch > 64) h->lim.max_batch = 64;
-    // (frontier mode: Stage A is batched too; the map-dependent part runs frame by frame, see run_slots)
-    if ((long long)h->lim.max_points * 256 > 0xFFFFFFF0ll && cfg->use_exploration_frontiers) {
-        h->err = "max_points too large for 32-bit miss insertion times";
-        return MLM_ERR_UNSUPPORTED;
+    int rc, n_cu = 0;
+    if ((rc = open_device(h, &n_cu))) return rc;
+    const MlmPlan plan = mlm_plan(*cfg, lim_in, knob, n_cu);
+    h->lim = plan.lim;
+    if (plan.status != MLM_OK) {
+        h->err = plan.err;
+        return plan.status;
     }
-    int ndev = 0;
-    HIPCHK(h, hipGetDeviceCount(&ndev));
-    if (ndev <= 0 || device < 0 || device >= ndev) {
-        h->err = "no such HIP device";
-        return MLM_ERR_HIP;
-    }
-    HIPCHK(h, hipSetDevice(device));
-    {
-        // Stage B+C (main stream) is the serial per-frame chain of short, latency-bound kernels; Stage A floods the
-        // chip with wide kernels.  MLM_CU_SPLIT=k (default 0 = off) reserves the first k CUs for the main stream and
-        // leaves the rest to Stage A, so that the chain is not stretched by queueing behind Stage A's waves.
-        int lo = 0, hi = 0; // numerically lower = higher priority
-        HIPCHK(h, hipDeviceGetStreamPriorityRange(&lo, &hi));
-        if (knob("expand_block", kv)) h->expand_block = (unsigned int)kv; // (whole waves in [64, 256]: knob_value_ok)
-        if (knob("sort_block", kv)) h->sort_block = (unsigned int)kv;
-        if (knob("sort_grid", kv)) h->sort_grid = (unsigned int)std::max(1, (int)kv);
-        if (knob("chain_grid", kv)) h->chain_grid = (unsigned int)std::max(1, (int)kv);
-        if (knob("rank_grid", kv)) h->rank_grid = (unsigned int)std::max(1, (int)kv);
-        else if ((long long)cfg->am_n_rho * cfg->am_n_z_below > 4000) h->rank_grid = 384; // (fine maps order a hundred thousand cells per frame: config 3 128 blocks 33.0 us, 256: 31.0, 512: 29.2)
-        if (knob("collect_grid", kv)) h->collect_grid = (unsigned int)std::max(1, (int)kv);
-        if (knob("sc_block", kv)) h->sc_block = (unsigned int)kv;
-        if (knob("sc_grid", kv)) {
-            h->sc_grid = (unsigned int)std::max(1, (int)kv);
-            h->sc_grid_fixed = true;
-        }
-        h->cu_split = knob("cu_split", kv) ? (int)kv : 0;
-        // MLM_CU_RESERVE=k: Stage A stays off the first k CUs, the main stream may use all of them
-        if (knob("cu_reserve", kv)) h->cu_reserve = std::max(0, (int)kv);
-        hipDeviceProp_t prop;
-        HIPCHK(h, hipGetDeviceProperties(&prop, device));
-        const int ncu = prop.multiProcessorCount;
-        if (std::max(h->cu_split, h->cu_reserve) >= ncu) { // (Stage A's streams would get an empty CU mask: nothing of theirs could run)
-            h->err = "knobs cu_split / cu_reserve must leave Stage A at least one of the device's " + std::to_string(ncu) + " CUs";
-            return MLM_ERR_INVALID;
-        }
-        if (h->cu_split > 0) {
-            std::vector<uint32_t> mask((size_t)(ncu + 31) / 32, 0u);
-            for (int c = 0; c < h->cu_split; ++c) mask[(size_t)c / 32] |= 1u << (c % 32);
-            HIPCHK(h, hipExtStreamCreateWithCUMask(&h->stream, (uint32_t)mask.size(), mask.data()));
-        } else {
-            h->cu_split = 0;
-            HIPCHK(h, hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, hi));
-        }
-    }
-    for (int k = 0; k < MLM_SETS; ++k) {
-        HIPCHK(h, hipEventCreateWithFlags(&h->batch_done[k], hipEventDisableTiming));
-        HIPCHK(h, hipHostMalloc((void **)&h->h_gb[k], sizeof(MlmGlobal), hipHostMallocDefault));
-        std::memset(h->h_gb[k], 0, sizeof(MlmGlobal));
-    }
-
-    MlmDev &P = h->P;
-    // awareness constants, map_awareness.cpp:21-32
-    P.dRho = cfg->am_d_rho;
-    P.dPhi = cfg->am_d_phi_deg * M_PI / 180;
-    P.dZ = cfg->am_d_z;
-    P.nRho = cfg->am_n_rho;
-    P.nPhi = static_cast<int>(360 / cfg->am_d_phi_deg);
-    P.nZ = cfg->am_n_z_below + cfg->am_n_z_over + 1;
-    P.zc = cfg->am_n_z_below;
-    P.z_border_min = -(cfg->am_n_z_below * cfg->am_d_z) - 0.5 * cfg->am_d_z;
-    P.nRhoPhi = P.nRho * P.nPhi;
-    const long long ncells = (long long)P.nRhoPhi * P.nZ;
-    if (ncells <= 0 || ncells > (1ll << 31) - 64) {
-        h->err = "awareness map too large";
-        return MLM_ERR_UNSUPPORTED;
-    }
-    if ((long long)h->lim.max_points * MLM_TIME_SLOTS > 0x7FFFFFF0ll) {
-        h->err = "max_points too large for 32-bit insertion times";
-        return MLM_ERR_UNSUPPORTED;
-    }
-    P.nCells = (int)ncells;
-    P.RW = (P.nRho + 31) / 32;
-    P.rw_m = mlm_host::strip_magic((unsigned int)P.RW); // (0 beyond 2^11 words: such a cylinder never takes the sector path, use_sectors below)
-    P.nMissWords = P.nZ * P.nPhi * P.RW;
-    P.visibility = cfg->use_raycasting != 0;
-    // local constants, map_local.cpp:56-62,126-130 (float casts as mlmap.cpp:77-81)
-    P.d_sub = cfg->subbox_d_xyz;
-    P.d_sub_half = P.d_sub * 0.5;
-    P.n = cfg->subbox_n;
-    P.d_glb = P.d_sub * P.n;
-    P.inv_dRho = 1.0 / P.dRho;
-    P.inv_dPhi = 1.0 / P.dPhi;
-    P.inv_dZ = 1.0 / P.dZ;
-    P.inv_d_max = std::max(P.inv_dRho, std::max(P.inv_dPhi, P.inv_dZ));
-    P.inv_d_sub = 1.0 / P.d_sub;
-    P.inv_d_glb = 1.0 / P.d_glb;
-    P.cells = P.n * P.n * P.n;
-    P.lo_min = static_cast<float>(cfg->log_odds_min);
-    P.lo_max = static_cast<float>(cfg->log_odds_max);
-    P.lo_miss = static_cast<float>(cfg->measurement_miss);
-    P.lo_sh = static_cast<float>(cfg->occupied_sh);
-    // camera, mlmap.cpp:15-18 (float members) and mlmap.h:85-86
-    P.cx = (float)cfg->cam_cx;
-    P.cy = (float)cfg->cam_cy;
-    P.fx = (float)cfg->cam_fx;
-    P.fy = (float)cfg->cam_fy;
-    P.inv_factor = 1.0 / 1000.0;
-    P.inv_fx = 1.0 / (double)P.fx;
-    P.inv_fy = 1.0 / (double)P.fy;
-    P.record_awareness = h->lim.record_awareness;
-    P.node_lds = 448;
-    P.agg_lds = 256;
-    P.explore = cfg->use_exploration_frontiers != 0;
-    P.max_blocks = h->lim.max_blocks;
-
-    // T_bs, mlmap.cpp:22-25
-    const double R[9] = {cfg->T_bs[0], cfg->T_bs[1], cfg->T_bs[2], cfg->T_bs[4], cfg->T_bs[5],
-                         cfg->T_bs[6], cfg->T_bs[8], cfg->T_bs[9], cfg->T_bs[10]};
-    h->q_bs = q_from_R(R);
-    h->t_bs = D3{cfg->T_bs[3], cfg->T_bs[7], cfg->T_bs[11]};
-
-    // tables (host libm, uploaded once)
-    OddsModel om{cfg->am_d_rho, cfg->depth_noise_coe};
-    h->odds_table.resize((size_t)21 * P.nRho);
-    for (int d = -MLM_DIFF_RANGE; d <= MLM_DIFF_RANGE; ++d)
-        for (int r = 0; r < P.nRho; ++r) h->odds_table[(size_t)(d + MLM_DIFF_RANGE) * P.nRho + r] = om.get_odds(d, (size_t)r);
-    std::vector<float> sigma3(P.nRho);
-    for (int r = 0; r < P.nRho; ++r) sigma3[r] = 3 * om.sigma_in_dr((size_t)r); // map_awareness.cpp:149
-    {
-        // The hit increment is the HOST libm's log10f(odd / (1 - odd)) in the reference (map_local.h:8, map_local.cpp:159).  If this
-        // host's log10f is the one mlm_glibc_log10f restates (checked on the table's own logit arguments and a sweep of the range),
-        // the kernels evaluate that restatement and every increment has the reference's float bits; else FP64 log10 rounded once.
-        std::vector<float> ratios(h->odds_table.size());
-        for (size_t i = 0; i < ratios.size(); ++i) ratios[i] = h->odds_table[i] / (1 - h->odds_table[i]);
-        P.logit_exact = host_log10f_matches(ratios.data(), ratios.size()) ? 1 : 0;
-        if (knob("logit_exact", kv)) P.logit_exact = P.logit_exact && (int)kv != 0;
-    }
-    {
-        // a point spreads into 1 + 2*dmax cells; the wider the spread, the more groups and distinct cells a block produces
-        int dmax = 0;
-        for (int r = 0; r < P.nRho; ++r) {
-            int d = 1;
-            while ((float)d < sigma3[r] && r + d < P.nRho && d <= MLM_DIFF_RANGE) ++d;
-            dmax = std::max(dmax, d - 1);
-        }
-        h->no_spread = dmax == 0; // (a point only ever hits its own cell: no cell collects several kinds, nothing to rank or replay)
-        if (dmax > 4) {
-            P.node_lds = 1024;
-            P.agg_lds = 512;
-        }
-        // block size of k_bin_points and its LDS buffers (the sizes above are per 256 threads); experiment knobs
-        P.bin_block = 256; // measured on config 2: 34.4k frames/s vs 33.6k with 512 and 31.9k with 1024
-        if (knob("bin_block", kv)) P.bin_block = ((int)kv >= 1024) ? 1024u : ((int)kv >= 512 ? 512u : 256u);
-        P.node_lds = P.node_lds * (P.bin_block / 256);
-        P.agg_lds = P.agg_lds * (P.bin_block / 256);
-        if (knob("node_lds", kv)) P.node_lds = (unsigned int)(int)kv;
-        if (knob("agg_lds", kv)) P.agg_lds = (unsigned int)(int)kv; // power of two >= bin_block
-        unsigned int lg = 0;
-        while ((1u << lg) < P.agg_lds) ++lg;
-        P.agg_shift = 32 - lg;
-        P.bin_lds_bytes = P.node_lds * (unsigned int)sizeof(MlmNode) + P.agg_lds * (unsigned int)(sizeof(MlmCellAgg) + 4) +
-                          MLM_RAY_LDS * 16;
-        if (P.bin_lds_bytes > 48 * 1024) { // above the default dynamic-LDS limit
-            HIPCHK(h, hipFuncSetAttribute((const void *)k_bin_points<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.bin_lds_bytes));
-            HIPCHK(h, hipFuncSetAttribute((const void *)k_bin_points<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.bin_lds_bytes));
-            HIPCHK(h, hipFuncSetAttribute((const void *)k_bin_points<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.bin_lds_bytes));
-        }
-    }
-    if ((size_t)(2 * MLM_DIFF_RANGE + 1) * P.nRho * sizeof(float) > 64u * 1024u) { // (k_chain keeps the odds table in LDS)
-        h->err = "am_n_Rho above 780 is not supported";
-        return MLM_ERR_UNSUPPORTED;
-    }
-    {
-        // sector path: LDS tables of one azimuth column (k_sector).  Cell table: a column rarely holds more hit cells than a
-        // few per range step; references: (record, kind) pairs of its multi-kind cells.  A column that needs more makes
-        // its frame fall back to the cell-table path.
-        // (the hit cells of a column grow faster than its range steps — finer cells also mean more distinct cells per pixel footprint:
-        // ~220 on config 2's 65 steps, ~1 000 on config 3's 130 — hence 6 entries per step for coarse maps, 12 for fine ones)
-        unsigned int tab = 512;
-        while (tab < (P.nRho > 100 ? 12u : 6u) * (unsigned int)P.nRho && tab < 2048u) tab <<= 1;
-        if (knob("sec_tab", kv)) tab = (unsigned int)std::max(256, (int)kv); // power of two
-        P.sec_tab = tab;
-        // a column's workgroup: 256 threads where the table allows (at most 4 entries per thread, one thread per range step) — the
-        // smaller workgroup and table leave wave slots and LDS of a CU to the other streams' kernels, which is worth more in the
-        // pipeline (+5 % frames/s on config 2) than the 10 % the kernel loses alone
-        h->sec_threads = (tab <= 1024u && P.nRho <= 256) ? 256 : 512;
-        if (knob("sec_threads", kv)) h->sec_threads = ((int)kv <= 256 && tab <= 1024u && P.nRho <= 256) ? 256 : 512;
-        if (P.sec_tab < (unsigned int)h->sec_threads) P.sec_tab = (unsigned int)h->sec_threads;
-        if (knob("sec_backoff", kv)) h->sector_backoff_len = std::max(0, (int)kv);
-        if (knob("sec_fail_every", kv)) P.sec_fail_every = (unsigned int)std::max(0, (int)kv);
-        P.sec_lds_bytes = mlm_sec_lds(P.sec_tab, (unsigned int)(P.nZ * (P.explore ? P.nRho : P.RW)), (unsigned int)P.nRho, (unsigned int)P.nZ, P.explore).total;
-        {
-            // second pass for the columns that overflow that table: the largest table (up to 4096 entries = 8 per thread) that
-            // fits a CU's LDS — an S1 column has 2 665 cells in all, so no scene overflows it there
-            unsigned int big = 4096;
-            while (big > P.sec_tab && mlm_sec_lds(big, (unsigned int)(P.nZ * (P.explore ? P.nRho : P.RW)), (unsigned int)P.nRho, (unsigned int)P.nZ, P.explore).total > 159u * 1024u) big >>= 1;
-            if (knob("sec_tab_big", kv)) big = (unsigned int)(int)kv; // (0 or <= MLM_SEC_TAB: no second pass)
-            P.sec_tab_big = big > P.sec_tab && big <= 8u * MLM_SEC_THREADS ? big : 0u;
-            P.sec_big_lds_bytes = P.sec_tab_big ? mlm_sec_lds(P.sec_tab_big, (unsigned int)(P.nZ * (P.explore ? P.nRho : P.RW)), (unsigned int)P.nRho, (unsigned int)P.nZ, P.explore).total : 0u;
-        }
-        {
-            // frame-local voxel grid: the awareness cylinder (radius nRho*dRho, height nZ*dZ) plus four voxels each side, cut
-            // into tiles over its whole height: the largest edge (8, 4, 2, 1 voxels) with at most 4096 voxels per tile — k_tile counts
-            // them in LDS, and the workgroup that applies a tile walks its records a few per thread and frame (measured: config 3's
-            // 0.05 m map, 110 layers, runs k_tile and k_apply_tiles 1.6x faster with 4x4 columns than with 8x8; config 2's 51 layers
-            // are best at 8x8)
-            const double R = P.nRho * P.dRho;
-            P.lv_nx = P.lv_ny = 2 * (int)std::ceil(R / P.d_sub) + 10;
-            P.lv_nz = (int)std::ceil(P.nZ * P.dZ / P.d_sub) + 10;
-            P.tile_sh = 3;
-            while (P.tile_sh > 0 && ((size_t)P.lv_nz << (2 * P.tile_sh)) > 4096) --P.tile_sh;
-            // (a handle sized for frame-by-frame calls — the default max_batch of 8 or less — takes 4x4 columns: a lone frame's k_tile
-            // lasts as long as its busiest tile, the sensor's own, and a quarter of that tile is done sooner: the 500-sample callback
-            // 104 -> 95 us, a dense VGA frame 184 -> 172 us; long batches keep 8x8, worth 3 % of their throughput)
-            if (h->lim.max_batch <= 8 && P.tile_sh > 2) P.tile_sh = 2;
-            if (knob("tile_sh", kv)) P.tile_sh = std::min(3, std::max(0, (int)kv));
-            const int edge = 1 << P.tile_sh;
-            P.lv_nx += edge; // (the grid's origin is snapped down to a tile boundary: frame_setup)
-            P.lv_ny += edge;
-            P.n_tx = (P.lv_nx + edge - 1) / edge;
-            P.n_tiles = P.n_tx * ((P.lv_ny + edge - 1) / edge);
-            P.tile_words = (unsigned int)(P.nPhi + 31) / 32u; // a column's ray crosses a tile once: one descriptor slot per (tile, column)
-            // (a camera frame reaches about a quarter of its grid's tiles: a workgroup takes eight candidate tiles, most of them empty.
-            // Measured on config 2, profiles/r4g: 121 workgroups per frame 95.1 k frames/s, 80: 97.0 k, 60: 97.7 k, 45: 98.6 k, 32: 98.3 k —
-            // the kernel alone is no faster with fewer, but its 29 KB of LDS per workgroup are the other streams' kernels' room)
-            h->tile_grid = (unsigned int)std::max(32, std::min(P.n_tiles, P.n_tiles / 8 + 1));
-            if (knob("tile_grid", kv)) h->tile_grid = (unsigned int)std::max(1, std::min(P.n_tiles, (int)kv));
-            {   // blocks a tile overlaps: an extent of e voxels starting anywhere touches at most (e - 1) / n + 2 blocks of n
-                const long long cx = (edge - 1) / P.n + 2, cz = (P.lv_nz - 1) / P.n + 2;
-                P.tile_combos = (unsigned int)std::min<long long>((cx * cx * cz + 3) & ~3ll, 1ll << 20);
-            }
-            h->tile_lds_bytes = mlm_tile_lds((unsigned int)(edge * edge * P.lv_nz), (unsigned int)P.lv_nz, P.tile_combos).total;
-            // (two grid heights of layers: frames of a range differ in z origin; launch_apply_tiles keeps a launch's spread within one)
-            h->apply_lds_bytes = mlm_apply_lds((unsigned int)edge, 2u * (unsigned int)P.lv_nz, (unsigned int)P.n).total;
-        }
-        // (frontier mode: no tiles; its insertion times hold point index * 256 + ray step in 32 bits)
-        // (k_sector lists a column's miss cells in its cell table's space; k_tile counts a voxel's misses and hits in 16 bits each:
-        // no voxel may collect 2^16 cells — at most (d_sub / dRho + 2) (d_sub / dZ + 2) nPhi cell centres fall into one)
-        const double cells_per_voxel = (std::ceil(P.d_sub / P.dRho) + 2) * (std::ceil(P.d_sub / P.dZ) + 2) * P.nPhi;
-        h->use_sectors = P.bin_block == 256 && P.sec_lds_bytes <= 160u * 1024u - 1024u && h->lim.max_points < (1 << MLM_SEC_CNT_BITS) && P.n <= 255 &&
-                         P.sec_tab <= 4u * (unsigned int)h->sec_threads && (size_t)P.nZ * P.RW * 64 <= (size_t)P.sec_tab * sizeof(MlmSecCell) && P.nZ * P.nRho < 65536 &&
-                         P.nZ < 32768 /* a column record holds z << 16 | rho below its top bit, MLM_SEC_OUTER (nZ * nRho < 65536 only implies it for nRho >= 2) */ &&
-                         P.nRho <= 512 /* k_chain_lanes: 128 bytes of LDS per rho; k_sector: one thread per rho */ &&
-                         P.nPhi <= 32 * MLM_TILE_WORDS /* k_tile: a tile's column mask */ &&
-                         (P.explore ? P.nRho <= 256
-                                    : (((size_t)P.lv_nz << (2 * P.tile_sh)) <= 65536 && h->tile_lds_bytes <= 96u * 1024u && cells_per_voxel < 65536.0 &&
-                                       P.n_tiles < (1 << 24) && P.lv_nz <= 1024 && h->apply_lds_bytes <= 150u * 1024u &&
-                                       // (blocks one tile may overlap: their pool slots live in k_tile's LDS)
-                                       P.tile_combos <= MLM_TILE_COMBOS));
-        if (knob("sectors", kv)) h->use_sectors = h->use_sectors && (int)kv != 0;
-        if (getenv("MLM_DEBUG_CREATE"))
-            fprintf(stderr, "[create] sector path %d: LDS %u bytes per column (table %u entries), frame-local grid %d x %d x %d in %d tiles of edge %d (%u bytes of LDS each)\n",
-                    (int)h->use_sectors, P.sec_lds_bytes, P.sec_tab, P.lv_nx, P.lv_ny, P.lv_nz, P.n_tiles, 1 << P.tile_sh, h->tile_lds_bytes);
-        if (h->use_sectors) {
-            if (P.explore) { // (both instantiations: a frame on its own takes the 512-thread one where the table allows)
-                HIPCHK(h, hipFuncSetAttribute((const void *)k_sector<true, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.sec_lds_bytes));
-                HIPCHK(h, hipFuncSetAttribute((const void *)k_sector<true, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.sec_lds_bytes));
-            } else { // (both: single frames take the 512-thread instantiation where the table allows)
-                HIPCHK(h, hipFuncSetAttribute((const void *)k_sector<false, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.sec_lds_bytes));
-                HIPCHK(h, hipFuncSetAttribute((const void *)k_sector<false, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.sec_lds_bytes));
-            }
-            if (!P.explore) HIPCHK(h, hipFuncSetAttribute((const void *)k_tile, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->tile_lds_bytes));
-            if (!P.explore) HIPCHK(h, hipFuncSetAttribute((const void *)k_apply_tiles, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->apply_lds_bytes));
-            if (P.sec_tab_big) {
-                if (P.explore)
-                    HIPCHK(h, hipFuncSetAttribute((const void *)k_sector_big<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.sec_big_lds_bytes));
-                else
-                    HIPCHK(h, hipFuncSetAttribute((const void *)k_sector_big<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.sec_big_lds_bytes));
-            }
-        }
-    }
-    std::vector<double> cphi(P.nPhi), sphi(P.nPhi);
-    for (int p = 0; p < P.nPhi; ++p) {
-        const double center_phi = P.dPhi / 2 + (p * P.dPhi); // map_awareness.cpp:59
-        cphi[p] = std::cos(center_phi);
-        sphi[p] = std::sin(center_phi);
-    }
-    float *d_odds;
-    float *d_s3;
-    double *d_c, *d_s;
-    int rc;
-    if ((rc = dev_alloc(h, &d_odds, h->odds_table.size()))) return rc;
-    if ((rc = dev_alloc(h, &d_s3, sigma3.size()))) return rc;
-    if ((rc = dev_alloc(h, &d_c, cphi.size()))) return rc;
-    if ((rc = dev_alloc(h, &d_s, sphi.size()))) return rc;
-    HIPCHK(h, hipMemcpy(d_odds, h->odds_table.data(), h->odds_table.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(d_s3, sigma3.data(), sigma3.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(d_c, cphi.data(), cphi.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(d_s, sphi.data(), sphi.size() * sizeof(double), hipMemcpyHostToDevice));
-    P.odds_table = d_odds;
-    P.sigma3 = d_s3;
-    {
-        const size_t nb = ((h->odds_table.size() + 3) & ~(size_t)3), nw = nb / 4 + ((sigma3.size() + 3) & ~(size_t)3);
-        std::vector<uint32_t> sc(nw, 0u);
-        for (size_t e = 0; e < h->odds_table.size(); ++e) ((uint8_t *)sc.data())[e] = (uint8_t)mlm_sec_strength(h->odds_table[e]);
-        std::memcpy(sc.data() + nb / 4, sigma3.data(), sigma3.size() * sizeof(float));
-        uint32_t *d_sc;
-        if ((rc = dev_alloc(h, &d_sc, nw))) return rc;
-        HIPCHK(h, hipMemcpy(d_sc, sc.data(), nw * sizeof(uint32_t), hipMemcpyHostToDevice));
-        P.sec_const = d_sc;
-        P.sec_const_words = (unsigned int)nw;
-    }
-    P.cos_phi = d_c;
-    P.sin_phi = d_s;
-    {
-        // order-free hit values (MlmDev::hit_p / hit_inc): filled on the device from the uploaded odds table with the kernels' own chain and
-        // logit, now that logit_exact is settled (neither changes during the handle's life).  Largest power of two up to the knob's
-        // (default 256) with which both tables fit 16 MB; S1 takes 2 x 1.4 MB.
-        unsigned int tn = 256;
-        if (knob("hit_tab_n", kv)) tn = (unsigned int)kv;
-        const size_t entries = h->odds_table.size();
-        while (tn && 2 * entries * tn * sizeof(float) > ((size_t)16 << 20)) tn >>= 1;
-        P.hit_tab_n = tn;
-        P.logit_one = 0.0f;
-        if (tn) {
-            float *d_hp, *d_hi, *d_one;
-            if ((rc = dev_alloc(h, &d_hp, entries * tn))) return rc;
-            if ((rc = dev_alloc(h, &d_hi, entries * tn))) return rc;
-            if ((rc = dev_alloc(h, &d_one, 1))) return rc;
-            hipLaunchKernelGGL(k_fill_hit_tables, dim3((unsigned int)((entries + 255) / 256)), dim3(256), 0, 0, P, d_hp, d_hi, d_one);
-            HIPCHK(h, hipGetLastError());
-            HIPCHK(h, hipMemcpy(&P.logit_one, d_one, sizeof(float), hipMemcpyDeviceToHost));
-            P.hit_p = d_hp;
-            P.hit_inc = d_hi;
-        }
-    }
-
-    const size_t NC = (size_t)P.nCells;
-    // the emulated container can never hold more than nCells keys: bucket counts stay below the first
-    // libstdc++ prime >= 2*nCells
-    {
-        std::__detail::_Prime_rehash_policy pol;
-        h->max_buckets = pol._M_next_bkt(2 * NC + 2);
-    }
-    if ((rc = dev_alloc(h, &P.bkt_first, h->max_buckets))) return rc;
-    P.bkt_stride = h->max_buckets;
-    if ((rc = dev_alloc(h, &P.bkt64, 2 * h->max_buckets))) return rc;
-    HIPCHK(h, hipMemset(P.bkt64, 0xFF, 2 * h->max_buckets * sizeof(unsigned long long)));
-
-    // block table + pool (shared by all slots; grows on demand: grow_pool)
-    if ((rc = dev_alloc(h, &P.g, 1))) return rc;
-    if ((rc = alloc_pool(h, P, h->lim.max_blocks))) return rc;
-    if (P.explore && (rc = dev_alloc(h, &P.bktm_first, h->max_buckets))) return rc;
-    {
-        MlmGlobal g0{};
-        g0.fail_frame = 0x7FFFFFFF;
-        HIPCHK(h, hipMemcpy(P.g, &g0, sizeof(MlmGlobal), hipMemcpyHostToDevice));
-    }
-    {
-        // most blocks ONE frame can create: those that overlap the frame-local voxel grid (every cell of the awareness cylinder
-        // falls inside it, else the frame is redone / rejected)
-        auto nb = [&](int nv) { return (long long)(nv + P.n - 1) / P.n + 1; };
-        const long long b = nb(P.lv_nx) * nb(P.lv_ny) * nb(P.lv_nz);
-        h->frame_block_bound = (size_t)std::min<long long>(b, 1ll << 30);
-        if (knob("pool_grow", kv)) h->pool_grow = (int)kv != 0;
-        if (knob("graph", kv)) h->use_graph = (int)kv != 0;
-        if (knob("big_grid", kv)) h->big_grid = (unsigned int)std::max(1, (int)kv);
-        if (knob("big_arm", kv)) h->big_arm_len = std::max(0, (int)kv);
-        if (knob("ex_spec", kv)) h->ex_spec = (int)kv;
-        if (knob("single_chain_grid", kv)) h->single_chain_grid = (unsigned int)std::max(1, (int)kv);
-        if (knob("single_rank_grid", kv)) h->single_rank_grid = (unsigned int)std::max(1, (int)kv);
-        if (knob("single_apply_grid", kv)) h->single_apply_grid = (unsigned int)std::max(1, (int)kv);
-        if (knob("mirror", kv)) h->mir.enabled = (int)kv != 0;
-        if (knob("mirror_mb", kv)) h->mir.max_bytes = (size_t)std::max(0, (int)kv) << 20;
-        if (knob("rays_grid", kv)) h->rays_grid = (unsigned int)kv;
-        if (knob("render_tile", kv)) h->render_tile = (int)kv;
-        if (knob("score_chunk", kv)) h->score_chunk = (int)kv;
-        if (knob("mirror_max", kv)) h->mir.max_clean = std::max(0, (int)kv), h->mir.max_dirty = std::min(h->mir.max_dirty, h->mir.max_clean);
-        mirror_apply_limit(h);
-    }
-    HIPCHK(h, hipHostMalloc((void **)&h->h_g, sizeof(MlmGlobal), hipHostMallocDefault));
-    std::memset(h->h_g, 0, sizeof(MlmGlobal));
-
-    // sort buffers
-    h->sort_tmp_bytes = mlm_sort_temp_bytes(NC);
-    if ((rc = dev_alloc(h, &h->sk_in, NC))) return rc;
-    if ((rc = dev_alloc(h, &h->sk_out, NC))) return rc;
-    if ((rc = dev_alloc(h, &h->sv_in, NC))) return rc;
-    if ((rc = dev_alloc(h, &h->sv_out, NC))) return rc;
-    if ((rc = dev_alloc(h, (char **)&h->sort_tmp, h->sort_tmp_bytes))) return rc;
-
-    // frame slots
-    if (knob("slot_sets", kv)) h->n_sets = std::min(MLM_SETS, std::max(2, (int)kv));
-    size_t NS = (size_t)h->lim.max_batch * h->n_sets; // one set being filled while the others are in flight
-    h->slots.resize(NS);
-    if ((rc = dev_alloc(h, &h->d_ctr_all, NS))) return rc;
-    if ((rc = dev_alloc(h, &h->d_slot_tab, NS))) return rc;
-    if ((rc = dev_alloc(h, &h->d_frame_tab, NS))) return rc;
-    HIPCHK(h, hipMemset(h->d_ctr_all, 0, NS * sizeof(MlmCounters)));
-    HIPCHK(h, hipHostMalloc((void **)&h->h_ctr_all, NS * sizeof(MlmCounters), hipHostMallocDefault));
-    HIPCHK(h, hipHostMalloc((void **)&h->h_frame_tab, NS * sizeof(MlmFrame), hipHostMallocDefault));
-    std::memset(h->h_ctr_all, 0, NS * sizeof(MlmCounters));
-    std::memset(h->h_frame_tab, 0, NS * sizeof(MlmFrame));
-    if (h->cu_split > 0 || h->cu_reserve > 0) {
-        hipDeviceProp_t prop;
-        HIPCHK(h, hipGetDeviceProperties(&prop, device));
-        const int ncu = prop.multiProcessorCount;
-        std::vector<uint32_t> mask((size_t)(ncu + 31) / 32, 0u);
-        for (int c = std::max(h->cu_split, h->cu_reserve); c < ncu; ++c) mask[(size_t)c / 32] |= 1u << (c % 32);
-        for (int k = 0; k < MLM_SETS; ++k)
-            HIPCHK(h, hipExtStreamCreateWithCUMask(&h->stream_as[k], (uint32_t)mask.size(), mask.data()));
-    } else {
-        for (int k = 0; k < MLM_SETS; ++k) HIPCHK(h, hipStreamCreateWithFlags(&h->stream_as[k], hipStreamNonBlocking));
-
-    }
-    for (int k = 0; k < MLM_SETS; ++k) {
-        HIPCHK(h, hipEventCreateWithFlags(&h->ex_counts[k], hipEventDisableTiming));
-        HIPCHK(h, hipEventCreateWithFlags(&h->ex_bc_done[k], hipEventDisableTiming));
-        HIPCHK(h, hipEventCreateWithFlags(&h->stage_a_done[k], hipEventDisableTiming));
-        HIPCHK(h, hipEventCreateWithFlags(&h->set_free[k], hipEventDisableTiming));
-    }
+    h->P = plan.P;
+    static_cast<MlmHandlePlan &>(*h) = plan.H;
+    static_cast<MlmMirrorLimits &>(h->mir) = plan.mir;
+    mirror_apply_limit(h);
+    const MlmDev &P = h->P;
+    if (getenv("MLM_DEBUG_CREATE"))
+        fprintf(stderr, "[create] sector path %d: LDS %u bytes per column (table %u entries), frame-local grid %d x %d x %d in %d tiles of edge %d (%u bytes of LDS each)\n",
+                (int)h->use_sectors, P.sec_lds_bytes, P.sec_tab, P.lv_nx, P.lv_ny, P.lv_nz, P.n_tiles, 1 << P.tile_sh, h->tile_lds_bytes);
+    if ((rc = create_main_stream(h, n_cu))) return rc;
+    if ((rc = set_kernel_lds(h))) return rc;
+    if ((rc = upload_tables(h, plan))) return rc;
+    if ((rc = alloc_map(h))) return rc;
+    if ((rc = create_stage_a(h, n_cu))) return rc;
     h->map_bytes = h->alloc_bytes;
-    // frame slots sized by need (see mlm_handle::need_sized; knob "need_slots" = 0: every list at its worst case, as up to round 4)
-    h->need_sized = h->use_sectors && !P.explore;
-    if (knob("need_slots", kv)) h->need_sized = h->need_sized && (int)kv != 0;
-    slot_capacities(h, sigma3);
-    {
-        // the frame slots are most of the footprint (S1 ~1 GB, S3 ~3.8 GB each): three sets of max_batch if they fit the device
-        // memory, else two sets (a few percent less throughput on config 2), else the error says what would be needed
-        const size_t mark = h->allocs.size();
-        size_t got = 0;
-        for (; got < NS; ++got)
-            if ((rc = alloc_slot(h, h->slots[got], got, sigma3))) break;
-        if (rc && got >= 2 * (size_t)h->lim.max_batch && h->n_sets > 2) {
-            (void)hipGetLastError();
-            // (keep the first two sets; give the partial third one back)
-            size_t keep = mark;
-            for (size_t i = 0; i < 2 * (size_t)h->lim.max_batch; ++i) keep = h->slots[i].alloc_end;
-            for (size_t a = keep; a < h->allocs.size(); ++a)
-                if (h->allocs[a]) hipFree(h->allocs[a]);
-            h->allocs.resize(keep);
-            for (size_t i = 2 * (size_t)h->lim.max_batch; i < NS; ++i)
-                if (h->slots[i].d_img) {
-                    hipFree(h->slots[i].d_img);
-                    h->slots[i].d_img = nullptr;
-                }
-            h->n_sets = 2;
-            NS = 2 * (size_t)h->lim.max_batch;
-            h->slots.resize(NS);
-            h->err.clear();
-            rc = MLM_OK;
-        }
-        if (rc) {
-            h->err += " (frame slots: lower mlm_limits.max_batch or max_points)";
-            return rc;
-        }
-    }
-    if (h->use_sectors) { // the cell-table path's buffers that the slots share (alloc_slot)
-        const MlmDev &P0 = h->slots[0].P;
-        if ((rc = dev_alloc(h, &h->fb_bnodes, (size_t)P0.nb_cap * P0.node_lds))) return rc;
-        if ((rc = dev_alloc(h, &h->fb_pairs, (size_t)P0.nb_cap * P0.agg_lds))) return rc;
-        if ((rc = dev_alloc(h, &h->fb_nodes, (size_t)MLM_RAY_LISTS * P0.node_cap))) return rc;
-        if ((rc = dev_alloc(h, &h->d_slot_tab_fb, NS))) return rc;
-        HIPCHK(h, hipEventCreateWithFlags(&h->fb_done, hipEventDisableTiming));
-    }
+    if ((rc = alloc_slots(h, plan.slot))) return rc;
+    if ((rc = alloc_ct_shared(h))) return rc;
     if ((rc = upload_slot_tab(h))) return rc;
     HIPCHK(h, hipDeviceSynchronize());
+    const size_t NS = h->slots.size();
     if (getenv("MLM_DEBUG_CREATE"))
         fprintf(stderr, "[create] device memory: %.2f GB (%zu frame slots in %d sets of %d, %.3f GB each; the map and the shared tables %.2f GB)\n",
                 h->alloc_bytes / 1e9, NS, h->n_sets, h->lim.max_batch, NS ? (h->alloc_bytes - h->map_bytes) / 1e9 / NS : 0.0, h->map_bytes / 1e9);

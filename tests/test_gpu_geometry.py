@@ -214,6 +214,42 @@ def test_large_table_pass_grid(knobs, monkeypatch, capfd, big_grid):
     assert st["n_sector_fallbacks"] <= 2, st
 
 
+def test_create_lines_equal_the_recorded_ones(knobs, monkeypatch, capfd):
+    """Three cases of tests/golden/create_plan.json (what mlm_create arrived at before its arithmetic became mlm_plan.h: see
+    tests/test_create_plan.py) on the device: both MLM_DEBUG_CREATE lines byte for byte — the path, LDS bytes, table entries, grid
+    and tiles, and through the device-memory total every capacity of the frame slots — and one frame against the oracle."""
+    import json
+    import os
+
+    from mlmapping_amd import mlmap
+    from mlmapping_amd.config import CONFIG2_YAML, CConfig, to_c
+    from mlmapping_amd.mlmap import MLMap
+    from oracle.binding import OracleMap
+
+    golden = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "create_plan.json")))["cases"]
+    monkeypatch.setenv("MLM_DEBUG_CREATE", "1")
+    for name, cfg in (("S1", S1), ("frontier", CONFIG2_YAML), ("knob_sectors_0", S1)):
+        case = next(c for c in golden if c["name"] == name)
+        c_cfg, lim = to_c(cfg), case["lim"]
+        for field, _ in CConfig._fields_:  # (the preset is the recorded configuration)
+            v = getattr(c_cfg, field)
+            assert (list(v) if field == "T_bs" else v) == case["cfg"][field], (name, field)
+        assert (lim["max_blocks"], lim["max_batch"], lim["record_awareness"]) == (1024, 2, 0)
+        for k, v in case["knobs"].items():
+            knobs.set(k, v)
+        capfd.readouterr()
+        gpu, cpu = MLMap(cfg, max_blocks=lim["max_blocks"], max_points=lim["max_points"], max_batch=lim["max_batch"]), OracleMap(cfg)
+        mlmap.debug_reset()
+        lines = [ln + "\n" for ln in capfd.readouterr().err.splitlines() if ln.startswith("[create]")]
+        assert lines == [case["line1"], case["line2"]], (name, lines)
+        img = syn.room_depth(cfg)
+        q, t = syn.translating_pose(1)
+        gpu.update_map(img, q, t)
+        cpu.update_depth(img, q, t)
+        assert compare_maps(gpu.export_blocks(), cpu.export_blocks(), f"recorded case {name}, one frame")["bit_mismatch"] == 0
+        gpu.close()
+
+
 def test_cu_reserve_that_leaves_stage_a_no_cu_is_refused(knobs):
     """cu_reserve (or cu_split) equal to the CU count would give Stage A's streams an empty CU mask: mlm_create refuses it, and the
     next handle, made with the default knobs, works.  One CU left is accepted and gives the oracle's map."""

@@ -25,7 +25,7 @@ def constant(text, pattern):
 def test_constants_are_the_headers():
     assert constant(source("mlm_kernels_sweeps.h"), r"constexpr int kSweepNB = ([^;]+);") == q.SWEEP_NB
     assert constant(source("mlm_views.h"), r"constexpr long long kViewLdsBits = ([^;]+);") == q.VIEW_LDS_BITS
-    handle = source("mlm_handle.h")
+    handle = source("mlm_plan.h")  # (MlmMirrorLimits: the limits mlm_handle.h's MlmMirror derives from)
     assert constant(handle, r"int max_clean = ([^;]+);") == 4 * q.MIRROR_CLEAN and constant(handle, r"int max_dirty = ([^;]+);") == 4 * 8
     # a batch of boxes, points, rays or poses takes four of those units per item
     assert source("mlm_mirror.h").count("n * 4 > (M.dirty ? M.max_dirty : M.max_clean)") + \

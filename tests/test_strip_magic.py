@@ -35,7 +35,8 @@ def test_strip_magic_range_is_what_the_sector_path_needs():
 
     src = open(os.path.join(ROOT, "mlmapping_amd", "csrc", "mlm_kernels_sector.h")).read()
     xt_bits = int(re.search(r"#define MLM_REC_XT_BITS (\d+)", src).group(1))
-    cnt_bits = int(re.search(r"#define MLM_SEC_CNT_BITS (\d+)", src).group(1))
+    host = open(os.path.join(ROOT, "mlmapping_amd", "csrc", "mlm_host.h")).read()  # (the sector path's limits that the host plans with)
+    cnt_bits = int(re.search(r"#define MLM_SEC_CNT_BITS (\d+)", host).group(1))
     max_width = ((1 << xt_bits) - 1) << 3                   # MLM_SEC_MAX_WIDTH
     assert (max_width + 31) // 32 <= 1 << 11                # strips per row of the widest image
     assert (1 << cnt_bits) // 128 + 256 <= 1 << 20          # MlmDev::nb_cap with mlm_limits.max_points < 2^MLM_SEC_CNT_BITS
