@@ -284,6 +284,14 @@ class mlmap {
         check(mlm_export_clusters(h_, lo, dims, flags, connectivity, min_size, labels, table, cap, summary), "mlm_export_clusters");
     }
 
+    // exact surface mesh of the obstacle set of a box: quads over shared vertices (mlm_export_mesh; flags MLM_MESH_*; quads / face4
+    // [cap_faces][4], vert3 / vert_xyz / vert_n3 [cap_verts][3], host or device memory, NULL = skipped, a cap is 0 iff all of its
+    // arrays are NULL; summary host memory: [0] faces, [1] vertices whatever the caps — a call with only summary sizes the next one)
+    void exportMesh(const int32_t lo[3], const int32_t dims[3], int flags, int32_t *quads, int32_t *face4, int64_t cap_faces, int32_t *vert3,
+                    float *vert_xyz, int8_t *vert_n3, int64_t cap_verts, int64_t summary[MLM_MESH_ROW] = nullptr) {
+        check(mlm_export_mesh(h_, lo, dims, flags, quads, face4, cap_faces, vert3, vert_xyz, vert_n3, cap_verts, summary), "mlm_export_mesh");
+    }
+
     // segment casts through the voxel map (mlm_query_rays; flags MLM_RAY_*; n x 3 end points; inputs and outputs host or device
     // memory, NULL output = skipped)
     void castRays(const double *p0, const double *p1, int n, int flags, int8_t *status, int32_t *voxel3 = nullptr, double *t = nullptr,

@@ -774,6 +774,55 @@ int mlm_query_paths(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], c
 #define MLM_CLUSTER_ROW 16      /* int64 per table row */
 int mlm_export_clusters(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], int flags, int connectivity, int min_size,
                         int32_t *labels, int64_t *table, int cap, int64_t summary[6]);
+/* Exact indexed surface mesh of the obstacle set of a box: the voxel faces between an obstacle and an open voxel, as quads over
+ * shared vertices (no reference counterpart: the reference has no mesh, its visualiser publishes point clouds; the classes behind
+ * the set are those of its point queries, faces, vertices and numbering are defined here, in integers).  Voxel indices, window,
+ * layout and centres are those of mlm_export_window; the classes are what its occ / infl channels return (released frontier-mode
+ * blocks and absent blocks included); a voxel whose index leaves int32 or the key range is UNKNOWN, as in mlm_export_clusters.
+ *   O(v): mlm_export_esdf's obstacle predicate for MLM_MESH_OCC / _INFL / _UNKNOWN (at least one of them is required).
+ *   open(u): !O(u); with MLM_MESH_SEEN !O(u) and occ(u) == FREE — a wall's never-observed back side has no faces.
+ *   Voxels outside the box are looked up in the whole map, so the meshes of adjacent boxes fit together without a seam or a doubled
+ *   face.  With MLM_MESH_CLOSED they are open and no obstacles whatever the other flags say: the mesh is then the closed boundary
+ *   of the box's obstacle set.
+ *   Faces: a face is a pair (v, a) with v in the box, O(v) and open(v + e_a); a = 0: -x, 1: +x, 2: -y, 3: +y, 4: -z, 5: +z (the face
+ *   numbering of mlm_export_clusters' row word 13).  Faces are numbered 0 .. F-1 in ascending order of linear(v) * 6 + a, linear(v)
+ *   = (z * dims[1] + y) * dims[0] + x in the box.
+ *   Vertices: lattice point k, lo[i] <= k[i] <= lo[i] + dims[i] (dims + 1 points per axis), is the lower corner of voxel k.  It is
+ *   a vertex iff it is a corner of at least one face; vertices are numbered 0 .. V-1 in ascending lattice linear index, x fastest.
+ *   quads    int32 [cap_faces][4]: the vertex numbers of the face's corners, counter-clockwise seen from the open side.  With
+ *            u = a >> 1, p = (u + 1) % 3, q = (u + 2) % 3 and b = v + (a & 1) e_u: b, b + e_p, b + e_p + e_q, b + e_q for odd a and
+ *            b, b + e_q, b + e_p + e_q, b + e_p for even a, so that (c1 - c0) x (c3 - c0) is the outward unit normal.  Triangles:
+ *            (0, 1, 2) and (0, 2, 3).
+ *   face4    int32 [cap_faces][4]: absolute x, y, z of v, then a — the surface element an inspection planner samples views from.
+ *   vert3    int32 [cap_verts][3]: the absolute lattice coordinates.
+ *   vert_xyz float [cap_verts][3]: per axis, with g = floor(k / subbox_n) and c = k - g * subbox_n,
+ *            (float)((double)g * (subbox_d_xyz * subbox_n) + (double)c * subbox_d_xyz), evaluated in IEEE double in that order,
+ *            uncontracted, rounded once: the voxel centre's formula without its + d / 2.
+ *   vert_n3  int8 [cap_verts][3]: the sum of the outward unit normals of the faces the vertex is a corner of, each component in
+ *            -4 .. 4 (normalise it for smooth shading; (0, 0, 0) at a pinch point).
+ *   summary  int64 x MLM_MESH_ROW (host memory): [0] F, [1] V, [2] obstacle voxels in the box, [3] those with at least one face,
+ *            [4..9] faces per direction 0..5, [10] faces whose open neighbour lies outside the box, [11] 0.
+ * F > cap_faces or V > cap_verts is no error: the first cap rows are written, rows beyond stay as they were, summary tells, and quads
+ * always carry the true vertex numbers; a call with only summary sizes the next one.  Every array may be host or device memory; any
+ * pointer may be NULL, at least one of the six must not be; a cap is 0 iff all of its arrays are NULL.  Ranks in a fixed order, no
+ * order of arrival anywhere: there is exactly one result whatever the schedule.  The call observes the map as queries do (async
+ * mode: waits for everything submitted), runs on the stream of mlm_set_stream and returns when the outputs are written.
+ * MLM_ERR_INVALID: mlm_export_window's window errors, more than 2^31 - 1 lattice points (every vertex number fits an int32), none
+ * of the three class bits or an unknown bit, a negative cap or a cap at odds with its arrays, no output.  MLM_ERR_CAPACITY: no
+ * device memory for the scratch: the whole box is resident at once, as for mlm_export_clusters — per voxel one face-mask byte and
+ * one state byte (the latter for the box grown by one voxel per side), per lattice point 3/16 byte (a vertex bit and a 32-bit
+ * base per 64 of them), 8 bytes per 2048 voxels and per 2048 lattice points, and for host destinations a staging copy of at most
+ * 2^20 rows per array; kept by the handle and counted in mlm_frame_stats.device_bytes.  The handle stays usable after either
+ * error. */
+#define MLM_MESH_OCC 1      /* same bits and same meaning as MLM_ESDF_OCC / _INFL / _UNKNOWN */
+#define MLM_MESH_INFL 2
+#define MLM_MESH_UNKNOWN 4
+#define MLM_MESH_SEEN 16    /* only faces towards a voxel with getOccupancy == FREE */
+#define MLM_MESH_CLOSED 32  /* every voxel outside the box counts as open and as no obstacle */
+#define MLM_MESH_ROW 12     /* int64 in summary */
+int mlm_export_mesh(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], int flags, int32_t *quads, int32_t *face4,
+                    int64_t cap_faces, int32_t *vert3, float *vert_xyz, int8_t *vert_n3, int64_t cap_verts,
+                    int64_t summary[MLM_MESH_ROW]);
 /* Load blocks into the map (no reference counterpart: the reference never persists or merges maps; this is how a
  * merged global map, mlmapping_amd/merge.py, is put back behind the query interface).  keys [n*3]; log_odds / occ /
  * infl [n*cells] and collapsed [n] as mlm_export_blocks / mlm_export_block_flags write them, any of them may be NULL

@@ -46,6 +46,7 @@
 #include "mlm_kernels_path.h"
 #include "mlm_kernels_score.h"
 #include "mlm_kernels_cluster.h"
+#include "mlm_kernels_mesh.h"
 #include "mlm_host.h"
 #include "mlm_plan.h"
 #include "mlm_mapview.h"
@@ -1182,6 +1183,103 @@ int mlm_export_clusters(mlm_handle *h, const int32_t lo[3], const int32_t dims[3
     }
     if (summary)
         for (int i = 0; i < 6; ++i) summary[i] = (int64_t)h_cnt[i];
+    return MLM_OK;
+}
+
+int mlm_export_mesh(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], int flags, int32_t *quads, int32_t *face4, int64_t cap_faces,
+                    int32_t *vert3, float *vert_xyz, int8_t *vert_n3, int64_t cap_verts, int64_t summary[MLM_MESH_ROW]) {
+    if (!h) return MLM_ERR_INVALID;
+    MLM_LOCK(h);
+    if (!lo || !dims || mlm_mesh_args(flags, cap_faces, quads || face4, cap_verts, vert3 || vert_xyz || vert_n3, summary != nullptr)) {
+        h->err = "mlm_export_mesh: null window, none of MLM_MESH_OCC / _INFL / _UNKNOWN or an unknown flag bit, a negative cap, a cap of 0 with "
+                 "one of its arrays or above 0 without any, or no output";
+        return MLM_ERR_INVALID;
+    }
+    long long D[3], nvox;
+    int rc = box_check(h, "mlm_export_mesh", lo, dims, D, nvox);
+    if (rc) return rc;
+    const MlmMeshPlan plan = mlm_mesh_plan(D);
+    if (plan.why) {
+        h->err = "mlm_export_mesh: more than 2^31 - 1 lattice points";
+        return MLM_ERR_INVALID;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    if ((rc = drain(h))) return rc;
+
+    // channels: quads, face4 (rows of faces), vert3, vert_xyz, vert_n3 (rows of vertices); in device memory (written in place) or
+    // staged through d_win_stage in ranges of the numbering
+    ReadoutChannels<5> ch(h->d_win_stage, h->win_stage_bytes,
+                          {{quads, 4 * sizeof(int32_t)}, {face4, 4 * sizeof(int32_t)}, {vert3, 3 * sizeof(int32_t)}, {vert_xyz, 3 * sizeof(float)},
+                           {vert_n3, 3}});
+    if ((rc = readout_reserve(h, h->d_mesh, h->mesh_bytes, (size_t)plan.scratch_bytes, "mlm_export_mesh"))) return rc;
+    if (!h->h_reach_ctrl) HIPCHK(h, hipHostMalloc((void **)&h->h_reach_ctrl, (size_t)kReachCtrlBytes, hipHostMallocDefault));
+    char *base = (char *)h->d_mesh;
+    const long long lo64[3] = {lo[0], lo[1], lo[2]};
+    const MlmMeshGeo G = mlm_mesh_geo(D, lo64, h->P.n, h->P.d_sub, h->P.d_glb, flags);
+    MlmMeshArrays A{};
+    A.state = (const uint8_t *)base;
+    A.fmask = (uint8_t *)(base + plan.off_fmask);
+    A.bits = (unsigned long long *)(base + plan.off_bits);
+    A.wbase = (uint32_t *)(base + plan.off_wbase);
+    A.fchunk = (unsigned long long *)(base + plan.off_fchunk);
+    A.vchunk = (unsigned long long *)(base + plan.off_vchunk);
+    A.cnt = (unsigned long long *)(base + plan.off_ctrl);
+    A.fchunks = plan.fchunks;
+    A.vchunks = plan.vchunks;
+
+    // states of the grown box, masks, bits and chunk counts, chunk bases and the totals
+    MlmMeshState E{};
+    for (int a = 0; a < 3; ++a) {
+        E.glo[a] = lo64[a] - 1;
+        E.gd[a] = D[a] + 2;
+    }
+    brick_cover(h, 3, E.glo, E.gd, E.b0, E.nb);
+    E.flags = flags;
+    E.out = (uint8_t *)base;
+    const long long n_bricks = (long long)E.nb[0] * E.nb[1] * E.nb[2];
+    HIPCHK(h, hipMemsetAsync(A.cnt, 0, (size_t)kMeshCtrlBytes, h->stream));
+    hipLaunchKernelGGL(k_mesh_state, dim3((unsigned int)std::min<long long>(n_bricks, kEsdfMaskGrid)), dim3(MLM_BLOCK), 0, h->stream, h->P, E);
+    const dim3 fgrid((unsigned int)std::min<long long>(plan.fchunks, kReachGrid)), vgrid((unsigned int)std::min<long long>(plan.vchunks, kReachGrid));
+    hipLaunchKernelGGL(k_mesh_count, vgrid, dim3(MLM_BLOCK), 0, h->stream, G, A); // (fchunks <= vchunks)
+    hipLaunchKernelGGL(k_mesh_scan, dim3(2), dim3(MLM_BLOCK), 0, h->stream, A);
+    HIPCHK(h, hipGetLastError());
+    unsigned long long *h_cnt = (unsigned long long *)h->h_reach_ctrl;
+    HIPCHK(h, hipMemcpyAsync(h_cnt, A.cnt, MLM_MESH_ROW * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    int64_t sm[MLM_MESH_ROW];
+    for (int i = 0; i < MLM_MESH_ROW; ++i) sm[i] = (int64_t)h_cnt[i];
+    sm[11] = 0;
+
+    // rows: the first min(F, cap_faces) faces and min(V, cap_verts) vertices, in ranges where a destination is staged; the word bases
+    // that the quads read come with the vertices' launch
+    const long long nF = std::min<long long>(sm[0], cap_faces), nV = std::min<long long>(sm[1], cap_verts);
+    const bool faces_staged = ch.staged[0] || ch.staged[1], verts_staged = ch.staged[2] || ch.staged[3] || ch.staged[4];
+    long long stage_rows = kMeshStageRows, kv;
+    if (knob("mesh_stage_rows", kv)) stage_rows = kv;
+    const long long fstep = faces_staged ? std::min(nF, stage_rows) : nF, vstep = verts_staged ? std::min(nV, stage_rows) : nV;
+    const size_t stage_counts[5] = {(size_t)fstep, (size_t)fstep, (size_t)vstep, (size_t)vstep, (size_t)vstep};
+    if ((rc = ch.reserve(h, "mlm_export_mesh", stage_counts))) return rc;
+    if (nV > 0 || (quads && nF > 0)) {
+        long long v0 = 0;
+        do {
+            const long long v1 = std::min(nV, v0 + vstep);
+            const bool rows = v1 > v0;
+            hipLaunchKernelGGL(k_mesh_verts, vgrid, dim3(MLM_BLOCK), 0, h->stream, G, A, v0, v1, (int32_t *)(rows ? ch.at(2, (size_t)v0) : nullptr),
+                               (float *)(rows ? ch.at(3, (size_t)v0) : nullptr), (int8_t *)(rows ? ch.at(4, (size_t)v0) : nullptr));
+            HIPCHK(h, hipGetLastError());
+            if ((rc = ch.copy_out(h, 2, 5, (size_t)v0, (size_t)(v1 - v0)))) return rc;
+            v0 = v1;
+        } while (v0 < nV);
+    }
+    for (long long f0 = 0; f0 < nF; f0 += fstep) {
+        const long long f1 = std::min(nF, f0 + fstep);
+        hipLaunchKernelGGL(k_mesh_faces, fgrid, dim3(MLM_BLOCK), 0, h->stream, G, A, f0, f1, (int32_t *)ch.at(0, (size_t)f0), (int32_t *)ch.at(1, (size_t)f0));
+        HIPCHK(h, hipGetLastError());
+        if ((rc = ch.copy_out(h, 0, 2, (size_t)f0, (size_t)(f1 - f0)))) return rc;
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (summary)
+        for (int i = 0; i < MLM_MESH_ROW; ++i) summary[i] = sm[i];
     return MLM_OK;
 }
 

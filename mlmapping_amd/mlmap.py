@@ -37,6 +37,8 @@ MLM_SCORE_CLASSES, MLM_SCORE_ROW = 1, 8
 # mlm_export_clusters: the set (FRONTIER alone, or a union of the class bits), labels off the set / in a dropped component, int64 per row
 MLM_CLUSTER_OCC, MLM_CLUSTER_INFL, MLM_CLUSTER_UNKNOWN, MLM_CLUSTER_FRONTIER = 1, 2, 4, 16
 MLM_CLUSTER_NONE, MLM_CLUSTER_SMALL, MLM_CLUSTER_ROW = -1, -2, 16
+# mlm_export_mesh: the class bits (their union), faces towards FREE voxels only, the box closed against its outside, int64 in summary
+MLM_MESH_OCC, MLM_MESH_INFL, MLM_MESH_UNKNOWN, MLM_MESH_SEEN, MLM_MESH_CLOSED, MLM_MESH_ROW = 1, 2, 4, 16, 32, 12
 # mlm_query_rays flags: what stops a ray (their union; 0: nothing, a pure count)
 MLM_RAY_OCC, MLM_RAY_INFL, MLM_RAY_UNKNOWN = 1, 2, 4
 # mlm_query_views: int64 per row of the table
@@ -56,7 +58,7 @@ ABI_SYMBOLS = [
     "mlm_query_odds", "mlm_query_odd_grad", "mlm_query_odds_at", "mlm_export_frontier_points", "mlm_import_blocks",
     "mlm_merge_pack", "mlm_merge_finish",
     "mlm_set_free_in_bound", "mlm_inflate_map", "mlm_block_count",
-    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_grid2d", "mlm_export_reach", "mlm_export_route", "mlm_export_clusters", "mlm_query_rays", "mlm_render_depth", "mlm_query_views", "mlm_query_boxes", "mlm_query_nearest", "mlm_query_sweeps", "mlm_query_paths", "mlm_score_poses", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
+    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_grid2d", "mlm_export_reach", "mlm_export_route", "mlm_export_clusters", "mlm_export_mesh", "mlm_query_rays", "mlm_render_depth", "mlm_query_views", "mlm_query_boxes", "mlm_query_nearest", "mlm_query_sweeps", "mlm_query_paths", "mlm_score_poses", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
     "mlm_get_awareness_hits",
     "mlm_get_awareness_misses", "mlm_get_T_ls", "mlm_get_odds_table", "mlm_get_kernel_times",
     "mlm_enable_kernel_timing", "mlm_set_timed_kernel", "mlm_host_register", "mlm_host_unregister", "mlm_debug_set", "mlm_debug_reset",
@@ -155,6 +157,7 @@ def load_library(path: Optional[str] = None):
     L.mlm_export_reach.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     L.mlm_export_route.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp]
     L.mlm_export_clusters.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i32, vp]
+    L.mlm_export_mesh.argtypes = [vp, vp, vp, i32, vp, vp, ctypes.c_int64, vp, vp, vp, ctypes.c_int64, vp]
     L.mlm_query_rays.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.mlm_render_depth.argtypes = [vp, vp, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp]
     L.mlm_query_views.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
@@ -687,6 +690,49 @@ class MLMap:
     def _cluster_flags(frontier, occ, infl, unknown) -> int:
         return ((MLM_CLUSTER_FRONTIER if frontier else 0) | (MLM_CLUSTER_OCC if occ else 0) | (MLM_CLUSTER_INFL if infl else 0) |
                 (MLM_CLUSTER_UNKNOWN if unknown else 0))
+
+    def export_mesh(self, lo, dims, occ=True, infl=False, unknown=False, seen=False, closed=False, normals=True) -> Dict[str, np.ndarray]:
+        """Exact surface mesh of the obstacle set (the union of occ / infl / unknown as in export_esdf) of the box lo <= v < lo + dims
+        (voxel indices as export_window): the voxel faces between an obstacle and an open voxel, as quads over shared vertices.
+        seen: only faces towards FREE voxels; closed: everything outside the box counts as open, the mesh is the closed boundary of
+        the box's obstacles.  Sizes the arrays with a summary-only call, then fills them: {"quads": int32 (F, 4) vertex numbers,
+        counter-clockwise seen from outside (triangles: 0 1 2 and 0 2 3); "faces": int32 (F, 4) voxel x y z and direction 0..5 (-x +x
+        -y +y -z +z); "verts": int32 (V, 3) lattice coordinates; "xyz": float32 (V, 3) positions; "normals": int8 (V, 3) sums of
+        the adjacent faces' normals (normals=True); "summary": int64 [F, V, obstacle voxels, those with a face, faces per direction x 6,
+        faces at the box's rim, 0]} (mlm_export_mesh)."""
+        lo_a, dims_a = self._window_args(lo, dims)
+        flags = self._mesh_flags(occ, infl, unknown, seen, closed)
+        sm = np.zeros(MLM_MESH_ROW, dtype=np.int64)
+        self._chk(self._L.mlm_export_mesh(self._h, _p(lo_a), _p(dims_a), flags, None, None, 0, None, None, None, 0, _p(sm)), "mlm_export_mesh")
+        F, V = int(sm[0]), int(sm[1])
+        out = {"quads": np.empty((F, 4), dtype=np.int32), "faces": np.empty((F, 4), dtype=np.int32), "verts": np.empty((V, 3), dtype=np.int32),
+               "xyz": np.empty((V, 3), dtype=np.float32), "summary": sm}
+        if normals:
+            out["normals"] = np.empty((V, 3), dtype=np.int8)
+        if F:  # (F > 0 iff V > 0; a cap of 0 goes with no array)
+            self._chk(self._L.mlm_export_mesh(self._h, _p(lo_a), _p(dims_a), flags, _p(out["quads"]), _p(out["faces"]), F, _p(out["verts"]),
+                                              _p(out["xyz"]), _p(out["normals"]) if normals else None, V, _p(sm)), "mlm_export_mesh")
+            if (int(sm[0]), int(sm[1])) != (F, V):
+                raise MlmError("mlm_export_mesh: the map changed between the sizing call and the export")
+        return out
+
+    def export_mesh_dev(self, lo, dims, occ=True, infl=False, unknown=False, seen=False, closed=False, quads: Optional[int] = None,
+                        faces: Optional[int] = None, cap_faces: int = 0, verts: Optional[int] = None, xyz: Optional[int] = None,
+                        normals: Optional[int] = None, cap_verts: int = 0, summary: bool = True) -> Optional[np.ndarray]:
+        """Same on device memory: quads / faces pointers (int) to cap_faces x 4 int32, verts to cap_verts x 3 int32, xyz to cap_verts x 3
+        float32, normals to cap_verts x 3 int8, None = skipped (a cap is 0 iff all of its arrays are None); rows beyond a cap are
+        not written.  summary=True returns the twelve int64 counters, which tell F and V whatever the caps."""
+        lo_a, dims_a = self._window_args(lo, dims)
+        sm = np.zeros(MLM_MESH_ROW, dtype=np.int64) if summary else None
+        ptr = [None if v is None else ctypes.c_void_p(v) for v in (quads, faces, verts, xyz, normals)]
+        self._chk(self._L.mlm_export_mesh(self._h, _p(lo_a), _p(dims_a), self._mesh_flags(occ, infl, unknown, seen, closed), ptr[0], ptr[1],
+                                          int(cap_faces), ptr[2], ptr[3], ptr[4], int(cap_verts), None if sm is None else _p(sm)), "mlm_export_mesh")
+        return sm
+
+    @staticmethod
+    def _mesh_flags(occ, infl, unknown, seen, closed) -> int:
+        return ((MLM_MESH_OCC if occ else 0) | (MLM_MESH_INFL if infl else 0) | (MLM_MESH_UNKNOWN if unknown else 0) |
+                (MLM_MESH_SEEN if seen else 0) | (MLM_MESH_CLOSED if closed else 0))
 
     def cast_rays(self, p0, p1, occ=True, infl=False, unknown=False) -> Dict[str, np.ndarray]:
         """Cast the segments p0[i] -> p1[i] (n x 3 world positions) through the voxel map (mlm_query_rays): {"status": int8 (1
