@@ -292,6 +292,15 @@ class mlmap {
         check(mlm_export_mesh(h_, lo, dims, flags, quads, face4, cap_faces, vert3, vert_xyz, vert_n3, cap_verts, summary), "mlm_export_mesh");
     }
 
+    // exact pruned occupancy octree of a box (mlm_export_octree; depth 1..31, 16: OctoMap's key space; flags MLM_OCT_*; words / inner4 /
+    // skip [cap_inner], leaf4 / leaf_class [cap_leaves], host or device memory, NULL = skipped, a cap is 0 iff all of its arrays are
+    // NULL; summary host memory: [0] inner nodes, [1] leaves whatever the caps — a call with only summary sizes the next one)
+    void octree(const int32_t lo[3], const int32_t dims[3], int depth, int flags, uint16_t *words, int32_t *inner4, int32_t *skip,
+                int64_t cap_inner, int32_t *leaf4, int8_t *leaf_class, int64_t cap_leaves, int64_t summary[MLM_OCT_ROW] = nullptr) {
+        check(mlm_export_octree(h_, lo, dims, depth, flags, words, inner4, skip, cap_inner, leaf4, leaf_class, cap_leaves, summary),
+              "mlm_export_octree");
+    }
+
     // segment casts through the voxel map (mlm_query_rays; flags MLM_RAY_*; n x 3 end points; inputs and outputs host or device
     // memory, NULL output = skipped)
     void castRays(const double *p0, const double *p1, int n, int flags, int8_t *status, int32_t *voxel3 = nullptr, double *t = nullptr,

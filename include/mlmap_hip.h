@@ -823,6 +823,49 @@ int mlm_export_clusters(mlm_handle *h, const int32_t lo[3], const int32_t dims[3
 int mlm_export_mesh(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], int flags, int32_t *quads, int32_t *face4,
                     int64_t cap_faces, int32_t *vert3, float *vert_xyz, int8_t *vert_n3, int64_t cap_verts,
                     int64_t summary[MLM_MESH_ROW]);
+/* Exact pruned occupancy octree of a box: occupied, free and absent cubes sized by how uniform the space is, the structure of
+ * OctoMap's binary tree (no reference counterpart: the reference publishes flat point markers; the classes behind the labels are
+ * those of its point queries, tree and numbering are defined here, in integers).  Voxel indices, window and layout are those of
+ * mlm_export_window; the classes are what its occ / infl channels return.
+ *   Classes: a voxel is OCC if occ == OCCUPIED, with MLM_OCT_INFL also if infl == OCCUPIED; FREE if occ == FREE and it is not OCC;
+ *   NONE otherwise — absent blocks, released frontier-mode blocks that say UNKNOWN and indices outside the key range included, as in
+ *   mlm_export_mesh.  Voxels outside the box are NONE and are not looked up.  With MLM_OCT_OCC_ONLY FREE voxels are NONE too (the small
+ *   tree a visualiser wants).
+ *   Tree: depth D is 1..31 and every index of the box lies in [-2^(D-1), 2^(D-1)).  The key of an index is k = index + 2^(D-1) per
+ *   axis; the level-l cell of a key is k >> l, on the absolute lattice, so the trees of adjacent boxes share their cell boundaries
+ *   (D = 16 is OctoMap's key space).  The root is the one level-D cell.  Child i of a cell takes bit 0 of i from x, bit 1 from y
+ *   and bit 2 from z of the next key bit.  The label of a level-0 cell is its voxel's class; a cell of level l > 0 is NONE if all
+ *   eight children are NONE, an OCC leaf if all eight are OCC leaves, a FREE leaf if all eight are FREE leaves, INNER otherwise: the
+ *   canonical pruned tree.
+ *   Numbering: depth-first pre-order, children in order 0..7; the inner nodes are numbered 0 .. N-1 and the leaves 0 .. M-1 in that
+ *   order (for the leaves the Morton order of their lower corners).
+ *   words      uint16 [cap_inner]: the sum over the children i of label << 2i, NONE 0, FREE 1, OCC 2, INNER 3; stored little-endian,
+ *              the stream is meant to be the payload of OctoMap's binary tree file.
+ *   inner4     int32 [cap_inner][4]: the cell's lower corner as voxel index x, y, z, then its level.
+ *   skip       int32 [cap_inner]: n + the inner nodes in n's subtree (n included): the next inner node outside the subtree — a
+ *              stackless traversal.
+ *   leaf4      int32 [cap_leaves][4]: lower corner x, y, z, then level.
+ *   leaf_class int8 [cap_leaves]: 0 OCCUPIED or 1 FREE.
+ *   summary    int64 x MLM_OCT_ROW (host memory): [0] N, [1] M, [2] OCC leaves, [3] FREE leaves, [4] OCC voxels, [5] FREE voxels, [6] the
+ *              root's label, [7] 0, [8 + l] leaves at level l, l = 0..31.
+ * N > cap_inner or M > cap_leaves is no error: the first cap rows are written, rows beyond stay as they were, summary tells; a call
+ * with only summary sizes the next one.  Every array may be host or device memory; any pointer may be NULL, at least one of the six
+ * must not be; a cap is 0 iff all of its arrays are NULL.  The labels are a function of the classes, the numbers an exclusive prefix
+ * over eight children, top-down: there is exactly one result whatever the schedule.  The call observes the map as queries do (async
+ * mode: waits for everything submitted), runs on the stream of mlm_set_stream and returns when the outputs are written.
+ * MLM_ERR_INVALID: mlm_export_window's window errors, more than 2^31 - 1 voxels, depth outside 1..31 or a box that leaves the key cube,
+ * an unknown flag bit, a negative cap or a cap at odds with its arrays, no output.  MLM_ERR_CAPACITY: no device memory for the
+ * scratch: with T = min(D, 4) and C the cells of levels T..D that meet the box (per level the product over the axes of
+ * ((khi - 1) >> l) - (klo >> l) + 1 for the box's keys [klo, khi)), up(C) + 4 up(4 C) + 1024 bytes, up() rounding up to a multiple
+ * of 256 — 17 bytes per 16^3 brick and a little for the levels above; nothing is stored per voxel, the levels below a brick's top
+ * are recomputed where the rows are written —, and for host destinations a staging copy of at most 2^20 rows per array; kept by the
+ * handle and counted in mlm_frame_stats.device_bytes.  The handle stays usable after either error. */
+#define MLM_OCT_INFL 1      /* infl == OCCUPIED makes a voxel OCC too */
+#define MLM_OCT_OCC_ONLY 2  /* FREE voxels count as NONE */
+#define MLM_OCT_ROW 40      /* int64 in summary */
+int mlm_export_octree(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], int depth, int flags, uint16_t *words,
+                      int32_t *inner4, int32_t *skip, int64_t cap_inner, int32_t *leaf4, int8_t *leaf_class, int64_t cap_leaves,
+                      int64_t summary[MLM_OCT_ROW]);
 /* Load blocks into the map (no reference counterpart: the reference never persists or merges maps; this is how a
  * merged global map, mlmapping_amd/merge.py, is put back behind the query interface).  keys [n*3]; log_odds / occ /
  * infl [n*cells] and collapsed [n] as mlm_export_blocks / mlm_export_block_flags write them, any of them may be NULL

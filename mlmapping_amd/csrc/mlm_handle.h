@@ -196,6 +196,10 @@ struct mlm_handle : MlmHandlePlan { // (MlmHandlePlan, mlm_plan.h: the members m
     // (mlm_mesh_plan; the counters' pinned copy is h_reach_ctrl)
     void *d_mesh = nullptr;
     size_t mesh_bytes = 0;
+    // mlm_export_octree: label, counts and numbers of every cell from the bricks up to the root, and the counters (mlm_oct_plan; the
+    // counters' pinned copy is h_reach_ctrl)
+    void *d_oct = nullptr;
+    size_t oct_bytes = 0;
     // the batched queries' staging: the host inputs / outputs of one chunk
     void *d_ray_stage = nullptr;
     size_t ray_stage_bytes = 0;

@@ -47,6 +47,7 @@
 #include "mlm_kernels_score.h"
 #include "mlm_kernels_cluster.h"
 #include "mlm_kernels_mesh.h"
+#include "mlm_kernels_octree.h"
 #include "mlm_host.h"
 #include "mlm_plan.h"
 #include "mlm_mapview.h"
@@ -1280,6 +1281,83 @@ int mlm_export_mesh(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], i
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (summary)
         for (int i = 0; i < MLM_MESH_ROW; ++i) summary[i] = sm[i];
+    return MLM_OK;
+}
+
+int mlm_export_octree(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], int depth, int flags, uint16_t *words, int32_t *inner4,
+                      int32_t *skip, int64_t cap_inner, int32_t *leaf4, int8_t *leaf_class, int64_t cap_leaves, int64_t summary[MLM_OCT_ROW]) {
+    if (!h) return MLM_ERR_INVALID;
+    MLM_LOCK(h);
+    if (!lo || !dims || mlm_oct_args(flags, cap_inner, words || inner4 || skip, cap_leaves, leaf4 || leaf_class, summary != nullptr)) {
+        h->err = "mlm_export_octree: null window, an unknown flag bit, a negative cap, a cap of 0 with one of its arrays or above 0 without "
+                 "any, or no output";
+        return MLM_ERR_INVALID;
+    }
+    long long D[3], nvox;
+    int rc = box_check(h, "mlm_export_octree", lo, dims, D, nvox);
+    if (rc) return rc;
+    const long long lo64[3] = {lo[0], lo[1], lo[2]};
+    const MlmOctPlan plan = mlm_oct_plan(lo64, D, depth);
+    if (plan.why) {
+        h->err = plan.why == 1 ? "mlm_export_octree: depth must be 1..31" : "mlm_export_octree: the box is not within [-2^(depth-1), 2^(depth-1)) per axis";
+        return MLM_ERR_INVALID;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    if ((rc = drain(h))) return rc;
+
+    // channels: words, inner4, skip (rows of inner nodes), leaf4, leaf_class (rows of leaves); in device memory (written in place) or
+    // staged through d_win_stage in ranges of the numbering
+    ReadoutChannels<5> ch(h->d_win_stage, h->win_stage_bytes,
+                          {{words, sizeof(uint16_t)}, {inner4, 4 * sizeof(int32_t)}, {skip, sizeof(int32_t)}, {leaf4, 4 * sizeof(int32_t)}, {leaf_class, 1}});
+    if ((rc = readout_reserve(h, h->d_oct, h->oct_bytes, (size_t)plan.scratch_bytes, "mlm_export_octree"))) return rc;
+    if (!h->h_reach_ctrl) HIPCHK(h, hipHostMalloc((void **)&h->h_reach_ctrl, (size_t)kReachCtrlBytes, hipHostMallocDefault));
+    const MlmOctGeo G = mlm_oct_geo(lo64, D, depth, flags, plan);
+    const MlmOctUpper U = mlm_oct_upper(h->d_oct, plan);
+
+    // up: the bricks, then the levels above them; down to the bricks; the counters
+    const dim3 bgrid((unsigned int)std::min<long long>(plan.bricks, kOctGrid));
+    HIPCHK(h, hipMemsetAsync(U.ctrl, 0, (size_t)kOctCtrlBytes, h->stream));
+    hipLaunchKernelGGL(k_oct_up, bgrid, dim3(MLM_BLOCK), 0, h->stream, h->P, G, U);
+    hipLaunchKernelGGL(k_oct_tail, dim3(1), dim3(MLM_BLOCK), 0, h->stream, G, U);
+    HIPCHK(h, hipGetLastError());
+    unsigned long long *h_cnt = (unsigned long long *)h->h_reach_ctrl;
+    HIPCHK(h, hipMemcpyAsync(h_cnt, U.ctrl, kOctCtrlWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    int64_t sm[MLM_OCT_ROW];
+    mlm_oct_summary(h_cnt, sm);
+
+    // rows: the first min(N, cap_inner) inner nodes and min(M, cap_leaves) leaves, in ranges where a destination is staged
+    const long long nN = std::min<long long>(sm[0], cap_inner), nM = std::min<long long>(sm[1], cap_leaves);
+    const bool inner_staged = ch.staged[0] || ch.staged[1] || ch.staged[2], leaves_staged = ch.staged[3] || ch.staged[4];
+    const long long nstep = inner_staged ? std::min(nN, kOctStageRows) : nN, mstep = leaves_staged ? std::min(nM, kOctStageRows) : nM;
+    const size_t stage_counts[5] = {(size_t)nstep, (size_t)nstep, (size_t)nstep, (size_t)mstep, (size_t)mstep};
+    if ((rc = ch.reserve(h, "mlm_export_octree", stage_counts))) return rc;
+    const long long upper_cells = plan.cells - plan.bricks;
+    const dim3 ugrid(std::max(1u, std::min<unsigned int>(grid_for((size_t)upper_cells), kOctGrid)));
+    for (long long n0 = 0, m0 = 0; n0 < nN || m0 < nM;) {
+        const long long n1 = std::min(nN, n0 + nstep), m1 = std::min(nM, m0 + mstep);
+        MlmOctOut O{};
+        if (n1 > n0) {
+            O.words = (uint16_t *)ch.at(0, (size_t)n0);
+            O.inner4 = (int32_t *)ch.at(1, (size_t)n0);
+            O.skip = (int32_t *)ch.at(2, (size_t)n0);
+        }
+        if (m1 > m0) {
+            O.leaf4 = (int32_t *)ch.at(3, (size_t)m0);
+            O.leaf_class = (int8_t *)ch.at(4, (size_t)m0);
+        }
+        O.n0 = n0, O.n1 = n1, O.m0 = m0, O.m1 = m1;
+        hipLaunchKernelGGL(k_oct_emit_upper, ugrid, dim3(MLM_BLOCK), 0, h->stream, G, U, O);
+        hipLaunchKernelGGL(k_oct_emit, bgrid, dim3(MLM_BLOCK), 0, h->stream, h->P, G, U, O);
+        HIPCHK(h, hipGetLastError());
+        if (n1 > n0 && (rc = ch.copy_out(h, 0, 3, (size_t)n0, (size_t)(n1 - n0)))) return rc;
+        if (m1 > m0 && (rc = ch.copy_out(h, 3, 5, (size_t)m0, (size_t)(m1 - m0)))) return rc;
+        n0 = n1;
+        m0 = m1;
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (summary)
+        for (int i = 0; i < MLM_OCT_ROW; ++i) summary[i] = sm[i];
     return MLM_OK;
 }
 
