@@ -301,6 +301,15 @@ class mlmap {
               "mlm_export_octree");
     }
 
+    // drop — or page out — the blocks outside (MLM_CROP_INSIDE: inside) a box of block keys, in place on the device (mlm_crop_blocks;
+    // flags MLM_CROP_*; keys [cap][3], log_odds / occ / infl [cap][cells], collapsed [cap], host or device memory, NULL = skipped: with
+    // none of them the blocks are just dropped; summary host memory: [2] dropped blocks whatever the cap — a MLM_CROP_DRY call sizes the next one)
+    void cropBlocks(const int32_t key_lo[3], const int32_t key_dims[3], int flags = MLM_CROP_OUTSIDE, int cap = 0, int32_t *keys = nullptr,
+                    float *log_odds = nullptr, uint8_t *occ = nullptr, uint8_t *infl = nullptr, uint8_t *collapsed = nullptr,
+                    int64_t summary[MLM_CROP_ROW] = nullptr) {
+        check(mlm_crop_blocks(h_, key_lo, key_dims, flags, cap, keys, log_odds, occ, infl, collapsed, summary), "mlm_crop_blocks");
+    }
+
     // segment casts through the voxel map (mlm_query_rays; flags MLM_RAY_*; n x 3 end points; inputs and outputs host or device
     // memory, NULL output = skipped)
     void castRays(const double *p0, const double *p1, int n, int flags, int8_t *status, int32_t *voxel3 = nullptr, double *t = nullptr,

@@ -874,6 +874,39 @@ int mlm_export_octree(mlm_handle *h, const int32_t lo[3], const int32_t dims[3],
 int mlm_import_blocks(mlm_handle *h, int n, const int32_t *keys, const float *log_odds, const uint8_t *occ,
                       const uint8_t *infl, const uint8_t *collapsed);
 
+/* Make the map smaller, in place on the device: drop — or page out — the blocks of a box of block KEYS (no reference counterpart:
+ * the reference's observed_group_map only ever grows, and so did the pool here; a vehicle that keeps flying ends with
+ * MLM_ERR_CAPACITY).  The box is in block keys — the glb_id of mlm_query_odds_at, the keys of mlm_export_blocks — not in voxels: a
+ * block is inside iff key_lo[a] <= key[a] < key_lo[a] + key_dims[a] on all three axes.  MLM_CROP_OUTSIDE drops the blocks outside the
+ * box (keep a window), MLM_CROP_INSIDE those inside it.  A dropped block is gone as if it had never been created: every query and
+ * read-out answers for its voxels what it answers for an absent block, a later frame that reaches it creates it afresh (allocate_ram);
+ * in frontier mode its frontier flags and its released / observed flags go with it, frontier cells of kept blocks stay.
+ *   Outputs (each may be NULL; cap blocks each, in the layout of mlm_export_blocks / mlm_export_block_flags; device memory of this
+ * device is written in place, any host memory is staged): the dropped blocks in ascending order of their old slot — what
+ * mlm_import_blocks takes to bring them back later.  collapsed is 0 outside frontier mode.  With any output given and cap smaller than
+ * the number of dropped blocks: MLM_ERR_CAPACITY, the map untouched, summary filled so the caller can size.  With no output, cap is
+ * ignored and the blocks are just dropped.
+ *   summary (may be NULL): [0] blocks before, [1] kept K, [2] dropped D, [3] dropped blocks written, [4] block capacity before,
+ * [5] after, [6] mlm_frame_stats.device_bytes before, [7] after.  MLM_CROP_DRY only counts: summary is filled, the map is not touched.
+ *   The pool is compacted in place by hole filling (mlmapping_amd/csrc/mlm_crop.h): with d(s) the number of dropped slots below slot
+ * s and H = d(K), the h-th dropped slot below K takes the h-th kept slot at or above K; at most min(D, K) blocks move, the kept blocks
+ * below K stay where they are, and mlm_export_blocks' raw order afterwards is that one answer.  D == 0 changes nothing at all.
+ *   MLM_CROP_SHRINK afterwards gives pool memory back: with c0 the capacity mlm_create gave the pool, the target is the smallest
+ * c0 * 2^k >= max(c0, 2 K); if that is below the current capacity the K blocks move into a pool of that size.  Best effort: if the
+ * smaller pool cannot be allocated next to the current one the crop still stands and summary[5] reports the unchanged capacity; ignored
+ * with the knob "pool_grow" = 0.
+ *   Like mlm_import_blocks the call waits for everything submitted first.  MLM_ERR_INVALID (with a text in mlm_last_error): a NULL box,
+ * a dim < 1, key_lo + key_dims beyond int32, an unknown flag bit, cap < 0.  Every check, the count and every allocation come before
+ * the first write into the pool: a failing call leaves the map as it was. */
+enum { MLM_CROP_OUTSIDE = 0,  /* drop the blocks whose key lies outside the box: keep a window */
+       MLM_CROP_INSIDE  = 1,  /* drop the blocks whose key lies inside the box */
+       MLM_CROP_DRY     = 2,  /* count only: summary is filled, the map is not touched */
+       MLM_CROP_SHRINK  = 4 };/* afterwards give pool memory back (rule above) */
+#define MLM_CROP_ROW 8
+int mlm_crop_blocks(mlm_handle *h, const int32_t key_lo[3], const int32_t key_dims[3], int flags, int cap,
+                    int32_t *keys, float *log_odds, uint8_t *occ, uint8_t *infl, uint8_t *collapsed,
+                    int64_t summary[MLM_CROP_ROW]);
+
 /* The two device-side steps of the optional global-map merge across GPUs (mlmapping_amd/merge.py; no reference
  * counterpart: SURVEY.md §8e).  All pointers are device memory; both calls return when the buffers are written.
  * pack:   row b of log_odds_dev / seen_dev [n*cells] = this map's cells of block keys_dev[3b..3b+2] (0 / 0 where the

@@ -18,7 +18,7 @@ struct KernelTime {
 // Test and experiment knobs (mlm_debug_set): named integers that mlm_create reads — launch geometries, forced fall-backs.
 // Process-wide, not part of the drop-in contract; the library reads no environment variable for them (only the three diagnostic
 // switches MLM_DEBUG_CREATE / MLM_DEBUG_ALLOC / MLM_DEBUG_DRAIN, which print).
-const char *const kKnobNames[] = {"agg_lds", "big_arm", "big_grid", "bin_block", "chain_grid", "cluster_tile", "collect_grid", "cu_reserve", "cu_split",
+const char *const kKnobNames[] = {"agg_lds", "big_arm", "big_grid", "bin_block", "chain_grid", "cluster_tile", "collect_grid", "crop_stage_rows", "cu_reserve", "cu_split",
                                   "esdf_tile_vox", "ex_spec", "expand_block", "graph", "grid_tile", "hit_tab_n", "logit_exact", "mesh_stage_rows", "mirror", "mirror_max", "mirror_mb", "need_slots", "node_lds", "pool_grow",
                                   "rank_grid", "rays_grid", "reach_group", "reach_tile", "render_tile", "route_group", "route_tile", "sc_block", "sc_grid", "score_chunk", "sec_backoff", "sec_fail_every", "sec_tab", "sec_tab_big", "sec_threads",
                                   "sectors", "single_apply_grid", "single_chain_grid", "single_rank_grid", "slot_sets", "sort_block", "sort_grid", "tile_grid", "tile_sh", "view_lds_bits"};
@@ -45,6 +45,7 @@ bool knob_value_ok(const char *name, long long v) {
     if (is("esdf_tile_vox")) return v >= kEsdfMinBoxVoxels && v <= kEsdfBoxVoxels; // (mlm_esdf_plan fits every call's tile then)
     if (is("grid_tile")) return mlm_grid_tile_ok(v); // (most cells of a tile of mlm_export_grid2d: 1 .. kGridStageCells, mlm_grid_plan)
     if (is("cluster_tile")) return mlm_reach_tile_ok(v); // (packed like reach_tile; the tile's labels within k_cluster_local's LDS)
+    if (is("crop_stage_rows")) return v >= 1 && v <= (1ll << 20); // (blocks of a round mlm_crop_blocks stages for host destinations)
     if (is("mesh_stage_rows")) return v >= 1 && v <= kMeshStageRows; // (rows of a range mlm_export_mesh stages for host destinations)
     if (is("reach_tile")) return mlm_reach_tile_ok(v);  // (x | y << 8 | z << 16, edges 1..64, tile + halo within k_reach_sweep's LDS)
     if (is("route_tile")) return mlm_reach_tile_ok(v);  // (packed like reach_tile; mlm_route_plan: the LDS of k_route_sweep)
@@ -200,6 +201,9 @@ struct mlm_handle : MlmHandlePlan { // (MlmHandlePlan, mlm_plan.h: the members m
     // counters' pinned copy is h_reach_ctrl)
     void *d_oct = nullptr;
     size_t oct_bytes = 0;
+    // mlm_crop_blocks: chunk counts, control words and the list of the slots, dropped ones first (mlm_kernels_crop.h): 4 bytes per block
+    void *d_crop = nullptr;
+    size_t crop_bytes = 0;
     // the batched queries' staging: the host inputs / outputs of one chunk
     void *d_ray_stage = nullptr;
     size_t ray_stage_bytes = 0;

@@ -239,21 +239,10 @@ int widen_sec_tab(mlm_handle *h) {
     return upload_slot_tab(h);
 }
 
-int grow_pool(mlm_handle *h, size_t want) {
-    MlmGlobal g{};
-    HIPCHK(h, hipMemcpy(&g, h->P.g, sizeof(g), hipMemcpyDeviceToHost));
-    const unsigned int nb = std::min<unsigned int>(g.n_blocks, (unsigned int)h->P.max_blocks);
-    const size_t cap = (size_t)(0x7FFFFFFFll / h->P.cells);
-    size_t target = std::max<size_t>(want, 2 * (size_t)h->P.max_blocks);
-    target = std::min(target, cap);
-    if (target <= (size_t)h->P.max_blocks) {
-        h->err = "block pool cannot grow further (2^31 voxels)";
-        return MLM_ERR_CAPACITY;
-    }
-    if (h->grow_failed_at && target >= h->grow_failed_at) { // (the device could not hold this much before: do not allocate-and-fail every frame)
-        h->err = "device memory exhausted while growing the block pool (a pool of " + std::to_string(h->grow_failed_at) + " blocks did not fit)";
-        return MLM_ERR_CAPACITY;
-    }
+// The pool replaced by one of `target` blocks (at least the nb in use, which are copied over with the table rebuilt on the device and
+// every parameter block re-pointed): grow_pool's larger pool, and the smaller one of mlm_crop_blocks' MLM_CROP_SHRINK.  g is the
+// map-wide state as just read from the device.  MLM_ERR_CAPACITY: the device cannot hold both pools (the old one stays, h->err says so).
+int resize_pool(mlm_handle *h, size_t target, MlmGlobal g, unsigned int nb) {
     MlmDev N = h->P;
     N.ht_keys = nullptr, N.ht_slot = nullptr, N.block_keys = nullptr, N.log_odds = nullptr, N.occ = nullptr, N.infl = nullptr, N.vox_head = nullptr,
     N.vox_miss = nullptr, N.frnt = nullptr, N.vox_tau = nullptr, N.blk_collapsed = nullptr, N.blk_observed = nullptr;
@@ -261,8 +250,6 @@ int grow_pool(mlm_handle *h, size_t want) {
     if (rc) {
         (void)hipGetLastError();
         free_pool(h, N); // (what was allocated before the failure; dev_free skips the null fields)
-        h->grow_failed_at = target;
-        h->err = "device memory exhausted while growing the block pool: " + h->err;
         return MLM_ERR_CAPACITY;
     }
     // (alloc_pool initialises the new arrays with hipMemset on the null stream, which the handle's non-blocking streams do not
@@ -292,10 +279,29 @@ int grow_pool(mlm_handle *h, size_t want) {
     *h->h_g = g;
     for (int k = 0; k < MLM_SETS; ++k) *h->h_gb[k] = g;
     for (size_t i = 0; i < h->slots.size(); ++i) copy_pool_fields(h->slots[i].P, N);
-    {
-        const int rc = upload_slot_tab(h);
-        if (rc) return rc;
+    return upload_slot_tab(h);
+}
+int grow_pool(mlm_handle *h, size_t want) {
+    MlmGlobal g{};
+    HIPCHK(h, hipMemcpy(&g, h->P.g, sizeof(g), hipMemcpyDeviceToHost));
+    const unsigned int nb = std::min<unsigned int>(g.n_blocks, (unsigned int)h->P.max_blocks);
+    const size_t cap = (size_t)(0x7FFFFFFFll / h->P.cells);
+    size_t target = std::max<size_t>(want, 2 * (size_t)h->P.max_blocks);
+    target = std::min(target, cap);
+    if (target <= (size_t)h->P.max_blocks) {
+        h->err = "block pool cannot grow further (2^31 voxels)";
+        return MLM_ERR_CAPACITY;
     }
+    if (h->grow_failed_at && target >= h->grow_failed_at) { // (the device could not hold this much before: do not allocate-and-fail every frame)
+        h->err = "device memory exhausted while growing the block pool (a pool of " + std::to_string(h->grow_failed_at) + " blocks did not fit)";
+        return MLM_ERR_CAPACITY;
+    }
+    const int rc = resize_pool(h, target, g, nb);
+    if (rc == MLM_ERR_CAPACITY) {
+        h->grow_failed_at = target;
+        h->err = "device memory exhausted while growing the block pool: " + h->err;
+    }
+    if (rc) return rc;
     h->n_pool_grows++;
     if (getenv("MLM_DEBUG_CREATE")) fprintf(stderr, "[pool] grown to %d blocks (%u in use)\n", h->P.max_blocks, nb);
     return MLM_OK;

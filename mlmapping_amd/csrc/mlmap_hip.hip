@@ -48,6 +48,7 @@
 #include "mlm_kernels_cluster.h"
 #include "mlm_kernels_mesh.h"
 #include "mlm_kernels_octree.h"
+#include "mlm_kernels_crop.h"
 #include "mlm_host.h"
 #include "mlm_plan.h"
 #include "mlm_mapview.h"
@@ -2061,6 +2062,194 @@ int mlm_import_blocks(mlm_handle *h, int n, const int32_t *keys, const float *lo
         return MLM_ERR_CAPACITY;
     }
     return MLM_OK;
+}
+
+namespace {
+static_assert(MLM_CROP_INSIDE == MLM_CROP_F_INSIDE && MLM_CROP_DRY == MLM_CROP_F_DRY && MLM_CROP_SHRINK == MLM_CROP_F_SHRINK && MLM_CROP_OUTSIDE == 0,
+              "mlm_crop.h restates the flags of include/mlmap_hip.h");
+constexpr unsigned int kCropGrid = 8192;      // most workgroups of the crop kernels (they stride over the rest)
+constexpr size_t kCropStageBytes = 64u << 20; // staged rows of a page-out into host memory, per round
+
+// the copy kernel K<FW, BW> for the lane widths fw (16 or 4 bytes: float plane) and bw (16, 4 or 1 bytes: byte planes)
+#define MLM_CROP_LAUNCH(K, fw, bw, grid, ...)                                                                                     \
+    do {                                                                                                                          \
+        if ((fw) == 16 && (bw) == 16) hipLaunchKernelGGL((K<16, 16>), dim3(grid), dim3(MLM_BLOCK), 0, h->stream, __VA_ARGS__);    \
+        else if ((fw) == 16 && (bw) == 4) hipLaunchKernelGGL((K<16, 4>), dim3(grid), dim3(MLM_BLOCK), 0, h->stream, __VA_ARGS__); \
+        else if ((fw) == 16) hipLaunchKernelGGL((K<16, 1>), dim3(grid), dim3(MLM_BLOCK), 0, h->stream, __VA_ARGS__);              \
+        else if ((bw) == 16) hipLaunchKernelGGL((K<4, 16>), dim3(grid), dim3(MLM_BLOCK), 0, h->stream, __VA_ARGS__);              \
+        else if ((bw) == 4) hipLaunchKernelGGL((K<4, 4>), dim3(grid), dim3(MLM_BLOCK), 0, h->stream, __VA_ARGS__);                \
+        else hipLaunchKernelGGL((K<4, 1>), dim3(grid), dim3(MLM_BLOCK), 0, h->stream, __VA_ARGS__);                               \
+    } while (0)
+inline int crop_width(int w, const void *p) { // the widest lane path of at most w bytes that p's alignment allows
+    const uintptr_t a = (uintptr_t)p;
+    return !p ? w : (w >= 16 && a % 16 == 0) ? 16 : (w >= 4 && a % 4 == 0) ? 4 : 1;
+}
+
+// The slots [K, nb) back at alloc_pool's initial values, on the handle's stream (a null-stream hipMemset is not ordered with it: grow_pool).
+int crop_reset_tail(mlm_handle *h, unsigned int K, unsigned int nb) {
+    const MlmDev &P = h->P;
+    const size_t C = (size_t)P.cells, v0 = (size_t)K * C, nv = (size_t)(nb - K) * C;
+    hipStream_t st = h->stream;
+    HIPCHK(h, hipMemsetAsync(P.log_odds + v0, 0, nv * sizeof(float), st));
+    HIPCHK(h, hipMemsetAsync(P.occ + v0, 'u', nv, st));
+    HIPCHK(h, hipMemsetAsync(P.infl + v0, 'u', nv, st));
+    for (int half = 0; half < 2; ++half) {
+        HIPCHK(h, hipMemsetAsync(P.vox_head + half * P.vox_stride + v0, 0xFF, nv * sizeof(int), st));
+        HIPCHK(h, hipMemsetAsync(P.vox_miss + half * P.vox_stride + v0, 0, nv * sizeof(uint32_t), st));
+    }
+    if (P.explore) {
+        HIPCHK(h, hipMemsetAsync(P.frnt + v0, 0, nv, st));
+        HIPCHK(h, hipMemsetAsync(P.vox_tau + v0, 0, nv * sizeof(unsigned long long), st));
+        HIPCHK(h, hipMemsetAsync(P.blk_collapsed + K, 0, (size_t)(nb - K), st));
+        HIPCHK(h, hipMemsetAsync(P.blk_observed + K, 0, (size_t)(nb - K), st));
+    }
+    return MLM_OK;
+}
+
+// everything of mlm_crop_blocks behind the argument check and the drain
+int crop_run(mlm_handle *h, const MlmCropBox &B, int flags, int cap, int32_t *keys, float *log_odds, uint8_t *occ, uint8_t *infl,
+             uint8_t *collapsed, int64_t *summary) {
+    int64_t sum[MLM_CROP_ROW] = {};
+    auto report = [&]() {
+        sum[7] = (int64_t)h->alloc_bytes;
+        if (summary) std::memcpy(summary, sum, sizeof(sum));
+    };
+    int rc = read_global(h);
+    if (rc) return rc;
+    const unsigned int nb = std::min<unsigned int>(h->h_g->n_blocks, (unsigned int)h->P.max_blocks);
+    h->stats.n_blocks = nb; // (mlm_frame_stats follows the calls that change the block count between frames as well)
+    h->stats.block_capacity = h->P.max_blocks;
+    sum[0] = sum[1] = nb;
+    sum[4] = sum[5] = h->P.max_blocks;
+    sum[6] = sum[7] = (int64_t)h->alloc_bytes;
+    const bool any_out = keys || log_odds || occ || infl || collapsed;
+    unsigned int D = 0, H = 0;
+    const unsigned int chunks = (nb + MLM_CROP_SLOTS_PER_CHUNK - 1) / MLM_CROP_SLOTS_PER_CHUNK;
+    unsigned int *chunk_cnt = nullptr, *ctrl = nullptr, *list = nullptr;
+    if (nb) {
+        // chunk counts | ctrl | list: 4 bytes per block, kept by the handle as the read-outs keep theirs
+        const size_t o_ctrl = mlm_align256((size_t)chunks * 4), o_list = o_ctrl + 256, total = o_list + (size_t)nb * 4;
+        if ((rc = readout_reserve(h, h->d_crop, h->crop_bytes, total, "mlm_crop_blocks"))) {
+            report();
+            return rc;
+        }
+        void *scratch = h->d_crop;
+        chunk_cnt = (unsigned int *)scratch, ctrl = (unsigned int *)((char *)scratch + o_ctrl), list = (unsigned int *)((char *)scratch + o_list);
+        const unsigned int grid = std::min(chunks, kCropGrid);
+        HIPCHK(h, hipMemsetAsync(ctrl, 0, MLM_CROP_CTRL_WORDS * 4, h->stream));
+        hipLaunchKernelGGL(k_crop_count, dim3(grid), dim3(MLM_BLOCK), 0, h->stream, h->P, B, nb, chunks, chunk_cnt);
+        hipLaunchKernelGGL(k_crop_scan, dim3(1), dim3(MLM_BLOCK), 0, h->stream, chunk_cnt, chunks, ctrl);
+        hipLaunchKernelGGL(k_crop_list, dim3(grid), dim3(MLM_BLOCK), 0, h->stream, h->P, B, nb, chunks, chunk_cnt, ctrl, list);
+        HIPCHK(h, hipGetLastError());
+        unsigned int c[MLM_CROP_CTRL_WORDS] = {};
+        HIPCHK(h, hipMemcpyAsync(c, ctrl, sizeof(c), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        D = c[0], H = c[1];
+        if (D > nb || H > std::min(D, nb - D)) {
+            h->err = "mlm_crop_blocks: the scan of the drop flags is inconsistent";
+            return MLM_ERR_HIP;
+        }
+    }
+    const unsigned int K = nb - D;
+    sum[1] = K, sum[2] = D;
+    if (any_out && (unsigned int)cap < D) {
+        h->err = "mlm_crop_blocks: " + std::to_string(D) + " blocks would be dropped, the outputs hold " + std::to_string(cap);
+        report();
+        return MLM_ERR_CAPACITY;
+    }
+    if ((flags & MLM_CROP_DRY) || D == 0) {
+        report();
+        return MLM_OK;
+    }
+    const size_t C = (size_t)h->P.cells;
+    const int fw = mlm_crop_float_width(h->P.cells), bw = mlm_crop_byte_width(h->P.cells);
+    if (any_out) { // the page-out first: the holes are among its sources
+        ReadoutChannels<5> ch(h->d_win_stage, h->win_stage_bytes, {{keys, 3 * sizeof(int32_t)}, {log_odds, C * sizeof(float)}, {occ, C}, {infl, C}, {collapsed, 1}});
+        size_t per_row = 0;
+        for (int k = 0; k < 5; ++k) per_row += ch.staged[k] ? ch.elem[k] : 0;
+        size_t rows = !ch.any_staged ? (size_t)D : std::min<size_t>(D, std::max<size_t>(1, kCropStageBytes / per_row));
+        long long kv;
+        if (ch.any_staged && knob("crop_stage_rows", kv)) rows = std::min<size_t>(D, (size_t)kv); // (test knob: rounds of a few rows)
+        if ((rc = ch.reserve(h, "mlm_crop_blocks", rows))) {
+            report();
+            return rc;
+        }
+        for (size_t r0 = 0; r0 < D; r0 += rows) {
+            const size_t r1 = std::min<size_t>(D, r0 + rows);
+            float *d_lo = (float *)ch.at(1, r0);
+            uint8_t *d_occ = (uint8_t *)ch.at(2, r0), *d_infl = (uint8_t *)ch.at(3, r0);
+            const int pfw = crop_width(fw, d_lo), pbw = std::min(crop_width(bw, d_occ), crop_width(bw, d_infl));
+            MLM_CROP_LAUNCH(k_crop_page, pfw, pbw, wave_grid(r1 - r0, kCropGrid), h->P, (const unsigned int *)list, nb, (unsigned int)r0, (unsigned int)r1,
+                            (int32_t *)ch.at(0, r0), d_lo, d_occ, d_infl, (uint8_t *)ch.at(4, r0));
+            HIPCHK(h, hipGetLastError());
+            if (ch.any_staged) {
+                if ((rc = ch.copy_out(h, 0, 5, r0, r1 - r0))) return rc;
+                HIPCHK(h, hipStreamSynchronize(h->stream)); // (the staging is reused by the next round)
+            }
+        }
+        sum[3] = D;
+    }
+    // From here on the pool changes.  The host mirror maps pool slot s to its own slot s: it forgets which blocks it knows.
+    mirror_finish_eager(h);
+    if (h->mir.cap) h->mir.view.table_reset(h->mir.cap);
+    h->mir.n_known = 0;
+    mirror_mark_all(h);
+    if (H) {
+        MLM_CROP_LAUNCH(k_crop_move, fw, bw, wave_grid(H, kCropGrid), h->P, (const unsigned int *)list, nb, D, K, H);
+        HIPCHK(h, hipGetLastError());
+    }
+    if ((rc = crop_reset_tail(h, K, nb))) return rc;
+    const size_t ht = (size_t)h->P.ht_mask + 1;
+    HIPCHK(h, hipMemsetAsync(h->P.ht_keys, 0xFF, ht * sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipMemsetAsync(h->P.ht_slot, 0xFF, ht * sizeof(int), h->stream));
+    if (K) {
+        hipLaunchKernelGGL(k_rehash_blocks, dim3(grid_for(K)), dim3(MLM_BLOCK), 0, h->stream, h->P, K);
+        HIPCHK(h, hipGetLastError());
+    }
+    MlmGlobal g = *h->h_g;
+    g.n_blocks = K;
+    g.err &= ~1u;
+    HIPCHK(h, hipMemcpyAsync(h->P.g, &g, sizeof(g), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    *h->h_g = g;
+    for (int k = 0; k < MLM_SETS; ++k) *h->h_gb[k] = g;
+    h->stats.n_blocks = K;
+    if ((flags & MLM_CROP_SHRINK) && h->pool_grow) { // best effort: the crop stands whether or not the smaller pool could be had
+        const long long target = mlm_crop_shrink_target(h->lim.max_blocks, h->P.max_blocks, K);
+        if (target > 0) {
+            const std::string err = h->err;
+            rc = resize_pool(h, (size_t)target, g, K);
+            if (rc == MLM_ERR_CAPACITY) {
+                h->err = err;
+            } else if (rc) {
+                return rc;
+            } else {
+                h->grow_failed_at = 0; // (memory went back to the device: what did not fit before may fit now)
+                if (getenv("MLM_DEBUG_CREATE")) fprintf(stderr, "[pool] shrunk to %d blocks (%u in use)\n", h->P.max_blocks, K);
+            }
+        }
+    }
+    h->stats.block_capacity = h->P.max_blocks;
+    sum[5] = h->P.max_blocks;
+    sum[7] = (int64_t)h->alloc_bytes;
+    report();
+    return MLM_OK;
+}
+} // namespace
+
+int mlm_crop_blocks(mlm_handle *h, const int32_t key_lo[3], const int32_t key_dims[3], int flags, int cap, int32_t *keys, float *log_odds,
+                    uint8_t *occ, uint8_t *infl, uint8_t *collapsed, int64_t summary[MLM_CROP_ROW]) {
+    if (!h) return MLM_ERR_INVALID;
+    MLM_LOCK(h);
+    MlmCropBox B{};
+    if (const int bad = mlm_crop_check(key_lo, key_dims, flags, cap, B)) {
+        h->err = std::string("mlm_crop_blocks: ") + mlm_crop_check_text(bad);
+        return MLM_ERR_INVALID;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = drain(h);
+    if (rc) return rc;
+    return crop_run(h, B, flags, cap, keys, log_odds, occ, infl, collapsed, summary);
 }
 
 int mlm_merge_pack(mlm_handle *h, const int32_t *keys_dev, int n, float *log_odds_dev, uint8_t *seen_dev) {

@@ -42,6 +42,8 @@ MLM_MESH_OCC, MLM_MESH_INFL, MLM_MESH_UNKNOWN, MLM_MESH_SEEN, MLM_MESH_CLOSED, M
 # mlm_export_octree: infl == OCCUPIED counts as OCC, FREE voxels count as NONE, int64 in summary; the labels a word holds per child
 MLM_OCT_INFL, MLM_OCT_OCC_ONLY, MLM_OCT_ROW = 1, 2, 40
 MLM_OCT_NONE, MLM_OCT_FREE, MLM_OCT_OCC, MLM_OCT_INNER = 0, 1, 2, 3
+# mlm_crop_blocks flags (OUTSIDE / INSIDE: which side of the key box is dropped), int64 in summary
+MLM_CROP_OUTSIDE, MLM_CROP_INSIDE, MLM_CROP_DRY, MLM_CROP_SHRINK, MLM_CROP_ROW = 0, 1, 2, 4, 8
 # mlm_query_rays flags: what stops a ray (their union; 0: nothing, a pure count)
 MLM_RAY_OCC, MLM_RAY_INFL, MLM_RAY_UNKNOWN = 1, 2, 4
 # mlm_query_views: int64 per row of the table
@@ -58,7 +60,7 @@ ABI_SYMBOLS = [
     "mlm_integrate_depth_u16", "mlm_integrate_depth_u16_dev", "mlm_integrate_depth_batch_dev",
     "mlm_integrate_depth_batch", "mlm_integrate_callback",
     "mlm_integrate_points", "mlm_query_occupancy", "mlm_query_occupancy_inflate", "mlm_query_inflate_occupancy",
-    "mlm_query_odds", "mlm_query_odd_grad", "mlm_query_odds_at", "mlm_export_frontier_points", "mlm_import_blocks",
+    "mlm_query_odds", "mlm_query_odd_grad", "mlm_query_odds_at", "mlm_export_frontier_points", "mlm_import_blocks", "mlm_crop_blocks",
     "mlm_merge_pack", "mlm_merge_finish",
     "mlm_set_free_in_bound", "mlm_inflate_map", "mlm_block_count",
     "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_grid2d", "mlm_export_reach", "mlm_export_route", "mlm_export_clusters", "mlm_export_mesh", "mlm_export_octree", "mlm_query_rays", "mlm_render_depth", "mlm_query_views", "mlm_query_boxes", "mlm_query_nearest", "mlm_query_sweeps", "mlm_query_paths", "mlm_score_poses", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
@@ -148,6 +150,7 @@ def load_library(path: Optional[str] = None):
     L.mlm_query_odds_at.argtypes = [vp, vp, vp, i32, vp]
     L.mlm_export_frontier_points.argtypes = [vp, i32, vp, vp]
     L.mlm_import_blocks.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    L.mlm_crop_blocks.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
     L.mlm_merge_pack.argtypes = [vp, vp, i32, vp, vp]
     L.mlm_merge_finish.argtypes = [vp, vp, vp, ctypes.c_size_t, vp]
     L.mlm_set_free_in_bound.argtypes = [vp, vp, vp]
@@ -404,8 +407,9 @@ class MLMap:
         self._chk(self._L.mlm_block_count(self._h, ctypes.byref(n)), "mlm_block_count")
         return n.value
 
-    def export_blocks(self) -> Dict[str, np.ndarray]:
-        """observed_group_map contents sorted by block key (same dict layout as the oracle binding)."""
+    def export_blocks(self, raw: bool = False) -> Dict[str, np.ndarray]:
+        """observed_group_map contents sorted by block key (same dict layout as the oracle binding); raw=True: in the pool's slot
+        order, as mlm_export_blocks writes them."""
         n, C = self.block_count(), self.cells
         keys = np.empty((n, 3), dtype=np.int32)
         lo = np.empty((n, C), dtype=np.float32)
@@ -416,7 +420,7 @@ class MLMap:
                   "mlm_export_blocks")
         col = np.zeros(n, dtype=np.uint8)
         self._chk(self._L.mlm_export_block_flags(self._h, n, _p(col), ctypes.byref(m)), "mlm_export_block_flags")
-        o = np.lexsort((keys[:, 2], keys[:, 1], keys[:, 0]))
+        o = np.arange(n) if raw else np.lexsort((keys[:, 2], keys[:, 1], keys[:, 0]))
         return {"keys": keys[o], "collapsed": col[o], "log_odds": lo[o], "occ": occ[o], "infl": infl[o]}
 
     def export_frontier(self) -> np.ndarray:
@@ -456,6 +460,43 @@ class MLMap:
         holds = [ptr(log_odds, np.float32), ptr(occ, np.uint8), ptr(infl, np.uint8), ptr(collapsed, np.uint8)]
         self._chk(self._L.mlm_import_blocks(self._h, n, kp, holds[0][0], holds[1][0], holds[2][0], holds[3][0]),
                   "mlm_import_blocks")
+
+    def crop_blocks(self, key_lo, key_dims, inside: bool = False, dry: bool = False, shrink: bool = False, out=None) -> Dict[str, np.ndarray]:
+        """Drop the blocks whose key lies outside (inside=True: inside) the box key_lo <= key < key_lo + key_dims of block keys, in
+        place on the device (mlm_crop_blocks).  out=None: the blocks are just dropped; out=True: they are paged out into host arrays
+        sized by a dry call and returned as "keys", "log_odds", "occ", "infl", "collapsed" (what import_blocks takes to bring them
+        back), in ascending order of their old slot; out={"cap": blocks, "keys": ptr, "log_odds": ptr, ...}: into device memory (ints,
+        any of them may be missing).  dry=True only counts.  shrink=True gives pool memory back afterwards.  Always returns
+        "summary": int64 [blocks before, kept, dropped, written, capacity before, after, device_bytes before, after]."""
+        lo_a = np.ascontiguousarray(key_lo, dtype=np.int32).reshape(3)
+        dims_a = np.ascontiguousarray(key_dims, dtype=np.int32).reshape(3)
+        flags = (MLM_CROP_INSIDE if inside else MLM_CROP_OUTSIDE) | (MLM_CROP_DRY if dry else 0) | (MLM_CROP_SHRINK if shrink else 0)
+        summary = np.zeros(MLM_CROP_ROW, dtype=np.int64)
+        names = ("keys", "log_odds", "occ", "infl", "collapsed")
+        res, cap, ptr = {"summary": summary}, 0, [None] * 5
+        if out is True and not dry:
+            self._chk(self._L.mlm_crop_blocks(self._h, _p(lo_a), _p(dims_a), flags | MLM_CROP_DRY, 0, None, None, None, None, None, _p(summary)),
+                      "mlm_crop_blocks")
+            cap, C = int(summary[2]), self.cells
+            res.update(keys=np.empty((cap, 3), dtype=np.int32), log_odds=np.empty((cap, C), dtype=np.float32),
+                       occ=np.empty((cap, C), dtype=np.uint8), infl=np.empty((cap, C), dtype=np.uint8), collapsed=np.empty(cap, dtype=np.uint8))
+            ptr = [_p(res[k]) for k in names]
+        elif out is not None:
+            cap = int(out["cap"])
+            ptr = [None if out.get(k) is None else ctypes.c_void_p(int(out[k])) for k in names]
+        if not dry:
+            self._merge_base = None  # (as import_blocks: the baseline of periodic merges no longer describes this map)
+        self._chk(self._L.mlm_crop_blocks(self._h, _p(lo_a), _p(dims_a), flags, cap, *ptr, _p(summary)), "mlm_crop_blocks")
+        return res
+
+    def retain_around(self, t_w, radius_m: float, shrink: bool = False, out=None) -> Dict[str, np.ndarray]:
+        """Keep a rolling window: drop every block farther than radius_m from t_w on some axis — the kept key box is
+        floor((t - r) / d_glb) - 1 .. floor((t + r) / d_glb) + 1 per axis (one block of margin).  See crop_blocks."""
+        t = _f64(t_w).reshape(3)
+        d_glb = self.cfg.subbox_d_xyz * self.cfg.subbox_n  # (map_local.cpp:60, as mlm_create computes it)
+        lo = np.floor((t - radius_m) / d_glb).astype(np.int64) - 1
+        hi = np.floor((t + radius_m) / d_glb).astype(np.int64) + 1
+        return self.crop_blocks(lo, hi - lo + 1, inside=False, shrink=shrink, out=out)
 
     def export_window(self, lo, dims, odds=True, occ=False, infl=False, grad=False, max_iter: int = 5) -> Dict[str, np.ndarray]:
         """Dense read-out of the voxel box lo <= v < lo + dims (voxel indices v = block key * subbox_n + cell coordinate, per axis
