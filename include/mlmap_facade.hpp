@@ -310,6 +310,16 @@ class mlmap {
         check(mlm_crop_blocks(h_, key_lo, key_dims, flags, cap, keys, log_odds, occ, infl, collapsed, summary), "mlm_crop_blocks");
     }
 
+    // the map resampled under a rigid transform (mlm_warp_blocks; T_sd maps the new frame to the map's; flags MLM_WARP_*; the emitted
+    // blocks in ascending key order into keys [cap][3], log_odds / occ / infl [cap][cells], host or device memory, NULL = skipped;
+    // summary host memory: [2] emitted blocks whatever the cap — a MLM_WARP_DRY call sizes the next one; MLM_WARP_REPLACE: the handle
+    // holds the warped map afterwards)
+    void warpBlocks(const double T_sd[12], const int32_t key_lo[3] = nullptr, const int32_t key_dims[3] = nullptr, int flags = 0, int cap = 0,
+                    int32_t *keys = nullptr, float *log_odds = nullptr, uint8_t *occ = nullptr, uint8_t *infl = nullptr,
+                    int64_t summary[MLM_WARP_ROW] = nullptr) {
+        check(mlm_warp_blocks(h_, T_sd, key_lo, key_dims, flags, cap, keys, log_odds, occ, infl, summary), "mlm_warp_blocks");
+    }
+
     // segment casts through the voxel map (mlm_query_rays; flags MLM_RAY_*; n x 3 end points; inputs and outputs host or device
     // memory, NULL output = skipped)
     void castRays(const double *p0, const double *p1, int n, int flags, int8_t *status, int32_t *voxel3 = nullptr, double *t = nullptr,

@@ -907,6 +907,42 @@ int mlm_crop_blocks(mlm_handle *h, const int32_t key_lo[3], const int32_t key_di
                     int32_t *keys, float *log_odds, uint8_t *occ, uint8_t *infl, uint8_t *collapsed,
                     int64_t summary[MLM_CROP_ROW]);
 
+/* Resample the map under a rigid transform: the map's voxel content written onto the lattice of another frame, as blocks in the layout
+ * mlm_import_blocks and the merge take (no reference counterpart: the reference's map lives in one frame for good).  What a pose
+ * correction (mlm_score_poses), a merge of maps whose origins differ, or blocks paged out before the odometry frame was corrected need.
+ *   T_sd: 12 doubles as in mlm_score_poses / mlm_render_depth (R row major, then o); it maps a point of the DESTINATION (new) frame to
+ * the SOURCE (current map) frame and is never inverted for the values.  The answer is defined per destination voxel v = g * subbox_n + c
+ * (block key g, cell coordinate c), in IEEE double, nothing fused (mlmapping_amd/csrc/mlm_warp.h):
+ *     centre   p_a = (g_a * d_glb + c_a * d_sub) + d_sub_half                (subbox_id2xyz_glb_vec);
+ *     source   w_a = ((R[a][0] * p_0 + R[a][1] * p_1) + R[a][2] * p_2) + o_a  (mlm_score_poses' rule);
+ *     voxel    floor((w_a / d_sub) * 1024) >> 10, invalid if a lattice value is not finite or beyond 2^40; block and cell by floor division.
+ * The voxel is LIVE iff the lattice step is valid, the source block's key lies inside the 21-bit key range and the block is present, and
+ * — with MLM_WARP_SEEN — the source voxel's occ != 'u' or its infl == 'o'.  A live voxel takes the source voxel's raw log_odds, occ and
+ * infl (a released block answers from element 0 with infl 'u', as the queries do); every other voxel is 0.0f / 'u' / 'u', what
+ * allocate_ram leaves.  Nearest voxel only: classes and log-odds stay consistent with each other and the result is exact.
+ *   A destination block is EMITTED iff it holds at least one live voxel, its key lies inside the 21-bit range and inside the key box
+ * (key_lo / key_dims: mlm_crop_blocks' box semantics; both NULL: no restriction).  The emitted blocks are written in ascending order
+ * of their packed key — x, then y, then z — into keys [cap*3], log_odds / occ / infl [cap*cells]; each may be NULL; device memory of
+ * this device is written in place, any host memory is staged.  With an output given and cap smaller than the number of emitted
+ * blocks: MLM_ERR_CAPACITY, nothing written but summary.  MLM_WARP_DRY only counts.
+ *   summary (may be NULL): [0] source blocks, [1] candidate blocks examined (an implementation count >= [2]), [2] emitted blocks E,
+ * [3] blocks written, [4] live voxels, [5] / [6] live voxels with occ 'o' / 'f', [7] live voxels with infl 'o'.
+ *   MLM_WARP_REPLACE: afterwards the handle holds the warped map instead of its own — exactly what "this call into device buffers, drop
+ * every block (mlm_crop_blocks, MLM_CROP_INSIDE, an all-covering box), mlm_import_blocks of the dump" does on the same handle, and made
+ * of those code paths.  Frame slots, graphs and container state survive as across a crop.  Every check, the count and every allocation
+ * come before the first write into the pool: a failing call leaves the map as it was.  Refused (MLM_ERR_INVALID) on a frontier-mode
+ * handle: frontier and released flags have no resampled meaning.  Without it the call only reads the map, frontier mode included.
+ *   Like mlm_import_blocks the call waits for everything submitted first.  MLM_ERR_INVALID (with a text in mlm_last_error): a NULL
+ * T_sd, a non-finite entry, max |R R^T - I| > 1e-9 (the transform must be rigid), one of key_lo / key_dims NULL and the other not,
+ * mlm_crop_blocks' box errors, an unknown flag bit, cap < 0. */
+enum { MLM_WARP_SEEN    = 1,  /* only voxels the source map has observed (occ != 'u') or inflated (infl == 'o') are live */
+       MLM_WARP_REPLACE = 2,  /* afterwards the handle holds the warped map */
+       MLM_WARP_DRY     = 4 };/* count only: summary is filled, nothing is written */
+#define MLM_WARP_ROW 8
+int mlm_warp_blocks(mlm_handle *h, const double T_sd[12], const int32_t key_lo[3], const int32_t key_dims[3],
+                    int flags, int cap, int32_t *keys, float *log_odds, uint8_t *occ, uint8_t *infl,
+                    int64_t summary[MLM_WARP_ROW]);
+
 /* The two device-side steps of the optional global-map merge across GPUs (mlmapping_amd/merge.py; no reference
  * counterpart: SURVEY.md §8e).  All pointers are device memory; both calls return when the buffers are written.
  * pack:   row b of log_odds_dev / seen_dev [n*cells] = this map's cells of block keys_dev[3b..3b+2] (0 / 0 where the

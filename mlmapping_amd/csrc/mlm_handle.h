@@ -204,6 +204,10 @@ struct mlm_handle : MlmHandlePlan { // (MlmHandlePlan, mlm_plan.h: the members m
     // mlm_crop_blocks: chunk counts, control words and the list of the slots, dropped ones first (mlm_kernels_crop.h): 4 bytes per block
     void *d_crop = nullptr;
     size_t crop_bytes = 0;
+    // mlm_warp_blocks: the candidate set with its chunk counts and control words, 8 bytes per entry; and what is sized by the
+    // candidates: their keys (twice, for the sort), the sort's values and scratch, four counters each, the emitted list
+    void *d_warp_set = nullptr, *d_warp = nullptr;
+    size_t warp_set_bytes = 0, warp_bytes = 0;
     // the batched queries' staging: the host inputs / outputs of one chunk
     void *d_ray_stage = nullptr;
     size_t ray_stage_bytes = 0;

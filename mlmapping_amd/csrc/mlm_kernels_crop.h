@@ -20,9 +20,10 @@ __device__ __forceinline__ bool mlm_crop_slot_drops(const MlmDev &P, const MlmCr
     return mlm_crop_drops(B, P.block_keys[3 * (size_t)s], P.block_keys[3 * (size_t)s + 1], P.block_keys[3 * (size_t)s + 2]);
 }
 
-// phase 1: dropped slots of every chunk
-__global__ __launch_bounds__(MLM_BLOCK) void k_crop_count(const MlmDev P, const MlmCropBox B, unsigned int nb, unsigned int chunks,
-                                                          unsigned int *__restrict__ chunk_cnt) {
+// The first and the third phase of the prefix over any flag of the items [0, nb) (mlm_warp_blocks numbers its candidates with them too).
+// phase 1: flagged items of every chunk; pred(s) for s < nb
+template <class Pred>
+__device__ __forceinline__ void mlm_crop_count_chunks(Pred pred, unsigned int nb, unsigned int chunks, unsigned int *__restrict__ chunk_cnt) {
     __shared__ unsigned int s_wave[MLM_BLOCK / 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (unsigned int c = blockIdx.x; c < chunks; c += gridDim.x) {
@@ -31,7 +32,7 @@ __global__ __launch_bounds__(MLM_BLOCK) void k_crop_count(const MlmDev P, const 
         // (whole workgroups stay in the loop: ballots and barriers see every lane)
         for (unsigned int r = 0; r < MLM_CROP_SLOTS_PER_CHUNK; r += MLM_BLOCK) {
             const unsigned long long s = s0 + r + threadIdx.x;
-            const bool drop = s < nb && mlm_crop_slot_drops(P, B, (unsigned int)s);
+            const bool drop = s < nb && pred((unsigned int)s);
             mine += (unsigned int)__builtin_popcountll(__ballot(drop));
         }
         __syncthreads(); // (the previous chunk's wave counts are read)
@@ -43,6 +44,38 @@ __global__ __launch_bounds__(MLM_BLOCK) void k_crop_count(const MlmDev P, const 
             chunk_cnt[c] = t;
         }
     }
+}
+// phase 3 (chunk_cnt scanned by k_crop_scan): emit(s, d, flag) for every s < nb, d the number of flagged items below s
+template <class Pred, class Emit>
+__device__ __forceinline__ void mlm_crop_rank_chunks(Pred pred, unsigned int nb, unsigned int chunks, const unsigned int *__restrict__ chunk_cnt, Emit emit) {
+    __shared__ unsigned int s_wave[MLM_BLOCK / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (unsigned int c = blockIdx.x; c < chunks; c += gridDim.x) {
+        const unsigned long long s0 = (unsigned long long)c * MLM_CROP_SLOTS_PER_CHUNK;
+        unsigned int base = chunk_cnt[c];
+        for (unsigned int r = 0; r < MLM_CROP_SLOTS_PER_CHUNK; r += MLM_BLOCK) {
+            const unsigned long long s = s0 + r + threadIdx.x;
+            const bool live = s < nb;
+            const bool drop = live && pred((unsigned int)s);
+            const unsigned long long bal = __ballot(drop);
+            __syncthreads(); // (the previous round's wave totals are read)
+            if (lane == 0) s_wave[wave] = (unsigned int)__builtin_popcountll(bal);
+            __syncthreads();
+            unsigned int before = 0, total = 0;
+            for (int w = 0; w < MLM_BLOCK / 64; ++w) {
+                if (w < wave) before += s_wave[w];
+                total += s_wave[w];
+            }
+            if (live) emit((unsigned int)s, base + before + (unsigned int)__builtin_popcountll(bal & ((1ull << lane) - 1ull)), drop);
+            base += total;
+        }
+    }
+}
+
+// phase 1: dropped slots of every chunk
+__global__ __launch_bounds__(MLM_BLOCK) void k_crop_count(const MlmDev P, const MlmCropBox B, unsigned int nb, unsigned int chunks,
+                                                          unsigned int *__restrict__ chunk_cnt) {
+    mlm_crop_count_chunks([&](unsigned int s) { return mlm_crop_slot_drops(P, B, s); }, nb, chunks, chunk_cnt);
 }
 
 // phase 2: exclusive scan of the chunk counts in place, by one workgroup; the total is D
@@ -71,34 +104,12 @@ __global__ __launch_bounds__(MLM_BLOCK) void k_crop_scan(unsigned int *__restric
 __global__ __launch_bounds__(MLM_BLOCK) void k_crop_list(const MlmDev P, const MlmCropBox B, unsigned int nb, unsigned int chunks,
                                                          const unsigned int *__restrict__ chunk_cnt, unsigned int *__restrict__ ctrl,
                                                          unsigned int *__restrict__ list) {
-    __shared__ unsigned int s_wave[MLM_BLOCK / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const unsigned int D = ctrl[0], K = nb - min(D, nb);
-    for (unsigned int c = blockIdx.x; c < chunks; c += gridDim.x) {
-        const unsigned long long s0 = (unsigned long long)c * MLM_CROP_SLOTS_PER_CHUNK;
-        unsigned int base = chunk_cnt[c];
-        for (unsigned int r = 0; r < MLM_CROP_SLOTS_PER_CHUNK; r += MLM_BLOCK) {
-            const unsigned long long s = s0 + r + threadIdx.x;
-            const bool live = s < nb;
-            const bool drop = live && mlm_crop_slot_drops(P, B, (unsigned int)s);
-            const unsigned long long bal = __ballot(drop);
-            __syncthreads(); // (the previous round's wave totals are read)
-            if (lane == 0) s_wave[wave] = (unsigned int)__builtin_popcountll(bal);
-            __syncthreads();
-            unsigned int before = 0, total = 0;
-            for (int w = 0; w < MLM_BLOCK / 64; ++w) {
-                if (w < wave) before += s_wave[w];
-                total += s_wave[w];
-            }
-            if (live) {
-                const unsigned int d = base + before + (unsigned int)__builtin_popcountll(bal & ((1ull << lane) - 1ull));
-                const unsigned int at = mlm_crop_list_pos((unsigned int)s, d, drop, D);
-                if (at < nb) list[at] = (unsigned int)s; // (always: the list is a permutation of the slots; the bound is the array's)
-                if ((unsigned int)s == K) ctrl[1] = d;
-            }
-            base += total;
-        }
-    }
+    mlm_crop_rank_chunks([&](unsigned int s) { return mlm_crop_slot_drops(P, B, s); }, nb, chunks, chunk_cnt, [&](unsigned int s, unsigned int d, bool drop) {
+        const unsigned int at = mlm_crop_list_pos(s, d, drop, D);
+        if (at < nb) list[at] = s; // (always: the list is a permutation of the slots; the bound is the array's)
+        if (s == K) ctrl[1] = d;
+    });
 }
 
 // `bytes` from src to dst by one wave, W bytes per lane and trip (both W-byte aligned, bytes a multiple of W)

@@ -49,6 +49,7 @@
 #include "mlm_kernels_mesh.h"
 #include "mlm_kernels_octree.h"
 #include "mlm_kernels_crop.h"
+#include "mlm_kernels_warp.h"
 #include "mlm_host.h"
 #include "mlm_plan.h"
 #include "mlm_mapview.h"
@@ -2018,6 +2019,42 @@ int mlm_export_frontier_points(mlm_handle *h, int cap_points, float *xyz, int *n
     return export_points(h, cap_points, xyz, n_out, 1, "mlm_export_frontier_points");
 }
 
+namespace {
+// the one staging buffer of an import of N blocks: keys | slots | log_odds | occ | infl | collapsed
+struct ImportStage {
+    size_t o_keys, o_slots, o_lo, o_occ, o_infl, o_col, total;
+};
+ImportStage import_stage(size_t N, size_t C) {
+    ImportStage L{};
+    L.o_keys = 0, L.o_slots = L.o_keys + N * 12, L.o_lo = (L.o_slots + N * 4 + 15) & ~(size_t)15, L.o_occ = L.o_lo + N * C * 4, L.o_infl = L.o_occ + N * C,
+    L.o_col = L.o_infl + N * C, L.total = L.o_col + N;
+    return L;
+}
+// The n blocks staged at d (device memory; a plane that is not staged is left as it is in the map) found or created and overwritten;
+// waits, and reports a pool that could not take them.  mlm_import_blocks, and the last step of mlm_warp_blocks' MLM_WARP_REPLACE.
+int import_staged(mlm_handle *h, char *d, const ImportStage &L, int n, bool log_odds, bool occ, bool infl, bool collapsed) {
+    const size_t C = (size_t)h->P.cells, N = (size_t)n;
+    hipLaunchKernelGGL(k_import_slots, dim3(grid_for(N)), dim3(MLM_BLOCK), 0, h->stream, h->P, (const int32_t *)(d + L.o_keys), n, (int *)(d + L.o_slots));
+    hipLaunchKernelGGL(k_import_cells, dim3(std::min<unsigned int>(4096u, grid_for(N * C))), dim3(MLM_BLOCK), 0, h->stream, h->P,
+                       (const int *)(d + L.o_slots), n, log_odds ? (const float *)(d + L.o_lo) : nullptr, occ ? (const uint8_t *)(d + L.o_occ) : nullptr,
+                       infl ? (const uint8_t *)(d + L.o_infl) : nullptr, collapsed ? (const uint8_t *)(d + L.o_col) : nullptr);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+        h->err = std::string("mlm_import_blocks: ") + hipGetErrorString(e);
+        return MLM_ERR_HIP;
+    }
+    const int rc = read_global(h);
+    if (rc) return rc;
+    if (h->h_g->err) {
+        h->err = "block pool or block hash table full (raise mlm_limits.max_blocks)";
+        clear_device_error(h);
+        return MLM_ERR_CAPACITY;
+    }
+    return MLM_OK;
+}
+} // namespace
+
 int mlm_import_blocks(mlm_handle *h, int n, const int32_t *keys, const float *log_odds, const uint8_t *occ, const uint8_t *infl,
                       const uint8_t *collapsed) {
     if (!h || n < 0 || (n > 0 && !keys)) return MLM_ERR_INVALID;
@@ -2029,39 +2066,24 @@ int mlm_import_blocks(mlm_handle *h, int n, const int32_t *keys, const float *lo
     rc = ensure_free_blocks_idle(h, (size_t)n);
     if (rc) return rc;
     const size_t C = (size_t)h->P.cells, N = (size_t)n;
-    // one staging buffer: keys | slots | log_odds | occ | infl | collapsed (sources may be host or device memory)
-    const size_t o_keys = 0, o_slots = o_keys + N * 12, o_lo = (o_slots + N * 4 + 15) & ~(size_t)15, o_occ = o_lo + N * C * 4,
-                 o_infl = o_occ + N * C, o_col = o_infl + N * C, total = o_col + N;
+    // (sources may be host or device memory)
+    const ImportStage L = import_stage(N, C);
     char *d = nullptr;
-    HIPCHK(h, hipMalloc((void **)&d, total));
-    hipError_t e = hipMemcpyAsync(d + o_keys, keys, N * 12, hipMemcpyDefault, h->stream);
-    if (e == hipSuccess && log_odds) e = hipMemcpyAsync(d + o_lo, log_odds, N * C * 4, hipMemcpyDefault, h->stream);
-    if (e == hipSuccess && occ) e = hipMemcpyAsync(d + o_occ, occ, N * C, hipMemcpyDefault, h->stream);
-    if (e == hipSuccess && infl) e = hipMemcpyAsync(d + o_infl, infl, N * C, hipMemcpyDefault, h->stream);
-    if (e == hipSuccess && collapsed) e = hipMemcpyAsync(d + o_col, collapsed, N, hipMemcpyDefault, h->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_import_slots, dim3(grid_for(N)), dim3(MLM_BLOCK), 0, h->stream, h->P, (const int32_t *)(d + o_keys), n,
-                           (int *)(d + o_slots));
-        hipLaunchKernelGGL(k_import_cells, dim3(std::min<unsigned int>(4096u, grid_for(N * C))), dim3(MLM_BLOCK), 0, h->stream, h->P,
-                           (const int *)(d + o_slots), n, log_odds ? (const float *)(d + o_lo) : nullptr,
-                           occ ? (const uint8_t *)(d + o_occ) : nullptr, infl ? (const uint8_t *)(d + o_infl) : nullptr,
-                           collapsed ? (const uint8_t *)(d + o_col) : nullptr);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    hipFree(d);
+    HIPCHK(h, hipMalloc((void **)&d, L.total));
+    hipError_t e = hipMemcpyAsync(d + L.o_keys, keys, N * 12, hipMemcpyDefault, h->stream);
+    if (e == hipSuccess && log_odds) e = hipMemcpyAsync(d + L.o_lo, log_odds, N * C * 4, hipMemcpyDefault, h->stream);
+    if (e == hipSuccess && occ) e = hipMemcpyAsync(d + L.o_occ, occ, N * C, hipMemcpyDefault, h->stream);
+    if (e == hipSuccess && infl) e = hipMemcpyAsync(d + L.o_infl, infl, N * C, hipMemcpyDefault, h->stream);
+    if (e == hipSuccess && collapsed) e = hipMemcpyAsync(d + L.o_col, collapsed, N, hipMemcpyDefault, h->stream);
     if (e != hipSuccess) {
+        (void)hipStreamSynchronize(h->stream);
+        hipFree(d);
         h->err = std::string("mlm_import_blocks: ") + hipGetErrorString(e);
         return MLM_ERR_HIP;
     }
-    rc = read_global(h);
-    if (rc) return rc;
-    if (h->h_g->err) {
-        h->err = "block pool or block hash table full (raise mlm_limits.max_blocks)";
-        clear_device_error(h);
-        return MLM_ERR_CAPACITY;
-    }
-    return MLM_OK;
+    rc = import_staged(h, d, L, n, log_odds != nullptr, occ != nullptr, infl != nullptr, collapsed != nullptr);
+    hipFree(d);
+    return rc;
 }
 
 namespace {
@@ -2251,6 +2273,8 @@ int mlm_crop_blocks(mlm_handle *h, const int32_t key_lo[3], const int32_t key_di
     if (rc) return rc;
     return crop_run(h, B, flags, cap, keys, log_odds, occ, infl, collapsed, summary);
 }
+
+#include "mlm_warp_host.h"
 
 int mlm_merge_pack(mlm_handle *h, const int32_t *keys_dev, int n, float *log_odds_dev, uint8_t *seen_dev) {
     if (!h || n < 0 || (n > 0 && (!keys_dev || !log_odds_dev || !seen_dev))) return MLM_ERR_INVALID;

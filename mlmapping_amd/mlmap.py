@@ -44,6 +44,8 @@ MLM_OCT_INFL, MLM_OCT_OCC_ONLY, MLM_OCT_ROW = 1, 2, 40
 MLM_OCT_NONE, MLM_OCT_FREE, MLM_OCT_OCC, MLM_OCT_INNER = 0, 1, 2, 3
 # mlm_crop_blocks flags (OUTSIDE / INSIDE: which side of the key box is dropped), int64 in summary
 MLM_CROP_OUTSIDE, MLM_CROP_INSIDE, MLM_CROP_DRY, MLM_CROP_SHRINK, MLM_CROP_ROW = 0, 1, 2, 4, 8
+# mlm_warp_blocks flags, int64 in summary
+MLM_WARP_SEEN, MLM_WARP_REPLACE, MLM_WARP_DRY, MLM_WARP_ROW = 1, 2, 4, 8
 # mlm_query_rays flags: what stops a ray (their union; 0: nothing, a pure count)
 MLM_RAY_OCC, MLM_RAY_INFL, MLM_RAY_UNKNOWN = 1, 2, 4
 # mlm_query_views: int64 per row of the table
@@ -60,7 +62,7 @@ ABI_SYMBOLS = [
     "mlm_integrate_depth_u16", "mlm_integrate_depth_u16_dev", "mlm_integrate_depth_batch_dev",
     "mlm_integrate_depth_batch", "mlm_integrate_callback",
     "mlm_integrate_points", "mlm_query_occupancy", "mlm_query_occupancy_inflate", "mlm_query_inflate_occupancy",
-    "mlm_query_odds", "mlm_query_odd_grad", "mlm_query_odds_at", "mlm_export_frontier_points", "mlm_import_blocks", "mlm_crop_blocks",
+    "mlm_query_odds", "mlm_query_odd_grad", "mlm_query_odds_at", "mlm_export_frontier_points", "mlm_import_blocks", "mlm_crop_blocks", "mlm_warp_blocks",
     "mlm_merge_pack", "mlm_merge_finish",
     "mlm_set_free_in_bound", "mlm_inflate_map", "mlm_block_count",
     "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_grid2d", "mlm_export_reach", "mlm_export_route", "mlm_export_clusters", "mlm_export_mesh", "mlm_export_octree", "mlm_query_rays", "mlm_render_depth", "mlm_query_views", "mlm_query_boxes", "mlm_query_nearest", "mlm_query_sweeps", "mlm_query_paths", "mlm_score_poses", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
@@ -151,6 +153,7 @@ def load_library(path: Optional[str] = None):
     L.mlm_export_frontier_points.argtypes = [vp, i32, vp, vp]
     L.mlm_import_blocks.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     L.mlm_crop_blocks.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.mlm_warp_blocks.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.mlm_merge_pack.argtypes = [vp, vp, i32, vp, vp]
     L.mlm_merge_finish.argtypes = [vp, vp, vp, ctypes.c_size_t, vp]
     L.mlm_set_free_in_bound.argtypes = [vp, vp, vp]
@@ -488,6 +491,47 @@ class MLMap:
             self._merge_base = None  # (as import_blocks: the baseline of periodic merges no longer describes this map)
         self._chk(self._L.mlm_crop_blocks(self._h, _p(lo_a), _p(dims_a), flags, cap, *ptr, _p(summary)), "mlm_crop_blocks")
         return res
+
+    def warp_blocks(self, T_sd, key_lo=None, key_dims=None, seen: bool = False, dry: bool = False, replace: bool = False,
+                    out=None) -> Dict[str, np.ndarray]:
+        """The map resampled under the rigid transform T_sd (12 float64: R row major, then o; it maps a point of the new frame to the
+        map's frame), nearest voxel, exact (mlm_warp_blocks): the blocks of the new frame's lattice that hold a live voxel, inside the
+        box key_lo <= key < key_lo + key_dims of block keys if one is given, in ascending key order.  out=None: nothing is written;
+        out=True: host arrays sized by a dry call, returned as "keys", "log_odds", "occ", "infl" (what import_blocks takes);
+        out={"cap": blocks, "keys": ptr, "log_odds": ptr, ...}: device memory (ints, any of them may be missing).  seen=True: only
+        voxels the map has observed or inflated are live.  dry=True only counts.  replace=True: afterwards this handle holds the warped
+        map (not in frontier mode).  Always returns "summary": int64 [source blocks, candidates examined, emitted, written, live voxels,
+        live with occ 'o', with occ 'f', with infl 'o']."""
+        T = np.ascontiguousarray(_f64(T_sd).reshape(12))
+        if (key_lo is None) != (key_dims is None):
+            raise MlmError("warp_blocks: key_lo and key_dims go together")
+        lo_a = None if key_lo is None else np.ascontiguousarray(key_lo, dtype=np.int32).reshape(3)
+        dims_a = None if key_dims is None else np.ascontiguousarray(key_dims, dtype=np.int32).reshape(3)
+        box = (None, None) if lo_a is None else (_p(lo_a), _p(dims_a))
+        flags = (MLM_WARP_SEEN if seen else 0) | (MLM_WARP_DRY if dry else 0) | (MLM_WARP_REPLACE if replace else 0)
+        summary = np.zeros(MLM_WARP_ROW, dtype=np.int64)
+        names = ("keys", "log_odds", "occ", "infl")
+        res, cap, ptr = {"summary": summary}, 0, [None] * 4
+        if out is True and not dry:
+            self._chk(self._L.mlm_warp_blocks(self._h, _p(T), *box, (flags | MLM_WARP_DRY) & ~MLM_WARP_REPLACE, 0, None, None, None, None, _p(summary)),
+                      "mlm_warp_blocks")
+            cap, C = int(summary[2]), self.cells
+            res.update(keys=np.empty((cap, 3), dtype=np.int32), log_odds=np.empty((cap, C), dtype=np.float32),
+                       occ=np.empty((cap, C), dtype=np.uint8), infl=np.empty((cap, C), dtype=np.uint8))
+            ptr = [_p(res[k]) for k in names]
+        elif out is not None and out is not True:
+            cap = int(out["cap"])
+            ptr = [None if out.get(k) is None else ctypes.c_void_p(int(out[k])) for k in names]
+        if replace and not dry:
+            self._merge_base = None  # (as import_blocks: the baseline of periodic merges no longer describes this map)
+        self._chk(self._L.mlm_warp_blocks(self._h, _p(T), *box, flags, cap, *ptr, _p(summary)), "mlm_warp_blocks")
+        return res
+
+    def reanchor(self, T_ds) -> Dict[str, np.ndarray]:
+        """Apply a frame correction to the map in place: T_ds (12 float64: R row major, then t) maps a point of the map's current frame
+        to the corrected one, as a caller thinks of a correction (new-from-old).  It is inverted here (invert_T) and handed to
+        warp_blocks(replace=True), whose "summary" is returned."""
+        return self.warp_blocks(invert_T(T_ds), replace=True)
 
     def retain_around(self, t_w, radius_m: float, shrink: bool = False, out=None) -> Dict[str, np.ndarray]:
         """Keep a rolling window: drop every block farther than radius_m from t_w on some axis — the kept key box is
@@ -1403,6 +1447,13 @@ def compose_T_ws(q_wb, t_wb, T_bs) -> np.ndarray:
     out[:, :9] = (R @ B[:3, :3]).reshape(-1, 9)
     out[:, 9:] = t + R @ B[:3, 3]
     return out
+
+
+def invert_T(T) -> np.ndarray:
+    """The inverse of a rigid transform T (12 float64: R row major, then o) in the same layout: R^T, then -R^T o, in float64."""
+    T = _f64(T).reshape(12)
+    Rt = T[:9].reshape(3, 3).T
+    return np.ascontiguousarray(np.concatenate([Rt.reshape(9), -(Rt @ T[9:])]))
 
 
 def best_score_row(table) -> int:
