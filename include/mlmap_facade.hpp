@@ -320,6 +320,15 @@ class mlmap {
         check(mlm_warp_blocks(h_, T_sd, key_lo, key_dims, flags, cap, keys, log_odds, occ, infl, summary), "mlm_warp_blocks");
     }
 
+    // a block dump fused into the live map in place, or — MLM_FUSE_DRY — only compared with it (mlm_fuse_blocks; keys [n][3], log_odds /
+    // occ / infl [n][cells] as mlm_export_blocks, cropBlocks and warpBlocks write them, host or device memory, infl may be NULL; mode
+    // MLM_FUSE_ADD / MAX / TAKE / FILL; per_row [n][MLM_FUSE_COLS] host or device memory or NULL; summary host memory: [2] created
+    // blocks, [7] conflicting voxels)
+    void fuseBlocks(int n, const int32_t *keys, const float *log_odds, const uint8_t *occ, const uint8_t *infl = nullptr, int mode = MLM_FUSE_ADD,
+                    int flags = 0, int32_t *per_row = nullptr, int64_t summary[MLM_FUSE_ROW] = nullptr) {
+        check(mlm_fuse_blocks(h_, n, keys, log_odds, occ, infl, mode, flags, per_row, summary), "mlm_fuse_blocks");
+    }
+
     // segment casts through the voxel map (mlm_query_rays; flags MLM_RAY_*; n x 3 end points; inputs and outputs host or device
     // memory, NULL output = skipped)
     void castRays(const double *p0, const double *p1, int n, int flags, int8_t *status, int32_t *voxel3 = nullptr, double *t = nullptr,

@@ -943,6 +943,48 @@ int mlm_warp_blocks(mlm_handle *h, const double T_sd[12], const int32_t key_lo[3
                     int flags, int cap, int32_t *keys, float *log_odds, uint8_t *occ, uint8_t *infl,
                     int64_t summary[MLM_WARP_ROW]);
 
+/* Fuse a block dump into the live map, in place on the device — or, with MLM_FUSE_DRY, only compare the two (no reference counterpart:
+ * the reference has one map).  What pages a region back in without destroying what was integrated there since (mlm_import_blocks
+ * overwrites whole blocks), loads another handle's or another robot's map after mlm_warp_blocks has put it on this lattice, and answers
+ * "where do these two maps disagree".  keys [n*3], log_odds / occ / infl [n*cells] as mlm_export_blocks, mlm_crop_blocks and
+ * mlm_warp_blocks write them; each pointer on its own may be host or device memory (host memory is staged); infl, per_row and summary
+ * may be NULL; summary is host memory, per_row host or device memory.  Rows are full blocks: there is no collapsed input (a dump of a
+ * frontier-mode handle is made with mlm_warp_blocks, which expands released blocks).
+ *   The rule per voxel (mlmapping_amd/csrc/mlm_fuse.h), IEEE single, nothing fused.  The map holds (La, occ_a, infl_a) — 0.0f / 'u' / 'u'
+ * where it has no block —, the dump (Lb, occ_b, infl_b); clamp(x) = !(x >= log_odds_min) ? log_odds_min : (x > log_odds_max ?
+ * log_odds_max : x), so a NaN becomes log_odds_min; Lb' = clamp(Lb).  The voxel CONTRIBUTES iff occ_b is 'f' or 'o'; seen_a = occ_a != 'u'.
+ * A contributing voxel is WRITTEN always in MLM_FUSE_ADD, MAX and TAKE, in MLM_FUSE_FILL iff !seen_a, with
+ *     ADD: L = La + Lb'      MAX: L = seen_a ? (La > Lb' ? La : Lb') : Lb'      TAKE, FILL: L = Lb'
+ * log_odds = clamp(L) and occ = clamp(L) > occupied_sh ? 'o' : 'f' — mlm_merge_finish's rule, not the integrate path's hysteresis.  A
+ * voxel that is not written keeps its log-odds and its class bit for bit.  With infl given and infl_b == 'o', infl_a becomes 'o', in
+ * every mode and whether or not the voxel contributes; otherwise infl_a is unchanged.
+ *   Blocks.  Row r TOUCHES iff it has a contributing voxel, or infl is given and it has a voxel with infl_b == 'o'.  A touching row
+ * whose block is absent creates it; the created blocks take the slots n_blocks_before + rank, rank = the number of created rows with a
+ * smaller row index (a prefix sum, not a race for a counter), so mlm_export_blocks' raw order afterwards is one answer, as it is after
+ * mlm_crop_blocks.  An absent row that touches nothing creates nothing; a present row that touches nothing changes nothing.
+ *   summary — all counts, one value whatever the schedule: [0] rows, [1] rows whose block the map held, [2] rows created, [3] rows that
+ * touch nothing, [4] contributing voxels, of those [5] with !seen_a, [6] both seen and occ_a == occ_b, [7] both seen and occ_a != occ_b
+ * (the conflicts; [4] == [5] + [6] + [7]), [8] voxels whose class is 'o' afterwards and was not before, [9] voxels whose class was 'o'
+ * and is 'f' afterwards, [10] voxels whose infl turned 'o', [11] voxels whose log-odds bits changed.
+ *   per_row [n][MLM_FUSE_COLS]: [0] contributing voxels of the row, [1] its conflicts, [2] its share of [8] + [9], [3] 0 block present,
+ * 1 created, 2 absent and left absent.
+ *   MLM_FUSE_DRY fills summary and per_row as the call without it would ([2] and per_row[3] == 1: would be created) and touches
+ * nothing: no block is created, no pool grows, the host mirror stays valid — the map diff.
+ *   Frontier mode: without MLM_FUSE_DRY the call is refused (MLM_ERR_INVALID), for mlm_warp_blocks' MLM_WARP_REPLACE's reason; with it a
+ * released block answers from element 0 with infl 'u', as mlm_merge_pack and the queries read it.
+ *   Like mlm_import_blocks the call waits for everything submitted first.  MLM_ERR_INVALID (with a text in mlm_last_error): n < 0;
+ * keys, log_odds or occ NULL with n > 0; a mode outside 0..3; an unknown flag bit; a key outside the 21-bit key range [-2^20, 2^20);
+ * two rows with the same key.  n == 0: MLM_OK, a zero summary.  MLM_ERR_CAPACITY: the pool cannot take the created blocks (knob
+ * "pool_grow" = 0, or no device memory), or no memory for the staging.  Every check, every count and every allocation — pool growth,
+ * staging, the handle's scratch (counted in device_bytes) — come before the first write into pool or hash table: a failing call leaves
+ * the map byte for byte as it was. */
+enum { MLM_FUSE_ADD = 0, MLM_FUSE_MAX = 1, MLM_FUSE_TAKE = 2, MLM_FUSE_FILL = 3 };  /* mode */
+enum { MLM_FUSE_DRY = 1 };                                                          /* flags */
+#define MLM_FUSE_ROW 12   /* int64 in summary */
+#define MLM_FUSE_COLS 4   /* int32 per row of per_row */
+int mlm_fuse_blocks(mlm_handle *h, int n, const int32_t *keys, const float *log_odds, const uint8_t *occ,
+                    const uint8_t *infl, int mode, int flags, int32_t *per_row, int64_t summary[MLM_FUSE_ROW]);
+
 /* The two device-side steps of the optional global-map merge across GPUs (mlmapping_amd/merge.py; no reference
  * counterpart: SURVEY.md §8e).  All pointers are device memory; both calls return when the buffers are written.
  * pack:   row b of log_odds_dev / seen_dev [n*cells] = this map's cells of block keys_dev[3b..3b+2] (0 / 0 where the

@@ -208,6 +208,10 @@ struct mlm_handle : MlmHandlePlan { // (MlmHandlePlan, mlm_plan.h: the members m
     // candidates: their keys (twice, for the sort), the sort's values and scratch, four counters each, the emitted list
     void *d_warp_set = nullptr, *d_warp = nullptr;
     size_t warp_set_bytes = 0, warp_bytes = 0;
+    // mlm_fuse_blocks: per row its slot, flags and created slot, the packed keys (twice, for the sort) with the sort's values and
+    // scratch, chunk counts, control words, the twelve sums and their partial rows: some 40 bytes per row and 96 KB
+    void *d_fuse = nullptr;
+    size_t fuse_bytes = 0;
     // the batched queries' staging: the host inputs / outputs of one chunk
     void *d_ray_stage = nullptr;
     size_t ray_stage_bytes = 0;

@@ -46,6 +46,9 @@ MLM_OCT_NONE, MLM_OCT_FREE, MLM_OCT_OCC, MLM_OCT_INNER = 0, 1, 2, 3
 MLM_CROP_OUTSIDE, MLM_CROP_INSIDE, MLM_CROP_DRY, MLM_CROP_SHRINK, MLM_CROP_ROW = 0, 1, 2, 4, 8
 # mlm_warp_blocks flags, int64 in summary
 MLM_WARP_SEEN, MLM_WARP_REPLACE, MLM_WARP_DRY, MLM_WARP_ROW = 1, 2, 4, 8
+# mlm_fuse_blocks modes and flag, int64 in summary, int32 per row of per_row
+MLM_FUSE_ADD, MLM_FUSE_MAX, MLM_FUSE_TAKE, MLM_FUSE_FILL, MLM_FUSE_DRY, MLM_FUSE_ROW, MLM_FUSE_COLS = 0, 1, 2, 3, 1, 12, 4
+FUSE_MODES = {"add": MLM_FUSE_ADD, "max": MLM_FUSE_MAX, "take": MLM_FUSE_TAKE, "fill": MLM_FUSE_FILL}
 # mlm_query_rays flags: what stops a ray (their union; 0: nothing, a pure count)
 MLM_RAY_OCC, MLM_RAY_INFL, MLM_RAY_UNKNOWN = 1, 2, 4
 # mlm_query_views: int64 per row of the table
@@ -62,7 +65,7 @@ ABI_SYMBOLS = [
     "mlm_integrate_depth_u16", "mlm_integrate_depth_u16_dev", "mlm_integrate_depth_batch_dev",
     "mlm_integrate_depth_batch", "mlm_integrate_callback",
     "mlm_integrate_points", "mlm_query_occupancy", "mlm_query_occupancy_inflate", "mlm_query_inflate_occupancy",
-    "mlm_query_odds", "mlm_query_odd_grad", "mlm_query_odds_at", "mlm_export_frontier_points", "mlm_import_blocks", "mlm_crop_blocks", "mlm_warp_blocks",
+    "mlm_query_odds", "mlm_query_odd_grad", "mlm_query_odds_at", "mlm_export_frontier_points", "mlm_import_blocks", "mlm_crop_blocks", "mlm_warp_blocks", "mlm_fuse_blocks",
     "mlm_merge_pack", "mlm_merge_finish",
     "mlm_set_free_in_bound", "mlm_inflate_map", "mlm_block_count",
     "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_grid2d", "mlm_export_reach", "mlm_export_route", "mlm_export_clusters", "mlm_export_mesh", "mlm_export_octree", "mlm_query_rays", "mlm_render_depth", "mlm_query_views", "mlm_query_boxes", "mlm_query_nearest", "mlm_query_sweeps", "mlm_query_paths", "mlm_score_poses", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
@@ -154,6 +157,7 @@ def load_library(path: Optional[str] = None):
     L.mlm_import_blocks.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     L.mlm_crop_blocks.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
     L.mlm_warp_blocks.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
+    L.mlm_fuse_blocks.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, vp, vp]
     L.mlm_merge_pack.argtypes = [vp, vp, i32, vp, vp]
     L.mlm_merge_finish.argtypes = [vp, vp, vp, ctypes.c_size_t, vp]
     L.mlm_set_free_in_bound.argtypes = [vp, vp, vp]
@@ -234,6 +238,7 @@ class MLMap:
                  record_awareness: bool = False, max_batch: int = 0):
         self.cfg = cfg
         self.cells = cfg.cells_per_block
+        self.device = device
         self._L = load_library()
         self._c = to_c(cfg)
         self._lim = Limits(max_blocks, max_points, max_batch, int(record_awareness))
@@ -526,6 +531,56 @@ class MLMap:
             self._merge_base = None  # (as import_blocks: the baseline of periodic merges no longer describes this map)
         self._chk(self._L.mlm_warp_blocks(self._h, _p(T), *box, flags, cap, *ptr, _p(summary)), "mlm_warp_blocks")
         return res
+
+    def fuse_blocks(self, keys, log_odds, occ, infl=None, mode="add", dry: bool = False, per_row: bool = False) -> Dict[str, np.ndarray]:
+        """Fuse a block dump (layout of export_blocks / crop_blocks / warp_blocks; host numpy arrays or device pointers (ints), keys
+        then as (device pointer, n), as import_blocks takes them) into the map in place (mlm_fuse_blocks).  mode "add": log-odds added
+        and clamped, class from occupied_sh (merge.py's rule); "max": the larger log-odds; "take": the dump's; "fill": the dump's where
+        the map has seen nothing.  Only voxels the dump has seen (occ 'f' / 'o') count; infl 'o' is or-ed in; blocks are created as
+        needed.  dry=True changes nothing and only counts: the map diff.  Returns "summary": int64 [rows, present, created, touching
+        nothing, contributing voxels, new to the map, agreeing, conflicting, turned occupied, occupied turned free, infl turned on,
+        log-odds changed] and "per_row": int32 [n, 4] (contributing, conflicts, class changes, 0 present / 1 created / 2 left absent)
+        or None."""
+        def ptr(a, dt):
+            if a is None:
+                return None, None
+            if isinstance(a, int):
+                return ctypes.c_void_p(a), None
+            arr = np.ascontiguousarray(a, dtype=dt)
+            return _p(arr), arr
+        if isinstance(keys, tuple):  # (device pointer, n)
+            kp, n, keep = ctypes.c_void_p(keys[0]), int(keys[1]), None
+        else:
+            keep = np.ascontiguousarray(keys, dtype=np.int32).reshape(-1, 3)
+            kp, n = _p(keep), keep.shape[0]
+        if mode not in FUSE_MODES:
+            raise MlmError(f"fuse_blocks: mode must be one of {sorted(FUSE_MODES)}")
+        holds = [ptr(log_odds, np.float32), ptr(occ, np.uint8), ptr(infl, np.uint8)]
+        summary = np.zeros(MLM_FUSE_ROW, dtype=np.int64)
+        rows = np.zeros((n, MLM_FUSE_COLS), dtype=np.int32) if per_row else None
+        if not dry:
+            self._merge_base = None  # (as import_blocks: the baseline of periodic merges no longer describes this map)
+        self._chk(self._L.mlm_fuse_blocks(self._h, n, kp, holds[0][0], holds[1][0], holds[2][0], FUSE_MODES[mode], MLM_FUSE_DRY if dry else 0,
+                                          None if rows is None else _p(rows), _p(summary)), "mlm_fuse_blocks")
+        return {"summary": summary, "per_row": rows}
+
+    def fuse_from(self, other: "MLMap", T_sd=None, mode="add", dry: bool = False) -> Dict[str, np.ndarray]:
+        """Fuse another handle's map into this one without the dump leaving the device: other.warp_blocks(T_sd, seen=True) into torch
+        tensors on this handle's device, sized by a dry call, then fuse_blocks on their pointers.  T_sd (12 float64: R row major, then
+        o; None: the identity) maps a point of THIS map's frame to other's, warp_blocks' convention.  Returns fuse_blocks' dict."""
+        import torch
+
+        T = np.array([1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0], dtype=np.float64) if T_sd is None else np.ascontiguousarray(_f64(T_sd).reshape(12))
+        E, C = int(other.warp_blocks(T, seen=True, dry=True)["summary"][2]), self.cells
+        if other.cells != C:
+            raise MlmError("fuse_from: the two maps differ in subbox_n")
+        dev = torch.device("cuda", self.device)
+        t = {"keys": torch.empty((max(E, 1), 3), dtype=torch.int32, device=dev), "log_odds": torch.empty((max(E, 1), C), dtype=torch.float32, device=dev),
+             "occ": torch.empty((max(E, 1), C), dtype=torch.uint8, device=dev), "infl": torch.empty((max(E, 1), C), dtype=torch.uint8, device=dev)}
+        torch.cuda.synchronize(dev)
+        if E:
+            other.warp_blocks(T, seen=True, out={"cap": E, **{k: v.data_ptr() for k, v in t.items()}})
+        return self.fuse_blocks((t["keys"].data_ptr(), E), t["log_odds"].data_ptr(), t["occ"].data_ptr(), t["infl"].data_ptr(), mode=mode, dry=dry)
 
     def reanchor(self, T_ds) -> Dict[str, np.ndarray]:
         """Apply a frame correction to the map in place: T_ds (12 float64: R row major, then t) maps a point of the map's current frame
