@@ -14,13 +14,6 @@ static_assert(MLM_FUSE_ADD == MLM_FUSE_M_ADD && MLM_FUSE_MAX == MLM_FUSE_M_MAX &
 
 constexpr unsigned int kFuseApplyGrid = 1024; // most workgroups of k_fuse_apply: a wave takes several rows, a workgroup writes one row of sums
 
-struct FuseTmp { // device memory of one call
-    void *p = nullptr;
-    ~FuseTmp() {
-        if (p) hipFree(p);
-    }
-};
-
 #define MLM_FUSE_LAUNCH(K, v, dry, grid, ...)                                                                            \
     do {                                                                                                                 \
         if ((v) == 4 && (dry)) hipLaunchKernelGGL((K<4, true>), dim3(grid), dim3(MLM_BLOCK), 0, h->stream, __VA_ARGS__); \
@@ -50,9 +43,9 @@ int fuse_run(mlm_handle *h, int n, const int32_t *keys, const float *log_odds, c
     const size_t o_flag = w4, o_new = 2 * w4, o_ka = 3 * w4, o_kb = o_ka + w8, o_va = o_kb + w8, o_vb = o_va + w4, o_ch = o_vb + w4,
                  o_ctrl = o_ch + mlm_align256((size_t)chunks * 4), o_part = o_ctrl + 256,
                  o_sort = o_part + mlm_align256((size_t)kFuseApplyGrid * MLM_FUSE_ROW * 8), total = o_sort + mlm_align256(sort_bytes);
-    if ((rc = readout_reserve(h, h->d_fuse, h->fuse_bytes, total, "mlm_fuse_blocks"))) return rc;
+    if ((rc = readout_reserve(h, h->d_fuse, total, "mlm_fuse_blocks"))) return rc;
     // a host per_row goes through the read-outs' staging
-    ReadoutChannels<1> ch(h->d_win_stage, h->win_stage_bytes, {{per_row, MLM_FUSE_COLS * sizeof(int32_t)}});
+    ReadoutChannels<1> ch(h->d_win_stage, {{per_row, MLM_FUSE_COLS * sizeof(int32_t)}});
     if ((rc = ch.reserve(h, "mlm_fuse_blocks", (size_t)N))) return rc;
     // host sources staged whole in one allocation; device sources are read in place
     const void *src[4] = {keys, log_odds, occ, infl};
@@ -64,7 +57,7 @@ int fuse_run(mlm_handle *h, int n, const int32_t *keys, const float *log_odds, c
         off[k] = stage_bytes;
         if (staged[k]) stage_bytes += mlm_align256(bytes[k]);
     }
-    FuseTmp stage;
+    DevTmp stage;
     if (stage_bytes && hipMalloc(&stage.p, stage_bytes) != hipSuccess) {
         (void)hipGetLastError();
         stage.p = nullptr;
@@ -82,7 +75,7 @@ int fuse_run(mlm_handle *h, int n, const int32_t *keys, const float *log_odds, c
             src[k] = (char *)stage.p + off[k];
         }
 
-    char *b = (char *)h->d_fuse;
+    char *b = (char *)h->d_fuse.p;
     MlmFuse F{};
     F.R = MlmFuseRule{h->P.lo_min, h->P.lo_max, h->P.lo_sh, mode, infl ? 1 : 0};
     F.n = N, F.nb = nb;
@@ -100,8 +93,7 @@ int fuse_run(mlm_handle *h, int n, const int32_t *keys, const float *log_odds, c
 
     HIPCHK(h, hipMemsetAsync(ctrl, 0, 256, h->stream));
     const unsigned int rows_grid = wave_grid(N, kCropGrid), scan_grid = std::min(chunks, kCropGrid);
-    if (V == 4) hipLaunchKernelGGL(k_fuse_probe<4>, dim3(rows_grid), dim3(MLM_BLOCK), 0, h->stream, h->P, F, keys_a, vals_a, ctrl);
-    else hipLaunchKernelGGL(k_fuse_probe<1>, dim3(rows_grid), dim3(MLM_BLOCK), 0, h->stream, h->P, F, keys_a, vals_a, ctrl);
+    launch(h, V == 4 ? k_fuse_probe<4> : k_fuse_probe<1>, rows_grid, 0, h->P, F, keys_a, vals_a, ctrl);
     HIPCHK(h, hipGetLastError());
     if (N > 1) {
         if (mlm_sort_pairs_u64_u32(b + o_sort, sort_bytes, keys_a, keys_b, vals_a, vals_b, N, h->stream) != 0) {
@@ -109,15 +101,14 @@ int fuse_run(mlm_handle *h, int n, const int32_t *keys, const float *log_odds, c
             h->err = "mlm_fuse_blocks: the sort of the packed keys failed";
             return MLM_ERR_HIP;
         }
-        hipLaunchKernelGGL(k_fuse_dups, dim3(std::min(grid_for(N), kCropGrid)), dim3(MLM_BLOCK), 0, h->stream, (const unsigned long long *)keys_b, N, ctrl);
+        launch(h, k_fuse_dups, lanes_grid(N, kCropGrid), 0, (const unsigned long long *)keys_b, N, ctrl);
     }
-    hipLaunchKernelGGL(k_fuse_count, dim3(scan_grid), dim3(MLM_BLOCK), 0, h->stream, F, chunks, chunk_cnt);
-    hipLaunchKernelGGL(k_crop_scan, dim3(1), dim3(MLM_BLOCK), 0, h->stream, chunk_cnt, chunks, ctrl);
-    hipLaunchKernelGGL(k_fuse_rank, dim3(scan_grid), dim3(MLM_BLOCK), 0, h->stream, F, chunks, (const unsigned int *)chunk_cnt);
+    launch(h, k_fuse_count, scan_grid, 0, F, chunks, chunk_cnt);
+    launch(h, k_crop_scan, 1u, 0, chunk_cnt, chunks, ctrl);
+    launch(h, k_fuse_rank, scan_grid, 0, F, chunks, (const unsigned int *)chunk_cnt);
     HIPCHK(h, hipGetLastError());
-    unsigned int c[MLM_FUSE_CTRL_WORDS] = {};
-    HIPCHK(h, hipMemcpyAsync(c, ctrl, sizeof(c), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const unsigned int *c;
+    if ((rc = read_back(h, (const unsigned int *)ctrl, MLM_FUSE_CTRL_WORDS, c))) return rc;
     if (c[1] || c[2]) {
         h->err = std::string("mlm_fuse_blocks: ") + mlm_fuse_check_text(c[1] ? 5 : 6);
         report();
@@ -143,7 +134,7 @@ int fuse_run(mlm_handle *h, int n, const int32_t *keys, const float *log_odds, c
         }
         // From here on the map changes.
         mirror_mark_all(h);
-        hipLaunchKernelGGL(k_fuse_create, dim3(std::min(grid_for(N), kCropGrid)), dim3(MLM_BLOCK), 0, h->stream, h->P, F, created);
+        launch(h, k_fuse_create, lanes_grid(N, kCropGrid), 0, h->P, F, created);
         HIPCHK(h, hipGetLastError());
         h->h_g->n_blocks = nb + created; // (k_fuse_create sets the device's)
         for (int k = 0; k < MLM_SETS; ++k) h->h_gb[k]->n_blocks = nb + created;
@@ -152,13 +143,10 @@ int fuse_run(mlm_handle *h, int n, const int32_t *keys, const float *log_odds, c
     }
     const unsigned int apply_grid = wave_grid(N, kFuseApplyGrid);
     MLM_FUSE_LAUNCH(k_fuse_apply, V, dry, apply_grid, h->P, F);
-    hipLaunchKernelGGL(k_fuse_sums, dim3(1), dim3(MLM_BLOCK), 0, h->stream, (const unsigned long long *)F.part, apply_grid, sums);
+    launch(h, k_fuse_sums, 1u, 0, (const unsigned long long *)F.part, apply_grid, sums);
     HIPCHK(h, hipGetLastError());
-    unsigned long long back[MLM_FUSE_ROW] = {};
-    HIPCHK(h, hipMemcpyAsync(back, sums, sizeof(back), hipMemcpyDeviceToHost, h->stream));
     if ((rc = ch.copy_out(h, 0, 1, 0, (size_t)N))) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (int k = 0; k < MLM_FUSE_ROW; ++k) sum[k] = (int64_t)back[k];
+    if ((rc = read_back(h, sums, MLM_FUSE_ROW, sum))) return rc;
     sum[0] = N, sum[2] = created;
     if (!dry) {
         h->stats.n_blocks = nb + created;

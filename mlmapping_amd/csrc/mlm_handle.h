@@ -160,6 +160,11 @@ constexpr long long kScoreGridTarget = 1024;
 // dependent trips to memory every kernel starts with (parameters, counts, its list); a dense frame's thousands of cells keep
 // k_chain_lanes' cell-per-lane replay (measured: 128 -> 201 us for a dense VGA frame with the chains in k_rank)
 constexpr unsigned int kFusedChainStrips = 16;
+// a device buffer a read-out keeps between calls, with its size (readout_reserve, mlm_readout.h)
+struct KeptBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+};
 static inline double mlm_now_us() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 struct mlm_handle : MlmHandlePlan { // (MlmHandlePlan, mlm_plan.h: the members mlm_create's plan decides)
     using SlotCaps = MlmSlotCaps;
@@ -175,55 +180,44 @@ struct mlm_handle : MlmHandlePlan { // (MlmHandlePlan, mlm_plan.h: the members m
     double *d_qpos = nullptr; // query positions
     void *d_qout = nullptr;
     size_t q_cap = 0;
-    // The read-outs' kept buffers (enlarged by need, never shrunk; mlm_readout.h).  Host arrays are staged by one rule, ReadoutChannels:
-    // the exports (window .. clusters, and a host exclude / mark of mlm_query_views) in d_win_stage, the batched queries (rays, render,
-    // boxes, nearest, sweeps, paths, score, and the rays of views) in d_ray_stage.  The comments below name what else each read-out keeps.
+    // The read-outs' kept buffers (KeptBuf: a device pointer with its size; enlarged by need through readout_reserve, never shrunk;
+    // mlm_readout.h).  Host arrays are staged by one rule, ReadoutChannels: the exports (window .. clusters, and a host exclude / mark
+    // of mlm_query_views) in d_win_stage, the batched queries (rays, render, boxes, nearest, sweeps, paths, score, and the rays of
+    // views) in d_ray_stage.  The comments below name what else each read-out keeps.
     // mlm_export_window: odds of the haloed tile (gradients)
-    void *d_win_scratch = nullptr, *d_win_stage = nullptr;
-    size_t win_scratch_bytes = 0, win_stage_bytes = 0;
+    KeptBuf d_win_scratch, d_win_stage;
     // mlm_export_esdf: obstacle mask and the two fields of the grown tile
-    void *d_esdf_scratch = nullptr;
-    size_t esdf_scratch_bytes = 0;
+    KeptBuf d_esdf_scratch;
     // mlm_export_reach: field, mask, dirty arrays, control block and seeds of the whole box (mlm_reach_plan; the ESDF passes of
-    // clearance > 0 use d_esdf_scratch); pinned copy of the control block
-    void *d_reach = nullptr;
-    size_t reach_bytes = 0;
-    unsigned int *h_reach_ctrl = nullptr;
+    // clearance > 0 use d_esdf_scratch)
+    KeptBuf d_reach;
+    // The pinned control block (MlmCtrlBlock, mlm_host.h; allocated on first use by ctrl_block): every small read of counters or
+    // control words that a call waits for goes through it (read_back), and mlm_export_route stages its penalty table there
+    MlmCtrlBlock *h_ctrl = nullptr;
     // mlm_export_clusters: field, size / number words, mask, grown occ classes, chunk counts, staged rows and counters of the whole
-    // box (mlm_cluster_plan; the counters' pinned copy is h_reach_ctrl)
-    void *d_cluster = nullptr;
-    size_t cluster_bytes = 0;
+    // box (mlm_cluster_plan)
+    KeptBuf d_cluster;
     // mlm_export_mesh: states of the grown box, face masks, vertex bits and word bases, chunk bases and counters of the whole box
-    // (mlm_mesh_plan; the counters' pinned copy is h_reach_ctrl)
-    void *d_mesh = nullptr;
-    size_t mesh_bytes = 0;
-    // mlm_export_octree: label, counts and numbers of every cell from the bricks up to the root, and the counters (mlm_oct_plan; the
-    // counters' pinned copy is h_reach_ctrl)
-    void *d_oct = nullptr;
-    size_t oct_bytes = 0;
+    // (mlm_mesh_plan)
+    KeptBuf d_mesh;
+    // mlm_export_octree: label, counts and numbers of every cell from the bricks up to the root, and the counters (mlm_oct_plan)
+    KeptBuf d_oct;
     // mlm_crop_blocks: chunk counts, control words and the list of the slots, dropped ones first (mlm_kernels_crop.h): 4 bytes per block
-    void *d_crop = nullptr;
-    size_t crop_bytes = 0;
+    KeptBuf d_crop;
     // mlm_warp_blocks: the candidate set with its chunk counts and control words, 8 bytes per entry; and what is sized by the
     // candidates: their keys (twice, for the sort), the sort's values and scratch, four counters each, the emitted list
-    void *d_warp_set = nullptr, *d_warp = nullptr;
-    size_t warp_set_bytes = 0, warp_bytes = 0;
+    KeptBuf d_warp_set, d_warp;
     // mlm_fuse_blocks: per row its slot, flags and created slot, the packed keys (twice, for the sort) with the sort's values and
     // scratch, chunk counts, control words, the twelve sums and their partial rows: some 40 bytes per row and 96 KB
-    void *d_fuse = nullptr;
-    size_t fuse_bytes = 0;
+    KeptBuf d_fuse;
     // the batched queries' staging: the host inputs / outputs of one chunk
-    void *d_ray_stage = nullptr;
-    size_t ray_stage_bytes = 0;
+    KeptBuf d_ray_stage;
     // mlm_query_views: per-view boxes, job lists, staged rows and the global path's bitsets of one chunk of views
-    void *d_views = nullptr;
-    size_t views_bytes = 0;
+    KeptBuf d_views;
     // mlm_query_paths: the traced paths of one chunk of goals (three int32 arrays of max_moves + 1 entries per goal)
-    void *d_path = nullptr;
-    size_t path_bytes = 0;
+    KeptBuf d_path;
     // mlm_score_poses: the device copy of a distance field handed over in host memory (4 bytes per voxel)
-    void *d_score_field = nullptr;
-    size_t score_field_bytes = 0;
+    KeptBuf d_score_field;
     // sort buffers (rehash frames only)
     unsigned long long *sk_in = nullptr, *sk_out = nullptr;
     uint32_t *sv_in = nullptr, *sv_out = nullptr;
@@ -366,6 +360,20 @@ template <class T> int dev_alloc(mlm_handle *h, T **p, size_t n) {
     return MLM_OK;
 }
 inline unsigned int grid_for(size_t n) { return (unsigned int)((n + MLM_BLOCK - 1) / MLM_BLOCK); }
+// workgroups of a grid-stride kernel: a lane per item (lanes_grid), or a workgroup per brick, tile or chunk (bricks_grid); `cap` at most
+inline unsigned int lanes_grid(size_t n, unsigned int cap) { return std::min(grid_for(n), cap); }
+inline unsigned int bricks_grid(long long nb, unsigned int cap) { return (unsigned int)std::min<long long>(nb, cap); }
+// a kernel of MLM_BLOCK threads on the handle's main stream
+template <class K, class... A> inline void launch(mlm_handle *h, K kernel, unsigned int grid, size_t lds, const A &...args) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(MLM_BLOCK), lds, h->stream, args...);
+}
+// device memory of one call
+struct DevTmp {
+    void *p = nullptr;
+    ~DevTmp() {
+        if (p) hipFree(p);
+    }
+};
 // blocks of k_bin_points for one frame (tile geometry: mlm_tile_item)
 inline unsigned int bin_grid(const MlmDev &P, const MlmFrame &F, int mode) {
     const int tile_h = (int)(P.bin_block / 256) * 8;

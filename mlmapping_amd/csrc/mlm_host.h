@@ -273,6 +273,28 @@ inline size_t mlm_stage_layout(int n, const bool *present, const bool *staged, c
     return total;
 }
 
+// The tiles of T[0] x T[1] x T[2] voxels that cut a box of D[0] x D[1] x D[2], z outermost and x innermost, the last tile per axis cut
+// to the box: fn(org, td, out_base) with the tile's origin and extent in the box and the index of its first voxel in the box's
+// [z][y][x] order.  Stops at, and returns, fn's first non-zero answer.  A plane is a box with D[2] = T[2] = 1.
+template <class F> inline int mlm_for_tiles(const long long D[3], const long long T[3], F fn) {
+    for (long long z0 = 0; z0 < D[2]; z0 += T[2])
+        for (long long y0 = 0; y0 < D[1]; y0 += T[1])
+            for (long long x0 = 0; x0 < D[0]; x0 += T[0]) {
+                const long long org[3] = {x0, y0, z0};
+                int td[3];
+                for (int a = 0; a < 3; ++a) td[a] = (int)std::min(T[a], D[a] - org[a]);
+                if (const int rc = fn(org, td, (z0 * D[1] + y0) * D[0] + x0)) return rc;
+            }
+    return 0;
+}
+
+// Rows per round when n rows (n >= 1) leave through a staging buffer: as many as `cap_bytes` hold at `per_row` staged bytes each,
+// one at least — or the test knob's count (knob_rows > 0) — and never more than n.  per_row == 0: nothing is staged, one round.
+inline size_t mlm_stage_rows(size_t n, size_t per_row, size_t cap_bytes, long long knob_rows = 0) {
+    if (!per_row) return n;
+    return std::min<size_t>(n, knob_rows > 0 ? (size_t)knob_rows : std::max<size_t>(1, cap_bytes / per_row));
+}
+
 // Tiles of mlm_export_grid2d (mlm_kernels_grid.h) for a plane of D[0] x D[1] cells, truncation C (cells), distances asked for or
 // not: mlm_esdf_plan's rule in two dimensions.  A tile is whole rows of the plane, else a piece of one row, so that its outputs
 // are one contiguous range of the plane's [D1][D0] layout.  The grown tile (the tile plus H = C - 1 cells per side with distances,
@@ -371,6 +393,21 @@ inline MlmReachPlan mlm_reach_plan(const long long D[3], long long tile_packed, 
 // box and seeds.
 constexpr long long kRouteTileDefault = kReachTileDefault, kRouteGroupDefault = kReachGroupDefault;
 constexpr long long kRoutePenOffset = 1280, kRoutePenWords = 64; // (within kReachCtrlBytes, behind kReachGroupMax words and the counters)
+// The control block of mlm_export_reach / mlm_export_route in device memory, and the handle's pinned block that stands for it on the
+// host: the device's "marked" words of a group (pinned: the 32- or 64-bit words the host read back last, whichever call they belong
+// to), the device's counters (not used in the pinned block) and route's penalty table (pinned: staged there on its way up).
+struct MlmCtrlBlock {
+    union {
+        uint32_t w32[kReachGroupMax];
+        unsigned long long w64[kReachGroupMax / 2];
+    } words;
+    unsigned long long cnt[(kRoutePenOffset - kReachGroupMax * 4) / 8];
+    uint32_t pen[kRoutePenWords];
+    unsigned char rest[kReachCtrlBytes - kRoutePenOffset - kRoutePenWords * 4];
+};
+static_assert(offsetof(MlmCtrlBlock, words) == 0 && offsetof(MlmCtrlBlock, cnt) == kReachGroupMax * 4 && offsetof(MlmCtrlBlock, pen) == kRoutePenOffset &&
+                  sizeof(MlmCtrlBlock) == kReachCtrlBytes,
+              "the control block of mlm_reach_plan / mlm_route_plan");
 struct MlmRoutePlan {
     bool ok;
     long long T[3], n[3], tiles, voxels;

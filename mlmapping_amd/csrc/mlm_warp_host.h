@@ -12,13 +12,6 @@ static_assert(MLM_WARP_SEEN == MLM_WARP_F_SEEN && MLM_WARP_REPLACE == MLM_WARP_F
               "mlm_warp.h restates the flags of include/mlmap_hip.h");
 static_assert(MLM_WARP_ROW == 4 + MLM_WARP_SUMS, "summary: four block counts, then the sums of k_warp_sums");
 
-struct WarpTmp { // device memory of one call
-    void *p = nullptr;
-    ~WarpTmp() {
-        if (p) hipFree(p);
-    }
-};
-
 // everything of mlm_warp_blocks behind the argument check and the drain
 int warp_run(mlm_handle *h, const MlmWarpPlan &W, int flags, int cap, int32_t *keys, float *log_odds, uint8_t *occ, uint8_t *infl, int64_t *summary) {
     int64_t sum[MLM_WARP_ROW] = {};
@@ -49,23 +42,21 @@ int warp_run(mlm_handle *h, const MlmWarpPlan &W, int flags, int cap, int32_t *k
         }
         set_chunks = (unsigned int)((nt + MLM_CROP_SLOTS_PER_CHUNK - 1) / MLM_CROP_SLOTS_PER_CHUNK);
         const size_t o_cnt = (size_t)nt * 8, o_ctrl = o_cnt + mlm_align256((size_t)set_chunks * 4);
-        if ((rc = readout_reserve(h, h->d_warp_set, h->warp_set_bytes, o_ctrl + 256, "mlm_warp_blocks"))) {
+        if ((rc = readout_reserve(h, h->d_warp_set, o_ctrl + 256, "mlm_warp_blocks"))) {
             report();
             return rc;
         }
-        unsigned long long *set = (unsigned long long *)h->d_warp_set;
-        set_cnt = (unsigned int *)((char *)h->d_warp_set + o_cnt);
-        unsigned int *set_ctrl = (unsigned int *)((char *)h->d_warp_set + o_ctrl);
+        unsigned long long *set = (unsigned long long *)h->d_warp_set.p;
+        set_cnt = (unsigned int *)((char *)h->d_warp_set.p + o_cnt);
+        unsigned int *set_ctrl = (unsigned int *)((char *)h->d_warp_set.p + o_ctrl);
         HIPCHK(h, hipMemsetAsync(set, 0xFF, (size_t)nt * 8, h->stream));
         HIPCHK(h, hipMemsetAsync(set_ctrl, 0, MLM_WARP_CTRL_WORDS * 4, h->stream));
-        hipLaunchKernelGGL(k_warp_candidates, dim3(std::min(grid_for(nb), kCropGrid)), dim3(MLM_BLOCK), 0, h->stream, h->P, W, nb, set, (uint32_t)(nt - 1), set_ctrl);
-        const unsigned int set_grid = std::min(set_chunks, kCropGrid);
-        hipLaunchKernelGGL(k_warp_set_count, dim3(set_grid), dim3(MLM_BLOCK), 0, h->stream, (const unsigned long long *)set, (unsigned int)nt, set_chunks, set_cnt);
-        hipLaunchKernelGGL(k_crop_scan, dim3(1), dim3(MLM_BLOCK), 0, h->stream, set_cnt, set_chunks, set_ctrl);
+        launch(h, k_warp_candidates, lanes_grid(nb, kCropGrid), 0, h->P, W, nb, set, (uint32_t)(nt - 1), set_ctrl);
+        launch(h, k_warp_set_count, std::min(set_chunks, kCropGrid), 0, (const unsigned long long *)set, (unsigned int)nt, set_chunks, set_cnt);
+        launch(h, k_crop_scan, 1u, 0, set_cnt, set_chunks, set_ctrl);
         HIPCHK(h, hipGetLastError());
-        unsigned int c[MLM_WARP_CTRL_WORDS] = {};
-        HIPCHK(h, hipMemcpyAsync(c, set_ctrl, sizeof(c), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
+        const unsigned int *c;
+        if ((rc = read_back(h, (const unsigned int *)set_ctrl, MLM_WARP_CTRL_WORDS, c))) return rc;
         NC = c[0];
         if (c[1] || NC > most) {
             h->err = "mlm_warp_blocks: the candidate set is inconsistent";
@@ -81,17 +72,17 @@ int warp_run(mlm_handle *h, const MlmWarpPlan &W, int flags, int cap, int32_t *k
         const size_t o_kb = mlm_align256((size_t)NC * 8), o_va = 2 * o_kb, o_vb = o_va + mlm_align256((size_t)NC * 4), o_cnt = o_vb + mlm_align256((size_t)NC * 4),
                      o_el = o_cnt + mlm_align256((size_t)NC * 16), o_ch = o_el + mlm_align256((size_t)NC * 4), o_ctrl = o_ch + mlm_align256((size_t)chunks * 4),
                      o_sort = o_ctrl + 256, total = o_sort + mlm_align256(sort_bytes);
-        if ((rc = readout_reserve(h, h->d_warp, h->warp_bytes, total, "mlm_warp_blocks"))) {
+        if ((rc = readout_reserve(h, h->d_warp, total, "mlm_warp_blocks"))) {
             report();
             return rc;
         }
-        char *b = (char *)h->d_warp;
+        char *b = (char *)h->d_warp.p;
         unsigned long long *keys_a = (unsigned long long *)b, *keys_b = (unsigned long long *)(b + o_kb);
         uint32_t *vals_a = (uint32_t *)(b + o_va), *vals_b = (uint32_t *)(b + o_vb), *cnt = (uint32_t *)(b + o_cnt);
         unsigned int *elist = (unsigned int *)(b + o_el), *chunk_cnt = (unsigned int *)(b + o_ch), *ctrl = (unsigned int *)(b + o_ctrl);
         unsigned long long *sums = (unsigned long long *)(b + o_ctrl + 64);
-        hipLaunchKernelGGL(k_warp_set_list, dim3(std::min(set_chunks, kCropGrid)), dim3(MLM_BLOCK), 0, h->stream, (const unsigned long long *)h->d_warp_set,
-                           (unsigned int)nt, set_chunks, (const unsigned int *)set_cnt, keys_a, vals_a, NC);
+        launch(h, k_warp_set_list, std::min(set_chunks, kCropGrid), 0, (const unsigned long long *)h->d_warp_set.p, (unsigned int)nt, set_chunks,
+               (const unsigned int *)set_cnt, keys_a, vals_a, NC);
         HIPCHK(h, hipGetLastError());
         if (mlm_sort_pairs_u64_u32(b + o_sort, sort_bytes, keys_a, keys_b, vals_a, vals_b, NC, h->stream) != 0) {
             h->err = "mlm_warp_blocks: the sort of the candidate keys failed";
@@ -99,16 +90,15 @@ int warp_run(mlm_handle *h, const MlmWarpPlan &W, int flags, int cap, int32_t *k
         }
         Q.cand = keys_b, Q.nc = NC, Q.cnt = cnt, Q.elist = elist;
         HIPCHK(h, hipMemsetAsync(ctrl, 0, 256, h->stream));
-        hipLaunchKernelGGL(k_warp_count, dim3(wave_grid(NC, kCropGrid)), dim3(MLM_BLOCK), 0, h->stream, h->P, Q);
-        hipLaunchKernelGGL(k_warp_sums, dim3(std::min(grid_for(NC) / 8 + 1, 64u)), dim3(MLM_BLOCK), 0, h->stream, (const uint32_t *)cnt, NC, sums);
+        launch(h, k_warp_count, wave_grid(NC, kCropGrid), 0, h->P, Q);
+        launch(h, k_warp_sums, std::min(grid_for(NC) / 8 + 1, 64u), 0, (const uint32_t *)cnt, NC, sums);
         const unsigned int grid = std::min(chunks, kCropGrid);
-        hipLaunchKernelGGL(k_warp_emit_count, dim3(grid), dim3(MLM_BLOCK), 0, h->stream, (const uint32_t *)cnt, NC, chunks, chunk_cnt);
-        hipLaunchKernelGGL(k_crop_scan, dim3(1), dim3(MLM_BLOCK), 0, h->stream, chunk_cnt, chunks, ctrl);
-        hipLaunchKernelGGL(k_warp_emit_list, dim3(grid), dim3(MLM_BLOCK), 0, h->stream, (const uint32_t *)cnt, NC, chunks, (const unsigned int *)chunk_cnt, elist);
+        launch(h, k_warp_emit_count, grid, 0, (const uint32_t *)cnt, NC, chunks, chunk_cnt);
+        launch(h, k_crop_scan, 1u, 0, chunk_cnt, chunks, ctrl);
+        launch(h, k_warp_emit_list, grid, 0, (const uint32_t *)cnt, NC, chunks, (const unsigned int *)chunk_cnt, elist);
         HIPCHK(h, hipGetLastError());
-        unsigned long long back[12] = {};
-        HIPCHK(h, hipMemcpyAsync(back, ctrl, sizeof(back), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
+        const unsigned long long *back; // the control words, then (from byte 64 on) the sums
+        if ((rc = read_back(h, (const unsigned long long *)ctrl, 12, back))) return rc;
         E = (unsigned int)(back[0] & 0xFFFFFFFFull);
         for (int k = 0; k < MLM_WARP_SUMS; ++k) sum[4 + k] = (int64_t)back[8 + k];
         if (E > NC) {
@@ -128,20 +118,13 @@ int warp_run(mlm_handle *h, const MlmWarpPlan &W, int flags, int cap, int32_t *k
     }
     // every allocation before the first write: the staging of host outputs, and for a replacing call the import's staging and a pool
     // that holds the E blocks
-    ReadoutChannels<4> ch(h->d_win_stage, h->win_stage_bytes, {{keys, 3 * sizeof(int32_t)}, {log_odds, C * sizeof(float)}, {occ, C}, {infl, C}});
-    size_t rows = E;
-    if (any_out && E) {
-        size_t per_row = 0;
-        for (int k = 0; k < 4; ++k) per_row += ch.staged[k] ? ch.elem[k] : 0;
-        if (ch.any_staged) rows = std::min<size_t>(E, std::max<size_t>(1, kCropStageBytes / per_row));
-        long long kv;
-        if (ch.any_staged && knob("crop_stage_rows", kv)) rows = std::min<size_t>(E, (size_t)kv); // (test knob: rounds of a few rows)
-        if ((rc = ch.reserve(h, "mlm_warp_blocks", rows))) {
-            report();
-            return rc;
-        }
+    ReadoutChannels<4> ch(h->d_win_stage, {{keys, 3 * sizeof(int32_t)}, {log_odds, C * sizeof(float)}, {occ, C}, {infl, C}});
+    const size_t rows = any_out && E ? page_rows(ch, E) : E;
+    if (any_out && E && (rc = ch.reserve(h, "mlm_warp_blocks", rows))) {
+        report();
+        return rc;
     }
-    WarpTmp stage;
+    DevTmp stage;
     const ImportStage L = import_stage(E, C);
     if (replace) {
         if (E && hipMalloc(&stage.p, L.total) != hipSuccess) {
@@ -163,23 +146,18 @@ int warp_run(mlm_handle *h, const MlmWarpPlan &W, int flags, int cap, int32_t *k
         }
     }
     if (any_out && E) {
-        for (size_t r0 = 0; r0 < E; r0 += rows) {
-            const size_t r1 = std::min<size_t>(E, r0 + rows);
-            hipLaunchKernelGGL(k_warp_write, dim3(wave_grid(r1 - r0, kCropGrid)), dim3(MLM_BLOCK), 0, h->stream, h->P, Q, (unsigned int)r0, (unsigned int)r1,
-                               (int32_t *)ch.at(0, r0), (float *)ch.at(1, r0), (uint8_t *)ch.at(2, r0), (uint8_t *)ch.at(3, r0));
-            HIPCHK(h, hipGetLastError());
-            if (ch.any_staged) {
-                if ((rc = ch.copy_out(h, 0, 4, r0, r1 - r0))) return rc;
-                HIPCHK(h, hipStreamSynchronize(h->stream)); // (the staging is reused by the next round)
-            }
-        }
+        rc = page_rounds(h, ch, E, rows, [&](size_t r0, size_t r1) {
+            launch(h, k_warp_write, wave_grid(r1 - r0, kCropGrid), 0, h->P, Q, (unsigned int)r0, (unsigned int)r1, (int32_t *)ch.at(0, r0),
+                   (float *)ch.at(1, r0), (uint8_t *)ch.at(2, r0), (uint8_t *)ch.at(3, r0));
+        });
+        if (rc) return rc;
         sum[3] = E;
     }
     if (replace) {
         char *d = (char *)stage.p;
         if (E) {
-            hipLaunchKernelGGL(k_warp_write, dim3(wave_grid(E, kCropGrid)), dim3(MLM_BLOCK), 0, h->stream, h->P, Q, 0u, E, (int32_t *)(d + L.o_keys),
-                               (float *)(d + L.o_lo), (uint8_t *)(d + L.o_occ), (uint8_t *)(d + L.o_infl));
+            launch(h, k_warp_write, wave_grid(E, kCropGrid), 0, h->P, Q, 0u, E, (int32_t *)(d + L.o_keys), (float *)(d + L.o_lo), (uint8_t *)(d + L.o_occ),
+                   (uint8_t *)(d + L.o_infl));
             HIPCHK(h, hipGetLastError());
         }
         // drop every block (the mirror forgets what it knows there), then import the dump

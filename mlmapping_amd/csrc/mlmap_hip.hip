@@ -9,7 +9,8 @@
 // are included in this order: mlm_plan.h (host only: what mlm_create decides without the device) -> mlm_handle.h (the handle, knobs, launch helpers) -> mlm_stage_a.h (Stage A launches, exact
 // ordering, statistics) -> mlm_explore_host.h (frontier mode) -> mlm_submit.h (submission, drain / replay, single-frame graph)
 // -> mlm_resources.h (device memory: mlm_create's stages, pool growth, frame slots, queries' launcher) -> mlm_mirror.h (host mirror of the map for small
-// query batches) -> mlm_readout.h (what the read-outs share: box check, staging of host arrays, ESDF tiles, settle loop); this file
+// query batches) -> mlm_readout.h (what the read-outs share: box check, kept buffers, pinned control block, staging of host arrays
+// and the loops over it, ESDF tiles, settle loop); this file
 // holds the extern "C" entry points.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -208,7 +209,7 @@ int mlm_destroy(mlm_handle *h) {
 
     for (auto &g : h->graphs) hipGraphExecDestroy(g.exec);
     if (h->h_stage) hipHostFree(h->h_stage);
-    if (h->h_reach_ctrl) hipHostFree(h->h_reach_ctrl);
+    if (h->h_ctrl) hipHostFree(h->h_ctrl);
     if (h->upload_ev) hipEventDestroy(h->upload_ev);
     if (h->host_read_ev) hipEventDestroy(h->host_read_ev);
     if (h->inputs_ready) hipEventDestroy(h->inputs_ready);
@@ -598,8 +599,8 @@ int mlm_set_free_in_bound(mlm_handle *h, const double bmin[3], const double bmax
     HIPCHK(h, hipMemcpyAsync(d + ax[0].size(), ax[1].data(), ax[1].size() * 8, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(d + ax[0].size() + ax[1].size(), ax[2].data(), ax[2].size() * 8, hipMemcpyHostToDevice,
                              h->stream));
-    hipLaunchKernelGGL(k_set_free, dim3(grid_for(total)), dim3(MLM_BLOCK), 0, h->stream, h->P, d, (int)ax[0].size(),
-                       d + ax[0].size(), (int)ax[1].size(), d + ax[0].size() + ax[1].size(), (int)ax[2].size());
+    launch(h, k_set_free, grid_for(total), 0, h->P, d, (int)ax[0].size(), d + ax[0].size(), (int)ax[1].size(), d + ax[0].size() + ax[1].size(),
+           (int)ax[2].size());
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MLM_OK;
@@ -632,9 +633,8 @@ int mlm_inflate_map(mlm_handle *h, const double ct_pos[3]) {
             mirror_mark_all(h);
         }
     }
-    hipLaunchKernelGGL(k_inflate_reset, dim3(grid_for(total)), dim3(MLM_BLOCK), 0, h->stream, h->P, cgx, cgy, cgz, G);
-    hipLaunchKernelGGL(k_inflate_spread, dim3(grid_for(total)), dim3(MLM_BLOCK), 0, h->stream, h->P, cgx, cgy, cgz, G, R,
-                       0.1 /* flate_height, map_local.h:65 */);
+    launch(h, k_inflate_reset, grid_for(total), 0, h->P, cgx, cgy, cgz, G);
+    launch(h, k_inflate_spread, grid_for(total), 0, h->P, cgx, cgy, cgz, G, R, 0.1 /* flate_height, map_local.h:65 */);
     HIPCHK(h, hipGetLastError());
     rc = read_global(h);
     if (rc) return rc;
@@ -692,49 +692,42 @@ int mlm_export_window(mlm_handle *h, const int32_t lo[3], const int32_t dims[3],
     HIPCHK(h, hipSetDevice(h->device));
     if ((rc = drain(h))) return rc;
 
-    ReadoutChannels<4> ch(h->d_win_stage, h->win_stage_bytes, {{odds, sizeof(float)}, {occ, 1}, {infl, 1}, {grad3, 3 * sizeof(double)}});
+    ReadoutChannels<4> ch(h->d_win_stage, {{odds, sizeof(float)}, {occ, 1}, {infl, 1}, {grad3, 3 * sizeof(double)}});
     // tiles as mlm_export_esdf's (C - 1 = H, the halo of the gradients): the haloed tile's odds take at most kEsdfBoxVoxels floats
     // (128 MB), a tile staged for host destinations at most kEsdfStageVoxels voxels (<= 30 bytes each); H <= MLM_WIN_HALO: a tile fits
     const long long H = grad3 ? std::min(max_iter, MLM_WIN_HALO) : 0;
     const MlmEsdfPlan plan = mlm_esdf_plan(D, (int)H + 1, false, grad3 ? kEsdfBoxVoxels : 1ll << 62, ch.any_staged ? kEsdfStageVoxels : 1ll << 62);
     const long long *T = plan.T;
-    if (grad3 && (rc = readout_reserve(h, h->d_win_scratch, h->win_scratch_bytes, (size_t)plan.grown * sizeof(float), "mlm_export_window")))
-        return rc;
+    if (grad3 && (rc = readout_reserve(h, h->d_win_scratch, (size_t)plan.grown * sizeof(float), "mlm_export_window"))) return rc;
     if ((rc = ch.reserve(h, "mlm_export_window", (size_t)(T[0] * T[1] * T[2])))) return rc;
 
-    for (long long z0 = 0; z0 < D[2]; z0 += T[2])
-        for (long long y0 = 0; y0 < D[1]; y0 += T[1])
-            for (long long x0 = 0; x0 < D[0]; x0 += T[0]) {
-                MlmWin W{};
-                const long long org[3] = {x0, y0, z0};
-                for (int a = 0; a < 3; ++a) {
-                    W.wlo[a] = lo[a];
-                    W.wd[a] = dims[a];
-                    W.tlo[a] = lo[a] + org[a];
-                    W.td[a] = (int)std::min(T[a], D[a] - org[a]);
-                    W.hlo[a] = W.tlo[a] - H;
-                    W.hd[a] = W.td[a] + (int)(2 * H);
-                }
-                brick_cover(h, 3, W.hlo, W.hd, W.b0, W.nb);
-                // (every channel pointer is where the tile's first voxel goes: out_base is the tile's index in the window)
-                W.out_base = (z0 * D[1] + y0) * D[0] + x0;
-                W.odds = (float *)ch.at(0, (size_t)W.out_base);
-                W.occ = (int8_t *)ch.at(1, (size_t)W.out_base);
-                W.infl = (int8_t *)ch.at(2, (size_t)W.out_base);
-                W.grad = (double *)ch.at(3, (size_t)W.out_base);
-                W.scratch = grad3 ? (float *)h->d_win_scratch : nullptr;
-                W.halo = (int)H;
-                W.max_iter = max_iter;
-                const long long n_bricks = (long long)W.nb[0] * W.nb[1] * W.nb[2];
-                hipLaunchKernelGGL(k_window_fill, dim3((unsigned int)std::min<long long>(n_bricks, kWinFillGrid)), dim3(MLM_BLOCK), 0, h->stream,
-                                   h->P, W);
-                const long long nt = (long long)W.td[0] * W.td[1] * W.td[2];
-                if (grad3)
-                    hipLaunchKernelGGL(k_window_grad, dim3(std::min<unsigned int>(grid_for((size_t)nt), kWinGradGrid)), dim3(MLM_BLOCK), 0,
-                                       h->stream, h->P, W);
-                HIPCHK(h, hipGetLastError());
-                if ((rc = ch.copy_out(h, 0, 4, (size_t)W.out_base, (size_t)nt))) return rc;
-            }
+    rc = mlm_for_tiles(D, T, [&](const long long org[3], const int td[3], long long out_base) -> int {
+        MlmWin W{};
+        for (int a = 0; a < 3; ++a) {
+            W.wlo[a] = lo[a];
+            W.wd[a] = dims[a];
+            W.tlo[a] = lo[a] + org[a];
+            W.td[a] = td[a];
+            W.hlo[a] = W.tlo[a] - H;
+            W.hd[a] = W.td[a] + (int)(2 * H);
+        }
+        brick_cover(h, 3, W.hlo, W.hd, W.b0, W.nb);
+        // (every channel pointer is where the tile's first voxel goes: out_base is the tile's index in the window)
+        W.out_base = out_base;
+        W.odds = (float *)ch.at(0, (size_t)out_base);
+        W.occ = (int8_t *)ch.at(1, (size_t)out_base);
+        W.infl = (int8_t *)ch.at(2, (size_t)out_base);
+        W.grad = (double *)ch.at(3, (size_t)out_base);
+        W.scratch = grad3 ? (float *)h->d_win_scratch.p : nullptr;
+        W.halo = (int)H;
+        W.max_iter = max_iter;
+        launch(h, k_window_fill, bricks_grid((long long)W.nb[0] * W.nb[1] * W.nb[2], kWinFillGrid), 0, h->P, W);
+        const long long nt = (long long)td[0] * td[1] * td[2];
+        if (grad3) launch(h, k_window_grad, lanes_grid((size_t)nt, kWinGradGrid), 0, h->P, W);
+        HIPCHK(h, hipGetLastError());
+        return ch.copy_out(h, 0, 4, (size_t)out_base, (size_t)nt);
+    });
+    if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MLM_OK;
 }
@@ -753,7 +746,7 @@ int mlm_export_esdf(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], i
     HIPCHK(h, hipSetDevice(h->device));
     if ((rc = drain(h))) return rc;
 
-    ReadoutChannels<3> ch(h->d_win_stage, h->win_stage_bytes, {{sqdist, sizeof(int32_t)}, {dist, sizeof(float)}, {grad3, 3 * sizeof(float)}});
+    ReadoutChannels<3> ch(h->d_win_stage, {{sqdist, sizeof(int32_t)}, {dist, sizeof(float)}, {grad3, 3 * sizeof(float)}});
     const bool sgn = (flags & MLM_ESDF_SIGNED) != 0;
     const int C = max_dist, G = grad3 ? 1 : 0;
     long long box_cap = kEsdfBoxVoxels, kv;
@@ -765,44 +758,42 @@ int mlm_export_esdf(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], i
     }
     // scratch: the mask, then two fields of the grown tile (the x pass and the z pass write the first, the y pass the second)
     const size_t fe = sgn ? 4 : 2, mask_bytes = mlm_align256((size_t)plan.grown), field_bytes = mlm_align256((size_t)plan.grown * fe);
-    if ((rc = readout_reserve(h, h->d_esdf_scratch, h->esdf_scratch_bytes, mask_bytes + 2 * field_bytes, "mlm_export_esdf"))) return rc;
+    if ((rc = readout_reserve(h, h->d_esdf_scratch, mask_bytes + 2 * field_bytes, "mlm_export_esdf"))) return rc;
     if ((rc = ch.reserve(h, "mlm_export_esdf", (size_t)(plan.T[0] * plan.T[1] * plan.T[2])))) return rc;
-    uint8_t *mask = (uint8_t *)h->d_esdf_scratch;
-    void *fa = (char *)h->d_esdf_scratch + mask_bytes, *fb = (char *)h->d_esdf_scratch + mask_bytes + field_bytes;
+    uint8_t *mask = (uint8_t *)h->d_esdf_scratch.p;
+    void *fa = mask + mask_bytes, *fb = mask + mask_bytes + field_bytes;
 
     const long long H = plan.H;
-    for (long long z0 = 0; z0 < D[2]; z0 += plan.T[2])
-        for (long long y0 = 0; y0 < D[1]; y0 += plan.T[1])
-            for (long long x0 = 0; x0 < D[0]; x0 += plan.T[0]) {
-                MlmEsdf E{};
-                MlmEsdfOut Q{};
-                const long long org[3] = {x0, y0, z0};
-                for (int a = 0; a < 3; ++a) {
-                    Q.t0[a] = org[a];
-                    Q.td[a] = (int)std::min(plan.T[a], D[a] - org[a]);
-                    Q.fd[a] = Q.td[a] + 2 * G;
-                    E.glo[a] = lo[a] + org[a] - H;
-                    E.gd[a] = Q.td[a] + (int)(2 * H);
-                }
-                brick_cover(h, 3, E.glo, E.gd, E.b0, E.nb);
-                E.flags = flags & 7;
-                E.mask = mask;
-                Q.wd0 = D[0];
-                Q.wd1 = D[1];
-                Q.G = G;
-                Q.out_base = (z0 * D[1] + y0) * D[0] + x0;
-                Q.d = (float)h->cfg.subbox_d_xyz;
-                Q.inv = (float)(0.5 / h->cfg.subbox_d_xyz);
-                Q.sqdist = (int32_t *)ch.at(0, (size_t)Q.out_base);
-                Q.dist = (float *)ch.at(1, (size_t)Q.out_base);
-                Q.grad = (float *)ch.at(2, (size_t)Q.out_base);
-                if (sgn)
-                    esdf_tile<true>(h, E, C, mask, fa, fb, Q);
-                else
-                    esdf_tile<false>(h, E, C, mask, fa, fb, Q);
-                HIPCHK(h, hipGetLastError());
-                if ((rc = ch.copy_out(h, 0, 3, (size_t)Q.out_base, (size_t)Q.td[0] * Q.td[1] * Q.td[2]))) return rc;
-            }
+    rc = mlm_for_tiles(D, plan.T, [&](const long long org[3], const int td[3], long long out_base) -> int {
+        MlmEsdf E{};
+        MlmEsdfOut Q{};
+        for (int a = 0; a < 3; ++a) {
+            Q.t0[a] = org[a];
+            Q.td[a] = td[a];
+            Q.fd[a] = Q.td[a] + 2 * G;
+            E.glo[a] = lo[a] + org[a] - H;
+            E.gd[a] = Q.td[a] + (int)(2 * H);
+        }
+        brick_cover(h, 3, E.glo, E.gd, E.b0, E.nb);
+        E.flags = flags & 7;
+        E.mask = mask;
+        Q.wd0 = D[0];
+        Q.wd1 = D[1];
+        Q.G = G;
+        Q.out_base = out_base;
+        Q.d = (float)h->cfg.subbox_d_xyz;
+        Q.inv = (float)(0.5 / h->cfg.subbox_d_xyz);
+        Q.sqdist = (int32_t *)ch.at(0, (size_t)out_base);
+        Q.dist = (float *)ch.at(1, (size_t)out_base);
+        Q.grad = (float *)ch.at(2, (size_t)out_base);
+        if (sgn)
+            esdf_tile<true>(h, E, C, mask, fa, fb, Q);
+        else
+            esdf_tile<false>(h, E, C, mask, fa, fb, Q);
+        HIPCHK(h, hipGetLastError());
+        return ch.copy_out(h, 0, 3, (size_t)out_base, (size_t)td[0] * td[1] * td[2]);
+    });
+    if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MLM_OK;
 }
@@ -827,8 +818,7 @@ int mlm_export_grid2d(mlm_handle *h, const int32_t lo[3], const int32_t dims[3],
     HIPCHK(h, hipSetDevice(h->device));
     if ((rc = drain(h))) return rc;
 
-    ReadoutChannels<4> ch(h->d_win_stage, h->win_stage_bytes,
-                          {{grid, 1}, {cols, MLM_GRID_COL * sizeof(int32_t)}, {sqdist, sizeof(int32_t)}, {dist, sizeof(float)}});
+    ReadoutChannels<4> ch(h->d_win_stage, {{grid, 1}, {cols, MLM_GRID_COL * sizeof(int32_t)}, {sqdist, sizeof(int32_t)}, {dist, sizeof(float)}});
     const int C = want_dist ? max_dist : 1;
     long long out_cap = ch.any_staged ? kGridStageCells : (1ll << 62), kv;
     if (knob("grid_tile", kv)) out_cap = std::min(out_cap, kv);
@@ -840,70 +830,62 @@ int mlm_export_grid2d(mlm_handle *h, const int32_t lo[3], const int32_t dims[3],
     // scratch: the summary counters, then (with distances) the mask and two u16 fields of the grown tile
     const size_t ctrl_bytes = 256, mask_bytes = want_dist ? mlm_align256((size_t)plan.grown) : 0,
                  field_bytes = want_dist ? mlm_align256((size_t)plan.grown * 2) : 0;
-    if ((rc = readout_reserve(h, h->d_esdf_scratch, h->esdf_scratch_bytes, ctrl_bytes + mask_bytes + 2 * field_bytes, "mlm_export_grid2d"))) return rc;
+    if ((rc = readout_reserve(h, h->d_esdf_scratch, ctrl_bytes + mask_bytes + 2 * field_bytes, "mlm_export_grid2d"))) return rc;
     if ((rc = ch.reserve(h, "mlm_export_grid2d", (size_t)(plan.T[0] * plan.T[1])))) return rc;
-    if (summary && !h->h_reach_ctrl) HIPCHK(h, hipHostMalloc((void **)&h->h_reach_ctrl, (size_t)kReachCtrlBytes, hipHostMallocDefault));
-    unsigned long long *sums = summary ? (unsigned long long *)h->d_esdf_scratch : nullptr;
-    uint8_t *mask = want_dist ? (uint8_t *)h->d_esdf_scratch + ctrl_bytes : nullptr;
-    uint16_t *fa = (uint16_t *)((char *)h->d_esdf_scratch + ctrl_bytes + mask_bytes), *fb = (uint16_t *)((char *)fa + field_bytes);
+    if (summary && (rc = ctrl_block(h))) return rc;
+    char *base = (char *)h->d_esdf_scratch.p;
+    unsigned long long *sums = summary ? (unsigned long long *)base : nullptr;
+    uint8_t *mask = want_dist ? (uint8_t *)base + ctrl_bytes : nullptr;
+    uint16_t *fa = (uint16_t *)(base + ctrl_bytes + mask_bytes), *fb = (uint16_t *)((char *)fa + field_bytes);
     if (sums) HIPCHK(h, hipMemsetAsync(sums, 0, 6 * sizeof(unsigned long long), h->stream));
 
     const int n = h->P.n;
     const long long H = plan.H;
     // a workgroup has one lane per column of a brick stack: whole waves, as many as a full brick's n^2 columns need
     const unsigned int block = (unsigned int)std::min<long long>(MLM_BLOCK, (((long long)n * n + 63) / 64) * 64);
-    for (long long y0 = 0; y0 < D[1]; y0 += plan.T[1])
-        for (long long x0 = 0; x0 < D[0]; x0 += plan.T[0]) {
-            MlmGrid G{};
-            const long long org[2] = {x0, y0};
-            for (int a = 0; a < 2; ++a) {
-                G.tlo[a] = lo[a] + org[a];
-                G.td[a] = (int)std::min(plan.T[a], D[a] - org[a]);
-                G.glo[a] = G.tlo[a] - H;
-                G.gd[a] = G.td[a] + (int)(2 * H);
-            }
-            brick_cover(h, 2, G.glo, G.gd, G.b0, G.nb);
-            G.zlo = lo[2];
-            G.zhi = lo[2] + dims[2];
-            mlm_brick_cover(n, G.zlo, dims[2], G.b0[2], G.nb[2]);
-            G.flags = flags;
-            G.min_free = min_free;
-            G.z_ref = z_ref;
-            const long long out_base = y0 * D[0] + x0; // (every channel pointer is where the tile's first cell goes)
-            G.grid = (int8_t *)ch.at(0, (size_t)out_base);
-            G.cols = (int32_t *)ch.at(1, (size_t)out_base);
-            G.mask = mask;
-            G.sums = sums;
-            const long long stacks = (long long)G.nb[0] * G.nb[1];
-            const dim3 cgrid((unsigned int)std::min<long long>(stacks, kGridColGrid));
-            if (cols)
-                hipLaunchKernelGGL(k_grid_columns<true>, cgrid, dim3(block), 0, h->stream, h->P, G);
-            else
-                hipLaunchKernelGGL(k_grid_columns<false>, cgrid, dim3(block), 0, h->stream, h->P, G);
-            const long long nt = (long long)G.td[0] * G.td[1];
-            if (want_dist) {
-                // x: mask [gd1][gd0] -> fa [gd1][td0];  y: fa -> fb [td1][td0]
-                const long long rows = G.gd[1], xtasks = rows * ((G.td[0] + 63) / 64);
-                hipLaunchKernelGGL(k_esdf_x<false>, dim3((unsigned int)std::min<long long>((xtasks + 3) / 4, kEsdfPassGrid)), dim3(MLM_BLOCK), 0,
-                                   h->stream, (const uint8_t *)mask, (void *)fa, rows, G.gd[0], G.td[0], C);
-                const int lc = (G.td[1] + MLM_ESDF_LINE_TL - 1) / MLM_ESDF_LINE_TL, TL = (G.td[1] + lc - 1) / lc;
-                const long long ltiles = (long long)lc * ((G.td[0] + 63) / 64);
-                hipLaunchKernelGGL(k_esdf_line<uint16_t>, dim3((unsigned int)std::min<long long>(ltiles, kEsdfPassGrid)), dim3(MLM_BLOCK),
-                                   (size_t)(TL + 2 * C - 2) * 64 * sizeof(uint16_t), h->stream, (const uint16_t *)fa, fb, (long long)G.td[0], G.td[1],
-                                   1, C, TL);
-                hipLaunchKernelGGL(k_grid_dist_out, dim3(std::min<unsigned int>(grid_for((size_t)nt), kEsdfPassGrid)), dim3(MLM_BLOCK), 0, h->stream,
-                                   (const uint16_t *)fb, nt, (float)h->cfg.subbox_d_xyz, (int32_t *)ch.at(2, (size_t)out_base),
-                                   (float *)ch.at(3, (size_t)out_base));
-            }
-            HIPCHK(h, hipGetLastError());
-            if ((rc = ch.copy_out(h, 0, 4, (size_t)out_base, (size_t)nt))) return rc;
+    const long long plane[3] = {D[0], D[1], 1}, ptile[3] = {plan.T[0], plan.T[1], 1}; // (the tiles cut the plane; a tile is the whole slab in z)
+    rc = mlm_for_tiles(plane, ptile, [&](const long long org[3], const int td[3], long long out_base) -> int {
+        MlmGrid G{};
+        for (int a = 0; a < 2; ++a) {
+            G.tlo[a] = lo[a] + org[a];
+            G.td[a] = td[a];
+            G.glo[a] = G.tlo[a] - H;
+            G.gd[a] = G.td[a] + (int)(2 * H);
         }
-    unsigned long long *h_cnt = (unsigned long long *)h->h_reach_ctrl;
-    if (summary) HIPCHK(h, hipMemcpyAsync(h_cnt, sums, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (summary)
-        for (int i = 0; i < 6; ++i) summary[i] = (int64_t)h_cnt[i];
-    return MLM_OK;
+        brick_cover(h, 2, G.glo, G.gd, G.b0, G.nb);
+        G.zlo = lo[2];
+        G.zhi = lo[2] + dims[2];
+        mlm_brick_cover(n, G.zlo, dims[2], G.b0[2], G.nb[2]);
+        G.flags = flags;
+        G.min_free = min_free;
+        G.z_ref = z_ref;
+        G.grid = (int8_t *)ch.at(0, (size_t)out_base); // (every channel pointer is where the tile's first cell goes)
+        G.cols = (int32_t *)ch.at(1, (size_t)out_base);
+        G.mask = mask;
+        G.sums = sums;
+        const dim3 cgrid(bricks_grid((long long)G.nb[0] * G.nb[1], kGridColGrid));
+        if (cols)
+            hipLaunchKernelGGL(k_grid_columns<true>, cgrid, dim3(block), 0, h->stream, h->P, G);
+        else
+            hipLaunchKernelGGL(k_grid_columns<false>, cgrid, dim3(block), 0, h->stream, h->P, G);
+        const long long nt = (long long)G.td[0] * G.td[1];
+        if (want_dist) {
+            // x: mask [gd1][gd0] -> fa [gd1][td0];  y: fa -> fb [td1][td0]
+            const long long rows = G.gd[1], xtasks = rows * ((G.td[0] + 63) / 64);
+            launch(h, k_esdf_x<false>, bricks_grid((xtasks + 3) / 4, kEsdfPassGrid), 0, (const uint8_t *)mask, (void *)fa, rows, G.gd[0], G.td[0], C);
+            const int lc = (G.td[1] + MLM_ESDF_LINE_TL - 1) / MLM_ESDF_LINE_TL, TL = (G.td[1] + lc - 1) / lc;
+            const long long ltiles = (long long)lc * ((G.td[0] + 63) / 64);
+            hipLaunchKernelGGL(k_esdf_line<uint16_t>, dim3((unsigned int)std::min<long long>(ltiles, kEsdfPassGrid)), dim3(MLM_BLOCK),
+                               (size_t)(TL + 2 * C - 2) * 64 * sizeof(uint16_t), h->stream, (const uint16_t *)fa, fb, (long long)G.td[0], G.td[1],
+                               1, C, TL);
+            launch(h, k_grid_dist_out, lanes_grid((size_t)nt, kEsdfPassGrid), 0, (const uint16_t *)fb, nt, (float)h->cfg.subbox_d_xyz,
+                   (int32_t *)ch.at(2, (size_t)out_base), (float *)ch.at(3, (size_t)out_base));
+        }
+        HIPCHK(h, hipGetLastError());
+        return ch.copy_out(h, 0, 4, (size_t)out_base, (size_t)nt);
+    });
+    if (rc) return rc;
+    return read_back(h, sums, summary ? 6 : 0, summary);
 }
 
 int mlm_export_reach(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], const int32_t *seeds3, int n_seeds, int flags, int clearance,
@@ -930,15 +912,15 @@ int mlm_export_reach(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], 
         return MLM_ERR_INVALID;
     }
     // outputs: written in place, or staged in ranges of the box
-    ReadoutChannels<2> ch(h->d_win_stage, h->win_stage_bytes, {{steps, sizeof(int32_t)}, {parent, 1}});
+    ReadoutChannels<2> ch(h->d_win_stage, {{steps, sizeof(int32_t)}, {parent, 1}});
     const long long chunk = ch.any_staged ? std::min(nvox, kEsdfStageVoxels) : nvox;
-    if ((rc = readout_reserve(h, h->d_reach, h->reach_bytes, (size_t)plan.scratch_bytes, "mlm_export_reach"))) return rc;
+    if ((rc = readout_reserve(h, h->d_reach, (size_t)plan.scratch_bytes, "mlm_export_reach"))) return rc;
     if ((rc = ch.reserve(h, "mlm_export_reach", (size_t)chunk))) return rc;
-    if (!h->h_reach_ctrl) HIPCHK(h, hipHostMalloc((void **)&h->h_reach_ctrl, (size_t)kReachCtrlBytes, hipHostMallocDefault));
-    char *base = (char *)h->d_reach;
+    if ((rc = ctrl_block(h))) return rc;
+    char *base = (char *)h->d_reach.p;
     uint8_t *mask = (uint8_t *)(base + plan.off_mask), *dirty[2] = {(uint8_t *)(base + plan.off_dirty), (uint8_t *)(base + plan.off_dirty + plan.dirty_bytes)};
     unsigned int *marked = (unsigned int *)(base + plan.off_ctrl);
-    unsigned long long *cnt = (unsigned long long *)(base + plan.off_ctrl + kReachGroupMax * 4);
+    unsigned long long *cnt = (unsigned long long *)(base + plan.off_ctrl + offsetof(MlmCtrlBlock, cnt));
     int32_t *seeds = (int32_t *)(base + plan.off_seeds);
     MlmReach R{};
     for (int a = 0; a < 3; ++a) {
@@ -956,34 +938,30 @@ int mlm_export_reach(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], 
     } else {
         // D_out <= clearance^2 of mlm_export_esdf at max_dist = clearance + 1
         rc = esdf_tiles(h, "mlm_export_reach", lo, D, clearance + 1, flags, [&](const uint16_t *fa, long long j0, long long nt) {
-            hipLaunchKernelGGL(k_reach_blocked, dim3(std::min<unsigned int>(grid_for((size_t)nt), kEsdfPassGrid)), dim3(MLM_BLOCK), 0, h->stream, fa,
-                               mask + j0, nt, (unsigned)(clearance * clearance));
+            launch(h, k_reach_blocked, lanes_grid((size_t)nt, kEsdfPassGrid), 0, fa, mask + j0, nt, (unsigned)(clearance * clearance));
         });
         if (rc) return rc;
     }
     // field, seeds, dirty arrays, control block
     HIPCHK(h, hipMemsetAsync(base + plan.off_dirty, 0, (size_t)(2 * plan.dirty_bytes + kReachCtrlBytes), h->stream));
     HIPCHK(h, hipMemcpyAsync(seeds, seeds3, (size_t)n_seeds * 12, hipMemcpyDefault, h->stream));
-    hipLaunchKernelGGL(k_reach_init, dim3(std::min<unsigned int>(grid_for((size_t)nvox), kReachGrid)), dim3(MLM_BLOCK), 0, h->stream, mask, R.field,
-                       nvox);
-    hipLaunchKernelGGL(k_reach_seed, dim3(std::min<unsigned int>(grid_for((size_t)n_seeds), 1024u)), dim3(MLM_BLOCK), 0, h->stream, R,
-                       (const int32_t *)seeds, n_seeds, (long long)lo[0], (long long)lo[1], (long long)lo[2], dirty[0]);
+    launch(h, k_reach_init, lanes_grid((size_t)nvox, kReachGrid), 0, mask, R.field, nvox);
+    launch(h, k_reach_seed, lanes_grid((size_t)n_seeds, 1024u), 0, R, (const int32_t *)seeds, n_seeds, (long long)lo[0], (long long)lo[1],
+           (long long)lo[2], dirty[0]);
     HIPCHK(h, hipGetLastError());
     // sweeps in groups (settle): the dirty arrays swap roles from sweep to sweep
     const size_t lds = (size_t)(plan.T[0] + 2) * (plan.T[1] + 2) * (plan.T[2] + 2) * sizeof(uint32_t);
-    const dim3 sgrid((unsigned int)std::min<long long>(plan.tiles, kReachGrid));
+    const unsigned int sgrid = bricks_grid(plan.tiles, kReachGrid);
     const long long needed = settle(h, "mlm_export_reach", plan.cap, group, marked, [&](long long s, unsigned int *word) {
-        hipLaunchKernelGGL(k_reach_sweep, sgrid, dim3(MLM_BLOCK), lds, h->stream, R, dirty[s & 1], dirty[(s & 1) ^ 1], word);
+        launch(h, k_reach_sweep, sgrid, lds, R, dirty[s & 1], dirty[(s & 1) ^ 1], word);
     });
     if (needed < 0) return (int)needed;
     // outputs and counters
-    for (long long j0 = 0; j0 < nvox; j0 += chunk) {
-        const long long j1 = std::min(nvox, j0 + chunk);
-        hipLaunchKernelGGL(k_reach_out, dim3(std::min<unsigned int>(grid_for((size_t)(j1 - j0)), kReachGrid)), dim3(MLM_BLOCK), 0, h->stream, R, j0, j1,
-                           (int32_t *)ch.at(0, (size_t)j0), (uint8_t *)ch.at(1, (size_t)j0), cnt);
-        HIPCHK(h, hipGetLastError());
-        if ((rc = ch.copy_out(h, 0, 2, (size_t)j0, (size_t)(j1 - j0)))) return rc;
-    }
+    rc = chunk_rounds(h, ch, (size_t)nvox, (size_t)chunk, 0, 0, 0, 2, [&](size_t j0, size_t m, void **at) {
+        launch(h, k_reach_out, lanes_grid(m, kReachGrid), 0, R, (long long)j0, (long long)(j0 + m), (int32_t *)at[0], (uint8_t *)at[1], cnt);
+        return MLM_OK;
+    });
+    if (rc) return rc;
     return settle_finish(h, cnt, needed, summary);
 }
 
@@ -1018,16 +996,16 @@ int mlm_export_route(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], 
         return MLM_ERR_INVALID;
     }
     // outputs: written in place, or staged in ranges of the box
-    ReadoutChannels<2> ch(h->d_win_stage, h->win_stage_bytes, {{cost, sizeof(int32_t)}, {parent, 1}});
+    ReadoutChannels<2> ch(h->d_win_stage, {{cost, sizeof(int32_t)}, {parent, 1}});
     const long long chunk = ch.any_staged ? std::min(nvox, kEsdfStageVoxels) : nvox;
-    if ((rc = readout_reserve(h, h->d_reach, h->reach_bytes, (size_t)plan.scratch_bytes, "mlm_export_route"))) return rc;
+    if ((rc = readout_reserve(h, h->d_reach, (size_t)plan.scratch_bytes, "mlm_export_route"))) return rc;
     if ((rc = ch.reserve(h, "mlm_export_route", (size_t)chunk))) return rc;
-    if (!h->h_reach_ctrl) HIPCHK(h, hipHostMalloc((void **)&h->h_reach_ctrl, (size_t)kReachCtrlBytes, hipHostMallocDefault));
-    char *base = (char *)h->d_reach;
+    if ((rc = ctrl_block(h))) return rc;
+    char *base = (char *)h->d_reach.p;
     uint8_t *cls = (uint8_t *)(base + plan.off_class), *dirty[2] = {(uint8_t *)(base + plan.off_dirty), (uint8_t *)(base + plan.off_dirty + plan.dirty_bytes)};
     unsigned int *marked = (unsigned int *)(base + plan.off_ctrl);
-    unsigned long long *cnt = (unsigned long long *)(base + plan.off_ctrl + kReachGroupMax * 4);
-    uint32_t *pen = (uint32_t *)(base + plan.off_ctrl + kRoutePenOffset);
+    unsigned long long *cnt = (unsigned long long *)(base + plan.off_ctrl + offsetof(MlmCtrlBlock, cnt));
+    uint32_t *pen = (uint32_t *)(base + plan.off_ctrl + offsetof(MlmCtrlBlock, pen));
     int32_t *seeds = (int32_t *)(base + plan.off_seeds);
     MlmRoute R{};
     for (int a = 0; a < 3; ++a) {
@@ -1049,39 +1027,35 @@ int mlm_export_route(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], 
     } else {
         // the rings of D_out of mlm_export_esdf at max_dist = clearance + n_penalty + 1
         rc = esdf_tiles(h, "mlm_export_route", lo, D, clearance + n_penalty + 1, flags, [&](const uint16_t *fa, long long j0, long long nt) {
-            hipLaunchKernelGGL(k_route_class, dim3(std::min<unsigned int>(grid_for((size_t)nt), kEsdfPassGrid)), dim3(MLM_BLOCK), 0, h->stream, fa,
-                               cls + j0, nt, clearance, n_penalty);
+            launch(h, k_route_class, lanes_grid((size_t)nt, kEsdfPassGrid), 0, fa, cls + j0, nt, clearance, n_penalty);
         });
         if (rc) return rc;
     }
     // field, seeds, dirty arrays, control block with the penalty table (staged in the pinned block behind what the host reads back)
-    uint32_t *h_pen = (uint32_t *)((char *)h->h_reach_ctrl + kRoutePenOffset);
+    uint32_t *h_pen = h->h_ctrl->pen;
     for (int k = 0; k < kRoutePenWords; ++k) h_pen[k] = k < n_penalty ? (uint32_t)penalty[k] : 0u;
     HIPCHK(h, hipMemsetAsync(base + plan.off_dirty, 0, (size_t)(2 * plan.dirty_bytes + kReachCtrlBytes), h->stream));
     HIPCHK(h, hipMemcpyAsync(pen, h_pen, (size_t)kRoutePenWords * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(seeds, seeds3, (size_t)n_seeds * 12, hipMemcpyDefault, h->stream));
-    hipLaunchKernelGGL(k_route_init, dim3(std::min<unsigned int>(grid_for((size_t)nvox), kReachGrid)), dim3(MLM_BLOCK), 0, h->stream, (const uint8_t *)cls,
-                       R.field, nvox, n_penalty);
-    hipLaunchKernelGGL(k_route_seed, dim3(std::min<unsigned int>(grid_for((size_t)n_seeds), 1024u)), dim3(MLM_BLOCK), 0, h->stream, R,
-                       (const int32_t *)seeds, n_seeds, (long long)lo[0], (long long)lo[1], (long long)lo[2], dirty[0]);
+    launch(h, k_route_init, lanes_grid((size_t)nvox, kReachGrid), 0, (const uint8_t *)cls, R.field, nvox, n_penalty);
+    launch(h, k_route_seed, lanes_grid((size_t)n_seeds, 1024u), 0, R, (const int32_t *)seeds, n_seeds, (long long)lo[0], (long long)lo[1],
+           (long long)lo[2], dirty[0]);
     HIPCHK(h, hipGetLastError());
     // sweeps in groups, as mlm_export_reach runs them
     auto sweep = connectivity == 6 ? k_route_sweep<6> : connectivity == 18 ? k_route_sweep<18> : k_route_sweep<26>;
     const size_t lds = (size_t)plan.lds_bytes;
     if (lds > 65536) HIPCHK(h, hipFuncSetAttribute((const void *)sweep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const dim3 sgrid((unsigned int)std::min<long long>(plan.tiles, kReachGrid));
+    const unsigned int sgrid = bricks_grid(plan.tiles, kReachGrid);
     const long long needed = settle(h, "mlm_export_route", plan.cap, group, marked, [&](long long s, unsigned int *word) {
-        hipLaunchKernelGGL(sweep, sgrid, dim3(MLM_BLOCK), lds, h->stream, R, dirty[s & 1], dirty[(s & 1) ^ 1], word);
+        launch(h, sweep, sgrid, lds, R, dirty[s & 1], dirty[(s & 1) ^ 1], word);
     });
     if (needed < 0) return (int)needed;
     // outputs and counters
-    for (long long j0 = 0; j0 < nvox; j0 += chunk) {
-        const long long j1 = std::min(nvox, j0 + chunk);
-        hipLaunchKernelGGL(k_route_out, dim3(std::min<unsigned int>(grid_for((size_t)(j1 - j0)), kReachGrid)), dim3(MLM_BLOCK), 0, h->stream, R, j0, j1,
-                           (int32_t *)ch.at(0, (size_t)j0), (uint8_t *)ch.at(1, (size_t)j0), cnt);
-        HIPCHK(h, hipGetLastError());
-        if ((rc = ch.copy_out(h, 0, 2, (size_t)j0, (size_t)(j1 - j0)))) return rc;
-    }
+    rc = chunk_rounds(h, ch, (size_t)nvox, (size_t)chunk, 0, 0, 0, 2, [&](size_t j0, size_t m, void **at) {
+        launch(h, k_route_out, lanes_grid(m, kReachGrid), 0, R, (long long)j0, (long long)(j0 + m), (int32_t *)at[0], (uint8_t *)at[1], cnt);
+        return MLM_OK;
+    });
+    if (rc) return rc;
     return settle_finish(h, cnt, needed, summary);
 }
 
@@ -1105,19 +1079,20 @@ int mlm_export_clusters(mlm_handle *h, const int32_t lo[3], const int32_t dims[3
 
     long long tile = kClusterTileDefault, kv;
     if (knob("cluster_tile", kv)) tile = kv;
-    const bool table_staged = table && !readout_in_place(table), labels_staged = labels && !readout_in_place(labels);
+    ReadoutChannels<1> ch(h->d_win_stage, {{labels, sizeof(int32_t)}});
+    const bool table_staged = table && !readout_in_place(table), labels_staged = ch.any_staged;
     const MlmClusterPlan plan = mlm_cluster_plan(D, tile, frontier, table_staged ? std::min<long long>(cap, nvox) : 0); // (K <= voxels)
     if (!plan.ok) { // (not with the tiles mlm_debug_set admits)
         h->err = "mlm_export_clusters: no such tile";
         return MLM_ERR_INVALID;
     }
-    // labels: written in place, or staged through d_win_stage in ranges of the box; rows: in place, or in the scratch
+    // labels: written in place, or staged through d_win_stage in ranges of the box (the one channel lies at the staging's start, and
+    // its bytes are reserved as they are, not rounded as ch.reserve would); rows: in place, or in the scratch
     const long long chunk = labels_staged ? std::min(nvox, kEsdfStageVoxels) : nvox;
-    if ((rc = readout_reserve(h, h->d_cluster, h->cluster_bytes, (size_t)plan.scratch_bytes, "mlm_export_clusters"))) return rc;
-    if (labels_staged && (rc = readout_reserve(h, h->d_win_stage, h->win_stage_bytes, (size_t)chunk * sizeof(int32_t), "mlm_export_clusters")))
-        return rc;
-    if (!h->h_reach_ctrl) HIPCHK(h, hipHostMalloc((void **)&h->h_reach_ctrl, (size_t)kReachCtrlBytes, hipHostMallocDefault));
-    char *base = (char *)h->d_cluster;
+    if ((rc = readout_reserve(h, h->d_cluster, (size_t)plan.scratch_bytes, "mlm_export_clusters"))) return rc;
+    if (labels_staged && (rc = readout_reserve(h, h->d_win_stage, (size_t)chunk * sizeof(int32_t), "mlm_export_clusters"))) return rc;
+    if ((rc = ctrl_block(h))) return rc;
+    char *base = (char *)h->d_cluster.p;
     uint8_t *mask = (uint8_t *)(base + plan.off_mask);
     unsigned int *chunk_cnt = (unsigned int *)(base + plan.off_chunk);
     unsigned long long *cnt = (unsigned long long *)(base + plan.off_ctrl);
@@ -1137,7 +1112,7 @@ int mlm_export_clusters(mlm_handle *h, const int32_t lo[3], const int32_t dims[3
     R.num = (uint32_t *)(base + plan.off_num);
 
     // the mask of the box
-    const dim3 vgrid(std::min<unsigned int>(grid_for((size_t)nvox), kReachGrid));
+    const unsigned int vgrid = lanes_grid((size_t)nvox, kReachGrid);
     if (frontier) {
         MlmClusterOcc E{};
         for (int a = 0; a < 3; ++a) {
@@ -1146,9 +1121,8 @@ int mlm_export_clusters(mlm_handle *h, const int32_t lo[3], const int32_t dims[3
         }
         brick_cover(h, 3, E.glo, E.gd, E.b0, E.nb);
         E.out = (uint8_t *)(base + plan.off_grown);
-        const long long n_bricks = (long long)E.nb[0] * E.nb[1] * E.nb[2];
-        hipLaunchKernelGGL(k_cluster_occ, dim3((unsigned int)std::min<long long>(n_bricks, kEsdfMaskGrid)), dim3(MLM_BLOCK), 0, h->stream, h->P, E);
-        hipLaunchKernelGGL(k_cluster_frontier, vgrid, dim3(MLM_BLOCK), 0, h->stream, (const uint8_t *)E.out, mask, D[0], D[1], nvox);
+        launch(h, k_cluster_occ, bricks_grid((long long)E.nb[0] * E.nb[1] * E.nb[2], kEsdfMaskGrid), 0, h->P, E);
+        launch(h, k_cluster_frontier, vgrid, 0, (const uint8_t *)E.out, mask, D[0], D[1], nvox);
     } else {
         mask_box(h, lo, dims, flags, mask);
     }
@@ -1156,37 +1130,32 @@ int mlm_export_clusters(mlm_handle *h, const int32_t lo[3], const int32_t dims[3
     // local, merge, flatten and sizes, numbering
     HIPCHK(h, hipMemsetAsync(cnt, 0, (size_t)kClusterCtrlBytes, h->stream));
     const size_t lds = (size_t)plan.T[0] * plan.T[1] * plan.T[2] * sizeof(uint32_t);
-    const dim3 cgrid((unsigned int)std::min<long long>(plan.chunks, kReachGrid));
-    hipLaunchKernelGGL(k_cluster_local, dim3((unsigned int)std::min<long long>(plan.tiles, kReachGrid)), dim3(MLM_BLOCK), lds, h->stream, R,
-                       (const uint8_t *)mask, cnt);
-    hipLaunchKernelGGL(k_cluster_merge, vgrid, dim3(MLM_BLOCK), 0, h->stream, R);
-    hipLaunchKernelGGL(k_cluster_flatten, vgrid, dim3(MLM_BLOCK), 0, h->stream, R, cnt);
-    hipLaunchKernelGGL(k_cluster_count, cgrid, dim3(MLM_BLOCK), 0, h->stream, R, plan.chunks, chunk_cnt, cnt);
-    hipLaunchKernelGGL(k_cluster_scan, dim3(1), dim3(MLM_BLOCK), 0, h->stream, chunk_cnt, plan.chunks, cnt);
-    hipLaunchKernelGGL(k_cluster_rank, cgrid, dim3(MLM_BLOCK), 0, h->stream, R, plan.chunks, (const unsigned int *)chunk_cnt, rows, cap);
+    const unsigned int cgrid = bricks_grid(plan.chunks, kReachGrid);
+    launch(h, k_cluster_local, bricks_grid(plan.tiles, kReachGrid), lds, R, (const uint8_t *)mask, cnt);
+    launch(h, k_cluster_merge, vgrid, 0, R);
+    launch(h, k_cluster_flatten, vgrid, 0, R, cnt);
+    launch(h, k_cluster_count, cgrid, 0, R, plan.chunks, chunk_cnt, cnt);
+    launch(h, k_cluster_scan, 1u, 0, chunk_cnt, plan.chunks, cnt);
+    launch(h, k_cluster_rank, cgrid, 0, R, plan.chunks, (const unsigned int *)chunk_cnt, rows, cap);
     HIPCHK(h, hipGetLastError());
     // labels and rows
-    if (labels || rows)
-        for (long long j0 = 0; j0 < nvox; j0 += chunk) {
-            const long long j1 = std::min(nvox, j0 + chunk);
-            int32_t *out = !labels ? nullptr : labels_staged ? (int32_t *)h->d_win_stage : labels + j0;
-            hipLaunchKernelGGL(k_cluster_write, dim3(std::min<unsigned int>(grid_for((size_t)(j1 - j0)), kReachGrid)), dim3(MLM_BLOCK), 0, h->stream, R,
-                               j0, j1, out, rows, cap);
-            HIPCHK(h, hipGetLastError());
-            if (labels_staged) HIPCHK(h, hipMemcpyAsync(labels + j0, out, (size_t)(j1 - j0) * sizeof(int32_t), hipMemcpyDefault, h->stream));
-        }
-    unsigned long long *h_cnt = (unsigned long long *)h->h_reach_ctrl;
-    if (summary || table_staged) HIPCHK(h, hipMemcpyAsync(h_cnt, cnt, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (labels || rows) {
+        rc = chunk_rounds(h, ch, (size_t)nvox, (size_t)chunk, 0, 0, 0, 1, [&](size_t j0, size_t m, void **at) {
+            launch(h, k_cluster_write, lanes_grid(m, kReachGrid), 0, R, (long long)j0, (long long)(j0 + m), (int32_t *)at[0], rows, cap);
+            return MLM_OK;
+        });
+        if (rc) return rc;
+    }
+    int64_t sm[6] = {};
+    if ((rc = read_back(h, cnt, summary || table_staged ? 6 : 0, sm))) return rc;
     if (table_staged) { // the rows that exist: min(K, cap)
-        const size_t k = (size_t)std::min<unsigned long long>(h_cnt[2], (unsigned long long)cap);
+        const size_t k = (size_t)std::min<unsigned long long>((unsigned long long)sm[2], (unsigned long long)cap);
         if (k) {
             HIPCHK(h, hipMemcpyAsync(table, rows, k * MLM_CLUSTER_ROW * sizeof(int64_t), hipMemcpyDefault, h->stream));
             HIPCHK(h, hipStreamSynchronize(h->stream));
         }
     }
-    if (summary)
-        for (int i = 0; i < 6; ++i) summary[i] = (int64_t)h_cnt[i];
+    if (summary) std::copy(sm, sm + 6, summary);
     return MLM_OK;
 }
 
@@ -1212,12 +1181,11 @@ int mlm_export_mesh(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], i
 
     // channels: quads, face4 (rows of faces), vert3, vert_xyz, vert_n3 (rows of vertices); in device memory (written in place) or
     // staged through d_win_stage in ranges of the numbering
-    ReadoutChannels<5> ch(h->d_win_stage, h->win_stage_bytes,
-                          {{quads, 4 * sizeof(int32_t)}, {face4, 4 * sizeof(int32_t)}, {vert3, 3 * sizeof(int32_t)}, {vert_xyz, 3 * sizeof(float)},
-                           {vert_n3, 3}});
-    if ((rc = readout_reserve(h, h->d_mesh, h->mesh_bytes, (size_t)plan.scratch_bytes, "mlm_export_mesh"))) return rc;
-    if (!h->h_reach_ctrl) HIPCHK(h, hipHostMalloc((void **)&h->h_reach_ctrl, (size_t)kReachCtrlBytes, hipHostMallocDefault));
-    char *base = (char *)h->d_mesh;
+    ReadoutChannels<5> ch(h->d_win_stage, {{quads, 4 * sizeof(int32_t)}, {face4, 4 * sizeof(int32_t)}, {vert3, 3 * sizeof(int32_t)},
+                                           {vert_xyz, 3 * sizeof(float)}, {vert_n3, 3}});
+    if ((rc = readout_reserve(h, h->d_mesh, (size_t)plan.scratch_bytes, "mlm_export_mesh"))) return rc;
+    if ((rc = ctrl_block(h))) return rc;
+    char *base = (char *)h->d_mesh.p;
     const long long lo64[3] = {lo[0], lo[1], lo[2]};
     const MlmMeshGeo G = mlm_mesh_geo(D, lo64, h->P.n, h->P.d_sub, h->P.d_glb, flags);
     MlmMeshArrays A{};
@@ -1240,18 +1208,14 @@ int mlm_export_mesh(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], i
     brick_cover(h, 3, E.glo, E.gd, E.b0, E.nb);
     E.flags = flags;
     E.out = (uint8_t *)base;
-    const long long n_bricks = (long long)E.nb[0] * E.nb[1] * E.nb[2];
     HIPCHK(h, hipMemsetAsync(A.cnt, 0, (size_t)kMeshCtrlBytes, h->stream));
-    hipLaunchKernelGGL(k_mesh_state, dim3((unsigned int)std::min<long long>(n_bricks, kEsdfMaskGrid)), dim3(MLM_BLOCK), 0, h->stream, h->P, E);
-    const dim3 fgrid((unsigned int)std::min<long long>(plan.fchunks, kReachGrid)), vgrid((unsigned int)std::min<long long>(plan.vchunks, kReachGrid));
-    hipLaunchKernelGGL(k_mesh_count, vgrid, dim3(MLM_BLOCK), 0, h->stream, G, A); // (fchunks <= vchunks)
-    hipLaunchKernelGGL(k_mesh_scan, dim3(2), dim3(MLM_BLOCK), 0, h->stream, A);
+    launch(h, k_mesh_state, bricks_grid((long long)E.nb[0] * E.nb[1] * E.nb[2], kEsdfMaskGrid), 0, h->P, E);
+    const unsigned int fgrid = bricks_grid(plan.fchunks, kReachGrid), vgrid = bricks_grid(plan.vchunks, kReachGrid);
+    launch(h, k_mesh_count, vgrid, 0, G, A); // (fchunks <= vchunks)
+    launch(h, k_mesh_scan, 2u, 0, A);
     HIPCHK(h, hipGetLastError());
-    unsigned long long *h_cnt = (unsigned long long *)h->h_reach_ctrl;
-    HIPCHK(h, hipMemcpyAsync(h_cnt, A.cnt, MLM_MESH_ROW * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
     int64_t sm[MLM_MESH_ROW];
-    for (int i = 0; i < MLM_MESH_ROW; ++i) sm[i] = (int64_t)h_cnt[i];
+    if ((rc = read_back(h, A.cnt, MLM_MESH_ROW, sm))) return rc;
     sm[11] = 0;
 
     // rows: the first min(F, cap_faces) faces and min(V, cap_verts) vertices, in ranges where a destination is staged; the word bases
@@ -1268,19 +1232,18 @@ int mlm_export_mesh(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], i
         do {
             const long long v1 = std::min(nV, v0 + vstep);
             const bool rows = v1 > v0;
-            hipLaunchKernelGGL(k_mesh_verts, vgrid, dim3(MLM_BLOCK), 0, h->stream, G, A, v0, v1, (int32_t *)(rows ? ch.at(2, (size_t)v0) : nullptr),
-                               (float *)(rows ? ch.at(3, (size_t)v0) : nullptr), (int8_t *)(rows ? ch.at(4, (size_t)v0) : nullptr));
+            launch(h, k_mesh_verts, vgrid, 0, G, A, v0, v1, (int32_t *)(rows ? ch.at(2, (size_t)v0) : nullptr),
+                   (float *)(rows ? ch.at(3, (size_t)v0) : nullptr), (int8_t *)(rows ? ch.at(4, (size_t)v0) : nullptr));
             HIPCHK(h, hipGetLastError());
             if ((rc = ch.copy_out(h, 2, 5, (size_t)v0, (size_t)(v1 - v0)))) return rc;
             v0 = v1;
         } while (v0 < nV);
     }
-    for (long long f0 = 0; f0 < nF; f0 += fstep) {
-        const long long f1 = std::min(nF, f0 + fstep);
-        hipLaunchKernelGGL(k_mesh_faces, fgrid, dim3(MLM_BLOCK), 0, h->stream, G, A, f0, f1, (int32_t *)ch.at(0, (size_t)f0), (int32_t *)ch.at(1, (size_t)f0));
-        HIPCHK(h, hipGetLastError());
-        if ((rc = ch.copy_out(h, 0, 2, (size_t)f0, (size_t)(f1 - f0)))) return rc;
-    }
+    rc = chunk_rounds(h, ch, (size_t)nF, (size_t)fstep, 0, 0, 0, 2, [&](size_t f0, size_t m, void **at) {
+        launch(h, k_mesh_faces, fgrid, 0, G, A, (long long)f0, (long long)(f0 + m), (int32_t *)at[0], (int32_t *)at[1]);
+        return MLM_OK;
+    });
+    if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (summary)
         for (int i = 0; i < MLM_MESH_ROW; ++i) summary[i] = sm[i];
@@ -1310,22 +1273,21 @@ int mlm_export_octree(mlm_handle *h, const int32_t lo[3], const int32_t dims[3],
 
     // channels: words, inner4, skip (rows of inner nodes), leaf4, leaf_class (rows of leaves); in device memory (written in place) or
     // staged through d_win_stage in ranges of the numbering
-    ReadoutChannels<5> ch(h->d_win_stage, h->win_stage_bytes,
-                          {{words, sizeof(uint16_t)}, {inner4, 4 * sizeof(int32_t)}, {skip, sizeof(int32_t)}, {leaf4, 4 * sizeof(int32_t)}, {leaf_class, 1}});
-    if ((rc = readout_reserve(h, h->d_oct, h->oct_bytes, (size_t)plan.scratch_bytes, "mlm_export_octree"))) return rc;
-    if (!h->h_reach_ctrl) HIPCHK(h, hipHostMalloc((void **)&h->h_reach_ctrl, (size_t)kReachCtrlBytes, hipHostMallocDefault));
+    ReadoutChannels<5> ch(h->d_win_stage, {{words, sizeof(uint16_t)}, {inner4, 4 * sizeof(int32_t)}, {skip, sizeof(int32_t)},
+                                           {leaf4, 4 * sizeof(int32_t)}, {leaf_class, 1}});
+    if ((rc = readout_reserve(h, h->d_oct, (size_t)plan.scratch_bytes, "mlm_export_octree"))) return rc;
+    if ((rc = ctrl_block(h))) return rc;
     const MlmOctGeo G = mlm_oct_geo(lo64, D, depth, flags, plan);
-    const MlmOctUpper U = mlm_oct_upper(h->d_oct, plan);
+    const MlmOctUpper U = mlm_oct_upper(h->d_oct.p, plan);
 
     // up: the bricks, then the levels above them; down to the bricks; the counters
-    const dim3 bgrid((unsigned int)std::min<long long>(plan.bricks, kOctGrid));
+    const unsigned int bgrid = bricks_grid(plan.bricks, kOctGrid);
     HIPCHK(h, hipMemsetAsync(U.ctrl, 0, (size_t)kOctCtrlBytes, h->stream));
-    hipLaunchKernelGGL(k_oct_up, bgrid, dim3(MLM_BLOCK), 0, h->stream, h->P, G, U);
-    hipLaunchKernelGGL(k_oct_tail, dim3(1), dim3(MLM_BLOCK), 0, h->stream, G, U);
+    launch(h, k_oct_up, bgrid, 0, h->P, G, U);
+    launch(h, k_oct_tail, 1u, 0, G, U);
     HIPCHK(h, hipGetLastError());
-    unsigned long long *h_cnt = (unsigned long long *)h->h_reach_ctrl;
-    HIPCHK(h, hipMemcpyAsync(h_cnt, U.ctrl, kOctCtrlWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const unsigned long long *h_cnt;
+    if ((rc = read_back(h, (const unsigned long long *)U.ctrl, kOctCtrlWords, h_cnt))) return rc;
     int64_t sm[MLM_OCT_ROW];
     mlm_oct_summary(h_cnt, sm);
 
@@ -1336,7 +1298,7 @@ int mlm_export_octree(mlm_handle *h, const int32_t lo[3], const int32_t dims[3],
     const size_t stage_counts[5] = {(size_t)nstep, (size_t)nstep, (size_t)nstep, (size_t)mstep, (size_t)mstep};
     if ((rc = ch.reserve(h, "mlm_export_octree", stage_counts))) return rc;
     const long long upper_cells = plan.cells - plan.bricks;
-    const dim3 ugrid(std::max(1u, std::min<unsigned int>(grid_for((size_t)upper_cells), kOctGrid)));
+    const unsigned int ugrid = std::max(1u, lanes_grid((size_t)upper_cells, kOctGrid));
     for (long long n0 = 0, m0 = 0; n0 < nN || m0 < nM;) {
         const long long n1 = std::min(nN, n0 + nstep), m1 = std::min(nM, m0 + mstep);
         MlmOctOut O{};
@@ -1350,8 +1312,8 @@ int mlm_export_octree(mlm_handle *h, const int32_t lo[3], const int32_t dims[3],
             O.leaf_class = (int8_t *)ch.at(4, (size_t)m0);
         }
         O.n0 = n0, O.n1 = n1, O.m0 = m0, O.m1 = m1;
-        hipLaunchKernelGGL(k_oct_emit_upper, ugrid, dim3(MLM_BLOCK), 0, h->stream, G, U, O);
-        hipLaunchKernelGGL(k_oct_emit, bgrid, dim3(MLM_BLOCK), 0, h->stream, h->P, G, U, O);
+        launch(h, k_oct_emit_upper, ugrid, 0, G, U, O);
+        launch(h, k_oct_emit, bgrid, 0, h->P, G, U, O);
         HIPCHK(h, hipGetLastError());
         if (n1 > n0 && (rc = ch.copy_out(h, 0, 3, (size_t)n0, (size_t)(n1 - n0)))) return rc;
         if (m1 > m0 && (rc = ch.copy_out(h, 3, 5, (size_t)m0, (size_t)(m1 - m0)))) return rc;
@@ -1375,7 +1337,7 @@ int mlm_query_rays(mlm_handle *h, const double *p0, const double *p1, int n, int
     if (n == 0) return MLM_OK;
     HIPCHK(h, hipSetDevice(h->device));
     // channels: the two inputs, then the five outputs; bytes per ray; in device memory (used in place) or staged
-    ReadoutChannels<7> ch(h->d_ray_stage, h->ray_stage_bytes,
+    ReadoutChannels<7> ch(h->d_ray_stage,
                           {{p0, 3 * sizeof(double)}, {p1, 3 * sizeof(double)}, {status, 1}, {voxel3, 3 * sizeof(int32_t)}, {t, sizeof(double)},
                            {n_steps, sizeof(int32_t)}, {n_unknown, sizeof(int32_t)}},
                           true);
@@ -1384,21 +1346,11 @@ int mlm_query_rays(mlm_handle *h, const double *p0, const double *p1, int n, int
     if (rc) return rc > 0 ? MLM_OK : rc;
     if ((rc = drain(h))) return rc;
     // chunks: staged channels of a chunk share one kept buffer (at most 77 bytes per ray)
-    const int chunk = std::min(n, kRayChunk);
-    if ((rc = ch.reserve(h, "mlm_query_rays", (size_t)chunk))) return rc;
-    for (int i0 = 0; i0 < n; i0 += chunk) {
-        const int m = std::min(chunk, n - i0);
-        void *at[7];
-        for (int c = 0; c < 7; ++c) at[c] = ch.at(c, (size_t)i0);
-        if ((rc = ch.copy_in(h, 0, 2, (size_t)i0, (size_t)m))) return rc;
-        MlmRays R{(const double *)at[0], (const double *)at[1], m, flags, (int8_t *)at[2], (int32_t *)at[3], (double *)at[4], (int32_t *)at[5], (int32_t *)at[6]};
-        const dim3 grid(std::min<unsigned int>(grid_for((size_t)m), h->rays_grid));
-        hipLaunchKernelGGL(k_rays, grid, dim3(MLM_BLOCK), 0, h->stream, h->P, R);
-        HIPCHK(h, hipGetLastError());
-        if ((rc = ch.copy_out(h, 2, 7, (size_t)i0, (size_t)m))) return rc;
-    }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return MLM_OK;
+    return for_chunks(h, ch, "mlm_query_rays", (size_t)n, (size_t)std::min(n, kRayChunk), 0, 2, 2, 7, [&](size_t, size_t m, void **at) {
+        MlmRays R{(const double *)at[0], (const double *)at[1], (int)m, flags, (int8_t *)at[2], (int32_t *)at[3], (double *)at[4], (int32_t *)at[5], (int32_t *)at[6]};
+        launch(h, k_rays, lanes_grid(m, h->rays_grid), 0, h->P, R);
+        return MLM_OK;
+    });
 }
 
 int mlm_render_depth(mlm_handle *h, const double *T_ws, int n_poses, int width, int height, const double K[4], int max_depth_mm, int flags,
@@ -1429,7 +1381,7 @@ int mlm_render_depth(mlm_handle *h, const double *T_ws, int n_poses, int width, 
     auto first_pixel = [&](long long q) { return ((q / tiles_y) * height + (q % tiles_y) * TH) * width; };
     // channels: the poses, the four per-pixel outputs, the table; in device memory (used in place) or staged — poses and table for the
     // whole call, the per-pixel outputs chunk by chunk (at most 19 bytes per pixel)
-    ReadoutChannels<6> ch(h->d_ray_stage, h->ray_stage_bytes,
+    ReadoutChannels<6> ch(h->d_ray_stage,
                           {{T_ws, 12 * sizeof(double)}, {depth, sizeof(uint16_t)}, {status, 1}, {voxel3, 3 * sizeof(int32_t)},
                            {n_unknown, sizeof(int32_t)}, {table, MLM_RENDER_ROW * sizeof(int64_t)}},
                           true);
@@ -1451,7 +1403,7 @@ int mlm_render_depth(mlm_handle *h, const double *T_ws, int n_poses, int width, 
         R.q0 = (int)q0, R.n_tiles = (int)((q1 - q0) * tiles_x), R.pix0 = i0;
         R.depth = (uint16_t *)at[1], R.status = (int8_t *)at[2], R.voxel3 = (int32_t *)at[3], R.n_unknown = (int32_t *)at[4];
         // one wave per tile, four to a workgroup
-        hipLaunchKernelGGL(kern, dim3(wave_grid((size_t)R.n_tiles)), dim3(MLM_BLOCK), 0, h->stream, h->P, R);
+        launch(h, kern, wave_grid((size_t)R.n_tiles), 0, h->P, R);
         HIPCHK(h, hipGetLastError());
         if ((rc = ch.copy_out(h, 1, 5, (size_t)i0, (size_t)m))) return rc;
     }
@@ -1488,29 +1440,19 @@ int mlm_query_boxes(mlm_handle *h, const int32_t *box6, int n, int flags, const 
     if (n == 0) return MLM_OK;
     HIPCHK(h, hipSetDevice(h->device));
     // channels: the input, then the four outputs; bytes per box; in device memory (used in place) or staged
-    ReadoutChannels<5> ch(h->d_ray_stage, h->ray_stage_bytes,
+    ReadoutChannels<5> ch(h->d_ray_stage,
                           {{box6, 6 * sizeof(int32_t)}, {status, 1}, {out6, 6 * sizeof(int32_t)}, {closed, 1}, {table, MLM_BOX_ROW * sizeof(int64_t)}}, true);
     // a planner's waypoint-by-waypoint calls: answered on the host (mlm_mirror.h), like mlm_query_rays' small batches
     int rc = mirror_try(h, ch.all_host && mirror_boxes_wanted(h, box6, n, L), n, [&] { h->mir.view.boxes(box6, n, flags, L, status, out6, closed, table); });
     if (rc) return rc > 0 ? MLM_OK : rc;
     if ((rc = drain(h))) return rc;
     // chunks: staged channels of a chunk share one kept buffer (at most 82 bytes per box)
-    const int chunk = std::min(n, kBoxChunk);
-    if ((rc = ch.reserve(h, "mlm_query_boxes", (size_t)chunk))) return rc;
-    for (int i0 = 0; i0 < n; i0 += chunk) {
-        const int m = std::min(chunk, n - i0);
-        void *at[5];
-        for (int c = 0; c < 5; ++c) at[c] = ch.at(c, (size_t)i0);
-        if ((rc = ch.copy_in(h, 0, 1, (size_t)i0, (size_t)m))) return rc;
-        MlmBoxes B{(const int32_t *)at[0], m, flags, L, (int8_t *)at[1], (int32_t *)at[2], (uint8_t *)at[3], (int64_t *)at[4]};
+    return for_chunks(h, ch, "mlm_query_boxes", (size_t)n, (size_t)std::min(n, kBoxChunk), 0, 1, 1, 5, [&](size_t, size_t m, void **at) {
+        MlmBoxes B{(const int32_t *)at[0], (int)m, flags, L, (int8_t *)at[1], (int32_t *)at[2], (uint8_t *)at[3], (int64_t *)at[4]};
         // one wave per box, four to a workgroup; at most kBoxGrid workgroups (grid-stride)
-        const dim3 grid(wave_grid((size_t)m, kBoxGrid));
-        hipLaunchKernelGGL(k_boxes, grid, dim3(MLM_BLOCK), 0, h->stream, h->P, B);
-        HIPCHK(h, hipGetLastError());
-        if ((rc = ch.copy_out(h, 1, 5, (size_t)i0, (size_t)m))) return rc;
-    }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return MLM_OK;
+        launch(h, k_boxes, wave_grid(m, kBoxGrid), 0, h->P, B);
+        return MLM_OK;
+    });
 }
 
 int mlm_query_nearest(mlm_handle *h, const double *pos, int n, int max_dist, int flags, int8_t *status, int32_t *voxel3, int32_t *delta3,
@@ -1525,7 +1467,7 @@ int mlm_query_nearest(mlm_handle *h, const double *pos, int n, int max_dist, int
     if (n == 0) return MLM_OK;
     HIPCHK(h, hipSetDevice(h->device));
     // channels: the input, then the five outputs; bytes per point; in device memory (used in place) or staged
-    ReadoutChannels<6> ch(h->d_ray_stage, h->ray_stage_bytes,
+    ReadoutChannels<6> ch(h->d_ray_stage,
                           {{pos, 3 * sizeof(double)}, {status, 1}, {voxel3, 3 * sizeof(int32_t)}, {delta3, 3 * sizeof(int32_t)}, {sq, sizeof(int64_t)},
                            {dist, sizeof(double)}},
                           true);
@@ -1534,22 +1476,12 @@ int mlm_query_nearest(mlm_handle *h, const double *pos, int n, int max_dist, int
     if (rc) return rc > 0 ? MLM_OK : rc;
     if ((rc = drain(h))) return rc;
     // chunks: staged channels of a chunk share one kept buffer (at most 65 bytes per point)
-    const int chunk = std::min(n, kNearChunk);
-    if ((rc = ch.reserve(h, "mlm_query_nearest", (size_t)chunk))) return rc;
-    for (int i0 = 0; i0 < n; i0 += chunk) {
-        const int m = std::min(chunk, n - i0);
-        void *at[6];
-        for (int c = 0; c < 6; ++c) at[c] = ch.at(c, (size_t)i0);
-        if ((rc = ch.copy_in(h, 0, 1, (size_t)i0, (size_t)m))) return rc;
-        MlmNearest Q{(const double *)at[0], m, max_dist, flags, (int8_t *)at[1], (int32_t *)at[2], (int32_t *)at[3], (int64_t *)at[4], (double *)at[5]};
+    return for_chunks(h, ch, "mlm_query_nearest", (size_t)n, (size_t)std::min(n, kNearChunk), 0, 1, 1, 6, [&](size_t, size_t m, void **at) {
+        MlmNearest Q{(const double *)at[0], (int)m, max_dist, flags, (int8_t *)at[1], (int32_t *)at[2], (int32_t *)at[3], (int64_t *)at[4], (double *)at[5]};
         // one wave per point, four to a workgroup; at most kNearGrid workgroups (grid-stride)
-        const dim3 grid(wave_grid((size_t)m, kNearGrid));
-        hipLaunchKernelGGL(k_nearest, grid, dim3(MLM_BLOCK), 0, h->stream, h->P, Q);
-        HIPCHK(h, hipGetLastError());
-        if ((rc = ch.copy_out(h, 1, 6, (size_t)i0, (size_t)m))) return rc;
-    }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return MLM_OK;
+        launch(h, k_nearest, wave_grid(m, kNearGrid), 0, h->P, Q);
+        return MLM_OK;
+    });
 }
 
 int mlm_query_sweeps(mlm_handle *h, const double *p0, const double *p1, int n, int radius, int flags, int8_t *status, int32_t *voxel3, double *t,
@@ -1564,7 +1496,7 @@ int mlm_query_sweeps(mlm_handle *h, const double *p0, const double *p1, int n, i
     if (n == 0) return MLM_OK;
     HIPCHK(h, hipSetDevice(h->device));
     // channels: the two inputs, then the seven outputs; bytes per ray; in device memory (used in place) or staged
-    ReadoutChannels<9> ch(h->d_ray_stage, h->ray_stage_bytes,
+    ReadoutChannels<9> ch(h->d_ray_stage,
                           {{p0, 3 * sizeof(double)}, {p1, 3 * sizeof(double)}, {status, 1}, {voxel3, 3 * sizeof(int32_t)}, {t, sizeof(double)},
                            {n_steps, sizeof(int32_t)}, {n_unknown, sizeof(int32_t)}, {hit3, 3 * sizeof(int32_t)}, {hit_sq, sizeof(int32_t)}},
                           true);
@@ -1573,28 +1505,17 @@ int mlm_query_sweeps(mlm_handle *h, const double *p0, const double *p1, int n, i
     if (rc) return rc > 0 ? MLM_OK : rc;
     if ((rc = drain(h))) return rc;
     // chunks: staged channels of a chunk share one kept buffer (at most 93 bytes per ray)
-    const int chunk = std::min(n, kSweepChunk);
-    if ((rc = ch.reserve(h, "mlm_query_sweeps", (size_t)chunk))) return rc;
     // the slots of the block box around the ball stay in LDS while the box has at most kSweepNB blocks per axis (mlm_kernels_sweeps.h)
     const bool cached = radius > 0 && (2 * radius - 1) / h->P.n + 2 <= kSweepNB;
-    for (int i0 = 0; i0 < n; i0 += chunk) {
-        const int m = std::min(chunk, n - i0);
-        void *at[9];
-        for (int c = 0; c < 9; ++c) at[c] = ch.at(c, (size_t)i0);
-        if ((rc = ch.copy_in(h, 0, 2, (size_t)i0, (size_t)m))) return rc;
-        MlmSweeps R{(const double *)at[0], (const double *)at[1], m, radius, flags, mlm_sweep_columns(radius), (int8_t *)at[2], (int32_t *)at[3],
+    return for_chunks(h, ch, "mlm_query_sweeps", (size_t)n, (size_t)std::min(n, kSweepChunk), 0, 2, 2, 9, [&](size_t, size_t m, void **at) {
+        MlmSweeps R{(const double *)at[0], (const double *)at[1], (int)m, radius, flags, mlm_sweep_columns(radius), (int8_t *)at[2], (int32_t *)at[3],
                     (double *)at[4], (int32_t *)at[5], (int32_t *)at[6], (int32_t *)at[7], (int32_t *)at[8]};
-        if (radius == 0) { // one lane per ray, as k_rays
-            hipLaunchKernelGGL(k_sweeps0, dim3(std::min<unsigned int>(grid_for((size_t)m), h->rays_grid)), dim3(MLM_BLOCK), 0, h->stream, h->P, R);
-        } else { // one wave per ray, four to a workgroup; at most kSweepGrid workgroups (grid-stride)
-            const dim3 grid(wave_grid((size_t)m, kSweepGrid));
-            hipLaunchKernelGGL(cached ? k_sweeps<true> : k_sweeps<false>, grid, dim3(MLM_BLOCK), 0, h->stream, h->P, R);
-        }
-        HIPCHK(h, hipGetLastError());
-        if ((rc = ch.copy_out(h, 2, 9, (size_t)i0, (size_t)m))) return rc;
-    }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return MLM_OK;
+        if (radius == 0) // one lane per ray, as k_rays
+            launch(h, k_sweeps0, lanes_grid(m, h->rays_grid), 0, h->P, R);
+        else // one wave per ray, four to a workgroup; at most kSweepGrid workgroups (grid-stride)
+            launch(h, cached ? k_sweeps<true> : k_sweeps<false>, wave_grid(m, kSweepGrid), 0, h->P, R);
+        return MLM_OK;
+    });
 }
 
 int mlm_query_paths(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], const uint8_t *parent, int kind, const int32_t *goals3, int n,
@@ -1616,7 +1537,7 @@ int mlm_query_paths(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], c
     const MlmPathField F{parent, {dims[0], dims[1], dims[2]}, mlm_path_seed_code(kind)};
     const double d = (double)(float)h->P.d_sub;
     // channels: the goals, then the four outputs; bytes per goal; way3 is read too (rows beyond W keep their content)
-    ReadoutChannels<5> chs(h->d_ray_stage, h->ray_stage_bytes,
+    ReadoutChannels<5> chs(h->d_ray_stage,
                            {{goals3, 3 * sizeof(int32_t)}, {status, 1}, {way3, (size_t)cap * 3 * sizeof(int32_t)}, {length, sizeof(double)},
                             {table, MLM_PATH_ROW * sizeof(int64_t)}},
                            true);
@@ -1663,29 +1584,18 @@ int mlm_query_paths(mlm_handle *h, const int32_t lo[3], const int32_t dims[3], c
     // the field is in device memory: k_paths, a wave per goal.  Chunks of goals: the path scratch of a chunk (12 bytes x (max_moves + 1)
     // per goal) takes at most kPathScratchBytes, its staged host channels at most kPathStageBytes, and it has at most kPathChunk goals
     const size_t per_goal = 3 * sizeof(int32_t) * ((size_t)max_moves + 1);
-    size_t stage_per_goal = 0;
-    for (int c = 0; c < 5; ++c)
-        if (chs.staged[c]) stage_per_goal += chs.elem[c];
+    const size_t stage_per_goal = chs.staged_elem_bytes();
     size_t chunk = std::min<size_t>({(size_t)n, (size_t)kPathChunk, std::max<size_t>(1, kPathScratchBytes / per_goal)});
     if (stage_per_goal) chunk = std::min(chunk, std::max<size_t>(1, kPathStageBytes / stage_per_goal));
-    if ((rc = readout_reserve(h, h->d_path, h->path_bytes, chunk * per_goal, "mlm_query_paths"))) return rc;
-    if ((rc = chs.reserve(h, "mlm_query_paths", chunk))) return rc;
-    for (size_t i0 = 0; i0 < (size_t)n; i0 += chunk) {
-        const size_t m = std::min(chunk, (size_t)n - i0);
-        void *at[5];
-        for (int c = 0; c < 5; ++c) at[c] = chs.at(c, i0);
-        for (int c : {0, 2}) // goals in; way3 in, for the rows the kernel leaves as they were
-            if ((rc = chs.copy_in(h, c, c + 1, i0, m))) return rc;
-        MlmPaths Q{F, {lo[0], lo[1], lo[2]}, (const int32_t *)at[0], (int)m, lookahead, max_moves, cap, d, (int32_t *)h->d_path,
+    if ((rc = readout_reserve(h, h->d_path, chunk * per_goal, "mlm_query_paths"))) return rc;
+    return for_chunks(h, chs, "mlm_query_paths", (size_t)n, chunk, 0, 1, 1, 5, [&](size_t i0, size_t m, void **at) -> int {
+        if (int rc2 = chs.copy_in(h, 2, 3, i0, m)) return rc2; // way3 in as well, for the rows the kernel leaves as they were
+        MlmPaths Q{F, {lo[0], lo[1], lo[2]}, (const int32_t *)at[0], (int)m, lookahead, max_moves, cap, d, (int32_t *)h->d_path.p,
                    (int8_t *)at[1], (int32_t *)at[2], (double *)at[3], (int64_t *)at[4]};
         // one wave per goal and scratch slot, four to a workgroup (m <= kPathChunk: at most 16 384 workgroups)
-        const dim3 grid(wave_grid(m));
-        hipLaunchKernelGGL(k_paths, grid, dim3(MLM_BLOCK), 0, h->stream, Q);
-        HIPCHK(h, hipGetLastError());
-        if ((rc = chs.copy_out(h, 1, 5, i0, m))) return rc;
-    }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return MLM_OK;
+        launch(h, k_paths, wave_grid(m), 0, Q);
+        return MLM_OK;
+    });
 }
 
 int mlm_score_poses(mlm_handle *h, const double *pts_s, int n_pts, const double *T_ws, int n_poses, int flags, const int32_t lo[3],
@@ -1713,7 +1623,7 @@ int mlm_score_poses(mlm_handle *h, const double *pts_s, int n_pts, const double 
     }
     // channels: the points, the poses, the rows; in device memory (used in place) or staged — the points for the whole call, poses and
     // rows chunk by chunk
-    ReadoutChannels<3> ch(h->d_ray_stage, h->ray_stage_bytes,
+    ReadoutChannels<3> ch(h->d_ray_stage,
                           {{pts_s, 3 * sizeof(double)}, {T_ws, 12 * sizeof(double)}, {table, MLM_SCORE_ROW * sizeof(int64_t)}}, true);
     const bool field_staged = field && !readout_in_place(sqdist);
     // a matcher's few hypotheses: answered on the host like mlm_query_nearest's small batches — from the host mirror (mlm_mirror.h) with
@@ -1734,9 +1644,9 @@ int mlm_score_poses(mlm_handle *h, const double *pts_s, int n_pts, const double 
     if (classes && (rc = drain(h))) return rc;
     if (field_staged) { // the field crosses the link once, into a buffer of its own
         const size_t bytes = (size_t)nvox * sizeof(int32_t);
-        if ((rc = readout_reserve(h, h->d_score_field, h->score_field_bytes, bytes, "mlm_score_poses"))) return rc;
-        HIPCHK(h, hipMemcpyAsync(h->d_score_field, sqdist, bytes, hipMemcpyHostToDevice, h->stream));
-        F.sqdist = (const int32_t *)h->d_score_field;
+        if ((rc = readout_reserve(h, h->d_score_field, bytes, "mlm_score_poses"))) return rc;
+        HIPCHK(h, hipMemcpyAsync(h->d_score_field.p, sqdist, bytes, hipMemcpyHostToDevice, h->stream));
+        F.sqdist = (const int32_t *)h->d_score_field.p;
     }
     const int pose_chunk = std::min(n_poses, kScorePoseChunk);
     if ((rc = ch.reserve(h, "mlm_score_poses", {(size_t)n_pts, (size_t)pose_chunk, (size_t)pose_chunk}))) return rc;
@@ -1817,16 +1727,16 @@ int mlm_query_views(mlm_handle *h, const double *p0, const double *p1, const int
     // a host exclude / mark: the whole box once (mark with its contents: bytes no view touches stay as they were)
     const size_t box_bytes = mlm_align256((size_t)nvox);
     if ((ex_staged || mark_staged) &&
-        (rc = readout_reserve(h, h->d_win_stage, h->win_stage_bytes, box_bytes * ((ex_staged ? 1 : 0) + (mark_staged ? 1 : 0)), "mlm_query_views")))
+        (rc = readout_reserve(h, h->d_win_stage, box_bytes * ((ex_staged ? 1 : 0) + (mark_staged ? 1 : 0)), "mlm_query_views")))
         return rc;
     const uint8_t *d_exclude = exclude;
     uint8_t *d_mark = mark;
     if (ex_staged) {
-        d_exclude = (const uint8_t *)h->d_win_stage;
-        HIPCHK(h, hipMemcpyAsync(h->d_win_stage, exclude, (size_t)nvox, hipMemcpyHostToDevice, h->stream));
+        d_exclude = (const uint8_t *)h->d_win_stage.p;
+        HIPCHK(h, hipMemcpyAsync(h->d_win_stage.p, exclude, (size_t)nvox, hipMemcpyHostToDevice, h->stream));
     }
     if (mark_staged) {
-        d_mark = (uint8_t *)h->d_win_stage + (ex_staged ? box_bytes : 0);
+        d_mark = (uint8_t *)h->d_win_stage.p + (ex_staged ? box_bytes : 0);
         HIPCHK(h, hipMemcpyAsync(d_mark, mark, (size_t)nvox, hipMemcpyHostToDevice, h->stream));
     }
 
@@ -1844,12 +1754,12 @@ int mlm_query_views(mlm_handle *h, const double *p0, const double *p1, const int
         const double *ray[2] = {p0, p1};
         const size_t ray_bytes = mlm_align256((size_t)nr * 3 * sizeof(double));
         if (nr && (p_staged[0] || p_staged[1]) &&
-            (rc = readout_reserve(h, h->d_ray_stage, h->ray_stage_bytes, ray_bytes * ((p_staged[0] ? 1 : 0) + (p_staged[1] ? 1 : 0)), "mlm_query_views")))
+            (rc = readout_reserve(h, h->d_ray_stage, ray_bytes * ((p_staged[0] ? 1 : 0) + (p_staged[1] ? 1 : 0)), "mlm_query_views")))
             return rc;
         for (int c = 0; c < 2; ++c) {
             if (!nr) continue;
             if (p_staged[c]) {
-                double *at = (double *)((char *)h->d_ray_stage + (c && p_staged[0] ? ray_bytes : 0));
+                double *at = (double *)((char *)h->d_ray_stage.p + (c && p_staged[0] ? ray_bytes : 0));
                 HIPCHK(h, hipMemcpyAsync(at, ray[c] + 3 * (size_t)r0, (size_t)nr * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
                 ray[c] = at;
             } else {
@@ -1862,9 +1772,9 @@ int mlm_query_views(mlm_handle *h, const double *p0, const double *p1, const int
             for (long long i = begin[(size_t)k]; i < begin[(size_t)k + 1]; i += kViewBoxRays)
                 jobs.push_back(MlmViewJob{k, (int)i, (int)std::min(i + kViewBoxRays, begin[(size_t)k + 1]), 0, 1, 0, 0});
         const size_t raw_bytes = mlm_align256((size_t)nv * sizeof(MlmViewBox));
-        if ((rc = readout_reserve(h, h->d_views, h->views_bytes, raw_bytes + mlm_align256(jobs.size() * sizeof(MlmViewJob)), "mlm_query_views"))) return rc;
-        MlmViewBox *d_raw = (MlmViewBox *)h->d_views;
-        MlmViewJob *d_jobs = (MlmViewJob *)((char *)h->d_views + raw_bytes);
+        if ((rc = readout_reserve(h, h->d_views, raw_bytes + mlm_align256(jobs.size() * sizeof(MlmViewJob)), "mlm_query_views"))) return rc;
+        MlmViewBox *d_raw = (MlmViewBox *)h->d_views.p;
+        MlmViewJob *d_jobs = (MlmViewJob *)((char *)h->d_views.p + raw_bytes);
         hipLaunchKernelGGL(k_views_box_init, dim3((unsigned int)((nv + 255) / 256)), dim3(256), 0, h->stream, d_raw, nv);
         if (!jobs.empty()) {
             HIPCHK(h, hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * sizeof(MlmViewJob), hipMemcpyHostToDevice, h->stream));
@@ -1887,9 +1797,9 @@ int mlm_query_views(mlm_handle *h, const double *p0, const double *p1, const int
         jobs.insert(jobs.end(), plan.global.begin(), plan.global.end());
         const size_t jobs_bytes = mlm_align256(jobs.size() * sizeof(MlmViewJob)), ref_bytes = mlm_align256(plan.refused.size() * sizeof(int)),
                      rows_bytes = table_staged ? mlm_align256((size_t)nv * kViewRow * sizeof(int64_t)) : 0;
-        if ((rc = readout_reserve(h, h->d_views, h->views_bytes, raw_bytes + jobs_bytes + ref_bytes + rows_bytes + (size_t)plan.scratch_words * 4, "mlm_query_views")))
+        if ((rc = readout_reserve(h, h->d_views, raw_bytes + jobs_bytes + ref_bytes + rows_bytes + (size_t)plan.scratch_words * 4, "mlm_query_views")))
             return rc;
-        char *base = (char *)h->d_views;
+        char *base = (char *)h->d_views.p;
         d_raw = (MlmViewBox *)base;
         d_jobs = (MlmViewJob *)(base + raw_bytes);
         int *d_ref = (int *)(base + raw_bytes + jobs_bytes);
@@ -1960,8 +1870,7 @@ int mlm_export_frontier(mlm_handle *h, int cap, int32_t *keys_cell, int *n_out) 
     HIPCHK(h, hipMalloc((void **)&d_cnt, sizeof(unsigned int)));
     HIPCHK(h, hipMemsetAsync(d_cnt, 0, sizeof(unsigned int), h->stream));
     if (nb > 0)
-        hipLaunchKernelGGL(k_ex_export_frontier, dim3(512), dim3(MLM_BLOCK), 0, h->stream, h->P, (unsigned int)nb, d_out,
-                           (unsigned int)cap, d_cnt);
+        launch(h, k_ex_export_frontier, 512u, 0, h->P, (unsigned int)nb, d_out, (unsigned int)cap, d_cnt);
     unsigned int cnt = 0;
     hipError_t e = hipMemcpyAsync(&cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
@@ -1990,8 +1899,7 @@ static int export_points(mlm_handle *h, int cap_points, float *xyz, int *n_out, 
     hipError_t e = hipMalloc((void **)&d_cnt, sizeof(unsigned int));
     if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, sizeof(unsigned int), h->stream);
     if (e == hipSuccess && nb > 0)
-        hipLaunchKernelGGL(k_export_global, dim3(1024), dim3(MLM_BLOCK), 0, h->stream, h->P, (unsigned int)nb, d_xyz,
-                           (unsigned int)cap_points, d_cnt, which);
+        launch(h, k_export_global, 1024u, 0, h->P, (unsigned int)nb, d_xyz, (unsigned int)cap_points, d_cnt, which);
     unsigned int cnt = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
@@ -2035,10 +1943,10 @@ ImportStage import_stage(size_t N, size_t C) {
 // waits, and reports a pool that could not take them.  mlm_import_blocks, and the last step of mlm_warp_blocks' MLM_WARP_REPLACE.
 int import_staged(mlm_handle *h, char *d, const ImportStage &L, int n, bool log_odds, bool occ, bool infl, bool collapsed) {
     const size_t C = (size_t)h->P.cells, N = (size_t)n;
-    hipLaunchKernelGGL(k_import_slots, dim3(grid_for(N)), dim3(MLM_BLOCK), 0, h->stream, h->P, (const int32_t *)(d + L.o_keys), n, (int *)(d + L.o_slots));
-    hipLaunchKernelGGL(k_import_cells, dim3(std::min<unsigned int>(4096u, grid_for(N * C))), dim3(MLM_BLOCK), 0, h->stream, h->P,
-                       (const int *)(d + L.o_slots), n, log_odds ? (const float *)(d + L.o_lo) : nullptr, occ ? (const uint8_t *)(d + L.o_occ) : nullptr,
-                       infl ? (const uint8_t *)(d + L.o_infl) : nullptr, collapsed ? (const uint8_t *)(d + L.o_col) : nullptr);
+    launch(h, k_import_slots, grid_for(N), 0, h->P, (const int32_t *)(d + L.o_keys), n, (int *)(d + L.o_slots));
+    launch(h, k_import_cells, lanes_grid(N * C, 4096u), 0, h->P, (const int *)(d + L.o_slots), n, log_odds ? (const float *)(d + L.o_lo) : nullptr,
+           occ ? (const uint8_t *)(d + L.o_occ) : nullptr, infl ? (const uint8_t *)(d + L.o_infl) : nullptr,
+           collapsed ? (const uint8_t *)(d + L.o_col) : nullptr);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) {
@@ -2071,6 +1979,7 @@ int mlm_import_blocks(mlm_handle *h, int n, const int32_t *keys, const float *lo
     const ImportStage L = import_stage(N, C);
     char *d = nullptr;
     HIPCHK(h, hipMalloc((void **)&d, L.total));
+    DevTmp stage{d};
     hipError_t e = hipMemcpyAsync(d + L.o_keys, keys, N * 12, hipMemcpyDefault, h->stream);
     if (e == hipSuccess && log_odds) e = hipMemcpyAsync(d + L.o_lo, log_odds, N * C * 4, hipMemcpyDefault, h->stream);
     if (e == hipSuccess && occ) e = hipMemcpyAsync(d + L.o_occ, occ, N * C, hipMemcpyDefault, h->stream);
@@ -2078,20 +1987,16 @@ int mlm_import_blocks(mlm_handle *h, int n, const int32_t *keys, const float *lo
     if (e == hipSuccess && collapsed) e = hipMemcpyAsync(d + L.o_col, collapsed, N, hipMemcpyDefault, h->stream);
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(h->stream);
-        hipFree(d);
         h->err = std::string("mlm_import_blocks: ") + hipGetErrorString(e);
         return MLM_ERR_HIP;
     }
-    rc = import_staged(h, d, L, n, log_odds != nullptr, occ != nullptr, infl != nullptr, collapsed != nullptr);
-    hipFree(d);
-    return rc;
+    return import_staged(h, d, L, n, log_odds != nullptr, occ != nullptr, infl != nullptr, collapsed != nullptr);
 }
 
 namespace {
 static_assert(MLM_CROP_INSIDE == MLM_CROP_F_INSIDE && MLM_CROP_DRY == MLM_CROP_F_DRY && MLM_CROP_SHRINK == MLM_CROP_F_SHRINK && MLM_CROP_OUTSIDE == 0,
               "mlm_crop.h restates the flags of include/mlmap_hip.h");
-constexpr unsigned int kCropGrid = 8192;      // most workgroups of the crop kernels (they stride over the rest)
-constexpr size_t kCropStageBytes = 64u << 20; // staged rows of a page-out into host memory, per round
+constexpr unsigned int kCropGrid = 8192; // most workgroups of the crop kernels (they stride over the rest)
 
 // the copy kernel K<FW, BW> for the lane widths fw (16 or 4 bytes: float plane) and bw (16, 4 or 1 bytes: byte planes)
 #define MLM_CROP_LAUNCH(K, fw, bw, grid, ...)                                                                                     \
@@ -2152,21 +2057,20 @@ int crop_run(mlm_handle *h, const MlmCropBox &B, int flags, int cap, int32_t *ke
     if (nb) {
         // chunk counts | ctrl | list: 4 bytes per block, kept by the handle as the read-outs keep theirs
         const size_t o_ctrl = mlm_align256((size_t)chunks * 4), o_list = o_ctrl + 256, total = o_list + (size_t)nb * 4;
-        if ((rc = readout_reserve(h, h->d_crop, h->crop_bytes, total, "mlm_crop_blocks"))) {
+        if ((rc = readout_reserve(h, h->d_crop, total, "mlm_crop_blocks"))) {
             report();
             return rc;
         }
-        void *scratch = h->d_crop;
+        void *scratch = h->d_crop.p;
         chunk_cnt = (unsigned int *)scratch, ctrl = (unsigned int *)((char *)scratch + o_ctrl), list = (unsigned int *)((char *)scratch + o_list);
         const unsigned int grid = std::min(chunks, kCropGrid);
         HIPCHK(h, hipMemsetAsync(ctrl, 0, MLM_CROP_CTRL_WORDS * 4, h->stream));
-        hipLaunchKernelGGL(k_crop_count, dim3(grid), dim3(MLM_BLOCK), 0, h->stream, h->P, B, nb, chunks, chunk_cnt);
-        hipLaunchKernelGGL(k_crop_scan, dim3(1), dim3(MLM_BLOCK), 0, h->stream, chunk_cnt, chunks, ctrl);
-        hipLaunchKernelGGL(k_crop_list, dim3(grid), dim3(MLM_BLOCK), 0, h->stream, h->P, B, nb, chunks, chunk_cnt, ctrl, list);
+        launch(h, k_crop_count, grid, 0, h->P, B, nb, chunks, chunk_cnt);
+        launch(h, k_crop_scan, 1u, 0, chunk_cnt, chunks, ctrl);
+        launch(h, k_crop_list, grid, 0, h->P, B, nb, chunks, chunk_cnt, ctrl, list);
         HIPCHK(h, hipGetLastError());
-        unsigned int c[MLM_CROP_CTRL_WORDS] = {};
-        HIPCHK(h, hipMemcpyAsync(c, ctrl, sizeof(c), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
+        const unsigned int *c;
+        if ((rc = read_back(h, (const unsigned int *)ctrl, MLM_CROP_CTRL_WORDS, c))) return rc;
         D = c[0], H = c[1];
         if (D > nb || H > std::min(D, nb - D)) {
             h->err = "mlm_crop_blocks: the scan of the drop flags is inconsistent";
@@ -2187,29 +2091,20 @@ int crop_run(mlm_handle *h, const MlmCropBox &B, int flags, int cap, int32_t *ke
     const size_t C = (size_t)h->P.cells;
     const int fw = mlm_crop_float_width(h->P.cells), bw = mlm_crop_byte_width(h->P.cells);
     if (any_out) { // the page-out first: the holes are among its sources
-        ReadoutChannels<5> ch(h->d_win_stage, h->win_stage_bytes, {{keys, 3 * sizeof(int32_t)}, {log_odds, C * sizeof(float)}, {occ, C}, {infl, C}, {collapsed, 1}});
-        size_t per_row = 0;
-        for (int k = 0; k < 5; ++k) per_row += ch.staged[k] ? ch.elem[k] : 0;
-        size_t rows = !ch.any_staged ? (size_t)D : std::min<size_t>(D, std::max<size_t>(1, kCropStageBytes / per_row));
-        long long kv;
-        if (ch.any_staged && knob("crop_stage_rows", kv)) rows = std::min<size_t>(D, (size_t)kv); // (test knob: rounds of a few rows)
+        ReadoutChannels<5> ch(h->d_win_stage, {{keys, 3 * sizeof(int32_t)}, {log_odds, C * sizeof(float)}, {occ, C}, {infl, C}, {collapsed, 1}});
+        const size_t rows = page_rows(ch, D);
         if ((rc = ch.reserve(h, "mlm_crop_blocks", rows))) {
             report();
             return rc;
         }
-        for (size_t r0 = 0; r0 < D; r0 += rows) {
-            const size_t r1 = std::min<size_t>(D, r0 + rows);
+        rc = page_rounds(h, ch, D, rows, [&](size_t r0, size_t r1) {
             float *d_lo = (float *)ch.at(1, r0);
             uint8_t *d_occ = (uint8_t *)ch.at(2, r0), *d_infl = (uint8_t *)ch.at(3, r0);
             const int pfw = crop_width(fw, d_lo), pbw = std::min(crop_width(bw, d_occ), crop_width(bw, d_infl));
             MLM_CROP_LAUNCH(k_crop_page, pfw, pbw, wave_grid(r1 - r0, kCropGrid), h->P, (const unsigned int *)list, nb, (unsigned int)r0, (unsigned int)r1,
                             (int32_t *)ch.at(0, r0), d_lo, d_occ, d_infl, (uint8_t *)ch.at(4, r0));
-            HIPCHK(h, hipGetLastError());
-            if (ch.any_staged) {
-                if ((rc = ch.copy_out(h, 0, 5, r0, r1 - r0))) return rc;
-                HIPCHK(h, hipStreamSynchronize(h->stream)); // (the staging is reused by the next round)
-            }
-        }
+        });
+        if (rc) return rc;
         sum[3] = D;
     }
     // From here on the pool changes.  The host mirror maps pool slot s to its own slot s: it forgets which blocks it knows.
@@ -2226,7 +2121,7 @@ int crop_run(mlm_handle *h, const MlmCropBox &B, int flags, int cap, int32_t *ke
     HIPCHK(h, hipMemsetAsync(h->P.ht_keys, 0xFF, ht * sizeof(unsigned long long), h->stream));
     HIPCHK(h, hipMemsetAsync(h->P.ht_slot, 0xFF, ht * sizeof(int), h->stream));
     if (K) {
-        hipLaunchKernelGGL(k_rehash_blocks, dim3(grid_for(K)), dim3(MLM_BLOCK), 0, h->stream, h->P, K);
+        launch(h, k_rehash_blocks, grid_for(K), 0, h->P, K);
         HIPCHK(h, hipGetLastError());
     }
     MlmGlobal g = *h->h_g;
@@ -2284,8 +2179,7 @@ int mlm_merge_pack(mlm_handle *h, const int32_t *keys_dev, int n, float *log_odd
     HIPCHK(h, hipSetDevice(h->device));
     const int rc = drain(h);
     if (rc || n == 0) return rc;
-    hipLaunchKernelGGL(k_merge_pack, dim3(std::min<unsigned int>(8192u, grid_for((size_t)n * h->P.cells))), dim3(MLM_BLOCK), 0, h->stream,
-                       h->P, keys_dev, n, log_odds_dev, seen_dev);
+    launch(h, k_merge_pack, lanes_grid((size_t)n * h->P.cells, 8192u), 0, h->P, keys_dev, n, log_odds_dev, seen_dev);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MLM_OK;
@@ -2296,8 +2190,7 @@ int mlm_merge_finish(mlm_handle *h, float *log_odds_dev, const uint8_t *seen_dev
     MLM_LOCK(h);
     HIPCHK(h, hipSetDevice(h->device));
     if (n_cells == 0) return MLM_OK;
-    hipLaunchKernelGGL(k_merge_finish, dim3(std::min<unsigned int>(8192u, grid_for(n_cells))), dim3(MLM_BLOCK), 0, h->stream, h->P,
-                       log_odds_dev, seen_dev, n_cells, occ_dev);
+    launch(h, k_merge_finish, lanes_grid(n_cells, 8192u), 0, h->P, log_odds_dev, seen_dev, n_cells, occ_dev);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MLM_OK;
@@ -2326,7 +2219,7 @@ int mlm_query_odds_at(mlm_handle *h, const int32_t *glb_id, const int32_t *subbo
     int32_t *d_g = (int32_t *)h->d_qpos, *d_s = d_g + 3 * (size_t)n;
     HIPCHK(h, hipMemcpyAsync(d_g, glb_id, (size_t)n * 12, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(d_s, subbox_id, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_query_odds_at, dim3(grid_for((size_t)n)), dim3(MLM_BLOCK), 0, h->stream, h->P, d_g, d_s, n, (float *)h->d_qout);
+    launch(h, k_query_odds_at, grid_for((size_t)n), 0, h->P, d_g, d_s, n, (float *)h->d_qout);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(out, h->d_qout, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));

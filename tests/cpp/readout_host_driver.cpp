@@ -4,6 +4,9 @@
 //   readout_host_driver box LO0 LO1 LO2 D0 D1 D2 ...   rc D0 D1 D2 nvox  per case (D and nvox as the call left them; preset to -7)
 //   readout_host_driver layout N (PRESENT STAGED ELEM COUNT) x N ...   off[0] .. off[N - 1] total  per case
 //   readout_host_driver window                    D0 D1 D2 H grad staged  T0 T1 T2 (mlm_esdf_plan)  T0 T1 T2 (the rule below)
+//   readout_host_driver tiles (DIMS D0 D1 D2 T0 T1 T2) ...   the tiles of mlm_for_tiles and of the loops it replaced; tiles_stop: its early end
+//   readout_host_driver rows                      mlm_stage_rows against the three lines of crop_run it replaced
+// (MlmCtrlBlock's layout is checked by the static_assert beside it, which this translation unit compiles.)
 #include <climits>
 #include <cstdio>
 #include <cstdlib>
@@ -30,8 +33,72 @@ static void window_rule_before(const long long D[3], long long H, long long box_
     }
 }
 
+// the tile walk of mlm_export_window, mlm_export_esdf and esdf_tiles (and, with two loops, of mlm_export_grid2d) as each of them spelled
+// it out before mlm_for_tiles, kept here for the comparison alone
+template <class F> static void tiles_before(const long long D[3], const long long T[3], F fn) {
+    for (long long z0 = 0; z0 < D[2]; z0 += T[2])
+        for (long long y0 = 0; y0 < D[1]; y0 += T[1])
+            for (long long x0 = 0; x0 < D[0]; x0 += T[0]) {
+                const long long org[3] = {x0, y0, z0};
+                int td[3];
+                for (int a = 0; a < 3; ++a) td[a] = (int)std::min(T[a], D[a] - org[a]);
+                fn(org, td, (z0 * D[1] + y0) * D[0] + x0);
+            }
+}
+template <class F> static void tiles2d_before(const long long D[2], const long long T[2], F fn) {
+    for (long long y0 = 0; y0 < D[1]; y0 += T[1])
+        for (long long x0 = 0; x0 < D[0]; x0 += T[0]) {
+            const long long org[3] = {x0, y0, 0};
+            int td[3] = {0, 0, 1};
+            for (int a = 0; a < 2; ++a) td[a] = (int)std::min(T[a], D[a] - org[a]);
+            fn(org, td, y0 * D[0] + x0);
+        }
+}
+// the rows per round of crop_run's page-out as its three lines computed them before mlm_stage_rows (per_row > 0: something is staged)
+static size_t stage_rows_before(size_t D, size_t per_row, size_t cap_bytes, bool any_staged, bool knob_set, long long kv) {
+    size_t rows = !any_staged ? (size_t)D : std::min<size_t>(D, std::max<size_t>(1, cap_bytes / per_row));
+    if (any_staged && knob_set) rows = std::min<size_t>(D, (size_t)kv);
+    return rows;
+}
+
 int main(int argc, char **argv) {
     const char *mode = argc > 1 ? argv[1] : "";
+    if (!std::strcmp(mode, "tiles")) { // (DIMS D0 D1 D2 T0 T1 T2) ...: which (0: mlm_for_tiles, 1: before) case org[3] td[3] out_base per tile
+        for (int i = 2, k = 0; i + 6 < argc; i += 7, ++k) {
+            const int nd = std::atoi(argv[i]);
+            long long D[3], T[3];
+            for (int a = 0; a < 3; ++a) D[a] = std::atoll(argv[i + 1 + a]), T[a] = std::atoll(argv[i + 4 + a]);
+            auto row = [&](int which) {
+                return [k, which](const long long org[3], const int td[3], long long base) {
+                    std::printf("%d %d %lld %lld %lld %d %d %d %lld\n", which, k, org[0], org[1], org[2], td[0], td[1], td[2], base);
+                    return 0;
+                };
+            };
+            if (mlm_for_tiles(D, T, row(0))) return 3;
+            if (nd == 2)
+                tiles2d_before(D, T, row(1));
+            else
+                tiles_before(D, T, row(1));
+        }
+        return 0;
+    }
+    if (!std::strcmp(mode, "tiles_stop")) { // the walk ends at the first non-zero answer: calls made, value returned
+        const long long D[3] = {5, 3, 2}, T[3] = {2, 2, 1};
+        int calls = 0;
+        const int rc = mlm_for_tiles(D, T, [&](const long long *, const int *, long long) { return ++calls == 3 ? 7 : 0; });
+        std::printf("%d %d\n", calls, rc);
+        return 0;
+    }
+    if (!std::strcmp(mode, "rows")) { // n per_row cap knob  rows (mlm_stage_rows)  rows (before)
+        const size_t wide = 12 + 6 * 512;
+        for (size_t n : {(size_t)1, (size_t)2, (size_t)1000})
+            for (size_t per_row : {(size_t)0, (size_t)1, (size_t)12, wide})
+                for (size_t cap : {(size_t)1, per_row ? per_row - 1 : 0, per_row, (size_t)64 << 20})
+                    for (long long kv : {0ll, 1ll, (long long)n + 5}) // (0: the knob is not set)
+                        std::printf("%zu %zu %zu %lld %zu %zu\n", n, per_row, cap, kv, mlm_stage_rows(n, per_row, cap, kv),
+                                    stage_rows_before(n, per_row, cap, per_row != 0, kv != 0, kv));
+        return 0;
+    }
     if (!std::strcmp(mode, "cover")) {
         for (int n : {1, 2, 3, 4, 5, 8, 16}) {
             std::vector<long long> los;

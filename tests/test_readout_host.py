@@ -4,7 +4,9 @@
 * mlm_brick_cover against numpy.floor_divide, around zero and around the int32 edges;
 * mlm_box_check's three answers, in the order the entry points report them;
 * mlm_stage_layout for random subsets of the channels of the chunked queries: offsets, disjoint ranges, the closed formula;
-* mlm_export_window's tiles: mlm_esdf_plan(D, H + 1, false, ...) gives what the window's own rule gave before it.
+* mlm_export_window's tiles: mlm_esdf_plan(D, H + 1, false, ...) gives what the window's own rule gave before it;
+* mlm_for_tiles against the tile loops of window, esdf and grid2d as they were spelled out before it;
+* mlm_stage_rows against the three lines of mlm_crop_blocks' page-out that it replaced.
 """
 import os
 import re
@@ -148,6 +150,49 @@ def test_stage_layout_full_chunks(driver):
     assert r[-1] >= 82 * (1 << 18) and sum(BOXES) == 82
     r = driver("layout", *layout_args([1] * 6, [1] * 6, NEAREST, [near_chunk] * 6))[0]
     assert r[-1] >= 65 * (1 << 18) and sum(NEAREST) == 65
+
+
+def test_for_tiles_is_the_loops_it_replaced(driver):
+    """origins, extents and out_base of every tile, in order, against the transcribed z / y / x loops (and grid2d's y / x loops)"""
+    cases = [  # dims of the walk, D, T
+        (3, (1, 1, 1), (1, 1, 1)),
+        (3, (5, 3, 2), (2, 2, 1)),
+        (3, (5, 3, 2), (5, 3, 2)),  # a tile equal to the box
+        (3, (5, 3, 2), (8, 4, 64)),  # a tile larger than the box
+        (3, (7, 5, 3), (7, 2, 1)), (3, (7, 5, 3), (3, 1, 1)),  # mlm_esdf_plan's shapes: whole rows, a piece of a row
+        (2, (5, 3, 1), (2, 2, 1)),  # a plane, as mlm_export_grid2d walks it
+        (2, (9, 4, 1), (9, 3, 1)),
+    ]
+    rows = driver("tiles", *[v for nd, D, T in cases for v in (nd, *D, *T)])
+    new, old = rows[rows[:, 0] == 0][:, 1:], rows[rows[:, 0] == 1][:, 1:]
+    assert np.array_equal(new, old)
+    for k, (nd, D, T) in enumerate(cases):
+        t = new[new[:, 0] == k]
+        n_tiles = int(np.prod([-(-d // s) for d, s in zip(D, T)]))
+        assert len(t) == n_tiles, (D, T)
+        org, td, base = t[:, 1:4], t[:, 4:7], t[:, 7]
+        assert (td >= 1).all() and (org + td <= np.array(D)).all()
+        assert td.prod(axis=1).sum() == np.prod(D)  # the tiles cover the box once
+        assert np.array_equal(base, (org[:, 2] * D[1] + org[:, 1]) * D[0] + org[:, 0])
+        assert list(map(tuple, org[:, ::-1])) == sorted(map(tuple, org[:, ::-1]))  # z outermost, x innermost
+    assert driver("tiles_stop").tolist() == [[3, 7]]
+
+
+def test_stage_rows_is_crop_runs_rule(driver):
+    rows = driver("rows")
+    n, per_row, cap, kv, got, before = rows.T
+    wide = 12 + 6 * 512
+    assert set(n) == {1, 2, 1000} and set(per_row) == {0, 1, 12, wide} and set(kv) == {0, 1, 6, 7, 1005}
+    for p in (1, 12, wide):
+        assert {1, p - 1, p, 64 << 20} <= set(cap[per_row == p])
+    assert len(rows) == 3 * 4 * 4 * 3
+    assert np.array_equal(got, before)
+    assert ((got >= 1) & (got <= n)).all()
+    assert (got[per_row == 0] == n[per_row == 0]).all()  # nothing staged: one round, whatever the knob
+    staged = per_row > 0
+    assert (got[staged & (kv > 0)] == np.minimum(n, kv)[staged & (kv > 0)]).all()
+    free = staged & (kv == 0)
+    assert (got[free] == np.minimum(n, np.maximum(1, cap // np.maximum(per_row, 1)))[free]).all()
 
 
 def test_window_tiles_are_esdf_plan(driver):
