@@ -329,6 +329,15 @@ class mlmap {
         check(mlm_fuse_blocks(h_, n, keys, log_odds, occ, infl, mode, flags, per_row, summary), "mlm_fuse_blocks");
     }
 
+    // the map aged in place: the log-odds of the blocks of a key box (both NULL: of every block; MLM_AGE_OUTSIDE: of the blocks outside
+    // it) scaled (MLM_AGE_SCALE, amount in [0, 1]) or stepped towards zero (MLM_AGE_STEP), small evidence forgotten (MLM_AGE_FORGET,
+    // |log-odds| <= forget), the blocks left empty dropped (MLM_AGE_DROP), or — MLM_AGE_DRY — only counted (mlm_age_blocks; per_block
+    // [blocks before][MLM_AGE_COLS] host or device memory or NULL; summary host memory: [2] blocks dropped, [6] forgotten voxels)
+    void ageBlocks(const int32_t key_lo[3] = nullptr, const int32_t key_dims[3] = nullptr, int mode = MLM_AGE_SCALE, float amount = 1.0f,
+                   float forget = 0.0f, int flags = 0, int32_t *per_block = nullptr, int64_t summary[MLM_AGE_ROW] = nullptr) {
+        check(mlm_age_blocks(h_, key_lo, key_dims, mode, amount, forget, flags, per_block, summary), "mlm_age_blocks");
+    }
+
     // segment casts through the voxel map (mlm_query_rays; flags MLM_RAY_*; n x 3 end points; inputs and outputs host or device
     // memory, NULL output = skipped)
     void castRays(const double *p0, const double *p1, int n, int flags, int8_t *status, int32_t *voxel3 = nullptr, double *t = nullptr,

@@ -985,6 +985,52 @@ enum { MLM_FUSE_DRY = 1 };                                                      
 int mlm_fuse_blocks(mlm_handle *h, int n, const int32_t *keys, const float *log_odds, const uint8_t *occ,
                     const uint8_t *infl, int mode, int flags, int32_t *per_row, int64_t summary[MLM_FUSE_ROW]);
 
+/* Age the map, in place on the device: decay the log-odds of the selected blocks towards zero, optionally forget voxels whose evidence
+ * has become small, and optionally drop the blocks that are empty afterwards (no reference counterpart: the reference's
+ * observed_group_map only ever accumulates evidence).  One pass over the planes of the selected blocks: 6 bytes read and at most 6
+ * written per voxel, no sum over floats.
+ *   Selection.  key_lo / key_dims are mlm_crop_blocks' box of block keys, with its checks and error texts; both NULL selects every block
+ * (MLM_AGE_OUTSIDE or not).  A block is SELECTED iff its key lies inside the box — with MLM_AGE_OUTSIDE iff it lies outside it ("age
+ * everything but where the sensor is looking").  A voxel of a block that is not selected keeps all three planes bit for bit.
+ *   The rule per voxel (La, occ_a, infl_a) of a selected block (mlmapping_amd/csrc/mlm_age.h), IEEE single, nothing fused, subnormals
+ * kept; clamp is mlm_fuse_blocks' (a NaN becomes log_odds_min).  The voxel is AGED iff occ_a != 'u' or (bits(La) & 0x7fffffff) != 0: it
+ * holds a class or evidence (a hit below occupied_sh leaves occ 'u' with nonzero log-odds); allocate_ram's 0.0f / 'u' and a -0.0f are
+ * not aged and keep their bits.  For an aged voxel
+ *     MLM_AGE_SCALE: L = La * amount      MLM_AGE_STEP: L = La > amount ? La - amount : (La < -amount ? La + amount : 0.0f)
+ * (towards zero, never across it), then L = clamp(L).  With MLM_AGE_FORGET and fabsf(L) <= forget the voxel is FORGOTTEN: log-odds
+ * +0.0f, occ 'u'.  Otherwise, if occ_a != 'u', occ = L > occupied_sh ? 'o' : 'f' — mlm_fuse_blocks' and mlm_merge_finish's rule, not
+ * the integrate path's hysteresis — and if occ_a == 'u' occ stays 'u': evidence that never reached a class decays, aging never
+ * classifies.  Log-odds = L.  infl is untouched, except with MLM_AGE_CLEAR_INFL, which sets the infl of EVERY voxel of a selected block
+ * to 'u', aged or not (a halo whose obstacle was forgotten is stale; the caller runs mlm_inflate_map again afterwards).
+ *   Empty blocks.  A selected block is EMPTY afterwards iff every voxel of it has occ 'u', infl other than 'o' and (bits(L) &
+ * 0x7fffffff) == 0.  With MLM_AGE_DROP the empty selected blocks — those that were empty before the call included — are dropped exactly
+ * as mlm_crop_blocks drops blocks: its hole-filling rule over that drop set, so mlm_export_blocks' raw order afterwards is one answer
+ * whatever the schedule; hash table, block count, mlm_frame_stats.n_blocks and the host mirror follow; frame slots, graphs and
+ * container state survive as across a crop.  Nothing is paged out and no pool memory is given back: a caller who wants that calls
+ * mlm_crop_blocks (MLM_CROP_SHRINK) afterwards.
+ *   summary (host memory, may be NULL) — all counts, one value whatever the schedule: [0] blocks before, [1] selected blocks, [2] blocks
+ * dropped, [3] blocks afterwards, [4] aged voxels, [5] voxels whose log-odds bits changed, [6] forgotten voxels, of those [7] with class
+ * 'o' and [8] with class 'f' ([6] - [7] - [8]: evidence only), [9] voxels 'o' -> 'f', [10] voxels 'f' -> 'o' (a negative occupied_sh),
+ * [11] voxels whose infl went 'o' -> 'u'.
+ *   per_block [blocks before][MLM_AGE_COLS] (host or device memory, or NULL; host memory is staged), indexed by the OLD slot: [0] aged
+ * voxels, [1] forgotten voxels, [2] the block's share of [9] + [10], [3] 0 not selected, 1 selected and kept, 2 selected and dropped —
+ * with MLM_AGE_DRY or without MLM_AGE_DROP 2 reads "empty, would be dropped".
+ *   MLM_AGE_DRY fills summary and per_block as the call without it would and touches nothing: no plane, no pool, the host mirror stays
+ * valid.  Like mlm_import_blocks the call waits for everything submitted first.  MLM_ERR_INVALID (with a text in mlm_last_error): one of
+ * key_lo / key_dims NULL and the other not, mlm_crop_blocks' box errors, an unknown flag bit, a mode outside 0..1, a non-finite amount,
+ * MLM_AGE_SCALE with amount outside [0, 1], MLM_AGE_STEP with amount < 0, MLM_AGE_FORGET with a non-finite or negative forget (without
+ * the flag forget is ignored), a frontier-mode handle, dry or not (frontier, released and observed flags have no aged meaning:
+ * MLM_WARP_REPLACE's reason).  Zero blocks: MLM_OK, a zero summary.  Every check and every allocation — the handle's scratch (counted
+ * in device_bytes), the staging of a host per_block — come before the first write into the pool: a failing call leaves the map byte
+ * for byte as it was. */
+enum { MLM_AGE_SCALE = 0, MLM_AGE_STEP = 1 };                       /* mode */
+enum { MLM_AGE_OUTSIDE = 1, MLM_AGE_DRY = 2, MLM_AGE_FORGET = 4,
+       MLM_AGE_DROP = 8, MLM_AGE_CLEAR_INFL = 16 };                  /* flags */
+#define MLM_AGE_ROW 12   /* int64 in summary */
+#define MLM_AGE_COLS 4   /* int32 per block of per_block */
+int mlm_age_blocks(mlm_handle *h, const int32_t key_lo[3], const int32_t key_dims[3], int mode, float amount, float forget,
+                   int flags, int32_t *per_block, int64_t summary[MLM_AGE_ROW]);
+
 /* The two device-side steps of the optional global-map merge across GPUs (mlmapping_amd/merge.py; no reference
  * counterpart: SURVEY.md §8e).  All pointers are device memory; both calls return when the buffers are written.
  * pack:   row b of log_odds_dev / seen_dev [n*cells] = this map's cells of block keys_dev[3b..3b+2] (0 / 0 where the

@@ -210,6 +210,9 @@ struct mlm_handle : MlmHandlePlan { // (MlmHandlePlan, mlm_plan.h: the members m
     // mlm_fuse_blocks: per row its slot, flags and created slot, the packed keys (twice, for the sort) with the sort's values and
     // scratch, chunk counts, control words, the twelve sums and their partial rows: some 40 bytes per row and 96 KB
     KeptBuf d_fuse;
+    // mlm_age_blocks: per block its state and its place in the drop list, chunk counts, the twelve sums with the control words and
+    // their partial rows: 8 bytes per block and 200 KB
+    KeptBuf d_age;
     // the batched queries' staging: the host inputs / outputs of one chunk
     KeptBuf d_ray_stage;
     // mlm_query_views: per-view boxes, job lists, staged rows and the global path's bitsets of one chunk of views

@@ -52,6 +52,7 @@
 #include "mlm_kernels_crop.h"
 #include "mlm_kernels_warp.h"
 #include "mlm_kernels_fuse.h"
+#include "mlm_kernels_age.h"
 #include "mlm_host.h"
 #include "mlm_plan.h"
 #include "mlm_mapview.h"
@@ -2034,6 +2035,40 @@ int crop_reset_tail(mlm_handle *h, unsigned int K, unsigned int nb) {
     return MLM_OK;
 }
 
+// The tail of a call that drops blocks (mlm_crop_blocks, mlm_age_blocks with MLM_AGE_DROP), behind every check, count and allocation:
+// `list` is mlm_crop.h's list over the nb slots in use — the D dropped ones in front — and H the pairs of the move.  The pool is
+// compacted by hole filling, the free tail reset, the table rebuilt, the block count set on both sides; g is the global state afterwards.
+int crop_compact(mlm_handle *h, const unsigned int *list, unsigned int nb, unsigned int D, unsigned int K, unsigned int H, MlmGlobal &g) {
+    int rc;
+    const int fw = mlm_crop_float_width(h->P.cells), bw = mlm_crop_byte_width(h->P.cells);
+    // From here on the pool changes.  The host mirror maps pool slot s to its own slot s: it forgets which blocks it knows.
+    mirror_finish_eager(h);
+    if (h->mir.cap) h->mir.view.table_reset(h->mir.cap);
+    h->mir.n_known = 0;
+    mirror_mark_all(h);
+    if (H) {
+        MLM_CROP_LAUNCH(k_crop_move, fw, bw, wave_grid(H, kCropGrid), h->P, list, nb, D, K, H);
+        HIPCHK(h, hipGetLastError());
+    }
+    if ((rc = crop_reset_tail(h, K, nb))) return rc;
+    const size_t ht = (size_t)h->P.ht_mask + 1;
+    HIPCHK(h, hipMemsetAsync(h->P.ht_keys, 0xFF, ht * sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipMemsetAsync(h->P.ht_slot, 0xFF, ht * sizeof(int), h->stream));
+    if (K) {
+        launch(h, k_rehash_blocks, grid_for(K), 0, h->P, K);
+        HIPCHK(h, hipGetLastError());
+    }
+    g = *h->h_g;
+    g.n_blocks = K;
+    g.err &= ~1u;
+    HIPCHK(h, hipMemcpyAsync(h->P.g, &g, sizeof(g), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    *h->h_g = g;
+    for (int k = 0; k < MLM_SETS; ++k) *h->h_gb[k] = g;
+    h->stats.n_blocks = K;
+    return MLM_OK;
+}
+
 // everything of mlm_crop_blocks behind the argument check and the drain
 int crop_run(mlm_handle *h, const MlmCropBox &B, int flags, int cap, int32_t *keys, float *log_odds, uint8_t *occ, uint8_t *infl,
              uint8_t *collapsed, int64_t *summary) {
@@ -2107,31 +2142,8 @@ int crop_run(mlm_handle *h, const MlmCropBox &B, int flags, int cap, int32_t *ke
         if (rc) return rc;
         sum[3] = D;
     }
-    // From here on the pool changes.  The host mirror maps pool slot s to its own slot s: it forgets which blocks it knows.
-    mirror_finish_eager(h);
-    if (h->mir.cap) h->mir.view.table_reset(h->mir.cap);
-    h->mir.n_known = 0;
-    mirror_mark_all(h);
-    if (H) {
-        MLM_CROP_LAUNCH(k_crop_move, fw, bw, wave_grid(H, kCropGrid), h->P, (const unsigned int *)list, nb, D, K, H);
-        HIPCHK(h, hipGetLastError());
-    }
-    if ((rc = crop_reset_tail(h, K, nb))) return rc;
-    const size_t ht = (size_t)h->P.ht_mask + 1;
-    HIPCHK(h, hipMemsetAsync(h->P.ht_keys, 0xFF, ht * sizeof(unsigned long long), h->stream));
-    HIPCHK(h, hipMemsetAsync(h->P.ht_slot, 0xFF, ht * sizeof(int), h->stream));
-    if (K) {
-        launch(h, k_rehash_blocks, grid_for(K), 0, h->P, K);
-        HIPCHK(h, hipGetLastError());
-    }
-    MlmGlobal g = *h->h_g;
-    g.n_blocks = K;
-    g.err &= ~1u;
-    HIPCHK(h, hipMemcpyAsync(h->P.g, &g, sizeof(g), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    *h->h_g = g;
-    for (int k = 0; k < MLM_SETS; ++k) *h->h_gb[k] = g;
-    h->stats.n_blocks = K;
+    MlmGlobal g{};
+    if ((rc = crop_compact(h, (const unsigned int *)list, nb, D, K, H, g))) return rc;
     if ((flags & MLM_CROP_SHRINK) && h->pool_grow) { // best effort: the crop stands whether or not the smaller pool could be had
         const long long target = mlm_crop_shrink_target(h->lim.max_blocks, h->P.max_blocks, K);
         if (target > 0) {
@@ -2172,6 +2184,7 @@ int mlm_crop_blocks(mlm_handle *h, const int32_t key_lo[3], const int32_t key_di
 
 #include "mlm_warp_host.h"
 #include "mlm_fuse_host.h"
+#include "mlm_age_host.h"
 
 int mlm_merge_pack(mlm_handle *h, const int32_t *keys_dev, int n, float *log_odds_dev, uint8_t *seen_dev) {
     if (!h || n < 0 || (n > 0 && (!keys_dev || !log_odds_dev || !seen_dev))) return MLM_ERR_INVALID;

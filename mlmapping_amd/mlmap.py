@@ -49,6 +49,10 @@ MLM_WARP_SEEN, MLM_WARP_REPLACE, MLM_WARP_DRY, MLM_WARP_ROW = 1, 2, 4, 8
 # mlm_fuse_blocks modes and flag, int64 in summary, int32 per row of per_row
 MLM_FUSE_ADD, MLM_FUSE_MAX, MLM_FUSE_TAKE, MLM_FUSE_FILL, MLM_FUSE_DRY, MLM_FUSE_ROW, MLM_FUSE_COLS = 0, 1, 2, 3, 1, 12, 4
 FUSE_MODES = {"add": MLM_FUSE_ADD, "max": MLM_FUSE_MAX, "take": MLM_FUSE_TAKE, "fill": MLM_FUSE_FILL}
+# mlm_age_blocks modes and flags, int64 in summary, int32 per block of per_block
+MLM_AGE_SCALE, MLM_AGE_STEP, MLM_AGE_ROW, MLM_AGE_COLS = 0, 1, 12, 4
+MLM_AGE_OUTSIDE, MLM_AGE_DRY, MLM_AGE_FORGET, MLM_AGE_DROP, MLM_AGE_CLEAR_INFL = 1, 2, 4, 8, 16
+AGE_MODES = {"scale": MLM_AGE_SCALE, "step": MLM_AGE_STEP}
 # mlm_query_rays flags: what stops a ray (their union; 0: nothing, a pure count)
 MLM_RAY_OCC, MLM_RAY_INFL, MLM_RAY_UNKNOWN = 1, 2, 4
 # mlm_query_views: int64 per row of the table
@@ -65,7 +69,7 @@ ABI_SYMBOLS = [
     "mlm_integrate_depth_u16", "mlm_integrate_depth_u16_dev", "mlm_integrate_depth_batch_dev",
     "mlm_integrate_depth_batch", "mlm_integrate_callback",
     "mlm_integrate_points", "mlm_query_occupancy", "mlm_query_occupancy_inflate", "mlm_query_inflate_occupancy",
-    "mlm_query_odds", "mlm_query_odd_grad", "mlm_query_odds_at", "mlm_export_frontier_points", "mlm_import_blocks", "mlm_crop_blocks", "mlm_warp_blocks", "mlm_fuse_blocks",
+    "mlm_query_odds", "mlm_query_odd_grad", "mlm_query_odds_at", "mlm_export_frontier_points", "mlm_import_blocks", "mlm_crop_blocks", "mlm_warp_blocks", "mlm_fuse_blocks", "mlm_age_blocks",
     "mlm_merge_pack", "mlm_merge_finish",
     "mlm_set_free_in_bound", "mlm_inflate_map", "mlm_block_count",
     "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_grid2d", "mlm_export_reach", "mlm_export_route", "mlm_export_clusters", "mlm_export_mesh", "mlm_export_octree", "mlm_query_rays", "mlm_render_depth", "mlm_query_views", "mlm_query_boxes", "mlm_query_nearest", "mlm_query_sweeps", "mlm_query_paths", "mlm_score_poses", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
@@ -158,6 +162,7 @@ def load_library(path: Optional[str] = None):
     L.mlm_crop_blocks.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
     L.mlm_warp_blocks.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.mlm_fuse_blocks.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, vp, vp]
+    L.mlm_age_blocks.argtypes = [vp, vp, vp, i32, ctypes.c_float, ctypes.c_float, i32, vp, vp]
     L.mlm_merge_pack.argtypes = [vp, vp, i32, vp, vp]
     L.mlm_merge_finish.argtypes = [vp, vp, vp, ctypes.c_size_t, vp]
     L.mlm_set_free_in_bound.argtypes = [vp, vp, vp]
@@ -591,11 +596,55 @@ class MLMap:
     def retain_around(self, t_w, radius_m: float, shrink: bool = False, out=None) -> Dict[str, np.ndarray]:
         """Keep a rolling window: drop every block farther than radius_m from t_w on some axis — the kept key box is
         floor((t - r) / d_glb) - 1 .. floor((t + r) / d_glb) + 1 per axis (one block of margin).  See crop_blocks."""
+        lo, dims = self.retain_box(t_w, radius_m)
+        return self.crop_blocks(lo, dims, inside=False, shrink=shrink, out=out)
+
+    def retain_box(self, t_w, radius_m: float):
+        """retain_around's and age_outside's key box as (key_lo, key_dims): floor((t - r) / d_glb) - 1 .. floor((t + r) / d_glb) + 1."""
         t = _f64(t_w).reshape(3)
         d_glb = self.cfg.subbox_d_xyz * self.cfg.subbox_n  # (map_local.cpp:60, as mlm_create computes it)
         lo = np.floor((t - radius_m) / d_glb).astype(np.int64) - 1
         hi = np.floor((t + radius_m) / d_glb).astype(np.int64) + 1
-        return self.crop_blocks(lo, hi - lo + 1, inside=False, shrink=shrink, out=out)
+        return lo, hi - lo + 1
+
+    def age_blocks(self, key_lo=None, key_dims=None, mode="scale", amount: float = 1.0, forget: Optional[float] = None, outside: bool = False,
+                   drop: bool = False, clear_infl: bool = False, dry: bool = False, per_block=False) -> Dict[str, np.ndarray]:
+        """Age the map in place on the device (mlm_age_blocks): in the blocks whose key lies inside the box key_lo <= key < key_lo +
+        key_dims (outside=True: outside it; no box: in every block) every voxel that holds a class or evidence gets its log-odds scaled
+        by amount (mode "scale", amount in [0, 1]) or moved towards zero by amount (mode "step"), clamped, and its class set from
+        occupied_sh; with forget=x a voxel whose |log-odds| <= x afterwards goes back to unknown; clear_infl=True resets the inflation of
+        the selected blocks; drop=True drops the selected blocks that are empty afterwards, as crop_blocks drops blocks.  dry=True
+        changes nothing and only counts.  per_block=True: also "per_block", int32 [blocks before, 4] by old slot (aged, forgotten, class
+        changes, 0 not selected / 1 kept / 2 empty: dropped); per_block=<int>: a device pointer to that many rows, written in place.
+        Returns "summary": int64 [blocks before, selected, dropped, afterwards, aged voxels, log-odds changed, forgotten, forgotten
+        'o', forgotten 'f', 'o' -> 'f', 'f' -> 'o', infl cleared]."""
+        if (key_lo is None) != (key_dims is None):
+            raise MlmError("age_blocks: key_lo and key_dims go together")
+        if mode not in AGE_MODES:
+            raise MlmError(f"age_blocks: mode must be one of {sorted(AGE_MODES)}")
+        lo_a = None if key_lo is None else np.ascontiguousarray(key_lo, dtype=np.int32).reshape(3)
+        dims_a = None if key_dims is None else np.ascontiguousarray(key_dims, dtype=np.int32).reshape(3)
+        box = (None, None) if lo_a is None else (_p(lo_a), _p(dims_a))
+        flags = ((MLM_AGE_OUTSIDE if outside else 0) | (MLM_AGE_DRY if dry else 0) | (MLM_AGE_FORGET if forget is not None else 0) |
+                 (MLM_AGE_DROP if drop else 0) | (MLM_AGE_CLEAR_INFL if clear_infl else 0))
+        summary = np.zeros(MLM_AGE_ROW, dtype=np.int64)
+        rows, pb = None, None
+        if per_block is True:
+            rows = np.zeros((self.block_count(), MLM_AGE_COLS), dtype=np.int32)
+            pb = _p(rows)
+        elif per_block is not False and per_block is not None:
+            pb = ctypes.c_void_p(int(per_block))
+        if not dry:
+            self._merge_base = None  # (as import_blocks: the baseline of periodic merges no longer describes this map)
+        self._chk(self._L.mlm_age_blocks(self._h, *box, AGE_MODES[mode], float(amount), 0.0 if forget is None else float(forget), flags, pb, _p(summary)),
+                  "mlm_age_blocks")
+        return {"summary": summary, "per_block": rows}
+
+    def age_outside(self, t_w, radius_m: float, **kw) -> Dict[str, np.ndarray]:
+        """Age everything but where the sensor is looking: age_blocks(outside=True) with retain_around's key box for the same t_w and
+        radius_m.  See age_blocks for the other arguments."""
+        lo, dims = self.retain_box(t_w, radius_m)
+        return self.age_blocks(lo, dims, outside=True, **kw)
 
     def export_window(self, lo, dims, odds=True, occ=False, infl=False, grad=False, max_iter: int = 5) -> Dict[str, np.ndarray]:
         """Dense read-out of the voxel box lo <= v < lo + dims (voxel indices v = block key * subbox_n + cell coordinate, per axis
