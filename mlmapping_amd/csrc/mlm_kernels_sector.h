@@ -1077,17 +1077,33 @@ __device__ __forceinline__ void mlm_sector_column(const MlmDev &P, const MlmFram
     if ((int)threadIdx.x < n_run) s_run_off[threadIdx.x] = v[3];
     const uint32_t n_occ = tot[0], n_multi = tot[1], n_rays = P.visibility ? tot[2] : 0u;
     const uint32_t tot_refs = wtot[0], tot_subs = wtot[1];
-    if (threadIdx.x == 0) {
-        s_base[0] = n_occ ? g_atomic_add(&mlm_gp(P.ctr)->u_hit, n_occ) : 0u;
-        s_base[1] = n_multi ? g_atomic_add(&mlm_gp(P.ctr)->n_multi, n_multi) : 0u;
-        s_base[2] = tot_refs ? g_atomic_add(&mlm_gp(P.ctr)->n_refs, tot_refs) : 0u;
-        s_base[3] = tot_subs ? g_atomic_add(&mlm_gp(P.ctr)->n_contrib, tot_subs) : 0u;
+    if (threadIdx.x < 4u) {
+        // Lanes 0..3 of wave 0 take one list each — hits, ranked cells, references, contributions — and reserve together: ONE returning
+        // add with per-lane addresses (the four counters share a 64-byte line of MlmCounters), one trip to memory and one wait for
+        // the column.  A lane with nothing to reserve stays masked off.
+        static_assert(offsetof(MlmCounters, u_hit) < 64 && offsetof(MlmCounters, n_multi) < 64 && offsetof(MlmCounters, n_refs) < 64 &&
+                          offsetof(MlmCounters, n_contrib) < 64, "the column's four counters lie in one line");
+        const uint32_t k = threadIdx.x;
+        const uint32_t amount = k == 0u ? n_occ : k == 1u ? n_multi : k == 2u ? tot_refs : tot_subs;
+        // (the lane's capacity comes with a vector load of its own field of MlmDev, issued in front of the add: the one wait covers both.
+        // P.ctr is read here, behind the branch — a scalar-cache trip beside that load —: fetched in front of the scans it cost
+        // k_sector<false,256> its last registers, 12 bytes of scratch)
+        const uint32_t cap = *(const MLM_GLOBAL uint32_t *)((const MLM_GLOBAL char *)mlm_gp(&P) + (k == 0u   ? offsetof(MlmDev, hl_cap)
+                                                                                                  : k == 1u ? offsetof(MlmDev, mt_cap)
+                                                                                                  : k == 2u ? offsetof(MlmDev, refs_cap)
+                                                                                                            : offsetof(MlmDev, contrib_cap)));
+        const uint32_t word = (uint32_t)(k == 0u   ? offsetof(MlmCounters, u_hit)
+                                         : k == 1u ? offsetof(MlmCounters, n_multi)
+                                         : k == 2u ? offsetof(MlmCounters, n_refs)
+                                                   : offsetof(MlmCounters, n_contrib)) / 4u;
+        uint32_t base = 0u;
+        if (amount) base = g_atomic_add((MLM_GLOBAL uint32_t *)mlm_gp(P.ctr) + word, amount);
+        s_base[k] = base;
         // (a cell's segment start is kept in 16 bits, in units of MLM_SEC_REF_ALIGN references from the column's first)
-        if (tot_refs >= 65536u * MLM_SEC_REF_ALIGN) s_fail = 1;
+        if (k == 2u && amount >= 65536u * MLM_SEC_REF_ALIGN) s_fail = 1;
         // (the frame's lists are sized by need: a column that does not fit writes nothing — s_fail 2, the slots are enlarged and the
-        // frame's Stage A runs again)
-        if (s_base[0] + n_occ > P.hl_cap || s_base[1] + n_multi > P.mt_cap || s_base[2] + tot_refs > P.refs_cap || s_base[3] + tot_subs > P.contrib_cap)
-            s_fail = 2;
+        // frame's Stage A runs again; this store follows the one above in the wave's order: 2 wins, as before)
+        if (base + amount > cap) s_fail = 2;
     }
     __syncthreads(); // (the runs' offsets and the column's places in the frame's lists are visible)
     MLM_PHASE(2);
@@ -2229,6 +2245,33 @@ __device__ __forceinline__ void mlm_tile_one(const MlmDev &P, const MlmFrame &F,
     auto combo_of = [&](uint32_t vxy, uint32_t zz) { // index of the block of tile voxel (vxy, zz) among the blocks the tile overlaps
         return ((int)(s_ztab[zz] & 0xFFFFu) * ngy + (int)(s_xytab[edge + (vxy >> P.tile_sh)] & 0xFFFFu)) * ngx + (int)(s_xytab[vxy & (edge - 1u)] & 0xFFFFu);
     };
+    // ---- compaction: a thread's voxels are contiguous; touched voxels get consecutive records, voxels with several hits
+    //      consecutive room in vr_hit.  The counts depend on s_cnt alone, so the tile's two reservations are made HERE, in front of
+    //      the block phase, by lanes 0 and 1 in ONE returning add (mvox_cnt[0][0], mvox_cnt[1][0]); the trip to memory runs while the
+    //      block look-ups arrive and missing blocks are created, and its result is looked at behind that phase.  A lane with nothing
+    //      to reserve stays masked off.  (A tile that gives the frame up afterwards has bumped the counters — as a tile that found
+    //      s_fail set always had: such a frame's Stage A is run again from k_frame_prologue, which clears them.)
+    uint32_t a[4] = {0u, 0u, 0u, 0u}, t4[4];
+    for (uint32_t v = v_lo; v < v_hi; ++v) {
+        const uint32_t c = s_cnt[v];
+        if (c) {
+            ++a[0];
+            if ((c >> 16) >= 2u) a[1] += c >> 16;
+        }
+    }
+    mlm_block_excl_scan4<MLM_TILE_THREADS / 64>(a, s_w, t4);
+    const uint32_t my_amount = threadIdx.x == 0u ? t4[0] : threadIdx.x == 1u ? t4[1] : 0u; // (lanes 0 and 1 of wave 0)
+    if (threadIdx.x == 0) {
+        if (t4[0] > 0xFFFFu || t4[1] >= 0xFFFFu) s_fail = 1; // (the packed places hold 16 bits each)
+        s_base[2] = t4[0]; // (what lives across the block phase lives in LDS: the kernel has no registers to spare)
+        s_base[3] = t4[1];
+    }
+    // (this thread's first record and first place in vr_hit, 16 bits each unless s_fail is set, wait in the place word of its first
+    // voxel: nothing reads that word before the thread itself rewrites it below)
+    if (v_lo < v_hi) s_place[v_lo] = a[0] | (a[1] << 16);
+    uint32_t my_base = 0u;
+    if (my_amount) // mvox_cnt[threadIdx.x][0]
+        my_base = g_atomic_add((MLM_GLOBAL uint32_t *)mlm_gp(P.ctr) + (uint32_t)offsetof(MlmCounters, mvox_cnt) / 4u + 32u * threadIdx.x, my_amount);
     // ---- the blocks the frame touches in this tile exist before the frame is applied (allocate_ram, map_local.h:215-231: any
     //      hit or miss cell creates its block; creating it earlier than the reference would is invisible — it stays 0 / 'u' until
     //      the frame is applied).  A full pool flags the frame: k_apply_tiles stops in front of it, the host grows the pool and
@@ -2251,26 +2294,14 @@ __device__ __forceinline__ void mlm_tile_one(const MlmDev &P, const MlmFrame &F,
             s_slot[c] = sl;
             if (sl < 0) mlm_gp(P.ctr)->pool_short = 1u;
         }
-    __syncthreads();
     MLM_TPHASE(3); // touched blocks, creation of the missing ones
-    // ---- compaction: a thread's voxels are contiguous; touched voxels get consecutive records, voxels with several hits
-    //      consecutive room in vr_hit
-    uint32_t a[4] = {0u, 0u, 0u, 0u}, t4[4];
-    for (uint32_t v = v_lo; v < v_hi; ++v) {
-        const uint32_t c = s_cnt[v];
-        if (c) {
-            ++a[0];
-            if ((c >> 16) >= 2u) a[1] += c >> 16;
-        }
+    // ---- the tile's places in the frame's lists (reserved above)
+    if (threadIdx.x < 2u) {
+        s_base[threadIdx.x] = my_base;
+        // (lists sized by need: enlarged, then the frame's Stage A runs again; 2 wins over the 1 set above)
+        if (my_base + s_base[2u + threadIdx.x] > (threadIdx.x == 0u ? P.rec_cap : P.vh_cap)) s_fail = 2;
     }
-    mlm_block_excl_scan4<MLM_TILE_THREADS / 64>(a, s_w, t4);
-    if (threadIdx.x == 0) {
-        if (t4[0] > 0xFFFFu || t4[1] >= 0xFFFFu) s_fail = 1; // (the packed places hold 16 bits each)
-        s_base[0] = t4[0] ? g_atomic_add(&mlm_gp(P.ctr)->mvox_cnt[0][0], t4[0]) : 0u;
-        s_base[1] = t4[1] ? g_atomic_add(&mlm_gp(P.ctr)->mvox_cnt[1][0], t4[1]) : 0u;
-        if (s_base[0] + t4[0] > P.rec_cap || s_base[1] + t4[1] > P.vh_cap) s_fail = 2; // (lists sized by need: enlarged, then the frame's Stage A runs again)
-    }
-    __syncthreads();
+    __syncthreads(); // (the slots of the created blocks and the places are visible)
     if (s_fail) { // (uniform) the frame is redone
         if (threadIdx.x == 0) mlm_sector_fail(P, F, s_fail == 2u);
         return;
@@ -2279,9 +2310,10 @@ __device__ __forceinline__ void mlm_tile_one(const MlmDev &P, const MlmFrame &F,
     rec_base = s_base[0];
     hit_base = s_base[1];
     if (threadIdx.x == 0) // the tile's records of this frame, for the workgroup that applies the world tile (k_apply_tiles)
-        *(MLM_GLOBAL mlm_u32x4 *)(mlm_gp(P.tile_dir) + 4 * (size_t)tile) = mlm_u32x4{rec_base, t4[0], (uint32_t)F.seq, 0u};
+        *(MLM_GLOBAL mlm_u32x4 *)(mlm_gp(P.tile_dir) + 4 * (size_t)tile) = mlm_u32x4{rec_base, s_base[2], (uint32_t)F.seq, 0u};
     {
-        uint32_t o_rec = a[0], o_hit = a[1];
+        const uint32_t o_pack = v_lo < v_hi ? s_place[v_lo] : 0u;
+        uint32_t o_rec = o_pack & 0xFFFFu, o_hit = o_pack >> 16;
         uint32_t vxy = v_lo / lvz, zz = v_lo - vxy * lvz;
         for (uint32_t v = v_lo; v < v_hi; ++v) {
             const uint32_t c = s_cnt[v];
@@ -2314,7 +2346,9 @@ __device__ __forceinline__ void mlm_tile_one(const MlmDev &P, const MlmFrame &F,
 // candidates in one go (a frame reaches a fraction of its grid's tiles: most masks are empty) and works on the tiles that some
 // column announced itself to.  No list of touched tiles, no per-tile counter: the columns hand over with plain stores and one
 // fire-and-forget atomic each (k_sector).
-__global__ __launch_bounds__(MLM_TILE_THREADS) void k_tile(MLM_SLOT_ARGS) {
+// (7 waves per SIMD: what the kernel reached unasked before a tile's reservations moved in front of its block phase — asked for since,
+// the allocator otherwise parks the values that live across that phase in registers of their own, 85 in all, at 5 waves)
+__global__ __launch_bounds__(MLM_TILE_THREADS) __attribute__((amdgpu_waves_per_eu(7))) void k_tile(MLM_SLOT_ARGS) {
     MLM_SLOT_SETUP
     MLM_SPAN_BEGIN(1)
     __shared__ uint32_t s_cand[MLM_TILE_THREADS];

@@ -11,8 +11,8 @@ from mlmapping_amd import mlmap as mm
 from mlmapping_amd import synthetic as syn
 from mlmapping_amd.config import S1
 
-NAMES = ["0 parameters, count + first descriptors, LDS clear", "1 counting pass", "2 block lookups arrive", "3 touched blocks + creation",
-         "4 compaction scan + reservations", "5 records", "6 placing pass", "7 -"]
+NAMES = ["0 parameters, count + first descriptors, LDS clear", "1 counting pass", "2 block lookups arrive", "3 compaction scan, reservations issued, touched blocks + creation",
+         "4 reservations consumed (before r12a: compaction scan + reservations, phase 3 without them)", "5 records", "6 placing pass", "7 -"]
 L = mm.load_library(os.path.join(os.path.dirname(mm.LIB_PATH), "libmlmap_hip_prof.so"))
 L.mlm_debug_tile_phases.argtypes = [ctypes.c_void_p]
 mm._lib = L
