@@ -338,6 +338,18 @@ class mlmap {
         check(mlm_age_blocks(h_, key_lo, key_dims, mode, amount, forget, flags, per_block, summary), "mlm_age_blocks");
     }
 
+    // what changed since the digest table prev_keys / prev_digest of an earlier call (n_prev 0: everything is new): the new table, the
+    // changed and the new blocks of a key box (both NULL: of every block) in import's layout with their kind, and the keys that are
+    // gone (mlm_delta_blocks; every pointer host or device memory, outputs may be NULL; MLM_DELTA_DRY only counts; summary host memory:
+    // [1] table rows, [5] + [6] emitted blocks, [7] gone keys: size with a dry call first)
+    void deltaBlocks(const int32_t key_lo[3], const int32_t key_dims[3], int n_prev, const int32_t *prev_keys, const uint64_t *prev_digest, int flags,
+                     int cap_table, int32_t *cur_keys, uint64_t *cur_digest, int cap, int32_t *keys, float *log_odds, uint8_t *occ, uint8_t *infl,
+                     uint8_t *kind, int cap_gone, int32_t *gone_keys, int64_t summary[MLM_DELTA_ROW]) {
+        check(mlm_delta_blocks(h_, key_lo, key_dims, n_prev, prev_keys, prev_digest, flags, cap_table, cur_keys, cur_digest, cap, keys, log_odds, occ, infl, kind, cap_gone,
+                               gone_keys, summary),
+              "mlm_delta_blocks");
+    }
+
     // segment casts through the voxel map (mlm_query_rays; flags MLM_RAY_*; n x 3 end points; inputs and outputs host or device
     // memory, NULL output = skipped)
     void castRays(const double *p0, const double *p1, int n, int flags, int8_t *status, int32_t *voxel3 = nullptr, double *t = nullptr,

@@ -1031,6 +1031,52 @@ enum { MLM_AGE_OUTSIDE = 1, MLM_AGE_DRY = 2, MLM_AGE_FORGET = 4,
 int mlm_age_blocks(mlm_handle *h, const int32_t key_lo[3], const int32_t key_dims[3], int mode, float amount, float forget,
                    int flags, int32_t *per_block, int64_t summary[MLM_AGE_ROW]);
 
+/* Which blocks differ from the last time the caller looked: a digest of 16 bytes per block, and — against the digest table an earlier
+ * call wrote — the blocks whose content differs, the blocks that are new and the keys that are gone (no reference counterpart: the
+ * reference hands its whole map out every time).  The call only reads the map: frontier-mode handles are accepted, the host mirror
+ * stays valid.  One pass over the planes of the selected blocks: 6 bytes read per voxel.
+ *   Selection.  key_lo / key_dims are mlm_crop_blocks' box of block keys, with its checks and error texts; both NULL selects every
+ * block.  A block of the map is SELECTED iff its key lies inside the box.  Rows of the previous table outside the box are ignored:
+ * neither compared, nor reported gone, nor copied into the new table.
+ *   The view of a block: its `cells` triples (log-odds bits, occ, infl) as mlm_warp_blocks reads them — a released block of a
+ * frontier-mode handle answers from element 0 with infl 'u' in every cell; with MLM_DELTA_NO_INFL infl is 'u' everywhere.
+ *   The digest (mlmapping_amd/csrc/mlm_delta.h): two uint64 per block, arithmetic mod 2^64, over the cell index c = 0 .. cells - 1:
+ *     w_c  = bits(L_c) | (uint64)occ_c << 32 | (uint64)infl_c << 40
+ *     x_c  = w_c ^ ((c + 1) * 0x9E3779B97F4A7C15)
+ *     f(x) : x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31
+ *     d[0] = sum_c f(x_c)            d[1] = sum_c f(x_c ^ 0xD6E8FEB86659FD93)
+ * A sum of integers: one value whatever the schedule, no atomic and no float.  It is over the bits, so -0.0f and +0.0f differ.
+ * "Changed" means the 128 bits differ.  A changed block is missed with probability about 2^-128 per comparison.  The digest is not
+ * secure against someone constructing collisions.
+ *   The tables.  prev_keys [n_prev*3] and prev_digest [n_prev*2] are the table an earlier call wrote: keys strictly ascending by
+ * packed key (x, then y, then z, each biased by 2^20) and inside the 21-bit range; n_prev == 0 means "everything is new".  cur_keys
+ * [cap_table*3] and cur_digest [cap_table*2] receive the S selected blocks in the same ascending order: a valid prev of the next call.
+ *   The join.  A selected block is UNCHANGED (its key is in prev with an equal digest), CHANGED (in prev with a different digest) or
+ * NEW (not in prev).  A prev row inside the box whose key the map does not hold is GONE.
+ *   Emitted blocks: the CHANGED and the NEW ones together, ascending by packed key — keys [cap*3] and the view's planes log_odds / occ
+ * / infl [cap*cells] in the layout mlm_import_blocks takes (a released block expanded, infl 'u' throughout with MLM_DELTA_NO_INFL),
+ * kind [cap] 1 changed / 2 new.  gone_keys [cap_gone*3], ascending.  Every output pointer may be NULL; each input or output pointer
+ * on its own may be host memory or memory of this device (host memory is staged); summary is host memory.
+ *   summary — all counts: [0] blocks in the map, [1] selected S, [2] n_prev, [3] prev rows inside the box P, [4] unchanged, [5] changed
+ * C, [6] new N, [7] gone G, [8] blocks written, [9] table rows written, [10] gone keys written, [11] selected blocks that are empty by
+ * mlm_age_blocks' predicate on the planes as they are (is an MLM_AGE_DROP worth it?).  S = [4] + C + N and P = [4] + C + G.
+ *   MLM_DELTA_DRY fills summary and writes nothing else.  Like mlm_import_blocks the call waits for everything submitted first.
+ * MLM_ERR_INVALID (with a text in mlm_last_error; no output is written, summary included): mlm_crop_blocks' box errors, one of key_lo
+ * / key_dims NULL and the other not, an unknown flag bit, a negative cap or n_prev, n_prev > 0 with a NULL prev pointer, a prev key
+ * outside the 21-bit range, prev keys not strictly ascending (the last two are found on the device).  MLM_ERR_CAPACITY if a given
+ * output's cap is below its count (cap_table < S with cur_keys or cur_digest given, cap < C + N with a block output given, cap_gone
+ * < G with gone_keys given): nothing is written but summary, so the caller can size.  An empty map with no previous table: MLM_OK
+ * and a summary of counts only.  Scratch is kept by the handle and counted in device_bytes; every allocation comes before the first
+ * store to a caller's buffer. */
+enum { MLM_DELTA_DRY = 1,       /* count only: summary is filled, nothing else is written */
+       MLM_DELTA_NO_INFL = 2 }; /* infl reads as 'u' in the digest and is not emitted as a difference */
+#define MLM_DELTA_ROW 12
+int mlm_delta_blocks(mlm_handle *h, const int32_t key_lo[3], const int32_t key_dims[3],
+                     int n_prev, const int32_t *prev_keys, const uint64_t *prev_digest, int flags,
+                     int cap_table, int32_t *cur_keys, uint64_t *cur_digest,
+                     int cap, int32_t *keys, float *log_odds, uint8_t *occ, uint8_t *infl, uint8_t *kind,
+                     int cap_gone, int32_t *gone_keys, int64_t summary[MLM_DELTA_ROW]);
+
 /* The two device-side steps of the optional global-map merge across GPUs (mlmapping_amd/merge.py; no reference
  * counterpart: SURVEY.md §8e).  All pointers are device memory; both calls return when the buffers are written.
  * pack:   row b of log_odds_dev / seen_dev [n*cells] = this map's cells of block keys_dev[3b..3b+2] (0 / 0 where the

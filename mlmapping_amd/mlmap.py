@@ -53,6 +53,9 @@ FUSE_MODES = {"add": MLM_FUSE_ADD, "max": MLM_FUSE_MAX, "take": MLM_FUSE_TAKE, "
 MLM_AGE_SCALE, MLM_AGE_STEP, MLM_AGE_ROW, MLM_AGE_COLS = 0, 1, 12, 4
 MLM_AGE_OUTSIDE, MLM_AGE_DRY, MLM_AGE_FORGET, MLM_AGE_DROP, MLM_AGE_CLEAR_INFL = 1, 2, 4, 8, 16
 AGE_MODES = {"scale": MLM_AGE_SCALE, "step": MLM_AGE_STEP}
+# mlm_delta_blocks flags, int64 in summary, the values of its kind output
+MLM_DELTA_DRY, MLM_DELTA_NO_INFL, MLM_DELTA_ROW = 1, 2, 12
+MLM_DELTA_CHANGED, MLM_DELTA_NEW = 1, 2
 # mlm_query_rays flags: what stops a ray (their union; 0: nothing, a pure count)
 MLM_RAY_OCC, MLM_RAY_INFL, MLM_RAY_UNKNOWN = 1, 2, 4
 # mlm_query_views: int64 per row of the table
@@ -69,7 +72,7 @@ ABI_SYMBOLS = [
     "mlm_integrate_depth_u16", "mlm_integrate_depth_u16_dev", "mlm_integrate_depth_batch_dev",
     "mlm_integrate_depth_batch", "mlm_integrate_callback",
     "mlm_integrate_points", "mlm_query_occupancy", "mlm_query_occupancy_inflate", "mlm_query_inflate_occupancy",
-    "mlm_query_odds", "mlm_query_odd_grad", "mlm_query_odds_at", "mlm_export_frontier_points", "mlm_import_blocks", "mlm_crop_blocks", "mlm_warp_blocks", "mlm_fuse_blocks", "mlm_age_blocks",
+    "mlm_query_odds", "mlm_query_odd_grad", "mlm_query_odds_at", "mlm_export_frontier_points", "mlm_import_blocks", "mlm_crop_blocks", "mlm_warp_blocks", "mlm_fuse_blocks", "mlm_age_blocks", "mlm_delta_blocks",
     "mlm_merge_pack", "mlm_merge_finish",
     "mlm_set_free_in_bound", "mlm_inflate_map", "mlm_block_count",
     "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_grid2d", "mlm_export_reach", "mlm_export_route", "mlm_export_clusters", "mlm_export_mesh", "mlm_export_octree", "mlm_query_rays", "mlm_render_depth", "mlm_query_views", "mlm_query_boxes", "mlm_query_nearest", "mlm_query_sweeps", "mlm_query_paths", "mlm_score_poses", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
@@ -163,6 +166,7 @@ def load_library(path: Optional[str] = None):
     L.mlm_warp_blocks.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.mlm_fuse_blocks.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, vp, vp]
     L.mlm_age_blocks.argtypes = [vp, vp, vp, i32, ctypes.c_float, ctypes.c_float, i32, vp, vp]
+    L.mlm_delta_blocks.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp]
     L.mlm_merge_pack.argtypes = [vp, vp, i32, vp, vp]
     L.mlm_merge_finish.argtypes = [vp, vp, vp, ctypes.c_size_t, vp]
     L.mlm_set_free_in_bound.argtypes = [vp, vp, vp]
@@ -232,6 +236,16 @@ def debug_set(name: str, value: int):
 
 def debug_reset():
     load_library().mlm_debug_reset()
+
+
+class Delta:
+    """What MLMap.delta returns: `table` = (keys, digest) of the selected blocks, the next call's prev; the changed and new blocks
+    `keys`, `log_odds`, `occ`, `infl` with their `kind`; the `gone` keys; `summary`.  Everything but summary is None after a dry call."""
+    __slots__ = ("table", "keys", "log_odds", "occ", "infl", "kind", "gone", "summary")
+
+    def __init__(self, summary):
+        self.table = self.keys = self.log_odds = self.occ = self.infl = self.kind = self.gone = None
+        self.summary = summary
 
 
 class MLMap:
@@ -645,6 +659,78 @@ class MLMap:
         radius_m.  See age_blocks for the other arguments."""
         lo, dims = self.retain_box(t_w, radius_m)
         return self.age_blocks(lo, dims, outside=True, **kw)
+
+    def delta(self, prev=None, box=None, no_infl: bool = False, dry: bool = False, device: bool = False) -> "Delta":
+        """Which blocks differ from the last time the caller looked (mlm_delta_blocks).  prev: the `table` (keys int32 [n, 3], digest
+        uint64 [n, 2]) an earlier call returned, or that call's Delta, as numpy arrays or torch tensors on this handle's device; None:
+        everything is new.  box: (key_lo, key_dims) of block keys, None: every block.  no_infl=True: infl reads as 'u' and is never a
+        difference.  The outputs are sized by a dry call; dry=True stops there (only `summary` is filled).  Returns a Delta: `table` (the
+        next call's prev), the changed and new blocks `keys`, `log_odds`, `occ`, `infl` in import_blocks' layout with `kind` (1 changed, 2
+        new), the `gone` keys and `summary`: int64 [blocks, selected, n_prev, prev rows inside the box, unchanged, changed, new, gone,
+        blocks written, table rows written, gone keys written, empty selected blocks] — numpy arrays, or with device=True torch tensors
+        on this handle's device (digest as int64: the same bits)."""
+        if isinstance(prev, Delta):
+            prev = prev.table
+        hold = []
+
+        def ptr(a, dt):  # numpy array or torch tensor -> pointer
+            if hasattr(a, "data_ptr"):
+                t = a.contiguous()
+                hold.append(t)
+                return ctypes.c_void_p(t.data_ptr()) if t.numel() else None
+            arr = np.ascontiguousarray(a, dtype=dt)
+            hold.append(arr)
+            return _p(arr) if arr.size else None
+        n_prev, pk, pd = 0, None, None
+        if prev is not None:
+            n_prev = int(prev[0].shape[0]) if hasattr(prev[0], "shape") else len(prev[0])
+            if n_prev:
+                pk, pd = ptr(prev[0], np.int32), ptr(prev[1], np.uint64)
+        lo_a = dims_a = None
+        if box is not None:
+            lo_a = np.ascontiguousarray(box[0], dtype=np.int32).reshape(3)
+            dims_a = np.ascontiguousarray(box[1], dtype=np.int32).reshape(3)
+        bx = (None, None) if lo_a is None else (_p(lo_a), _p(dims_a))
+        flags = MLM_DELTA_NO_INFL if no_infl else 0
+        summary = np.zeros(MLM_DELTA_ROW, dtype=np.int64)
+        self._chk(self._L.mlm_delta_blocks(self._h, *bx, n_prev, pk, pd, flags | MLM_DELTA_DRY, 0, None, None, 0, None, None, None, None, None, 0, None, _p(summary)),
+                  "mlm_delta_blocks")
+        d = Delta(summary=summary)
+        if dry:
+            return d
+        S, E, G, C = int(summary[1]), int(summary[5] + summary[6]), int(summary[7]), self.cells
+        shapes = (("tk", (S, 3), np.int32), ("td", (S, 2), np.uint64), ("keys", (E, 3), np.int32), ("log_odds", (E, C), np.float32), ("occ", (E, C), np.uint8),
+                  ("infl", (E, C), np.uint8), ("kind", (E,), np.uint8), ("gone", (G, 3), np.int32))
+        if device:
+            import torch
+
+            dev = torch.device("cuda", self.device)
+            tt = {np.int32: torch.int32, np.uint64: torch.int64, np.float32: torch.float32, np.uint8: torch.uint8}
+            out = {k: torch.empty(shape, dtype=tt[dt], device=dev) for k, shape, dt in shapes}
+            torch.cuda.synchronize(dev)
+            p = {k: ctypes.c_void_p(v.data_ptr()) if v.numel() else None for k, v in out.items()}
+        else:
+            out = {k: np.empty(shape, dtype=dt) for k, shape, dt in shapes}
+            p = {k: _p(v) if v.size else None for k, v in out.items()}
+        self._chk(self._L.mlm_delta_blocks(self._h, *bx, n_prev, pk, pd, flags, S, p["tk"], p["td"], E, p["keys"], p["log_odds"], p["occ"], p["infl"], p["kind"],
+                                           G, p["gone"], _p(summary)), "mlm_delta_blocks")
+        d.table = (out["tk"], out["td"])
+        d.keys, d.log_odds, d.occ, d.infl, d.kind, d.gone = (out[k] for k in ("keys", "log_odds", "occ", "infl", "kind", "gone"))
+        return d
+
+    def apply_delta(self, d: "Delta"):
+        """Make this handle — a replica of the one d came from — follow: import_blocks of the emitted blocks (whole blocks are
+        overwritten or created), then one crop_blocks(inside=True) with a one-key box per gone key (a crop by key list is not built).
+        d's arrays may be numpy arrays or torch tensors on this handle's device."""
+        n = int(d.keys.shape[0])
+        if n:
+            if hasattr(d.keys, "data_ptr"):
+                self.import_blocks((d.keys.data_ptr(), n), d.log_odds.data_ptr(), d.occ.data_ptr(), d.infl.data_ptr())
+            else:
+                self.import_blocks(d.keys, d.log_odds, d.occ, d.infl)
+        gone = d.gone.cpu().numpy() if hasattr(d.gone, "cpu") else np.asarray(d.gone)
+        for k in gone.reshape(-1, 3):
+            self.crop_blocks(k, [1, 1, 1], inside=True)
 
     def export_window(self, lo, dims, odds=True, occ=False, infl=False, grad=False, max_iter: int = 5) -> Dict[str, np.ndarray]:
         """Dense read-out of the voxel box lo <= v < lo + dims (voxel indices v = block key * subbox_n + cell coordinate, per axis
