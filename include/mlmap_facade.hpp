@@ -350,6 +350,20 @@ class mlmap {
               "mlm_delta_blocks");
     }
 
+    // the lossless packed stream of the live map's blocks of a key box (keys NULL; both box pointers NULL: of every block), or of n rows
+    // of a dump (mlm_pack_blocks; MLM_PACK_DRY or a NULL stream only sizes: summary [1] is the stream's bytes; stream host memory or
+    // 8-byte-aligned device memory) ...
+    void packBlocks(const int32_t key_lo[3], const int32_t key_dims[3], int n, const int32_t *keys, const float *log_odds, const uint8_t *occ, const uint8_t *infl,
+                    int flags, size_t cap_bytes, void *stream, int64_t summary[MLM_PACK_ROW]) {
+        check(mlm_pack_blocks(h_, key_lo, key_dims, n, keys, log_odds, occ, infl, flags, cap_bytes, stream, summary), "mlm_pack_blocks");
+    }
+    // ... and a stream back into rows in import's layout (mlm_unpack_blocks; validated whole before the first store; all outputs NULL
+    // sizes: summary [0] is the blocks)
+    void unpackBlocks(const void *stream, size_t bytes, int flags, int cap, int32_t *keys, float *log_odds, uint8_t *occ, uint8_t *infl,
+                      int64_t summary[MLM_PACK_ROW]) {
+        check(mlm_unpack_blocks(h_, stream, bytes, flags, cap, keys, log_odds, occ, infl, summary), "mlm_unpack_blocks");
+    }
+
     // segment casts through the voxel map (mlm_query_rays; flags MLM_RAY_*; n x 3 end points; inputs and outputs host or device
     // memory, NULL output = skipped)
     void castRays(const double *p0, const double *p1, int n, int flags, int8_t *status, int32_t *voxel3 = nullptr, double *t = nullptr,

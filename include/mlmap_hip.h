@@ -1077,6 +1077,55 @@ int mlm_delta_blocks(mlm_handle *h, const int32_t key_lo[3], const int32_t key_d
                      int cap, int32_t *keys, float *log_odds, uint8_t *occ, uint8_t *infl, uint8_t *kind,
                      int cap_gone, int32_t *gone_keys, int64_t summary[MLM_DELTA_ROW]);
 
+/* A lossless packed block stream, and back (no reference counterpart).  The block dump costs 12 bytes of key and 6 bytes per voxel
+ * whatever a block holds; the stream uses what is regular in a map — occ and infl hold one of three bytes, unseen voxels are +0.0f,
+ * long-observed ones sit exactly on log_odds_min or log_odds_max — and nothing else: every bit comes back.  One byte string per input,
+ * whatever the schedule.  mlm_pack_blocks only reads the map: frontier-mode handles are accepted, the host mirror stays valid.
+ *   The stream, little endian.  C = subbox_n^3 cells per block, W = ceil(C / 64).  A PLANE is W uint64: bit i of word j belongs to cell
+ * 64 j + i, bits of cells >= C are zero.
+ *     header, 64 bytes:  0 "MLMPACK1" | 8 u32 C | 12 u32 subbox_n | 16 u32 n blocks | 20 u32 flags (bit 0: infl was left out) | 24 u32
+ *                        bits of (float)log_odds_min | 28 u32 bits of (float)log_odds_max | 32 u64 total bytes of the stream | 40 u64
+ *                        literals in the stream | 48..63 zero
+ *     directory, 16 bytes per block in row order: int32 key[3] | u32 offset of the block's record in 8-byte units from the start
+ *     records, back to back in row order behind the directory, each 8-byte aligned: u32 presence (bits 0..5) | u32 n_lit | the present
+ *                        planes in the order occ0 occ1 infl0 infl1 val0 val1 | n_lit uint32 literals | zero padding to 8 bytes
+ *   Codes per cell.  occ and infl: 'u' 0, 'f' 1, 'o' 2 — bit 0 in plane 0, bit 1 in plane 1; code 3 never occurs.  val, decided on the
+ * log-odds BITS in this order: 0 if they are zero, 1 if they equal the header's lo_min bits, 2 if they equal its lo_max bits, 3
+ * otherwise; a code-3 cell appends its 32 bits to the literals, in cell order (so -0.0f, NaNs and subnormals survive as bits).  The
+ * encoder writes a plane iff it has a set bit (the canonical stream); a blank block (+0.0f / 'u' / 'u' throughout) is 8 bytes of
+ * record and its directory row.
+ *   mlm_pack_blocks.  keys == NULL packs the live map: the blocks of the key box key_lo / key_dims (mlm_delta_blocks' box, with its
+ * checks and texts; both NULL: every block) in ascending packed-key order, each seen through mlm_delta_blocks' view (a released block
+ * of a frontier-mode handle expanded); n is ignored; the call waits for everything submitted first.  keys != NULL packs n rows of a
+ * dump in the layout mlm_import_blocks takes, in row order (the box must be NULL; infl == NULL reads as 'u'; each pointer on its own
+ * host memory or memory of this device).  MLM_PACK_NO_INFL: infl reads 'u', header flag bit 0 is set.  MLM_PACK_DRY, or a NULL stream:
+ * only the summary.  stream [cap_bytes] is host memory (staged) or 8-byte-aligned device memory.
+ *   summary: [0] blocks, [1] stream bytes, [2] raw bytes n (12 + 6 C), [3] blank blocks, [4] literals, [5] cells coded lo_min, [6]
+ * cells coded lo_max, [7] bytes written.
+ *   MLM_ERR_INVALID (a text in mlm_last_error, nothing written): the box errors, a box together with rows, a negative n, rows without
+ * log_odds or occ, an unknown flag, a misaligned device stream, an occ or infl byte outside 'u' 'f' 'o' (found on the device; the text
+ * names the row).  MLM_ERR_CAPACITY with the summary filled: cap_bytes below [1], or a stream beyond 2^32 - 1 eight-byte units.  Every
+ * check, the sizes, the prefix and every allocation come before the first store to stream.  Scratch is kept by the handle and counted
+ * in device_bytes.
+ *   mlm_unpack_blocks writes the rows mlm_import_blocks, mlm_fuse_blocks and mlm_warp_blocks' consumers take: keys [cap*3], log_odds
+ * / occ / infl [cap*cells], each NULL, host or device memory; all NULL only sizes (summary[0] blocks).  lo_min / lo_max come from
+ * the stream's header, not from the handle.  The whole stream is validated before the first store, no byte beyond `bytes` is read, and
+ * any byte content gets a verdict.  MLM_ERR_INVALID with the check's number in the text: 1 bytes below the header, 2 a wrong magic, 3
+ * C or subbox_n not the handle's, 4 the header's total above bytes (or below header + directory), 5 a directory offset that is not
+ * exactly the previous record's end (the first: (64 + 16 n) / 8), 6 presence >= 64, 7 a set bit for a cell >= C, 8 an occ or infl code
+ * 3, 9 n_lit other than the popcount of val0 & val1, 10 a record running past the total (or the last one ending short of it); 11 .. 14
+ * the arguments (a NULL stream, a flag — none is defined —, a negative cap, a misaligned device stream).  The verdict is the failure with
+ * the smallest (block, check).  MLM_ERR_CAPACITY if cap < n with an output given.  summary as above, [7] the bytes written to the
+ * outputs. */
+enum { MLM_PACK_DRY = 1,       /* size only: summary is filled, nothing else is written */
+       MLM_PACK_NO_INFL = 2 }; /* infl reads as 'u' and the header says so */
+#define MLM_PACK_ROW 8
+int mlm_pack_blocks(mlm_handle *h, const int32_t key_lo[3], const int32_t key_dims[3],
+                    int n, const int32_t *keys, const float *log_odds, const uint8_t *occ, const uint8_t *infl,
+                    int flags, size_t cap_bytes, void *stream, int64_t summary[MLM_PACK_ROW]);
+int mlm_unpack_blocks(mlm_handle *h, const void *stream, size_t bytes, int flags, int cap,
+                      int32_t *keys, float *log_odds, uint8_t *occ, uint8_t *infl, int64_t summary[MLM_PACK_ROW]);
+
 /* The two device-side steps of the optional global-map merge across GPUs (mlmapping_amd/merge.py; no reference
  * counterpart: SURVEY.md §8e).  All pointers are device memory; both calls return when the buffers are written.
  * pack:   row b of log_odds_dev / seen_dev [n*cells] = this map's cells of block keys_dev[3b..3b+2] (0 / 0 where the

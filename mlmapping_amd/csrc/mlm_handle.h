@@ -19,7 +19,7 @@ struct KernelTime {
 // Process-wide, not part of the drop-in contract; the library reads no environment variable for them (only the three diagnostic
 // switches MLM_DEBUG_CREATE / MLM_DEBUG_ALLOC / MLM_DEBUG_DRAIN, which print).
 const char *const kKnobNames[] = {"agg_lds", "big_arm", "big_grid", "bin_block", "chain_grid", "cluster_tile", "collect_grid", "crop_stage_rows", "cu_reserve", "cu_split", "delta_grid",
-                                  "esdf_tile_vox", "ex_spec", "expand_block", "graph", "grid_tile", "hit_tab_n", "logit_exact", "mesh_stage_rows", "mirror", "mirror_max", "mirror_mb", "need_slots", "node_lds", "pool_grow",
+                                  "esdf_tile_vox", "ex_spec", "expand_block", "graph", "grid_tile", "hit_tab_n", "logit_exact", "mesh_stage_rows", "mirror", "mirror_max", "mirror_mb", "need_slots", "node_lds", "pack_grid", "pool_grow",
                                   "rank_grid", "rays_grid", "reach_group", "reach_tile", "render_tile", "route_group", "route_tile", "sc_block", "sc_grid", "score_chunk", "sec_backoff", "sec_fail_every", "sec_tab", "sec_tab_big", "sec_threads",
                                   "sectors", "single_apply_grid", "single_chain_grid", "single_rank_grid", "slot_sets", "sort_block", "sort_grid", "tile_grid", "tile_sh", "view_lds_bits"};
 struct KnobStore {
@@ -38,7 +38,7 @@ bool knob_value_ok(const char *name, long long v) {
     auto is = [&](const char *k) { return strcmp(name, k) == 0; };
     if (is("expand_block") || is("sort_block") || is("sc_block")) return v >= 64 && v <= 256 && v % 64 == 0;
     if (is("bin_block")) return v == 256 || v == 512 || v == 1024;
-    if (is("big_grid") || is("chain_grid") || is("collect_grid") || is("rank_grid") || is("rays_grid") || is("sc_grid") || is("single_apply_grid") || is("delta_grid") ||
+    if (is("big_grid") || is("chain_grid") || is("collect_grid") || is("rank_grid") || is("rays_grid") || is("sc_grid") || is("single_apply_grid") || is("delta_grid") || is("pack_grid") ||
         is("single_chain_grid") || is("single_rank_grid") || is("sort_grid") || is("tile_grid"))
         return v >= 1 && v <= (1ll << 20);
     if (is("cu_split") || is("cu_reserve")) return v >= 0 && v <= 0x7FFFFFFFll;
@@ -216,6 +216,9 @@ struct mlm_handle : MlmHandlePlan { // (MlmHandlePlan, mlm_plan.h: the members m
     // mlm_delta_blocks: per block its packed key and slot (twice, for the sort), its digest, its kind and its place in the emitted
     // list, per previous row its state and its place in the gone list, chunk counts, sums and the sort's scratch: some 50 bytes per block
     KeptBuf d_delta;
+    // mlm_pack_blocks / mlm_unpack_blocks: per row its size, counts, presence and verdict (32 bytes), its offset, the chunk sums and the
+    // totals; for the live-map source the packed keys and slots (twice, for the sort) and the sort's scratch: some 70 bytes per block
+    KeptBuf d_pack;
     // the batched queries' staging: the host inputs / outputs of one chunk
     KeptBuf d_ray_stage;
     // mlm_query_views: per-view boxes, job lists, staged rows and the global path's bitsets of one chunk of views

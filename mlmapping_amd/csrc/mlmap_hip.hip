@@ -54,6 +54,7 @@
 #include "mlm_kernels_fuse.h"
 #include "mlm_kernels_age.h"
 #include "mlm_kernels_delta.h"
+#include "mlm_kernels_pack.h"
 #include "mlm_host.h"
 #include "mlm_plan.h"
 #include "mlm_mapview.h"
@@ -2187,6 +2188,7 @@ int mlm_crop_blocks(mlm_handle *h, const int32_t key_lo[3], const int32_t key_di
 #include "mlm_fuse_host.h"
 #include "mlm_age_host.h"
 #include "mlm_delta_host.h"
+#include "mlm_pack_host.h"
 
 int mlm_merge_pack(mlm_handle *h, const int32_t *keys_dev, int n, float *log_odds_dev, uint8_t *seen_dev) {
     if (!h || n < 0 || (n > 0 && (!keys_dev || !log_odds_dev || !seen_dev))) return MLM_ERR_INVALID;

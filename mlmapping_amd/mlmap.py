@@ -56,6 +56,8 @@ AGE_MODES = {"scale": MLM_AGE_SCALE, "step": MLM_AGE_STEP}
 # mlm_delta_blocks flags, int64 in summary, the values of its kind output
 MLM_DELTA_DRY, MLM_DELTA_NO_INFL, MLM_DELTA_ROW = 1, 2, 12
 MLM_DELTA_CHANGED, MLM_DELTA_NEW = 1, 2
+# mlm_pack_blocks flags, int64 in the summary of mlm_pack_blocks and mlm_unpack_blocks
+MLM_PACK_DRY, MLM_PACK_NO_INFL, MLM_PACK_ROW = 1, 2, 8
 # mlm_query_rays flags: what stops a ray (their union; 0: nothing, a pure count)
 MLM_RAY_OCC, MLM_RAY_INFL, MLM_RAY_UNKNOWN = 1, 2, 4
 # mlm_query_views: int64 per row of the table
@@ -73,7 +75,7 @@ ABI_SYMBOLS = [
     "mlm_integrate_depth_batch", "mlm_integrate_callback",
     "mlm_integrate_points", "mlm_query_occupancy", "mlm_query_occupancy_inflate", "mlm_query_inflate_occupancy",
     "mlm_query_odds", "mlm_query_odd_grad", "mlm_query_odds_at", "mlm_export_frontier_points", "mlm_import_blocks", "mlm_crop_blocks", "mlm_warp_blocks", "mlm_fuse_blocks", "mlm_age_blocks", "mlm_delta_blocks",
-    "mlm_merge_pack", "mlm_merge_finish",
+    "mlm_pack_blocks", "mlm_unpack_blocks", "mlm_merge_pack", "mlm_merge_finish",
     "mlm_set_free_in_bound", "mlm_inflate_map", "mlm_block_count",
     "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_grid2d", "mlm_export_reach", "mlm_export_route", "mlm_export_clusters", "mlm_export_mesh", "mlm_export_octree", "mlm_query_rays", "mlm_render_depth", "mlm_query_views", "mlm_query_boxes", "mlm_query_nearest", "mlm_query_sweeps", "mlm_query_paths", "mlm_score_poses", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
     "mlm_get_awareness_hits",
@@ -167,6 +169,8 @@ def load_library(path: Optional[str] = None):
     L.mlm_fuse_blocks.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, vp, vp]
     L.mlm_age_blocks.argtypes = [vp, vp, vp, i32, ctypes.c_float, ctypes.c_float, i32, vp, vp]
     L.mlm_delta_blocks.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp]
+    L.mlm_pack_blocks.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, i32, ctypes.c_size_t, vp, vp]
+    L.mlm_unpack_blocks.argtypes = [vp, vp, ctypes.c_size_t, i32, i32, vp, vp, vp, vp, vp]
     L.mlm_merge_pack.argtypes = [vp, vp, i32, vp, vp]
     L.mlm_merge_finish.argtypes = [vp, vp, vp, ctypes.c_size_t, vp]
     L.mlm_set_free_in_bound.argtypes = [vp, vp, vp]
@@ -240,11 +244,13 @@ def debug_reset():
 
 class Delta:
     """What MLMap.delta returns: `table` = (keys, digest) of the selected blocks, the next call's prev; the changed and new blocks
-    `keys`, `log_odds`, `occ`, `infl` with their `kind`; the `gone` keys; `summary`.  Everything but summary is None after a dry call."""
-    __slots__ = ("table", "keys", "log_odds", "occ", "infl", "kind", "gone", "summary")
+    `keys`, `log_odds`, `occ`, `infl` with their `kind`; the `gone` keys; `summary`.  Everything but summary is None after a dry call.
+    With packed=True `stream` holds the emitted blocks as a packed stream (MLMap.pack), and without device=True the four planes stay
+    None: the stream carries them."""
+    __slots__ = ("table", "keys", "log_odds", "occ", "infl", "kind", "gone", "summary", "stream")
 
     def __init__(self, summary):
-        self.table = self.keys = self.log_odds = self.occ = self.infl = self.kind = self.gone = None
+        self.table = self.keys = self.log_odds = self.occ = self.infl = self.kind = self.gone = self.stream = None
         self.summary = summary
 
 
@@ -660,7 +666,7 @@ class MLMap:
         lo, dims = self.retain_box(t_w, radius_m)
         return self.age_blocks(lo, dims, outside=True, **kw)
 
-    def delta(self, prev=None, box=None, no_infl: bool = False, dry: bool = False, device: bool = False) -> "Delta":
+    def delta(self, prev=None, box=None, no_infl: bool = False, dry: bool = False, device: bool = False, packed: bool = False) -> "Delta":
         """Which blocks differ from the last time the caller looked (mlm_delta_blocks).  prev: the `table` (keys int32 [n, 3], digest
         uint64 [n, 2]) an earlier call returned, or that call's Delta, as numpy arrays or torch tensors on this handle's device; None:
         everything is new.  box: (key_lo, key_dims) of block keys, None: every block.  no_infl=True: infl reads as 'u' and is never a
@@ -668,7 +674,9 @@ class MLMap:
         next call's prev), the changed and new blocks `keys`, `log_odds`, `occ`, `infl` in import_blocks' layout with `kind` (1 changed, 2
         new), the `gone` keys and `summary`: int64 [blocks, selected, n_prev, prev rows inside the box, unchanged, changed, new, gone,
         blocks written, table rows written, gone keys written, empty selected blocks] — numpy arrays, or with device=True torch tensors
-        on this handle's device (digest as int64: the same bits)."""
+        on this handle's device (digest as int64: the same bits).  packed=True: the emitted blocks go into device tensors and from there
+        into `stream`, a packed stream (pack; a numpy uint8 array, or with device=True a device tensor); without device=True `keys`,
+        `log_odds`, `occ`, `infl` stay None (apply_delta takes the stream)."""
         if isinstance(prev, Delta):
             prev = prev.table
         hold = []
@@ -701,27 +709,41 @@ class MLMap:
         S, E, G, C = int(summary[1]), int(summary[5] + summary[6]), int(summary[7]), self.cells
         shapes = (("tk", (S, 3), np.int32), ("td", (S, 2), np.uint64), ("keys", (E, 3), np.int32), ("log_odds", (E, C), np.float32), ("occ", (E, C), np.uint8),
                   ("infl", (E, C), np.uint8), ("kind", (E,), np.uint8), ("gone", (G, 3), np.int32))
-        if device:
+        on_dev = {k for k, _, _ in shapes} if device else {"keys", "log_odds", "occ", "infl"} if packed else set()
+        out = {k: np.empty(shape, dtype=dt) for k, shape, dt in shapes if k not in on_dev}
+        p = {k: _p(v) if v.size else None for k, v in out.items()}
+        if on_dev:
             import torch
 
             dev = torch.device("cuda", self.device)
             tt = {np.int32: torch.int32, np.uint64: torch.int64, np.float32: torch.float32, np.uint8: torch.uint8}
-            out = {k: torch.empty(shape, dtype=tt[dt], device=dev) for k, shape, dt in shapes}
+            out.update({k: torch.empty(shape, dtype=tt[dt], device=dev) for k, shape, dt in shapes if k in on_dev})
             torch.cuda.synchronize(dev)
-            p = {k: ctypes.c_void_p(v.data_ptr()) if v.numel() else None for k, v in out.items()}
-        else:
-            out = {k: np.empty(shape, dtype=dt) for k, shape, dt in shapes}
-            p = {k: _p(v) if v.size else None for k, v in out.items()}
+            p.update({k: ctypes.c_void_p(out[k].data_ptr()) if out[k].numel() else None for k in on_dev})
         self._chk(self._L.mlm_delta_blocks(self._h, *bx, n_prev, pk, pd, flags, S, p["tk"], p["td"], E, p["keys"], p["log_odds"], p["occ"], p["infl"], p["kind"],
                                            G, p["gone"], _p(summary)), "mlm_delta_blocks")
         d.table = (out["tk"], out["td"])
         d.keys, d.log_odds, d.occ, d.infl, d.kind, d.gone = (out[k] for k in ("keys", "log_odds", "occ", "infl", "kind", "gone"))
+        if packed:
+            d.stream = self.pack(rows=(d.keys, d.log_odds, d.occ, d.infl), no_infl=no_infl, device=device)
+            if not device:
+                d.keys = d.log_odds = d.occ = d.infl = None
         return d
 
     def apply_delta(self, d: "Delta"):
         """Make this handle — a replica of the one d came from — follow: import_blocks of the emitted blocks (whole blocks are
         overwritten or created), then one crop_blocks(inside=True) with a one-key box per gone key (a crop by key list is not built).
-        d's arrays may be numpy arrays or torch tensors on this handle's device."""
+        d's arrays may be numpy arrays or torch tensors on this handle's device; a Delta that carries only `stream` (delta(packed=True))
+        is unpacked into device tensors first."""
+        if d.keys is None and d.stream is not None:
+            rows = self.unpack(d.stream, device=True)
+            n = int(rows["keys"].shape[0])
+            if n:
+                self.import_blocks((rows["keys"].data_ptr(), n), rows["log_odds"].data_ptr(), rows["occ"].data_ptr(), rows["infl"].data_ptr())
+            gone = d.gone.cpu().numpy() if hasattr(d.gone, "cpu") else np.asarray(d.gone)
+            for k in gone.reshape(-1, 3):
+                self.crop_blocks(k, [1, 1, 1], inside=True)
+            return
         n = int(d.keys.shape[0])
         if n:
             if hasattr(d.keys, "data_ptr"):
@@ -731,6 +753,112 @@ class MLMap:
         gone = d.gone.cpu().numpy() if hasattr(d.gone, "cpu") else np.asarray(d.gone)
         for k in gone.reshape(-1, 3):
             self.crop_blocks(k, [1, 1, 1], inside=True)
+
+    def pack(self, box=None, rows=None, no_infl: bool = False, device: bool = False):
+        """The lossless packed stream (mlm_pack_blocks; the format: include/mlmap_hip.h) of the live map's blocks — of the key box
+        box = (key_lo, key_dims), None: of every block, ascending by key — or of rows = (keys, log_odds, occ, infl) of a dump in
+        import_blocks' layout, in their order (numpy arrays or torch tensors on this handle's device; infl may be None).  no_infl=True:
+        infl reads 'u'.  Sized by a dry call; returns a numpy uint8 array, or with device=True a torch uint8 tensor on this handle's
+        device.  `pack_summary` holds the last call's summary: int64 [blocks, stream bytes, raw bytes, blank blocks, literals, cells on
+        log_odds_min, cells on log_odds_max, bytes written]."""
+        hold = []
+
+        def ptr(a, dt):
+            if a is None:
+                return None
+            if hasattr(a, "data_ptr"):
+                t = a.contiguous()
+                hold.append(t)
+                return ctypes.c_void_p(t.data_ptr()) if t.numel() else None
+            arr = np.ascontiguousarray(a, dtype=dt)
+            hold.append(arr)
+            return _p(arr) if arr.size else None
+        bx, n, src = (None, None), 0, (None, None, None, None)
+        if rows is not None:
+            if box is not None:
+                raise MlmError("pack: a box selects blocks of the live map, it does not go with rows")
+            n = int(rows[0].shape[0])
+            one = np.zeros(3, dtype=np.int32)  # (zero rows: still the rows source, so a pointer that is not NULL)
+            hold.append(one)
+            src = tuple(ptr(a, dt) for a, dt in zip(rows, (np.int32, np.float32, np.uint8, np.uint8)))
+            if n == 0:
+                src = (_p(one), None, None, None)
+        elif box is not None:
+            lo_a = np.ascontiguousarray(box[0], dtype=np.int32).reshape(3)
+            dims_a = np.ascontiguousarray(box[1], dtype=np.int32).reshape(3)
+            hold += [lo_a, dims_a]
+            bx = (_p(lo_a), _p(dims_a))
+        flags = MLM_PACK_NO_INFL if no_infl else 0
+        summary = np.zeros(MLM_PACK_ROW, dtype=np.int64)
+        self._chk(self._L.mlm_pack_blocks(self._h, *bx, n, *src, flags | MLM_PACK_DRY, 0, None, _p(summary)), "mlm_pack_blocks")
+        size = int(summary[1])
+        if device:
+            import torch
+
+            dev = torch.device("cuda", self.device)
+            out = torch.empty(size, dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize(dev)
+            op = ctypes.c_void_p(out.data_ptr())
+        else:
+            out = np.empty(size, dtype=np.uint8)
+            op = _p(out)
+        self._chk(self._L.mlm_pack_blocks(self._h, *bx, n, *src, flags, size, op, _p(summary)), "mlm_pack_blocks")
+        self.pack_summary = summary
+        return out
+
+    def unpack(self, stream, device: bool = False) -> Dict[str, np.ndarray]:
+        """A packed stream (bytes, a numpy uint8 array or a torch uint8 tensor on this handle's device) back into rows (mlm_unpack_blocks):
+        "keys" int32 [n, 3], "log_odds" float32 [n, C], "occ", "infl" uint8 [n, C] in import_blocks' layout — numpy arrays, or with
+        device=True torch tensors on this handle's device — and "summary".  The stream is validated whole before anything is written;
+        a stream that is not one raises MlmError with the number of the failed check."""
+        if hasattr(stream, "data_ptr"):
+            keep = stream.contiguous()
+            sp, size = ctypes.c_void_p(keep.data_ptr()), int(keep.numel())
+        else:
+            keep = np.frombuffer(stream, dtype=np.uint8) if isinstance(stream, (bytes, bytearray, memoryview)) else np.ascontiguousarray(stream, dtype=np.uint8)
+            sp, size = _p(keep), int(keep.size)
+        if size == 0:
+            keep = np.zeros(1, dtype=np.uint8)
+            sp = _p(keep)
+        summary = np.zeros(MLM_PACK_ROW, dtype=np.int64)
+        self._chk(self._L.mlm_unpack_blocks(self._h, sp, size, 0, 0, None, None, None, None, _p(summary)), "mlm_unpack_blocks")
+        n, C = int(summary[0]), self.cells
+        shapes = (("keys", (n, 3), np.int32), ("log_odds", (n, C), np.float32), ("occ", (n, C), np.uint8), ("infl", (n, C), np.uint8))
+        if device:
+            import torch
+
+            dev = torch.device("cuda", self.device)
+            tt = {np.int32: torch.int32, np.float32: torch.float32, np.uint8: torch.uint8}
+            out = {k: torch.empty(shape, dtype=tt[dt], device=dev) for k, shape, dt in shapes}
+            torch.cuda.synchronize(dev)
+            p = [ctypes.c_void_p(out[k].data_ptr()) if n else None for k, _, _ in shapes]
+        else:
+            out = {k: np.empty(shape, dtype=dt) for k, shape, dt in shapes}
+            p = [_p(out[k]) if n else None for k, _, _ in shapes]
+        if n:
+            self._chk(self._L.mlm_unpack_blocks(self._h, sp, size, 0, n, *p, _p(summary)), "mlm_unpack_blocks")
+        out["summary"] = summary
+        return out
+
+    def save(self, path, box=None, no_infl: bool = False) -> int:
+        """The map (its blocks of the key box, if one is given) as a packed stream in a file; returns the bytes written.  See pack."""
+        stream = self.pack(box=box, no_infl=no_infl)
+        with open(path, "wb") as f:
+            f.write(stream.tobytes())
+        return int(stream.size)
+
+    def load(self, path, fuse: Optional[str] = None) -> Dict[str, np.ndarray]:
+        """A file save wrote, brought into this map: unpacked into device tensors (the dump never exists on the host), then
+        import_blocks — whole blocks are overwritten or created — or, with fuse="add" / "max" / "take" / "fill", fuse_blocks with that
+        mode.  Returns unpack's "summary" (and fuse_blocks' dict under "fuse")."""
+        rows = self.unpack(np.fromfile(path, dtype=np.uint8), device=True)
+        n = int(rows["keys"].shape[0])
+        res = {"summary": rows["summary"]}
+        if n and fuse is None:
+            self.import_blocks((rows["keys"].data_ptr(), n), rows["log_odds"].data_ptr(), rows["occ"].data_ptr(), rows["infl"].data_ptr())
+        elif n:
+            res["fuse"] = self.fuse_blocks((rows["keys"].data_ptr(), n), rows["log_odds"].data_ptr(), rows["occ"].data_ptr(), rows["infl"].data_ptr(), mode=fuse)
+        return res
 
     def export_window(self, lo, dims, odds=True, occ=False, infl=False, grad=False, max_iter: int = 5) -> Dict[str, np.ndarray]:
         """Dense read-out of the voxel box lo <= v < lo + dims (voxel indices v = block key * subbox_n + cell coordinate, per axis
