@@ -149,18 +149,19 @@ MLM_HD inline __attribute__((always_inline)) uint32_t mlm_sec_strength(float a) 
 struct MlmSecLds {
     uint32_t tab, miss, odds, sigma, rays, occ, multi, chunk, ray_p0, vox, aux, total;
 };
+// staged chunk descriptors of the record passes; between them the column's centre list (16 bits per table entry, and behind it target lists
+// of the spread pass); later the list of occupied table entries (L.occ)
+MLM_HD inline uint32_t mlm_sec_chunk_bytes(uint32_t TAB) {
+    uint32_t b = 2u * MLM_SEC_CHUNKS * 4u;
+    if (b < TAB * 2u) b = TAB * 2u;
+    return (b + 15u) & ~15u;
+}
 // n_miss: words of the column's miss table (bit mask: nZ * RW; frontier mode keeps insertion times: nZ * nRho)
 MLM_HD inline MlmSecLds mlm_sec_lds(uint32_t TAB, uint32_t n_miss, uint32_t n_rho, uint32_t n_z, bool explore) {
     MlmSecLds L;
     uint32_t o = 0;
     L.tab = o;      o += TAB * (uint32_t)sizeof(MlmSecCell);
-    {
-        // staged chunk descriptors of the record passes; later the list of occupied table entries (L.occ)
-        uint32_t b = 2u * MLM_SEC_CHUNKS * 4u;
-        if (b < TAB * 2u) b = TAB * 2u;
-        L.chunk = o;
-        o += (b + 15u) & ~15u;
-    }
+    L.chunk = o;    o += mlm_sec_chunk_bytes(TAB);
     L.odds = o;     o += ((2u * MLM_DIFF_RANGE + 1u) * n_rho + 3u) & ~3u; // a byte per entry of the odds table: its strength
     L.sigma = o;    o += ((n_rho + 3u) & ~3u) * 4u;
     L.miss = o;     o += ((n_miss + 3u) & ~3u) * 4u;

@@ -44,6 +44,7 @@
 #include "mlm_kernels.h"
 #include "mlm_sector_refs.h"
 #include "mlm_sector_ray.h"
+#include "mlm_sector_book.h"
 
 // Wave votes on a bool.  HIP's __ballot / __any / __all take an int: the predicate is materialised as 0 / 1 in a register and compared
 // with zero again (v_cndmask + v_cmp per vote); the builtin takes the compare's lane mask as it stands.
@@ -66,6 +67,7 @@ __device__ __forceinline__ bool mlm_lowest_lane_of(unsigned long long m) {
 
 #define MLM_SEC_KIND_BITS 21 // MlmSecCell::kg: 2 * MLM_DIFF_RANGE + 1 kinds below the reference count
 #define MLM_SEC_KIND_MASK ((1u << MLM_SEC_KIND_BITS) - 1u)
+static_assert(MLM_SEC_KIND_BITS == MLM_BOOK_KIND_BITS, "mlm_sector_book.h packs MlmSecCell::kg");
 #define MLM_SEC_CNT_MASK ((1u << MLM_SEC_CNT_BITS) - 1u)
 // Does the float noisy-OR chain of the cell (update_odds_hashmap, map_awareness.h:147-154: p <- 1 - (1 - p)(1 - a), each
 // operation rounded) depend on the order of its contributions?  Not with one kind only.  And not once the contributions
@@ -549,7 +551,8 @@ __device__ __forceinline__ int mlm_sec_entry(MlmSecCell *tab, uint32_t tab_mask,
     for (uint32_t probe = 0; probe <= max_probe; ++probe) {
         if (INSERT) {
             const uint32_t prev = atomicCAS(&tab[e].key, MLM_NIL, key);
-            if (prev == MLM_NIL || prev == key) return (int)e;
+            // (a hit centre's entry carries its place in the column's centre list above the key while the column books: k_sector's spread pass)
+            if (prev == MLM_NIL || (prev & MLM_SEC_KEY_MASK) == key) return (int)e;
         } else {
             const uint32_t k = tab[e].key;
             if (k == MLM_NIL) return -1;
@@ -633,6 +636,23 @@ __device__ __forceinline__ void mlm_fold_bin_stats(const MlmDev &P, int n_bin_bl
     }
 }
 
+// the column's cell table in LDS as mlm_sector_book.h books on it
+struct MlmSecBookLds {
+    MlmSecCell *tab;
+    uint32_t *ov, *ov_n; // table entries whose reference count wrapped (the first eight), their number
+    __device__ __forceinline__ void min_t(int e, uint32_t t) { atomicMin(&tab[e].tmin, t); }
+    __device__ __forceinline__ void or_kg(int e, uint32_t bits) { atomicOr(&tab[e].kg, bits); }
+    __device__ __forceinline__ void add_cnt(int e, uint32_t amount) { atomicAdd(&tab[e].cnt, amount); }
+    __device__ __forceinline__ uint32_t add_kg(int e, uint32_t amount) { return atomicAdd(&tab[e].kg, amount); }
+    __device__ __forceinline__ void rows_wrapped(int e) {
+        // more than 2 047 references: the count has wrapped.  That happens to cells a few decimetres in front of the sensor (thousands of
+        // pixels), which have one kind or saturate and need no references at all: the entry is remembered and the frame only gives up if
+        // such a cell does need its order (checked behind the booking)
+        const uint32_t k = atomicAdd(ov_n, 1u);
+        if (k < 8u) ov[k] = (uint32_t)e;
+    }
+};
+
 // EX: frontier mode (use_exploration_frontiers).  The miss container's iteration order matters there (mlm_kernels_explore.h),
 // so a miss cell keeps its first insertion time — point index * 256 + step of the ray, map_awareness.cpp:266-274 — instead
 // of a bit, and the map-dependent part is frontier mode's own (explore_stage_bc): the kernel ends with the unique hit list
@@ -692,6 +712,7 @@ __device__ __forceinline__ void mlm_sector_column(const MlmDev &P, const MlmFram
     __shared__ uint32_t s_base[8];
     __shared__ unsigned int s_fail, s_nouter, s_tab_full;
     __shared__ uint32_t s_ref_ov[8], s_ref_ov_n; // table entries whose reference count wrapped
+    __shared__ uint32_t s_ncent;                 // hit centres of the column (the spread pass's list)
     const MLM_GLOBAL uint32_t *chunks = mlm_gp(P.col_chunks) + 2 * (size_t)phi * P.chunk_cap;
     const MLM_GLOBAL mlm_u32x4 *recs = (const MLM_GLOBAL mlm_u32x4 *)mlm_gp(P.bnodes); // 16-byte column records (k_bin_sectors)
     // flat record r of the staged chunks -> index into `bnodes`
@@ -747,6 +768,7 @@ __device__ __forceinline__ void mlm_sector_column(const MlmDev &P, const MlmFram
         s_nouter = 0;
         s_tab_full = 0;
         s_ref_ov_n = 0;
+        s_ncent = 0;
     }
     __syncthreads();
     // Which world voxel a cell of this column falls into (get_global_idx / get_subbox_id of its centre moved by T_wa,
@@ -844,9 +866,13 @@ __device__ __forceinline__ void mlm_sector_column(const MlmDev &P, const MlmFram
     // (both kept records' in a 256-thread workgroup, whose columns usually have a second record per thread: its targets went through an
     // FP64 slope and the table's probe loop again before.  Not with 512 threads: a second record is rare there — a column of more than
     // 512 — and the three registers would not fit that form's 80 without scratch)
+    // (the lists are made once per CENTRE by the spread pass below, which leaves them in LDS; while the column books, a kept record only
+    // remembers its centre's table entry: the first record's in the low half of keep_ent, the second's in the high half)
     constexpr bool KEEP2 = NT <= 256;
     unsigned long long keep_lo = 0, keep2_lo = 0;
     uint32_t keep_hi = 0, keep2_hi = 0;
+    uint32_t keep_ent = 0;
+    MlmSecBookLds book{s_tab, s_ref_ov, &s_ref_ov_n};
     // A cell's origin — the row and tile column of its first pixel, what its references are relative to — is worked out once per
     // cell (the hit list's loop below puts it in place of MlmSecCell::tmin), not once per (record, cell) pair; a record's non-empty
     // mask rows are kept as flags and taken with a find-first-bit (mlm_sector_refs.h).
@@ -964,46 +990,24 @@ __device__ __forceinline__ void mlm_sector_column(const MlmDev &P, const MlmFram
                         keep2_yx = a.y;
                         keep2_mask = mask;
                     }
-                    uint32_t nt = 0;
                     const int l0 = __ffsll((long long)mask) - 1; // lowest lane = earliest insertion time of the record
                     // (the wave's first work item from the tile origin: dense y0 * width + x0, lists 64 items per "row")
                     const uint32_t i00 = tile_w > 0 ? ((a.y >> MLM_REC_XT_BITS) << 3) * (uint32_t)tile_w + ((a.y & MLM_REC_XT_MASK) << 3) : (a.y >> 11) << 6;
                     const uint32_t i_first = i00 + (tile_w > 0 ? (uint32_t)((l0 >> 3) * tile_w + (l0 & 7)) : (uint32_t)l0);
                     const uint32_t cnt = (uint32_t)__popcll(mask), n_rows = mlm_mask_rows(mask);
-                    mlm_sec_targets(P, rho, phi, z, s_sigma[rho], [&](uint32_t key, int sub, int rho_t) {
-                        const int e = mlm_sec_entry<true>(s_tab, tab_mask, key);
-                        if (e < 0) {
-                            s_tab_full = 1;
-                            return;
-                        }
-                        if (kept || (KEEP2 && kept2)) { // (each into its own registers: no copy of the three lives across the loop)
-                            const uint32_t t = (uint32_t)e | (uint32_t)sub << 12;
-                            if (kept) {
-                                if (nt < 4u) keep_lo |= (unsigned long long)t << (16u * nt);
-                                else keep_hi |= t & 0xFFFFu;
-                            } else if constexpr (KEEP2) {
-                                if (nt < 4u) keep2_lo |= (unsigned long long)t << (16u * nt);
-                                else keep2_hi |= t & 0xFFFFu;
-                            }
-                            if (nt >= 5u || sub > 15) nt = MLM_SEC_KEEP_MORE - 1u;
-                            ++nt;
-                        }
-                        atomicMin(&s_tab[e].tmin, i_first * MLM_TIME_SLOTS + (uint32_t)sub);
-                        atomicOr(&s_tab[e].kg, 1u << sub);
-                        // contributions, and in the upper 11 bits (mod 2048) the sum of their strengths (mlm_sec_needs_order)
-                        const uint32_t strength = s_strength[mlm_contribution_index(P, rho_t, sub)];
-                        atomicAdd(&s_tab[e].cnt, cnt | ((cnt * strength) << MLM_SEC_CNT_BITS));
-                        if ((atomicAdd(&s_tab[e].kg, n_rows << MLM_SEC_KIND_BITS) >> MLM_SEC_KIND_BITS) + n_rows > (0xFFFFFFFFu >> MLM_SEC_KIND_BITS)) {
-                            // more than 2 047 references: the count has wrapped.  That happens to cells a few decimetres in front of
-                            // the sensor (thousands of pixels), which have one kind or saturate and need no references at all: the entry
-                            // is remembered and the frame only gives up if such a cell does need its order (checked below)
-                            const uint32_t k = atomicAdd(&s_ref_ov_n, 1u);
-                            if (k < 8u) s_ref_ov[k] = (uint32_t)e;
-                        }
-                        if (EX && sub == 0) atomicMin(&s_p0[e], i_first);
-                    });
-                    if (kept) keep_hi |= nt << 16;
-                    if (KEEP2 && kept2) keep2_hi |= nt << 16;
+                    // CENTRE PASS.  A record books on its centre cell only — target 0 of its spread.  The spread depends on the centre alone,
+                    // and several 8x8 tiles feed the same centre (3.3 records per centre in a camera frame): the other targets get the
+                    // centre's totals once, from the spread pass below.
+                    const int e = mlm_sec_entry<true>(s_tab, tab_mask, (uint32_t)(z * P.nRho + rho));
+                    if (e < 0) {
+                        s_tab_full = 1;
+                        continue;
+                    }
+                    if (kept) keep_ent |= (uint32_t)e;
+                    if (KEEP2 && kept2) keep_ent |= (uint32_t)e << 16;
+                    // (contributions, and in the upper 11 bits (mod 2048) the sum of their strengths: mlm_sec_needs_order)
+                    mlm_book_record_centre(book, e, i_first, cnt, n_rows, s_strength[mlm_contribution_index(P, rho, 0)]);
+                    if (EX) atomicMin(&s_p0[e], i_first);
                 }
             }
             if (pass == 0 && c0 == 0) keep_total = total;
@@ -1011,6 +1015,86 @@ __device__ __forceinline__ void mlm_sector_column(const MlmDev &P, const MlmFram
     };
     __syncthreads();
     for_records(0);
+    __syncthreads();
+    // ---- SPREAD PASS: every hit centre spreads ONCE, with the totals of its records.  Every occupied entry is a centre by now and holds
+    // exactly those totals (mlm_sector_book.h: the equalities that make the table the one booked record by record, bit for bit; only the
+    // number of times a wrapped cell is flagged, s_ref_ov_n, can be smaller — a column gives up less often, never more often).
+    //   1. the centres are listed densely (a lane per centre in the spread, not a lane per table entry: one entry in five holds one);
+    //      a centre's place k in the list goes above its key;
+    //   2. thread k takes centre k's totals into registers — all of them before any spread adds to a centre's entry as a target;
+    //   3. it spreads them over the other targets and leaves the centre's packed target list in slot k for the reference pass.
+    // The list and the slots lie in LDS that is idle here: the chunk staging (dead until the second record pass) and the ray starts.
+    const uint32_t per = TAB / NT; // entries e = threadIdx.x * per + q: contiguous per thread (per <= PER_MAX)
+    uint16_t *s_cent = (uint16_t *)(s_dyn + L.chunk);
+    const uint32_t n_slot_a = TAB / 4u, n_slot_b = (mlm_sec_chunk_bytes(TAB) - TAB * 2u) / 8u; // 8-byte slots over L.rays / behind the centre list
+    auto slot_of = [&](uint32_t k) -> uint32_t * {
+        if (k < n_slot_a) return (uint32_t *)(s_dyn + L.rays) + 2u * k;
+        if (k - n_slot_a < n_slot_b) return (uint32_t *)(s_dyn + L.chunk + TAB * 2u) + 2u * (k - n_slot_a);
+        return nullptr;
+    };
+#pragma unroll
+    for (uint32_t q = 0; q < (uint32_t)PER_MAX; ++q) {
+        if (q >= per) break;
+        const uint32_t e = threadIdx.x * per + q;
+        const bool is_centre = s_tab[e].key != MLM_NIL;
+        const unsigned long long m = mlm_ballot(is_centre);
+        if (m) { // (uniform per wave: one LDS atomic per wave)
+            uint32_t base = 0;
+            if (lane == 0) base = atomicAdd(&s_ncent, (uint32_t)__popcll(m));
+            base = __builtin_amdgcn_readfirstlane(base);
+            if (is_centre) {
+                const uint32_t k = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                s_cent[k] = (uint16_t)e;
+                s_tab[e].key |= k << 16;
+                s_tab[e].kg = mlm_book_centre_kind(s_tab[e].kg); // (kind 0, once per centre: nothing else writes the entry here)
+            }
+        }
+    }
+    __syncthreads();
+    const uint32_t n_cent = s_ncent;
+    MlmBookCentre cen[PER_MAX];
+    {
+        const uint32_t n_ov = min(s_ref_ov_n, 8u); // (more: the column gives up below)
+#pragma unroll
+        for (uint32_t j = 0; j < (uint32_t)PER_MAX; ++j) {
+            cen[j] = MlmBookCentre{0u, 0u};
+            if (j >= per) break;
+            const uint32_t k = threadIdx.x + j * (uint32_t)NT;
+            if (k < n_cent) {
+                const uint32_t e = s_cent[k];
+                bool wrapped = false;
+                for (uint32_t i = 0; i < n_ov; ++i) wrapped = wrapped || s_ref_ov[i] == e;
+                cen[j] = mlm_book_centre(s_tab[e].tmin, s_tab[e].kg, s_tab[e].cnt, wrapped);
+            }
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t j = 0; j < (uint32_t)PER_MAX; ++j) {
+        if (j >= per) break;
+        const uint32_t k = threadIdx.x + j * (uint32_t)NT;
+        if (k < n_cent && !*(volatile unsigned int *)&s_tab_full) {
+            int rho, z;
+            key_rz(s_tab[s_cent[k]].key & MLM_SEC_KEY_MASK, rho, z);
+            unsigned long long list = 0;
+            uint32_t nt = 0;
+            mlm_sec_targets(P, rho, phi, z, s_sigma[rho], [&](uint32_t key, int sub, int rho_t) {
+                if (sub == 0) return; // (the centre itself: booked by its records)
+                const int e = mlm_sec_entry<true>(s_tab, tab_mask, key);
+                if (e < 0) {
+                    s_tab_full = 1;
+                    return;
+                }
+                list = mlm_book_list_add(list, nt++, e, (uint32_t)sub);
+                mlm_book_centre_target(book, e, (uint32_t)sub, cen[j], s_strength[mlm_contribution_index(P, rho_t, sub)]);
+            });
+            uint32_t *slot = slot_of(k);
+            if (slot) {
+                slot[0] = (uint32_t)list;
+                slot[1] = (uint32_t)(list >> 32);
+            }
+        }
+    }
     __syncthreads();
     if (s_tab_full) { // (uniform) nothing has left the workgroup yet
         if (threadIdx.x == 0) {
@@ -1032,6 +1116,22 @@ __device__ __forceinline__ void mlm_sector_column(const MlmDev &P, const MlmFram
         }
         return;
     }
+    // A kept record takes its centre's target list from the centre's slot, in the form the reference pass reads: (entry | kind << 12) in
+    // 16 bits each, the centre itself first (kind 0), four in keep_lo, the fifth in keep_hi's low half, the count in its high half.
+    auto kept_list = [&](uint32_t e, unsigned long long &k_lo, uint32_t &k_hi) {
+        const uint32_t *slot = slot_of(s_tab[e].key >> 16);
+        const unsigned long long list = slot ? (unsigned long long)slot[0] | (unsigned long long)slot[1] << 32 : MLM_BOOK_LIST_MORE;
+        if (list == MLM_BOOK_LIST_MORE) {
+            k_hi = MLM_SEC_KEEP_MORE << 16;
+        } else {
+            k_lo = (unsigned long long)e | list << 16;
+            k_hi = (uint32_t)(list >> 48) | (1u + mlm_book_list_count(list)) << 16;
+        }
+    };
+    if (keep_cell != MLM_NIL) kept_list(keep_ent & 0xFFFFu, keep_lo, keep_hi);
+    if constexpr (KEEP2) {
+        if (keep2_cell != MLM_NIL) kept_list(keep_ent >> 16, keep2_lo, keep2_hi);
+    }
     if (threadIdx.x == 0 && s_ref_ov_n) { // (see the booking pass: a wrapped reference count only matters for a cell that needs its order)
         if (s_ref_ov_n > 8u) s_fail = 1;
         for (uint32_t k = 0; k < min(s_ref_ov_n, 8u); ++k)
@@ -1042,7 +1142,6 @@ __device__ __forceinline__ void mlm_sector_column(const MlmDev &P, const MlmFram
     //      the column's reservations in the frame's lists (one round trip)
     //      The hit list is ordered by tile run (the hits of one tile are contiguous): rank inside the run from a returning
     //      LDS atomic, the runs' offsets from the same block scan that places the other lists.
-    const uint32_t per = TAB / NT; // entries e = threadIdx.x * per + q: contiguous per thread (per <= PER_MAX)
     uint32_t v[4] = {0u, 0u, 0u, 0u}; // occupied, multi, ray starts, hits of tile run `threadIdx.x`
     uint32_t w[4] = {0u, 0u, 0u, 0u}; // reference slots (a cell's count rounded up to MLM_SEC_REF_ALIGN) / ordered-kinds slots of this thread's multi-kind cells
     uint32_t hk[PER_MAX];           // this thread's entries: rank among their tile run's hits
@@ -1065,7 +1164,7 @@ __device__ __forceinline__ void mlm_sector_column(const MlmDev &P, const MlmFram
             p0r[EX ? q : 0] = s_p0[threadIdx.x * per + q];
         } else {
             int rho, z;
-            key_rz(c.key, rho, z);
+            key_rz(c.key & MLM_SEC_KEY_MASK, rho, z); // (above a centre's key: its place in the centre list)
             hk[q] = atomicAdd(&s_run_hits[s_vr[rho].w], 1u);
         }
     }
@@ -1131,7 +1230,7 @@ __device__ __forceinline__ void mlm_sector_column(const MlmDev &P, const MlmFram
                 s_rays[o_rays++] = (uint16_t)e;
             }
             int c_rho, c_z;
-            key_rz(c.key, c_rho, c_z);
+            key_rz(c.key & MLM_SEC_KEY_MASK, c_rho, c_z);
             const uint32_t place = (EX ? v[0] : s_run_off[s_vr[c_rho].w]) + hk[q];
             s_occ[place] = (uint16_t)e;
             if (mlm_sec_needs_order(c)) {
