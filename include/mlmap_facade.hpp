@@ -468,6 +468,18 @@ class mlmap {
                     const int32_t *dims = nullptr, const int32_t *sqdist = nullptr, int sq_cap = 64) {
         check(mlm_score_poses(h_, pts_s, n_pts, T_ws, n_poses, flags, lo, dims, sqdist, sq_cap, table), "mlm_score_poses");
     }
+    // segment casts through a distance field (mlm_query_clearance): the walk of queryRays through sqdist over the box lo, dims (as
+    // mlm_export_esdf wrote it), stopped at the first voxel with f <= sq_stop or outside the box (flags MLM_CLEAR_OUTSIDE_PASS: outside
+    // voxels have f = sq_cap); per ray the stop, the minimum clearance and where, the summed cost and the near voxels; with group_begin
+    // (n_groups + 1 offsets) one row of MLM_CLEAR_ROW int64 per group in table; every array host or device memory
+    void queryClearance(const double *p0, const double *p1, int n, const int32_t *lo, const int32_t *dims, const int32_t *sqdist, int sq_stop,
+                        int sq_cap, int flags, int8_t *status, int32_t *voxel3 = nullptr, double *t = nullptr, int32_t *n_steps = nullptr,
+                        int32_t *min_sq = nullptr, int32_t *min3 = nullptr, int64_t *cost = nullptr, int32_t *n_near = nullptr,
+                        const int32_t *group_begin = nullptr, int n_groups = 0, int64_t *table = nullptr) {
+        check(mlm_query_clearance(h_, p0, p1, n, lo, dims, sqdist, sq_stop, sq_cap, flags, status, voxel3, t, n_steps, min_sq, min3, cost, n_near,
+                                  group_begin, n_groups, table),
+              "mlm_query_clearance");
+    }
 
     // planners that query thousands of positions per cycle should use the batched entry points directly
     mlm_handle *handle() { return h_; }

@@ -592,6 +592,63 @@ int mlm_query_sweeps(mlm_handle *h, const double *p0, const double *p1, int n, i
 #define MLM_SCORE_ROW 8
 int mlm_score_poses(mlm_handle *h, const double *pts_s, int n_pts, const double *T_ws, int n_poses, int flags,
                     const int32_t lo[3], const int32_t dims[3], const int32_t *sqdist, int sq_cap, int64_t *table);
+/* Exact batched segment casts through a distance field: "is the piece from a to b free for a vehicle of radius r, how close does it
+ * come to an obstacle, where, and what does that cost?" — the edge check and the edge weight of a sampling planner, from a field the
+ * caller already holds.  (No reference counterpart: the reference has no segment query and no distance field; the path is
+ * mlm_query_rays', the field is mlm_export_esdf's sqdist, the rule is defined here, in integers, with exactly one answer.)  Segment i
+ * runs from p0[3i .. 3i+2] to p1[3i .. 3i+2].  The lattice, the validity rule, the path u_0 .. u_N, the tie rule of the walk and t are
+ * mlm_query_rays'.
+ *   Field: lo, dims and sqdist are required.  The window follows mlm_export_window's rules and errors; sqdist holds one int32 per
+ *   voxel, laid out [dims[2]][dims[1]][dims[0]]: what mlm_export_esdf wrote for that box, unsigned or signed, but the answer is defined
+ *   for any content: f(v) = min(max(sqdist[v], 0), sq_cap) for v in the box.  sq_cap lies in 1 .. 2^20, sq_stop in -1 .. 2^20 (-1:
+ *   nothing stops the walk).
+ *   Stop: the walk stops at K, the smallest path index for which u_K lies outside the box and MLM_CLEAR_OUTSIDE_PASS is not set (status
+ *   MLM_CLEAR_LEFT), or f(u_K) <= sq_stop (status 1); without one K = N + 1 and status is 0.  With MLM_CLEAR_OUTSIDE_PASS a voxel
+ *   outside the box has f = sq_cap (mlm_score_poses' rule) and only the second test is made: such a voxel stops the walk iff
+ *   sq_cap <= sq_stop.  Passed = u_0 .. u_{K-1}; seen = passed, plus u_K at status 1.
+ *   Per ray:                status 1 / 2                         status 0      invalid
+ *     status     int8       1 (the field) / MLM_CLEAR_LEFT       0             -1
+ *     voxel3     int32 x 3  u_K                                  e             0,0,0
+ *     t          double     (double)m / (double)|D| of the step  1.0           0.0
+ *                           that entered u_K; 0.0 for K = 0
+ *     n_steps    int32      K                                    N + 1         0
+ *     min_sq     int32      the minimum of f over seen; MLM_CLEAR_NONE when seen is empty        MLM_CLEAR_NONE
+ *     min3       int32 x 3  the seen voxel of smallest path index attaining min_sq; 0,0,0 with MLM_CLEAR_NONE
+ *     cost       int64      the sum over passed of sq_cap - f, at most (3 * 2^15 + 1) * 2^20      0
+ *     n_near     int32      the passed voxels with f < sq_cap                                     0
+ *   At status 1 min_sq == f(u_K) <= sq_stop and min3 == voxel3.  With a field of mlm_export_esdf at max_dist r + 1, sq_stop = r^2 and
+ *   every path inside the box, status, voxel3, t and n_steps are mlm_query_sweeps' bytes at radius r with the same class bits, and
+ *   min_sq at a stop is its hit_sq: an edge checked here agrees voxel for voxel with mlm_export_reach / mlm_export_route about "free
+ *   for radius r".
+ *   Groups (group_begin and table both given or both NULL): group_begin is int32 [n_groups + 1], first entry >= 0, non-decreasing,
+ *   last entry <= n (validated on the host, as mlm_query_views' view_begin); group g is the segments group_begin[g] ..
+ *   group_begin[g + 1] - 1 in index order (a trajectory's pieces; the end points need not join; rays in no group are allowed).  j* is
+ *   the first segment of the group with status != 0 (an invalid one counts), C the segments from the group's first to j* inclusive, or
+ *   all of them without one.  Row g of table (int64 [n_groups][MLM_CLEAR_ROW]): [0] segments in the group, [1] j* - begin or -1,
+ *   [2] status of j* or 0, [3] the minimum of min_sq over C, ignoring MLM_CLEAR_NONE; -1 if there is none, [4] the index within the group
+ *   of the first segment attaining [3] or -1, [5] the sum of cost over C, [6] of n_steps, [7] of n_near.  The row does not depend on
+ *   which per-ray outputs were requested.
+ * Every pointer but lo and dims may be host or device memory, each on its own.  Any output may be NULL (table counts as one), at least
+ * one must not be.  The call reads no map state and waits for no frame, as mlm_query_paths; it runs on the stream of mlm_set_stream and
+ * returns when the outputs are written.  When every array is host memory, n <= 64, the valid rays' sum of N + 1 is at most 2^18 and the
+ * host mirror is not switched off (mlm_set_host_mirror_limit(h, 0)), the batch is answered on the host by the same rule, with no launch
+ * and no copy (counted in mlm_frame_stats.n_host_queries); everything else runs as a kernel: a host sqdist crosses the link once into
+ * the buffer mlm_score_poses keeps for its field, host rays and outputs are staged in chunks of 2^18 rays (at most 101 bytes per ray,
+ * each part rounded up to 256 bytes, in the buffer mlm_query_rays stages in), and with groups 21 bytes per ray of the whole batch plus a
+ * host group_begin and table live in a kept scratch; all of it is counted in mlm_frame_stats.device_bytes.  MLM_ERR_INVALID: n < 0, a
+ * NULL input with n > 0, a NULL lo, dims or sqdist, a window error, sq_stop outside -1 .. 2^20, sq_cap outside 1 .. 2^20, an unknown
+ * flag bit, no output, group_begin and table not both given or both NULL, n_groups < 0, a bad group_begin; n == 0 with n_groups == 0
+ * is MLM_OK (n == 0 with groups writes their rows).  MLM_ERR_CAPACITY: no device memory for staging, scratch or the field copy.  The
+ * handle stays usable after either error. */
+#define MLM_CLEAR_OUTSIDE_PASS 1 /* path voxels outside the box have f = sq_cap and never end the walk by leaving */
+#define MLM_CLEAR_NONE (-1)      /* min_sq of a ray that saw no voxel */
+#define MLM_CLEAR_LEFT 2         /* status: the walk reached a path voxel outside the box */
+#define MLM_CLEAR_ROW 8          /* int64 per group row */
+int mlm_query_clearance(mlm_handle *h, const double *p0, const double *p1, int n,
+                        const int32_t lo[3], const int32_t dims[3], const int32_t *sqdist, int sq_stop, int sq_cap, int flags,
+                        int8_t *status, int32_t *voxel3, double *t, int32_t *n_steps,
+                        int32_t *min_sq, int32_t *min3, int64_t *cost, int32_t *n_near,
+                        const int32_t *group_begin, int n_groups, int64_t *table);
 /* Cost-to-go field through the free space of a box of voxels (no reference counterpart: the reference has no such field; the
  * classes behind it are those of its point queries, the field is defined here, in integers).  Voxel indices, window, layout
  * ([dims[2]][dims[1]][dims[0]], x fastest) and centres are those of mlm_export_window.

@@ -18,7 +18,7 @@ struct KernelTime {
 // Test and experiment knobs (mlm_debug_set): named integers that mlm_create reads — launch geometries, forced fall-backs.
 // Process-wide, not part of the drop-in contract; the library reads no environment variable for them (only the three diagnostic
 // switches MLM_DEBUG_CREATE / MLM_DEBUG_ALLOC / MLM_DEBUG_DRAIN, which print).
-const char *const kKnobNames[] = {"agg_lds", "big_arm", "big_grid", "bin_block", "chain_grid", "cluster_tile", "collect_grid", "crop_stage_rows", "cu_reserve", "cu_split", "delta_grid",
+const char *const kKnobNames[] = {"agg_lds", "big_arm", "big_grid", "bin_block", "chain_grid", "clear_ahead", "cluster_tile", "collect_grid", "crop_stage_rows", "cu_reserve", "cu_split", "delta_grid",
                                   "esdf_tile_vox", "ex_spec", "expand_block", "graph", "grid_tile", "hit_tab_n", "logit_exact", "mesh_stage_rows", "mirror", "mirror_max", "mirror_mb", "need_slots", "node_lds", "pack_grid", "pool_grow",
                                   "rank_grid", "rays_grid", "reach_group", "reach_tile", "render_tile", "route_group", "route_tile", "sc_block", "sc_grid", "score_chunk", "sec_backoff", "sec_fail_every", "sec_tab", "sec_tab_big", "sec_threads",
                                   "sectors", "single_apply_grid", "single_chain_grid", "single_rank_grid", "slot_sets", "sort_block", "sort_grid", "tile_grid", "tile_sh", "view_lds_bits"};
@@ -54,6 +54,7 @@ bool knob_value_ok(const char *name, long long v) {
     if (is("reach_group")) return v >= 1 && v <= kReachGroupMax; // (sweeps between two looks at the "marked" words)
     if (is("hit_tab_n")) return v >= 0 && v <= 65536 && (v & (v - 1)) == 0; // (entries per chain of MlmDev::hit_p / hit_inc: a power of two, 0 = no tables)
     if (is("render_tile")) return v >= 0 && v <= 2; // (k_render has three instantiations: 64 x 1, 16 x 4, 8 x 8)
+    if (is("clear_ahead")) return v == 1 || v == 4; // (k_clearance has two instantiations: voxels looked ahead per lane)
     if (is("score_chunk")) return v >= 0 && v <= (1ll << 22) && v % MLM_SCORE_TILE == 0; // (points per chunk of k_score: whole LDS tiles; 0: automatic)
     return true;
 }
@@ -151,6 +152,13 @@ constexpr size_t kPathStageBytes = (size_t)64 << 20;
 // mlm_score_poses: poses per launch of k_score (bounds the staging of host poses and rows: 160 bytes per pose), the most pairs and —
 // mlm_query_nearest's rule — poses of a batch in host memory that the host code answers, and the workgroups the automatic chunk aims
 // at (four per CU of a 256-CU chip: a lane per pose leaves a grid of few poses and many points empty otherwise)
+// mlm_query_clearance: rays per launch of k_clearance (bounds the staging of host inputs / outputs: 101 bytes per ray), the most rays
+// and — known from the end points before anything is walked — path voxels of a batch in host memory that the host code answers, and the
+// most workgroups of k_clearance_groups (a lane per group, grid-stride)
+constexpr int kClearChunk = 1 << 18;
+constexpr int kClearHostRays = 64;
+constexpr long long kClearHostVoxels = 1ll << 18;
+constexpr unsigned int kClearGroupGrid = 4096;
 constexpr int kScorePoseChunk = 1 << 18;
 constexpr long long kScoreHostPairs = 1ll << 16;
 constexpr long long kScoreGridTarget = 1024;
@@ -227,6 +235,9 @@ struct mlm_handle : MlmHandlePlan { // (MlmHandlePlan, mlm_plan.h: the members m
     KeptBuf d_path;
     // mlm_score_poses: the device copy of a distance field handed over in host memory (4 bytes per voxel)
     KeptBuf d_score_field;
+    // mlm_query_clearance: with groups, the five words per ray the rows need (21 bytes per ray of the whole batch), and the staging of
+    // a host group_begin and table; a host field goes to d_score_field
+    KeptBuf d_clear;
     // sort buffers (rehash frames only)
     unsigned long long *sk_in = nullptr, *sk_out = nullptr;
     uint32_t *sv_in = nullptr, *sv_out = nullptr;

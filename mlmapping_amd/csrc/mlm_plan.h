@@ -76,6 +76,7 @@ struct MlmHandlePlan {
     int score_chunk = 0; // points per chunk of k_score (knob "score_chunk"; 0: automatic)
     unsigned int rays_grid = 1024; // most workgroups of k_rays (knob "rays_grid"): 2^20 rays are four per lane
     int render_tile = kRenderTileDefault; // (knob "render_tile")
+    int clear_ahead = 1; // voxels a lane of k_clearance looks ahead (knob "clear_ahead": 1 or 4; DESIGN.md has the measurement)
     // Frame slots sized by NEED (sector-path handles, not frontier mode): the per-frame lists whose worst case is
     // "every awareness cell is a multi-kind hit" start at what a camera frame of max_points pixels needs and are doubled at a
     // drained point when a frame's Stage A runs out of room (grow_slots, like grow_pool for the block pool).  The cell-table path,
@@ -203,6 +204,7 @@ template <class Knob> MlmPlan mlm_plan(const mlm_config &cfg, const mlm_limits *
     if (knob("rays_grid", kv)) H.rays_grid = (unsigned int)kv;
     if (knob("render_tile", kv)) H.render_tile = (int)kv;
     if (knob("score_chunk", kv)) H.score_chunk = (int)kv;
+    if (knob("clear_ahead", kv)) H.clear_ahead = (int)kv;
     if (knob("mirror_max", kv)) pl.mir.max_clean = std::max(0, (int)kv), pl.mir.max_dirty = std::min(pl.mir.max_dirty, pl.mir.max_clean);
     if (knob("slot_sets", kv)) H.n_sets = std::min(MLM_SETS, std::max(2, (int)kv));
     // Stage B+C (main stream) is the serial per-frame chain of short, latency-bound kernels; Stage A floods the

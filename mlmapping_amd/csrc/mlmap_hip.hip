@@ -46,6 +46,7 @@
 #include "mlm_kernels_route.h"
 #include "mlm_kernels_path.h"
 #include "mlm_kernels_score.h"
+#include "mlm_kernels_clearance.h"
 #include "mlm_kernels_cluster.h"
 #include "mlm_kernels_mesh.h"
 #include "mlm_kernels_octree.h"
@@ -1677,8 +1678,147 @@ int mlm_score_poses(mlm_handle *h, const double *pts_s, int n_pts, const double 
     return MLM_OK;
 }
 
+int mlm_query_clearance(mlm_handle *h, const double *p0, const double *p1, int n, const int32_t lo[3], const int32_t dims[3], const int32_t *sqdist,
+                        int sq_stop, int sq_cap, int flags, int8_t *status, int32_t *voxel3, double *t, int32_t *n_steps, int32_t *min_sq,
+                        int32_t *min3, int64_t *cost, int32_t *n_near, const int32_t *group_begin, int n_groups, int64_t *table) {
+    if (!h) return MLM_ERR_INVALID;
+    MLM_LOCK(h);
+    if (n < 0 || (n > 0 && (!p0 || !p1)) || !lo || !dims || !sqdist || sq_stop < -1 || sq_stop > MLM_CLEAR_MAX_SQ || sq_cap < 1 ||
+        sq_cap > MLM_CLEAR_MAX_SQ || (flags & ~MLM_CLEAR_OUTSIDE_PASS) || (!group_begin != !table) || n_groups < 0 ||
+        (!status && !voxel3 && !t && !n_steps && !min_sq && !min3 && !cost && !n_near && !table)) {
+        h->err = "mlm_query_clearance: negative n, a null input, a null lo, dims or sqdist, sq_stop outside [-1, 2^20], sq_cap outside [1, 2^20], an "
+                 "unknown flag bit, group_begin without table or table without group_begin, negative n_groups, or no output";
+        return MLM_ERR_INVALID;
+    }
+    long long D[3], nvox = 0;
+    int rc = box_check(h, "mlm_query_clearance", lo, dims, D, nvox);
+    if (rc) return rc;
+    const bool grouped = table != nullptr;
+    if (n == 0 && (!grouped || n_groups == 0)) return MLM_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    // group_begin: validated on the host (copied back when it is device memory, behind the caller's work on the stream)
+    std::vector<int32_t> gb_copy;
+    const int32_t *gb = group_begin;
+    const bool gb_dev = grouped && readout_in_place(group_begin);
+    if (gb_dev) {
+        gb_copy.resize((size_t)n_groups + 1);
+        HIPCHK(h, hipMemcpyAsync(gb_copy.data(), group_begin, gb_copy.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        gb = gb_copy.data();
+    }
+    if (grouped) {
+        bool ok = gb[0] >= 0;
+        for (int g = 0; g < n_groups && ok; ++g) ok = gb[g + 1] >= gb[g];
+        if (!ok || gb[n_groups] > n) {
+            h->err = "mlm_query_clearance: group_begin must start at >= 0, must not decrease and must end at <= n";
+            return MLM_ERR_INVALID;
+        }
+    }
+    MlmClearField F{};
+    F.sqdist = sqdist;
+    for (int a = 0; a < 3; ++a) F.lo[a] = lo[a], F.dims[a] = dims[a];
+    F.sq_stop = sq_stop, F.sq_cap = sq_cap, F.outside_pass = (flags & MLM_CLEAR_OUTSIDE_PASS) ? 1 : 0;
+    const double d = h->P.d_sub;
+    // channels: the two inputs, then the eight per-ray outputs; bytes per ray; in device memory (used in place) or staged
+    ReadoutChannels<10> ch(h->d_ray_stage,
+                           {{p0, 3 * sizeof(double)}, {p1, 3 * sizeof(double)}, {status, 1}, {voxel3, 3 * sizeof(int32_t)}, {t, sizeof(double)},
+                            {n_steps, sizeof(int32_t)}, {min_sq, sizeof(int32_t)}, {min3, 3 * sizeof(int32_t)}, {cost, sizeof(int64_t)},
+                            {n_near, sizeof(int32_t)}},
+                           true);
+    const bool field_staged = !readout_in_place(sqdist), table_staged = grouped && !readout_in_place(table);
+
+    // a planner's edge-by-edge calls: the shared rule on the host, no launch and no copy (no mirror either: the call reads no map state)
+    bool on_host = ch.all_host && field_staged && (!grouped || (!gb_dev && table_staged)) && n <= kClearHostRays && h->mir.enabled;
+    if (on_host) {
+        long long vox = 0;
+        for (int i = 0; i < n; ++i) {
+            MlmRayState S;
+            if (!mlm_ray_setup(p0 + 3 * (size_t)i, p1 + 3 * (size_t)i, d, 1, S)) continue;
+            vox += 1 + (long long)S.r[0] + S.r[1] + S.r[2];
+        }
+        on_host = vox <= kClearHostVoxels;
+    }
+    if (on_host) {
+        int8_t w_status[kClearHostRays];
+        int32_t w_min[kClearHostRays], w_steps[kClearHostRays], w_near[kClearHostRays];
+        int64_t w_cost[kClearHostRays];
+        for (int i = 0; i < n; ++i) {
+            MlmClearResult o;
+            mlm_clear_walk<1>(p0 + 3 * (size_t)i, p1 + 3 * (size_t)i, d, F, o);
+            w_status[i] = (int8_t)o.status, w_min[i] = o.min_sq, w_steps[i] = o.n_steps, w_near[i] = o.n_near, w_cost[i] = (int64_t)o.cost;
+            if (status) status[i] = (int8_t)o.status;
+            if (t) t[i] = o.t;
+            if (n_steps) n_steps[i] = o.n_steps;
+            if (min_sq) min_sq[i] = o.min_sq;
+            if (cost) cost[i] = (int64_t)o.cost;
+            if (n_near) n_near[i] = o.n_near;
+            for (int a = 0; a < 3; ++a) {
+                if (voxel3) voxel3[3 * (size_t)i + a] = o.voxel[a];
+                if (min3) min3[3 * (size_t)i + a] = o.min3[a];
+            }
+        }
+        for (int g = 0; grouped && g < n_groups; ++g)
+            mlm_clear_group(gb[g], gb[g + 1], w_status, w_min, w_cost, w_steps, w_near, table + (size_t)g * MLM_CLEAR_WORDS);
+        h->mir.n_host_queries += n;
+        return MLM_OK;
+    }
+
+    if (field_staged) { // the field crosses the link once, into the buffer mlm_score_poses keeps for its field
+        const size_t bytes = (size_t)nvox * sizeof(int32_t);
+        if ((rc = readout_reserve(h, h->d_score_field, bytes, "mlm_query_clearance"))) return rc;
+        HIPCHK(h, hipMemcpyAsync(h->d_score_field.p, sqdist, bytes, hipMemcpyHostToDevice, h->stream));
+        F.sqdist = (const int32_t *)h->d_score_field.p;
+    }
+    // with groups: the five words per ray of the whole batch, then the staging of a host group_begin and of a host table
+    MlmClearGroups G{};
+    char *g_words[5] = {};
+    if (grouped) {
+        const size_t N = (size_t)n, part[5] = {mlm_align256(N * sizeof(int64_t)), mlm_align256(N * sizeof(int32_t)), mlm_align256(N * sizeof(int32_t)),
+                                               mlm_align256(N * sizeof(int32_t)), mlm_align256(N)};
+        const size_t gb_bytes = gb_dev ? 0 : mlm_align256(((size_t)n_groups + 1) * sizeof(int32_t));
+        const size_t tab_bytes = table_staged ? mlm_align256((size_t)n_groups * MLM_CLEAR_WORDS * sizeof(int64_t)) : 0;
+        if ((rc = readout_reserve(h, h->d_clear, part[0] + part[1] + part[2] + part[3] + part[4] + gb_bytes + tab_bytes, "mlm_query_clearance"))) return rc;
+        char *at = (char *)h->d_clear.p;
+        for (int w = 0; w < 5; ++w) {
+            g_words[w] = at;
+            at += part[w];
+        }
+        G.begin = gb_dev ? group_begin : (const int32_t *)at;
+        G.table = table_staged ? (int64_t *)(at + gb_bytes) : table;
+        G.n_groups = n_groups;
+        G.cost = (const int64_t *)g_words[0], G.min_sq = (const int32_t *)g_words[1], G.n_steps = (const int32_t *)g_words[2];
+        G.n_near = (const int32_t *)g_words[3], G.status = (const int8_t *)g_words[4];
+        if (!gb_dev) HIPCHK(h, hipMemcpyAsync(at, group_begin, ((size_t)n_groups + 1) * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    }
+    // chunks: staged channels of a chunk share one kept buffer (at most 101 bytes per ray); one lane per ray, as k_rays
+    void (*const kern)(const MlmClear) = h->clear_ahead == 4 ? k_clearance<4> : k_clearance<1>;
+    if (n > 0) {
+        const size_t chunk = (size_t)std::min(n, kClearChunk);
+        if ((rc = ch.reserve(h, "mlm_query_clearance", chunk))) return rc;
+        rc = chunk_rounds(h, ch, (size_t)n, chunk, 0, 2, 2, 10, [&](size_t i0, size_t m, void **at) {
+            MlmClear R{(const double *)at[0], (const double *)at[1], (int)m, d, F, (int8_t *)at[2], (int32_t *)at[3], (double *)at[4], (int32_t *)at[5],
+                       (int32_t *)at[6], (int32_t *)at[7], (int64_t *)at[8], (int32_t *)at[9], nullptr, nullptr, nullptr, nullptr, nullptr};
+            if (grouped) {
+                R.g_cost = (int64_t *)g_words[0] + i0, R.g_min_sq = (int32_t *)g_words[1] + i0, R.g_steps = (int32_t *)g_words[2] + i0;
+                R.g_near = (int32_t *)g_words[3] + i0, R.g_status = (int8_t *)g_words[4] + i0;
+            }
+            launch(h, kern, lanes_grid(m, h->rays_grid), 0, R);
+            return MLM_OK;
+        });
+        if (rc) return rc;
+    }
+    if (grouped && n_groups > 0) { // behind the last chunk: one lane per group
+        launch(h, k_clearance_groups, lanes_grid((size_t)n_groups, kClearGroupGrid), 0, G);
+        HIPCHK(h, hipGetLastError());
+        if (table_staged)
+            HIPCHK(h, hipMemcpyAsync(table, G.table, (size_t)n_groups * MLM_CLEAR_WORDS * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MLM_OK;
+}
+
 namespace {
-constexpr int kViewChunkViews = 1 << 16;    // views per pass: bounds the job lists and the staged rows (64 bytes per view)
+constexpr int kViewChunkViews = 1 << 16;   // views per pass: bounds the job lists and the staged rows (64 bytes per view)
 constexpr unsigned int kViewGrid = 1 << 16; // most workgroups of a launch (grid-stride over the jobs)
 } // namespace
 

@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import ctypes
 import importlib.util
+import math
 import os
 import sys
 from typing import Dict, List, Optional, Tuple
@@ -34,6 +35,8 @@ MLM_REACH_OCC, MLM_REACH_INFL, MLM_REACH_UNKNOWN, MLM_REACH_NONE, MLM_REACH_SEED
 MLM_ROUTE_OCC, MLM_ROUTE_INFL, MLM_ROUTE_UNKNOWN, MLM_ROUTE_NONE, MLM_ROUTE_SEED = 1, 2, 4, -1, 26
 MLM_PATH_REACH, MLM_PATH_ROUTE, MLM_PATH_ROW = 0, 1, 8
 MLM_SCORE_CLASSES, MLM_SCORE_ROW = 1, 8
+# mlm_query_clearance: the flag, min_sq of a ray that saw no voxel, the status of a walk that left the box, int64 per group row
+MLM_CLEAR_OUTSIDE_PASS, MLM_CLEAR_NONE, MLM_CLEAR_LEFT, MLM_CLEAR_ROW = 1, -1, 2, 8
 # mlm_export_clusters: the set (FRONTIER alone, or a union of the class bits), labels off the set / in a dropped component, int64 per row
 MLM_CLUSTER_OCC, MLM_CLUSTER_INFL, MLM_CLUSTER_UNKNOWN, MLM_CLUSTER_FRONTIER = 1, 2, 4, 16
 MLM_CLUSTER_NONE, MLM_CLUSTER_SMALL, MLM_CLUSTER_ROW = -1, -2, 16
@@ -77,7 +80,7 @@ ABI_SYMBOLS = [
     "mlm_query_odds", "mlm_query_odd_grad", "mlm_query_odds_at", "mlm_export_frontier_points", "mlm_import_blocks", "mlm_crop_blocks", "mlm_warp_blocks", "mlm_fuse_blocks", "mlm_age_blocks", "mlm_delta_blocks",
     "mlm_pack_blocks", "mlm_unpack_blocks", "mlm_merge_pack", "mlm_merge_finish",
     "mlm_set_free_in_bound", "mlm_inflate_map", "mlm_block_count",
-    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_grid2d", "mlm_export_reach", "mlm_export_route", "mlm_export_clusters", "mlm_export_mesh", "mlm_export_octree", "mlm_query_rays", "mlm_render_depth", "mlm_query_views", "mlm_query_boxes", "mlm_query_nearest", "mlm_query_sweeps", "mlm_query_paths", "mlm_score_poses", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
+    "mlm_export_blocks", "mlm_export_block_flags", "mlm_export_window", "mlm_export_esdf", "mlm_export_grid2d", "mlm_export_reach", "mlm_export_route", "mlm_export_clusters", "mlm_export_mesh", "mlm_export_octree", "mlm_query_rays", "mlm_render_depth", "mlm_query_views", "mlm_query_boxes", "mlm_query_nearest", "mlm_query_sweeps", "mlm_query_paths", "mlm_score_poses", "mlm_query_clearance", "mlm_export_frontier", "mlm_export_global_map", "mlm_sync", "mlm_set_async", "mlm_set_host_mirror_limit", "mlm_get_frame_stats",
     "mlm_get_awareness_hits",
     "mlm_get_awareness_misses", "mlm_get_T_ls", "mlm_get_odds_table", "mlm_get_kernel_times",
     "mlm_enable_kernel_timing", "mlm_set_timed_kernel", "mlm_host_register", "mlm_host_unregister", "mlm_debug_set", "mlm_debug_reset",
@@ -193,6 +196,7 @@ def load_library(path: Optional[str] = None):
     L.mlm_query_sweeps.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.mlm_query_paths.argtypes = [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp]
     L.mlm_score_poses.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp, vp, i32, vp]
+    L.mlm_query_clearance.argtypes = [vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]
     L.mlm_export_global_map.argtypes = [vp, i32, vp, vp]
     L.mlm_export_block_flags.argtypes = [vp, i32, vp, vp]
     L.mlm_export_frontier.argtypes = [vp, i32, vp, vp]
@@ -1610,6 +1614,141 @@ class MLMap:
         vp = lambda v: None if v is None else ctypes.c_void_p(v)
         self._chk(self._L.mlm_score_poses(self._h, vp(pts_s), int(n_pts), vp(T_ws), int(n_poses), MLM_SCORE_CLASSES if classes else 0,
                                           lo_p, dims_p, vp(sqdist), int(sq_cap), vp(table)), "mlm_score_poses")
+
+    CLEARANCE_OUTPUTS = ("status", "voxel", "t", "n_steps", "min_sq", "min", "cost", "n_near")
+
+    def query_clearance(self, p0, p1, lo, dims, sqdist, sq_stop: int, sq_cap: int, outside_pass=False, group_begin=None, outputs=None):
+        """Segment casts through a distance field (mlm_query_clearance): segment i runs from p0[i] to p1[i] (n x 3 float64 world
+        positions — numpy arrays give numpy results, torch device tensors torch device results) along cast_rays' path through the
+        field sqdist over the voxel box lo, dims (dz x dy x dx int32 as export_esdf's "sqdist"; a numpy array or a device tensor,
+        whatever the rest is), f = sqdist clamped to 0 .. sq_cap.  The walk stops at the first path voxel with f <= sq_stop (status
+        1; sq_stop -1: never) or outside the box (status 2; with outside_pass such voxels have f = sq_cap instead).  group_begin:
+        n_groups + 1 int32 offsets into the segments (array or device tensor): one row per group in "table".  outputs: the names
+        wanted (None: all eight; "table" comes with group_begin).  {"status": int8, "voxel": int32 (n, 3), "t": float64, "n_steps":
+        int32, "min_sq": int32 the smallest f seen (-1: none), "min": int32 (n, 3) where, "cost": int64 the sum of sq_cap - f over
+        the voxels passed, "n_near": int32 those with f < sq_cap, "table": int64 (n_groups, 8) [segments, first segment that did not
+        reach its end or -1, its status, smallest min_sq up to it, which segment, summed cost, n_steps, n_near]}."""
+        names = self.CLEARANCE_OUTPUTS if outputs is None else tuple(outputs)
+        if any(k not in self.CLEARANCE_OUTPUTS for k in names) or (not names and group_begin is None):
+            raise MlmError("query_clearance: outputs must name at least one of " + ", ".join(self.CLEARANCE_OUTPUTS) + " (or group_begin be given)")
+        lo_a, dims_a = self._window_args(lo, dims)
+        nvox = int(dims_a[0]) * int(dims_a[1]) * int(dims_a[2])
+        keep = []
+        if hasattr(sqdist, "data_ptr") and not isinstance(sqdist, np.ndarray):
+            import torch
+
+            if sqdist.dtype != torch.int32 or sqdist.numel() != nvox or not sqdist.is_contiguous():
+                raise MlmError("query_clearance: a tensor of sqdist must be contiguous int32 with one value per voxel of the box")
+            sq_p = ctypes.c_void_p(sqdist.data_ptr())
+        else:
+            f = np.ascontiguousarray(sqdist, dtype=np.int32)
+            if f.size != nvox:
+                raise MlmError("query_clearance: sqdist must hold one value per voxel of the box")
+            keep.append(f)
+            sq_p = _p(f)
+        on_dev = hasattr(p0, "data_ptr") and not isinstance(p0, np.ndarray)
+        if on_dev:
+            import torch
+
+            for x in (p0, p1):
+                if not hasattr(x, "data_ptr") or x.dtype != torch.float64 or x.numel() % 3 or not x.is_contiguous():
+                    raise MlmError("query_clearance: tensors of end points must be contiguous float64 with 3 values per point")
+            if p0.numel() != p1.numel() or p0.device != p1.device:
+                raise MlmError("query_clearance: p0 and p1 differ in size or device")
+            n = p0.numel() // 3
+            dev = p0.device
+            shapes = {"status": ((n,), torch.int8), "voxel": ((n, 3), torch.int32), "t": ((n,), torch.float64), "n_steps": ((n,), torch.int32),
+                      "min_sq": ((n,), torch.int32), "min": ((n, 3), torch.int32), "cost": ((n,), torch.int64), "n_near": ((n,), torch.int32)}
+            out = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev) for k in names}
+            ptr = [ctypes.c_void_p(p0.data_ptr()), ctypes.c_void_p(p1.data_ptr())] + \
+                  [ctypes.c_void_p(out[k].data_ptr()) if k in out else None for k in self.CLEARANCE_OUTPUTS]
+        else:
+            a, b = _f64(p0).reshape(-1, 3), _f64(p1).reshape(-1, 3)
+            if a.shape != b.shape:
+                raise MlmError("query_clearance: p0 and p1 differ in shape")
+            n = a.shape[0]
+            shapes = {"status": ((n,), np.int8), "voxel": ((n, 3), np.int32), "t": ((n,), np.float64), "n_steps": ((n,), np.int32),
+                      "min_sq": ((n,), np.int32), "min": ((n, 3), np.int32), "cost": ((n,), np.int64), "n_near": ((n,), np.int32)}
+            out = {k: np.empty(*shapes[k]) for k in names}
+            ptr = [_p(a), _p(b)] + [_p(out[k]) if k in out else None for k in self.CLEARANCE_OUTPUTS]
+        gb_p = tab_p = None
+        ng = 0
+        if group_begin is not None:
+            if hasattr(group_begin, "data_ptr") and not isinstance(group_begin, np.ndarray):
+                import torch
+
+                if group_begin.dtype != torch.int32 or group_begin.numel() < 1 or not group_begin.is_contiguous():
+                    raise MlmError("query_clearance: a tensor of group_begin must be contiguous int32 with at least one entry")
+                ng = group_begin.numel() - 1
+                gb_p = ctypes.c_void_p(group_begin.data_ptr())
+            else:
+                gb = np.ascontiguousarray(np.asarray(group_begin, dtype=np.int32).reshape(-1))
+                if gb.size < 1:
+                    raise MlmError("query_clearance: group_begin needs at least one entry")
+                keep.append(gb)
+                ng = gb.size - 1
+                gb_p = _p(gb)
+            if on_dev:
+                out["table"] = torch.empty((ng, MLM_CLEAR_ROW), dtype=torch.int64, device=dev)
+                tab_p = ctypes.c_void_p(out["table"].data_ptr())
+            else:
+                out["table"] = np.empty((ng, MLM_CLEAR_ROW), dtype=np.int64)
+                tab_p = _p(out["table"])
+        self._chk(self._L.mlm_query_clearance(self._h, ptr[0], ptr[1], n, _p(lo_a), _p(dims_a), sq_p, int(sq_stop), int(sq_cap),
+                                              MLM_CLEAR_OUTSIDE_PASS if outside_pass else 0, *ptr[2:], gb_p, ng, tab_p), "mlm_query_clearance")
+        return out
+
+    def check_edges(self, p0, p1, radius: int, occ=True, infl=False, unknown=False, sq_cap: Optional[int] = None, group_begin=None,
+                    max_voxels: int = 2 ** 28):
+        """The edge check of a vehicle of `radius` voxels (0 .. 63) with its clearance along the edge: export_esdf {sqdist} over the
+        voxel box of all end points into a device tensor, at max_dist = max(radius + 1, ceil(sqrt(sq_cap))) (at most 64; sq_cap None:
+        (radius + 1)^2), then query_clearance on it with sq_stop = radius^2: the field never leaves the device.  A path never leaves
+        the box of its two end voxels (every axis is monotone), so no walk leaves the box; status, voxel, t and n_steps are
+        query_sweeps' at that radius.  p0, p1, group_begin and the results as query_clearance (numpy arrays are copied to the device
+        and the results come back as numpy); occ, infl, unknown as export_esdf.  Raises ValueError, naming the box, when it holds
+        more than max_voxels voxels: split the batch, or use query_sweeps, which needs no box."""
+        import torch
+
+        radius = int(radius)
+        if radius < 0 or radius > 63:
+            raise MlmError("check_edges: radius must lie in 0 .. 63")
+        max_dist = radius + 1
+        if sq_cap is None:
+            sq_cap = max_dist * max_dist
+        sq_cap = int(sq_cap)
+        if sq_cap < 1 or sq_cap > 1 << 20:
+            raise MlmError("check_edges: sq_cap must lie in 1 .. 2^20")
+        root = math.isqrt(sq_cap)
+        max_dist = min(64, max(max_dist, root if root * root == sq_cap else root + 1))
+        host = not (hasattr(p0, "data_ptr") and not isinstance(p0, np.ndarray))
+        dev = torch.device("cuda", torch.cuda.current_device())
+        if host:
+            a, b = _f64(p0).reshape(-1, 3), _f64(p1).reshape(-1, 3)
+            if a.shape != b.shape:
+                raise MlmError("check_edges: p0 and p1 differ in shape")
+            p0, p1 = torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev)
+        # the voxel box of the end points that lie on the lattice (the others belong to invalid segments)
+        q = torch.floor((torch.cat([p0.reshape(-1, 3), p1.reshape(-1, 3)]) / self.cfg.subbox_d_xyz) * 1024.0)
+        q = q[(q.abs() < 2.0 ** 40).all(dim=1)]
+        if q.shape[0] == 0:
+            lo_v, dims_v = [0, 0, 0], [1, 1, 1]
+        else:
+            v = torch.floor(q / 1024.0)
+            vlo, vhi = v.min(dim=0).values.cpu().numpy().astype(np.int64), v.max(dim=0).values.cpu().numpy().astype(np.int64)
+            lo_v, dims_v = [int(x) for x in vlo], [int(x) for x in vhi - vlo + 1]
+        if dims_v[0] * dims_v[1] * dims_v[2] > int(max_voxels):
+            raise ValueError(f"check_edges: the box of the end points, {dims_v[0]} x {dims_v[1]} x {dims_v[2]} voxels from {tuple(lo_v)}, holds more "
+                             f"than max_voxels = {int(max_voxels)}: split the batch or use query_sweeps")
+        lo_a, dims_a = self._window_args(lo_v, dims_v)
+        field = torch.empty((dims_v[2], dims_v[1], dims_v[0]), dtype=torch.int32, device=p0.device)
+        self.export_esdf_dev(lo_a, dims_a, max_dist, occ, infl, unknown, False, sqdist=field.data_ptr())
+        if group_begin is not None and not (hasattr(group_begin, "data_ptr") and not isinstance(group_begin, np.ndarray)):
+            group_begin = torch.from_numpy(np.ascontiguousarray(np.asarray(group_begin, dtype=np.int32).reshape(-1))).to(p0.device)
+        out = self.query_clearance(p0, p1, lo_a, dims_a, field, radius * radius, sq_cap, False, group_begin)
+        if host:
+            out = {k: v.cpu().numpy() for k, v in out.items()}
+        out["box"] = (np.asarray(lo_v, dtype=np.int64), np.asarray(dims_v, dtype=np.int64))
+        return out
 
     def match_pose(self, pts_s, T_ws, lo, dims, max_dist: int = 8, occ=True, infl=False, unknown=False, classes=False):
         """export_esdf {sqdist} into a device tensor, then score_poses on it with sq_cap = max_dist^2: the likelihood-field cost of
